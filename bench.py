@@ -38,6 +38,8 @@ LDS_PEAK_GBS = 256.0 * 256 * 2.4
 PMC_SUMMARY = os.path.join("profiles", "r04_pmc_summary.json")
 FP64_VALU_PEAK_TFLOPS = 78.6  # MI355X FP64 vector peak (MI355X_MICROARCH.md; SURVEY 8d: what bounds the exact KNN)
 TIMING_STRIDE = 4  # filter applications per HIP event pair
+DUMP_LIMIT_BYTES = 64 * 10**6  # --dump-outputs: all files together
+DUMP_SAMPLE_SEED = 20251015  # --dump-outputs: the rows kept when the per-vertex arrays do not fit
 
 
 def spmv_algorithmic_bytes(n, nnz_l):
@@ -89,6 +91,29 @@ def hot_path_step(ctxs, mesh_t, mesh_s, k, n_samples, timers, keep_graphs=False)
     if keep_graphs:
         return graphs
     return idx, res, (gt.device.nnz_l, gs.device.nnz_l), (gt.eig_vecs, gs.eig_vecs, w, gt.eig_vals, gs.eig_vals)
+
+
+def dump_outputs(out_dir, idx, results, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: what one step of the hot path hands its caller - both meshes' eigenvalues and eigenvectors (after
+    eigsort's column order and sign fixes), the spectral weights, and the target index of every source vertex - as float64
+    `out_dir/<name>.npy`.  When the files would exceed `limit` bytes in all, the per-vertex arrays keep the same fixed,
+    seeded sample of rows, written next to them as `rows.npy`."""
+    vecs_t, vecs_s, w, vals_t, vals_s = results
+    per_vertex = {"target_eig_vecs": vecs_t, "source_eig_vecs": vecs_s, "correspondence": idx}
+    arrays = {"target_eig_vals": vals_t, "source_eig_vals": vals_s, "spectral_weights": w}
+    n = len(idx)
+    if any(len(a) != n for a in per_vertex.values()):
+        raise ValueError("--dump-outputs: target and source meshes of different sizes")
+    per_row = 8 * (sum(int(np.prod(np.shape(a)[1:])) for a in per_vertex.values()) + 1)
+    budget = limit - 8 * sum(np.size(a) for a in arrays.values()) - 4096  # (4096: the .npy headers)
+    if n * (per_row - 8) > budget:
+        rows = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, size=budget // per_row, replace=False))
+        per_vertex = {name: np.asarray(a)[rows] for name, a in per_vertex.items()}
+        arrays["rows"] = rows
+    arrays.update(per_vertex)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def cpu_baseline(meshes, k, coords, gpu_vals, gpu_idx, eigs_runs=3):
@@ -461,6 +486,9 @@ def main():
     ap.add_argument("--streams", type=int, default=1, choices=(1, 2),
                     help="1: target and source Chebyshev recurrences in lockstep, two graphs per launch on one stream; "
                          "2: two host threads, one HIP stream each")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed (rank 0's pair: eigenvalues, eigenvectors, "
+                         "spectral weights, correspondences) as DIR/<name>.npy, float64, at most 64 MB in all")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -469,6 +497,8 @@ def main():
     if args.k < 2:
         raise SystemExit("bench.py: --k must be >= 2 (with a single eigenmap the reference's eigenvalue-gap cost, "
                          "eigsort.py:149-158, is the mean of an empty difference: NaN)")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # a plain `python bench.py --gpus N`: start the N ranks ourselves, as fresh child processes (one per GPU over
         # torch.distributed.run), BEFORE this process has made any GPU call - it never will: it relays the ranks' output
@@ -561,6 +591,8 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=tdev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, idx, coords)
     timing_stride = max(int(os.environ.get("PF_BENCH_TIMING", TIMING_STRIDE)), 1)
     tms = [c.timing() for c in set(ctxs)]
     clocks = [_hip.persist_clock(c) for c in set(ctxs)]  # every resident launch of the timed steps, on the device's own clock

@@ -573,3 +573,38 @@ def test_w1_quantile_form_equals_scipy(n, m):
     lens, iu, iv = _w1_quantile_plan(n, m)
     assert abs(lens.sum() - 1.0) < 1e-12 and iu.max() == n - 1 and iv.max() == m - 1
     np.testing.assert_allclose((np.abs(u[iu] - v[iv]) * lens).sum(), wasserstein_distance(u, v), rtol=1e-12, atol=1e-15)
+
+
+# ------------------------------------------------------------------------------- bench.py
+def test_bench_dump_outputs(tmp_path, monkeypatch):
+    """`bench.py --dump-outputs`: one float64 .npy file per result of the step; over the size limit the per-vertex arrays
+    keep the same seeded sample of rows in every run (`rows.npy`) and the files stay within the limit."""
+    for var in ("OMP_NUM_THREADS", "OPENBLAS_NUM_THREADS", "MKL_NUM_THREADS"):  # (bench.py sets them on import)
+        monkeypatch.setenv(var, os.environ.get(var, "1"))
+    import bench
+
+    rng = np.random.default_rng(7)
+    n, k = 3000, 5
+    vecs_t, vecs_s, idx = rng.normal(size=(n, k + 1)), rng.normal(size=(n, k)), rng.integers(0, n, n)
+    results = (vecs_t, vecs_s, rng.uniform(size=k), np.sort(rng.uniform(size=k + 1)), np.sort(rng.uniform(size=k)))
+
+    def dumped(name, **kw):
+        bench.dump_outputs(str(tmp_path / name), idx, results, **kw)
+        files = sorted(os.listdir(tmp_path / name))
+        assert sum(os.path.getsize(tmp_path / name / f) for f in files) <= kw.get("limit", bench.DUMP_LIMIT_BYTES)
+        return {f[:-4]: np.load(tmp_path / name / f) for f in files}
+
+    full = dumped("full")
+    assert sorted(full) == ["correspondence", "source_eig_vals", "source_eig_vecs", "spectral_weights", "target_eig_vals",
+                            "target_eig_vecs"]
+    assert all(a.dtype == np.float64 for a in full.values())
+    for name, a in zip(("target_eig_vecs", "source_eig_vecs", "spectral_weights", "target_eig_vals", "source_eig_vals"), results):
+        assert np.array_equal(full[name], a), name
+    assert np.array_equal(full["correspondence"], idx)
+
+    a, b = dumped("a", limit=100000), dumped("b", limit=100000)
+    rows = a["rows"].astype(np.int64)
+    assert 0 < len(rows) < n and np.all(np.diff(rows) > 0)
+    assert np.array_equal(a["target_eig_vecs"], vecs_t[rows]) and np.array_equal(a["source_eig_vecs"], vecs_s[rows])
+    assert np.array_equal(a["correspondence"], idx[rows]) and np.array_equal(a["target_eig_vals"], results[3])
+    assert sorted(a) == sorted(b) and all(np.array_equal(a[name], b[name]) for name in a)

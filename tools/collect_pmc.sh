@@ -3,7 +3,7 @@
 # of the profiled run that are already in profiles/:   bash tools/collect_pmc.sh r03_e
 set -e
 tag=${1:-r03_e}
-root=${GRAFT_REPO_ROOT:-/root/repo}
+root=$(cd "$(dirname "$0")/.." && pwd)
 out=$root/gpurun_out/pmc
 rm -rf $out && mkdir -p $out
 cd /tmp && export TMPDIR=/tmp

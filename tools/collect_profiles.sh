@@ -8,7 +8,7 @@
 # 4. PMC passes (FETCH_SIZE, WRITE_SIZE separately; resident kernel, then PF_PERSIST=0 for the streaming kernel)
 # 5. tools/pmc_make_summary.py
 set -e
-root=${GRAFT_REPO_ROOT:-/root/repo}
+root=$(cd "$(dirname "$0")/.." && pwd)
 out=$root/gpurun_out/final
 rm -rf $out && mkdir -p $out
 cd /tmp && export TMPDIR=/tmp

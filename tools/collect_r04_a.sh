@@ -1,7 +1,7 @@
 #!/bin/bash
 # round 4 collection, part A (kernel statistics of the headline workload + PMC passes): results in gpurun_out/final_a/
 set -e
-root=${GRAFT_REPO_ROOT:-/root/repo}
+root=$(cd "$(dirname "$0")/.." && pwd)
 out=$root/gpurun_out/final_a
 rm -rf $out && mkdir -p $out
 cd /tmp && export TMPDIR=/tmp

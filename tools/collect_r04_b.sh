@@ -1,6 +1,6 @@
 #!/bin/bash
 # round 4 collection, part B: a quick test of the assembly, then the full bench line (extras + measured CPU baseline)
-root=${GRAFT_REPO_ROOT:-/root/repo}
+root=$(cd "$(dirname "$0")/.." && pwd)
 out=$root/gpurun_out/final_b
 rm -rf $out && mkdir -p $out
 cd $root

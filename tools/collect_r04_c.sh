@@ -1,6 +1,6 @@
 #!/bin/bash
 # round 4 collection, part C: kernel statistics of the C5 step (1M-vertex pair, k = 10) on one GPU, the size sweep
-root=${GRAFT_REPO_ROOT:-/root/repo}
+root=$(cd "$(dirname "$0")/.." && pwd)
 out=$root/gpurun_out/final_c
 rm -rf $out && mkdir -p $out
 cd /tmp && export TMPDIR=/tmp

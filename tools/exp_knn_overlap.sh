@@ -2,7 +2,7 @@
 # How long the main 1-NN kernel runs with the eigenvector downloads beside it (PF_DOWNLOAD_DEFER=1, the default) and
 # without (=0): kernel trace of 6 steps each, the rows of k_knn_coop / copyBuffer kept.   bash tools/exp_knn_overlap.sh
 set -e
-root=${GRAFT_REPO_ROOT:-/root/repo}
+root=$(cd "$(dirname "$0")/.." && pwd)
 out=$root/gpurun_out/knn_overlap
 rm -rf $out && mkdir -p $out
 cd /tmp && export TMPDIR=/tmp

@@ -1,6 +1,6 @@
 #!/bin/bash
 # kernel trace of the 1M / k=10 step (C5 on one GPU): where do assembly and eigsort go superlinear?
-root=${GRAFT_REPO_ROOT:-/root/repo}
+root=$(cd "$(dirname "$0")/.." && pwd)
 out=$root/gpurun_out/r03_1m
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp

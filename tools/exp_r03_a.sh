@@ -1,7 +1,7 @@
 #!/bin/bash
 # round-3 experiment A: what would conflict-free LDS placement / free hand-offs buy the resident kernel (timing only)
 set -e
-root=${GRAFT_REPO_ROOT:-/root/repo}
+root=$(cd "$(dirname "$0")/.." && pwd)
 out=$root/gpurun_out/r03_a
 mkdir -p $out
 cd $root

@@ -1,6 +1,6 @@
 #!/bin/bash
 # round-3 experiment B: two steps per exchange - bit identity, then timing
-root=${GRAFT_REPO_ROOT:-/root/repo}
+root=$(cd "$(dirname "$0")/.." && pwd)
 out=$root/gpurun_out/r03_b
 mkdir -p $out
 cd $root

@@ -1,6 +1,6 @@
 #!/bin/bash
 # kernel trace of the headline step: gaps and the timeline of the last step -> gpurun_out/$1/
-root=${GRAFT_REPO_ROOT:-/root/repo}
+root=$(cd "$(dirname "$0")/.." && pwd)
 out=$root/gpurun_out/$1
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp

@@ -1,6 +1,6 @@
 #!/bin/bash
 # bench_cheb over every tuning build in pyfocusr_amd/csrc/variants: tools/exp_variants.sh OUTDIR [bench_cheb args]
-root=${GRAFT_REPO_ROOT:-/root/repo}
+root=$(cd "$(dirname "$0")/.." && pwd)
 out=$root/gpurun_out/$1; shift
 mkdir -p $out
 cd $root

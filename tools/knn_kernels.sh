@@ -1,7 +1,7 @@
 #!/bin/bash
 # per-kernel time of the KNN stage of the 250k pair (rocprofv3 kernel stats of tools/profile_eigsort.py): run on the GPU box
 set -e
-root=${GRAFT_REPO_ROOT:-/root/repo}
+root=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
 rm -rf $root/gpurun_out/trace_knn
 rocprofv3 --kernel-trace --stats --output-format csv -d $root/gpurun_out/trace_knn -- python3 $root/tools/profile_eigsort.py > $root/gpurun_out/knn_prof_stdout.txt 2>&1

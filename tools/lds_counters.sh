@@ -1,7 +1,7 @@
 #!/bin/bash
 # LDS bank conflicts of the resident kernel (250k pair), by counters: SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE
 set -e
-root=${GRAFT_REPO_ROOT:-/root/repo}
+root=$(cd "$(dirname "$0")/.." && pwd)
 out=$root/gpurun_out/n_lds
 rm -rf $out && mkdir -p $out
 cd /tmp && export TMPDIR=/tmp

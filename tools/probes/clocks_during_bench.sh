@@ -1,7 +1,7 @@
 #!/bin/bash
 # Shader clock and socket power while bench.py's timed loop runs (is the step clock- or power-limited?).
 #   bash tools/probes/clocks_during_bench.sh      -> gpurun_out/clocks/
-root=${GRAFT_REPO_ROOT:-/root/repo}
+root=$(cd "$(dirname "$0")/../.." && pwd)
 out=$root/gpurun_out/clocks
 rm -rf $out && mkdir -p $out
 rocm-smi --showclocks --showpower --showmaxpower > $out/idle.txt 2>&1

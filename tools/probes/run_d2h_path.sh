@@ -1,7 +1,7 @@
 #!/bin/bash
 # bash tools/probes/run_d2h_path.sh   (on the GPU box; binary built beforehand with hipcc, see d2h_path.hip)
 set -e
-root=${GRAFT_REPO_ROOT:-/root/repo}
+root=$(cd "$(dirname "$0")/../.." && pwd)
 out=$root/gpurun_out/d2h_path
 rm -rf $out && mkdir -p $out
 cd /tmp && export TMPDIR=/tmp

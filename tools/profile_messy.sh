@@ -1,6 +1,6 @@
 #!/bin/bash
 # kernel statistics + idle gaps of the 250k pair with scan defects (asymmetric W: restarted Arnoldi): gpurun_out/messy_prof/
-root=${GRAFT_REPO_ROOT:-/root/repo}
+root=$(cd "$(dirname "$0")/.." && pwd)
 out=$root/gpurun_out/messy_prof
 rm -rf $out && mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
