@@ -482,6 +482,39 @@ int pf_cpd_download(pf_cpd* h, double* TY, double* P1, double* Pt1, double* PX);
 int pf_cpd_gram(pf_ctx* ctx, const double* A, int64_t n_a, const double* B, int64_t n_b, int32_t d, double beta,
                 const double* V, int32_t n_cols, double* out);
 
+/* ---- optimal one-to-one assignment (replaces linear_sum_assignment(cdist(rows, cols)), focusr.py:340-349) ---------- */
+/* Exact linear assignment on Euclidean costs C[i][j] = sqrt(sum_c (rows[i][c] - cols[j][c])^2), accumulated left to right
+ * without FMA contraction (cdist's `euclidean`); costs are recomputed from the coordinates, no n x n matrix exists.
+ * Forward auction with eps-scaling on the problem padded to square by n_cols - n_rows virtual rows of cost 0, candidate
+ * lists of each row's 16 nearest columns (a row bids from its list only when the list provably holds its best and
+ * second-best column, otherwise it scans every column), then a dense certificate pass:
+ *   u_i = min_j (C_ij - v_j) over ALL columns, v_j <= 0 (column prices, shifted), slack_i = C_i,col(i) - u_i - v_col(i) >= 0
+ * so that (u, v) is dual-feasible (u_i + v_j <= C_ij) and gap_bound = sum of the slacks (virtual rows included) bounds
+ * total_cost - optimum.  The final eps is chosen so that n_cols * eps <= 1e-10 * sum_i min_j C_ij; an eps below
+ * 2^-43 * (max C + max price) is not representable and is clamped there (eps_floor_hit; gap_bound then only promises
+ * n_cols * eps).  1 <= d <= 16, 1 <= n_rows <= n_cols < 2^31; non-finite coordinates: PF_E_ARG.  Equal costs (duplicate
+ * points) may yield another optimal assignment than scipy's.  Deterministic: identical inputs give identical outputs.
+ * col_of_row[n_rows]; u_out[n_rows], v_out[n_cols] and stats nullable. */
+typedef struct pf_assign_stats {
+    int32_t phases;           /* eps-scaling phases run                                                            */
+    int32_t dense_passes;     /* certificate passes over all n_rows x n_cols pairs                                  */
+    int64_t rounds;           /* Jacobi bid rounds, summed over the phases                                          */
+    int64_t bids;             /* bids placed (each row of a round that bid)                                          */
+    int64_t dense_bids;       /* ... of them after a scan of all columns (the candidate list could not decide)       */
+    int64_t candidate_edges;  /* entries of the candidate lists (n_rows * 16, or n_rows * n_cols when n_cols <= 16)   */
+    int64_t launches;         /* kernel launches                                                                      */
+    int64_t device_bytes;     /* device memory the call allocated: O(n * (d + 16))                                    */
+    int32_t k;                /* candidates per row                                                                   */
+    int32_t eps_floor_hit;    /* the final eps was clamped at the float64 floor                                        */
+    double eps_initial, eps_final, eps_floor;
+    double total_cost;        /* sum of C over the assigned pairs                                                      */
+    double gap_bound;         /* proven upper bound of total_cost - optimum (sum of the slacks)                        */
+    double lower_bound;       /* sum over the rows of their smallest cost                                              */
+    double ms_candidates, ms_auction, ms_certificate;  /* device time of the three stages (HIP events)               */
+} pf_assign_stats;
+int pf_assign(pf_ctx* ctx, const double* rows, int64_t n_rows, const double* cols, int64_t n_cols, int32_t d,
+              int64_t* col_of_row, double* u_out, double* v_out, pf_assign_stats* stats);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,6 +7,7 @@ call loads `csrc/libpyfocusr_hip.so` and fails loudly if it (or an MI355X) is
 missing — there is no CPU fallback.
 """
 from . import vtk_functions
+from .assignment import euclidean_assignment
 from .eigsort import eigsort
 from .focusr import *  # noqa: F401,F403
 from .graph import *  # noqa: F401,F403

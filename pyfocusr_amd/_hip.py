@@ -52,6 +52,18 @@ class Timing(C.Structure):
                 ("persist_steps", C.c_int64), ("persist_bytes", C.c_double), ("persist_lds_bytes", C.c_double)]
 
 
+class AssignStats(C.Structure):
+    _fields_ = [("phases", C.c_int32), ("dense_passes", C.c_int32), ("rounds", C.c_int64), ("bids", C.c_int64),
+                ("dense_bids", C.c_int64), ("candidate_edges", C.c_int64), ("launches", C.c_int64),
+                ("device_bytes", C.c_int64), ("k", C.c_int32), ("eps_floor_hit", C.c_int32), ("eps_initial", C.c_double),
+                ("eps_final", C.c_double), ("eps_floor", C.c_double), ("total_cost", C.c_double),
+                ("gap_bound", C.c_double), ("lower_bound", C.c_double), ("ms_candidates", C.c_double),
+                ("ms_auction", C.c_double), ("ms_certificate", C.c_double)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 # name -> (restype, argtypes): every symbol include/pyfocusr_hip.h declares.
 SIGNATURES = {
     "pf_version": (C.c_int, []),
@@ -166,6 +178,8 @@ SIGNATURES = {
     "pf_cpd_apply_deform": (C.c_int, [C.c_void_p, _f64p, _f64p]),
     "pf_cpd_download": (C.c_int, [C.c_void_p, _f64p, _f64p, _f64p, _f64p]),
     "pf_cpd_gram": (C.c_int, [C.c_void_p, _f64p, C.c_int64, _f64p, C.c_int64, C.c_int32, C.c_double, _f64p, C.c_int32, _f64p]),
+    "pf_assign": (C.c_int, [C.c_void_p, _f64p, C.c_int64, _f64p, C.c_int64, C.c_int32, _i64p, _f64p, _f64p,
+                            C.POINTER(AssignStats)]),
 }
 
 _lib = None
@@ -435,6 +449,26 @@ class Context(object):
         _check(self._lib.pf_knn1(self._h, _f64(ref), ref.shape[0], _f64(qry), qry.shape[0], ref.shape[1],
                                  idx.ctypes.data_as(_i64p), _f64(d2) if return_d2 else None))
         return (idx, d2) if return_d2 else idx
+
+    def assign(self, rows, cols, return_duals=False):
+        """Optimal one-to-one assignment on Euclidean costs (`pf_assign`): col_of_row (int64, n_rows) minimising
+        sum_i ||rows[i] - cols[col_of_row[i]]||, n_rows <= n_cols, 1 <= d <= 16, and the call's AssignStats (total_cost,
+        gap_bound, ...).  return_duals: also u (n_rows) and v (n_cols) with u_i + v_j <= C_ij, v <= 0, whose slacks on the
+        assigned pairs sum to stats.gap_bound.  Non-finite coordinates raise ValueError."""
+        rows, cols = _c_f64(rows), _c_f64(cols)
+        if rows.ndim != 2 or cols.ndim != 2 or rows.shape[1] != cols.shape[1]:
+            raise ValueError("rows and cols must be (n, d) arrays with equal d")
+        if not (np.isfinite(rows).all() and np.isfinite(cols).all()):
+            raise ValueError("coordinates must be finite")
+        n_r, n_c = rows.shape[0], cols.shape[0]
+        col = np.empty(n_r, dtype=np.int64)
+        u = np.empty(n_r) if return_duals else None
+        v = np.empty(n_c) if return_duals else None
+        stats = AssignStats()
+        _check(self._lib.pf_assign(self._h, _f64(rows), n_r, _f64(cols), n_c, rows.shape[1], col.ctypes.data_as(_i64p),
+                                   _f64(u) if return_duals else None, _f64(v) if return_duals else None,
+                                   C.byref(stats)))
+        return (col, stats, u, v) if return_duals else (col, stats)
 
     def knn(self, ref, qry, k):
         """(idx (n_qry, k) int64, squared distances (n_qry, k)), ascending by (distance, index); k <= 4, d <= 4."""

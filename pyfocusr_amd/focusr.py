@@ -23,6 +23,7 @@ behind `get_smoothed_correspondences` (focusr.py:368-396) and the 3-NN query of
 import numpy as np
 
 from . import _hip
+from .assignment import euclidean_assignment
 from .eigsort import eigsort
 from .graph import Graph, compute_spectra, spectral_knn
 from .main import print_header
@@ -253,12 +254,10 @@ class Focusr(object):
         self.corresponding_target_idx_for_each_source_pt = self._ctx.knn1(target_pts, spectral_pts)
 
     def get_hungarian_correspondence(self, target_pts, spectral_pts):
-        """focusr.py:340-349: optimal one-to-one assignment on the dense distance matrix — scipy on the host
-        exactly as the reference issues it (O(N^2) memory, O(N^3) time: small meshes only)."""
-        from scipy.optimize import linear_sum_assignment
-        from scipy.spatial.distance import cdist
-
-        _, target_idx = linear_sum_assignment(cdist(spectral_pts, target_pts))
+        """focusr.py:340-349: optimal one-to-one assignment on the Euclidean distances.  On the device
+        (`euclidean_assignment`: exact, no n x n matrix) for up to 16 coordinates; scipy on the dense matrix, exactly as
+        the reference issues it, for more, or with PF_ASSIGN=host (scipy's choice among exactly tied optima)."""
+        _, target_idx = euclidean_assignment(spectral_pts, target_pts, ctx=self._ctx)
         self.corresponding_target_idx_for_each_source_pt = target_idx
 
     def get_initial_correspondences(self):
