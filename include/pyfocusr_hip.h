@@ -163,9 +163,9 @@ int pf_persist_enable(int on);
 /* Level 1 by default: single-graph recurrences (pf_cheb) on graphs with windows of 1024 rows (up to ~262k rows) whose
  * windows see each other symmetrically (any symmetric W) exchange boundary values every SECOND step: a window repeats
  * the odd steps of the outside rows it reads itself (k_cheb_resident2: one memory-side hand-off per two steps; 250k
- * rows: 1.41 -> 1.24 us per step).  Level 2: paired recurrences (pf_cheb2) as well - measured slower than one step
- * per exchange there (2.08 against 1.85 us per step of a 250k pair), kept for the record.  0: one step per exchange
- * everywhere.  Bit-identical results at every level.  Environment: PF_PERSIST_S2=0/1/2; process-wide. */
+ * rows: 1.41 -> 1.24 us per step).  Paired recurrences (pf_cheb2) always take one step per exchange: two steps were
+ * measured slower there (2.08 against 1.85 us per step of a 250k pair).  0: one step per exchange everywhere; any level
+ * above 1 means 1.  Bit-identical results at every level.  Environment: PF_PERSIST_S2=0/1; process-wide. */
 int pf_persist_two_step(int level);
 /* On by default: a paired recurrence (pf_cheb2) on windows of 1024 rows whose outside-row lists fit half a block runs the
  * kernel whose two halves take the graphs in opposite order (k_cheb_resident<2,1,8,true>), so that both graphs'
@@ -180,7 +180,7 @@ int pf_persist_clock(pf_ctx* ctx, double* kernel_ms, int64_t* launches, int rese
 /* What the resident path is doing, for callers that want to know whether they are on the fast path. */
 typedef struct pf_persist_info {
     int32_t enabled;           /* 1: filter applications use the resident kernels where a graph allows it             */
-    int32_t two_step;          /* the pf_persist_two_step level: 0, 1 (single-graph recurrences) or 2 (pairs too)      */
+    int32_t two_step;          /* the pf_persist_two_step level: 0 or 1 (single-graph recurrences)                    */
     int32_t owner;             /* 1: `ctx` owns the path, 0: no ctx has used it yet, -1: another ctx of the process  */
     int32_t timeouts;          /* waits that ran out since the process started (each reported as PF_E_PERSIST_TIMEOUT) */
     int64_t launches;          /* resident launches of this process                                                   */
@@ -318,6 +318,10 @@ int pf_knn_tree_stats(pf_ctx* ctx, int32_t enable_counting, int64_t* leaves_scan
 /* The same for the grid search (k = 1, d <= 9): candidate-query pairs whose squared distance the last counted search
  * evaluated (3 d floating-point operations each): the work behind the 1-NN stage's roofline entry in bench.py. */
 int pf_knn_count(pf_ctx* ctx, int32_t enable_counting, int64_t* pairs);
+/* Diagnostics of the last COUNTED grid search: the waves' own run times - their sum and the slowest wave, in us - the
+ * number of waves, the candidates of the wave that scanned most, and detail[5]: chunks, scans, scan us, bounds us and
+ * candidates that pass the off-plane coordinates, summed over the waves. */
+int pf_knn_wave_stats(pf_ctx* ctx, double* sum_us, double* max_us, int64_t* waves, int64_t* max_candidates, double* detail);
 /* k nearest neighbours (1 <= k <= 4, d <= 4), ascending by (distance, index): the 3-NN of
  * Focusr.get_weighted_final_node_locations (focusr.py:409-412).  idx_out / d2_out: n_qry x k row-major. */
 int pf_knn(pf_ctx* ctx, const double* ref, int64_t n_ref, const double* qry, int64_t n_qry, int32_t d, int32_t k,

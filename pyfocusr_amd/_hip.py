@@ -143,6 +143,8 @@ SIGNATURES = {
     "pf_knn_download": (C.c_int, [C.c_void_p, _i64p, _f64p]),
     "pf_eigs_smallest": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _f64p, _f64p, C.POINTER(C.c_int32), C.POINTER(EigsStats)]),
     "pf_knn_count": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int64)]),
+    "pf_knn_wave_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                    _f64p]),
     "pf_host_detach": (C.c_int, [C.c_void_p]),
     "pf_orth_device_passes": (C.c_int, [C.c_void_p, C.c_int32]),
     "pf_eigs_smallest_ex": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _f64p, _f64p, _f64p, C.POINTER(C.c_int32),
@@ -320,8 +322,8 @@ def orth_one_launch(on=True):
 
 def persist_two_step(level=1):
     """Process-wide level of the two-steps-per-exchange form of the resident kernel (csrc/pf_persist.hip:
-    k_cheb_resident2): 0 off, 1 single-graph recurrences (default), 2 paired recurrences too.  Results are
-    bit-identical at every level."""
+    k_cheb_resident2): 0 off, 1 single-graph recurrences (default; a higher level means 1).  Paired recurrences
+    always take one step per exchange.  Results are bit-identical at every level."""
     _check(load_library().pf_persist_two_step(int(level)))
 
 

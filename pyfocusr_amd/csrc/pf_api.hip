@@ -34,23 +34,20 @@ int pf_copy_by_kernel(hipStream_t st, const void* src, void* dst, size_t bytes) 
     return PF_OK;
 }
 
-static pf_ctx* ctx_of_stream(hipStream_t st, int* sid = nullptr) {
+// (stream_b: the scan of a pair build's side chain takes its temporary there)
+static pf_ctx* ctx_of_stream(hipStream_t st) {
     std::lock_guard<std::mutex> lk(g_ctx_mutex);
-    for (pf_ctx* c : g_ctxs) {
-        if (c->stream == st || (c->stream_b && c->stream_b == st)) {
-            if (sid) *sid = c->stream == st ? 0 : 1;
-            return c;
-        }
-    }
+    for (pf_ctx* c : g_ctxs)
+        if (c->stream == st || (c->stream_b && c->stream_b == st)) return c;
     return nullptr;
 }
 
-int pf_pinned_scratch(pf_ctx* c, size_t bytes, void** out, int sid) {
-    void*& buf = sid == 2 ? c->pinned_scratch_knn : (sid ? c->pinned_scratch_b : c->pinned_scratch);
-    size_t& have = sid == 2 ? c->pinned_scratch_knn_bytes : (sid ? c->pinned_scratch_b_bytes : c->pinned_scratch_bytes);
+int pf_pinned_scratch(pf_ctx* c, size_t bytes, void** out, int which) {
+    void*& buf = which == 2 ? c->pinned_scratch_knn : (which ? c->pinned_scratch_b : c->pinned_scratch);
+    size_t& have = which == 2 ? c->pinned_scratch_knn_bytes : (which ? c->pinned_scratch_b_bytes : c->pinned_scratch_bytes);
     if (bytes > have) {
         if (buf) {
-            PF_HIP(hipStreamSynchronize(sid == 1 ? c->stream_b : c->stream));
+            PF_HIP(hipStreamSynchronize(c->stream));
             PF_HIP(hipHostFree(buf));
             buf = nullptr;
             have = 0;
@@ -99,67 +96,16 @@ hipStream_t pf_stream_b(pf_ctx* c) {
     return c->stream_b;
 }
 
-void pf_worker_run(pf_ctx* c, std::function<void()> task) {
-    std::unique_lock<std::mutex> lk(c->worker_mutex);
-    if (!c->worker.joinable()) {
-        c->worker = std::thread([c] {
-            (void)hipSetDevice(c->device);
-            std::unique_lock<std::mutex> l(c->worker_mutex);
-            for (;;) {
-                c->worker_cv.wait(l, [c] { return c->worker_stop || (c->worker_busy && c->worker_task); });
-                if (c->worker_stop) return;
-                std::function<void()> t = std::move(c->worker_task);
-                c->worker_task = nullptr;
-                l.unlock();
-                t();
-                l.lock();
-                c->worker_busy = false;
-                c->worker_cv.notify_all();
-            }
-        });
-    }
-    c->worker_cv.wait(lk, [c] { return !c->worker_busy; });
-    c->worker_task = std::move(task);
-    c->worker_busy = true;
-    c->worker_cv.notify_all();
-}
-
-void pf_worker_wait(pf_ctx* c) {
-    std::unique_lock<std::mutex> lk(c->worker_mutex);
-    c->worker_cv.wait(lk, [c] { return !c->worker_busy; });
-}
-
-int pf_streams_join(pf_ctx* c, int waiter_sid) {
-    PF_CHECK(c->stream_b != nullptr, PF_E_STATE, "pf_streams_join: no second stream");
-    hipStream_t waiter = waiter_sid ? c->stream_b : c->stream, other = waiter_sid ? c->stream : c->stream_b;
-    PF_HIP(hipEventRecord(c->join_ev, other));
-    PF_HIP(hipStreamWaitEvent(waiter, c->join_ev, 0));
-    c->alloc_epoch += 1;
-    c->visible[waiter_sid] = c->alloc_epoch;
-    return PF_OK;
-}
-
 hipError_t pf_malloc(hipStream_t st, void** p, size_t bytes) {
     *p = nullptr;
-    int sid = 0;
-    pf_ctx* c = ctx_of_stream(st, &sid);
+    pf_ctx* c = ctx_of_stream(st);
     if (!c) return hipErrorInvalidValue;
     std::lock_guard<std::mutex> lk(c->alloc_mutex);
     bytes = (std::max<size_t>(bytes, 1) + 255) & ~(size_t)255;
-    auto range = c->free_blocks.equal_range(bytes);
-    // a block released on this stream (ordered by it) first; else one the other stream released before this stream last
-    // waited for it (taking those first would drain the other stream's supply of exactly the sizes both use)
-    auto pick = range.second;
-    for (auto it = range.first; it != range.second; ++it) {
-        if (it->second.sid == sid) {
-            pick = it;
-            break;
-        }
-        if (pick == range.second && it->second.epoch < c->visible[sid]) pick = it;
-    }
-    if (pick != range.second) {
-        *p = pick->second.p;
-        c->free_blocks.erase(pick);
+    const auto it = c->free_blocks.lower_bound(bytes);
+    if (it != c->free_blocks.end() && it->first == bytes) {
+        *p = it->second;
+        c->free_blocks.erase(it);
     }
     if (!*p) {
         c->alloc_misses += 1;
@@ -167,12 +113,12 @@ hipError_t pf_malloc(hipStream_t st, void** p, size_t bytes) {
         const auto t_miss = std::chrono::steady_clock::now();
         hipError_t e = hipMalloc(p, bytes);
         if (dbg_alloc)
-            fprintf(stderr, "libpyfocusr_hip: allocation %lld of ctx %p went to the driver: %zu bytes, stream %d, %.0f us\n", (long long)c->alloc_misses,
-                    (void*)c, bytes, sid, std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_miss).count());
+            fprintf(stderr, "libpyfocusr_hip: allocation %lld of ctx %p went to the driver: %zu bytes, %.0f us\n", (long long)c->alloc_misses,
+                    (void*)c, bytes, std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_miss).count());
         if (e != hipSuccess) {  // give cached blocks back to the driver and retry once
             (void)hipStreamSynchronize(c->stream);
             if (c->stream_b) (void)hipStreamSynchronize(c->stream_b);
-            for (auto& kv : c->free_blocks) (void)hipFree(kv.second.p);
+            for (auto& kv : c->free_blocks) (void)hipFree(kv.second);
             c->free_blocks.clear();
             e = hipMalloc(p, bytes);
             if (e != hipSuccess) return e;
@@ -188,13 +134,12 @@ void pf_free(hipStream_t st, void* p) {
         pfl::tl_rec->frees.emplace_back(st, p);
         return;
     }
-    int sid = 0;
-    pf_ctx* c = ctx_of_stream(st, &sid);
+    pf_ctx* c = ctx_of_stream(st);
     if (!c) return;
     std::lock_guard<std::mutex> lk(c->alloc_mutex);
     auto it = c->live_blocks.find(p);
     if (it == c->live_blocks.end()) return;  // not ours (or already released)
-    c->free_blocks.emplace(it->second, pf_ctx::FreeBlock{p, sid, c->alloc_epoch});
+    c->free_blocks.emplace(it->second, p);
     c->live_blocks.erase(it);
 }
 
@@ -364,15 +309,6 @@ void pf_destroy(pf_ctx* c) {
         hipStreamSynchronize(c->copy_stream);
         hipStreamDestroy(c->copy_stream);
     }
-    if (c->worker.joinable()) {
-        {
-            std::unique_lock<std::mutex> lk(c->worker_mutex);
-            c->worker_cv.wait(lk, [c] { return !c->worker_busy; });
-            c->worker_stop = true;
-            c->worker_cv.notify_all();
-        }
-        c->worker.join();
-    }
     if (c->stream_b) {
         hipStreamSynchronize(c->stream_b);
         hipStreamDestroy(c->stream_b);
@@ -382,7 +318,7 @@ void pf_destroy(pf_ctx* c) {
     }
     if (c->pinned_scratch_b) hipHostFree(c->pinned_scratch_b);
     if (c->pinned_scratch_knn) hipHostFree(c->pinned_scratch_knn);
-    for (auto& kv : c->free_blocks) hipFree(kv.second.p);
+    for (auto& kv : c->free_blocks) hipFree(kv.second);
     for (auto& kv : c->live_blocks) hipFree(kv.first);  // graphs the caller forgot to free
     c->free_blocks.clear();
     c->live_blocks.clear();

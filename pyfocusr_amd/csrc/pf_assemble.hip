@@ -17,9 +17,7 @@
 #include <string.h>
 
 #include <algorithm>
-#include <chrono>
 #include <string>
-#include <thread>
 
 #include "pf_internal.h"
 #include "pf_launch.h"
@@ -656,9 +654,9 @@ struct k_report {
 // `d_extra` / `h_extra` (8 ints, optional): device flags of the caller that ride in this job's one read-back; when
 // any is set end() returns at once (PF_OK, extra_hit = true) and the caller reports ITS error.  `nnz_from_rowptr`:
 // g->nnz_w is read back here too (the mesh path sizes col / w by their upper bound instead of waiting for the count).
-// Two halves around the ONE synchronisation of a build: begin() queues everything up to the read-back on the graph's
-// build stream and returns; end() waits, decides, and queues the SELL fill.  Two meshes of a pair run their halves
-// interleaved on two streams (pf_graph_build_device2): their ~75 small kernels each overlap on the device.
+// Two halves around the ONE synchronisation of a build: begin() queues everything up to the read-back on the ctx stream
+// and returns; end() waits, decides, and queues the SELL fill.  Two meshes of a pair run their halves interleaved, their
+// launches shared (pf_graph_build_device2).
 struct FinishJob {
     pf_graph* g = nullptr;
     const double* d_pts = nullptr;
@@ -669,7 +667,7 @@ struct FinishJob {
     bool nnz_from_rowptr = false;
     const unsigned long long* d_pmin = nullptr;
     double* h_pmin = nullptr;
-    int sid = 0;  // 0: the ctx stream, 1: its second stream
+    int pos = 0;  // the mesh's position in a pair build (0: alone or first): its own pinned read-back buffer
 
     static constexpr int PF_CC_ROUNDS = 128;
     static constexpr int PF_CC_FIRST = 12;
@@ -693,7 +691,7 @@ struct FinishJob {
     }
 
     int begin_stats_and_labels() {
-        st = g->build_stream ? g->build_stream : g->ctx->stream;
+        st = g->ctx->stream;
         const int64_t n = g->n;
         PF_TRY(dev_alloc(st, &flags, 8 + PF_CC_ROUNDS));  // the flags and the labelling rounds' flags: one block, one fill
         tmp.push_back(flags);
@@ -759,7 +757,7 @@ struct FinishJob {
                                         reinterpret_cast<const int32_t*>(d_pmin), flags, report);
         PF_HIP(hipGetLastError());
         slice_bytes = sizeof(int64_t) * (size_t)(g->n_slices + 1);
-        PF_TRY(pf_pinned_scratch(g->ctx, slice_bytes + sizeof(int32_t) * PF_REPORT_INTS, &pin, sid));
+        PF_TRY(pf_pinned_scratch(g->ctx, slice_bytes + sizeof(int32_t) * PF_REPORT_INTS, &pin, pos));
         h_report = reinterpret_cast<int32_t*>(static_cast<unsigned char*>(pin) + slice_bytes);
         PF_HIP(pfl::memcpy_async(st, pin, g->slice_ptr, slice_bytes, hipMemcpyDeviceToHost));
         PF_HIP(pfl::memcpy_async(st, h_report, report, sizeof(int32_t) * PF_REPORT_INTS, hipMemcpyDeviceToHost));
@@ -869,7 +867,7 @@ namespace {
 struct MeshBuild {
     pf_mesh* mesh = nullptr;
     pf_graph* g = nullptr;
-    int sid = 0;
+    int pos = 0;  // 0: alone or the first mesh of a pair, 1: the second
     hipStream_t st = nullptr;
     std::vector<void*> tmp;
     bool ok = false;
@@ -886,10 +884,7 @@ struct MeshBuild {
     }
     ~MeshBuild() {
         release();
-        if (!ok && g) {
-            g->build_stream = nullptr;
-            pf_graph_free(g);
-        }
+        if (!ok && g) pf_graph_free(g);
     }
 
     template <typename T>
@@ -906,28 +901,25 @@ struct MeshBuild {
     double* b_rw = nullptr;
     double* pts_m = nullptr;     // the points and ...
     int32_t* faces_m = nullptr;  // ... faces renumbered by the Morton rank of the points (m-space)
-    bool fork_ok = false;        // set by the pair build: independent chains of the build may run on the ctx's second stream
     bool robust = false;         // the Morton order by the general sort (second attempt: vertices piled into one cell)
     bool needs_robust = false;   // end(): the counting sort gave up - build once more with robust = true
 
-    int begin(pf_mesh* m, int stream_id) {
-        PF_TRY(prepare(m, stream_id));
+    int begin(pf_mesh* m) {
+        PF_TRY(prepare(m, 0));
         for (int k = 0; k < N_PHASES; ++k) PF_TRY(phase(k));
         return PF_OK;
     }
 
-    // one_stream: the second mesh of a pair whose launches are shared (pf_launch.h) - everything on the ctx stream
-    int prepare(pf_mesh* m, int stream_id, bool one_stream = false) {
+    int prepare(pf_mesh* m, int pair_pos) {
         mesh = m;
-        sid = stream_id;
+        pos = pair_pos;
         pf_ctx* ctx = mesh->ctx;
-        st = (sid && !one_stream) ? ctx->stream_b : ctx->stream;
+        st = ctx->stream;
         const int64_t n = mesh->n, n_faces = mesh->n_faces;
         const int32_t vpf = mesh->vpf;
         n_edges = n_faces * vpf;
         g = new pf_graph();
         g->ctx = ctx;
-        g->build_stream = st;
         g->n = n;
         g->n_faces = n_faces;
         g->vpf = vpf;
@@ -972,7 +964,7 @@ struct MeshBuild {
             PF_TRY(dev_alloc(st, &g->iperm_m, g->n_pad));
             PF_HIP(pfl::memset_words(st, zeroed, 0, sizeof(int32_t) * (size_t)(2 * zstride + 8)));
             PF_HIP(pfl::memset_words(st, g->deg, 0, sizeof(double) * 3 * g->n_pad));
-            if (sid == 0) PF_HIP(pfl::event_record(st, ctx->ev0));
+            if (pos == 0) PF_HIP(pfl::event_record(st, ctx->ev0));
             // m-space first: the Morton rank of every point (positions only), points and faces renumbered by it.  Every
             // gather of the build from here on - edge ends, reverse edges, neighbours' degrees, window flags - lands in
             // lines that the neighbouring threads share, whatever order the caller's vertices came in (round 3: ~35 x
@@ -1020,7 +1012,7 @@ struct MeshBuild {
             // Fork (pair builds: their launches are recorded, so blocks released below go back only after the join has been
             // queued): the face bound and, in the last phase, the order inside windows have nothing to do with the row
             // statistics and the 12 labelling rounds - they run beside them on the ctx's second stream.
-            if (fork_ok && pfl::tl_rec && pf_stream_b(ctx) && ctx->fork_ev) {
+            if (pfl::tl_rec && pf_stream_b(ctx) && ctx->fork_ev) {
                 hipStream_t side = ctx->stream_b;
                 hipEvent_t ev = ctx->fork_ev;
                 pfl::call(st, [=](hipStream_t s) {
@@ -1034,7 +1026,7 @@ struct MeshBuild {
                 PF_HIP(hipGetLastError());
             }
             fin.g = g, fin.d_pts = d_pts, fin.numeric_symmetry = false, fin.d_extra = b_flags, fin.h_extra = h_flags;
-            fin.nnz_from_rowptr = true, fin.d_pmin = pmin, fin.h_pmin = &h_pmin, fin.sid = sid;
+            fin.nnz_from_rowptr = true, fin.d_pmin = pmin, fin.h_pmin = &h_pmin, fin.pos = pos;
             return PF_OK;
         }
         if (k == 2) return fin.begin_stats_and_labels();
@@ -1186,16 +1178,15 @@ int pf_graph_build_device(pf_mesh* mesh, pf_graph** out) {
     *out = nullptr;
     PF_HIP(hipSetDevice(ctx->device));
     MeshBuild job;
-    PF_TRY(job.begin(mesh, 0));
+    PF_TRY(job.begin(mesh));
     PF_TRY(job.end());
     if (job.needs_robust) {
         if (getenv("PF_DEBUG_WINDOWS")) fprintf(stderr, "pyfocusr_hip: renumbering by counting gave up, building again with the general sort\n");
         MeshBuild again;
         again.robust = true;
-        PF_TRY(again.begin(mesh, 0));
+        PF_TRY(again.begin(mesh));
         PF_TRY(again.end());
         PF_HIP(pfl::sync(ctx->stream));
-        again.g->build_stream = nullptr;
         again.ok = true;
         *out = again.g;
         return PF_OK;
@@ -1203,16 +1194,17 @@ int pf_graph_build_device(pf_mesh* mesh, pf_graph** out) {
     PF_HIP(pfl::event_record(ctx->stream, ctx->ev1));  // (no wait for the SELL fill: see pf_graph_build_device2)
     ctx->build_pending = true;
     if (pf_persist_enabled()) PF_TRY(pf_window_slots_begin(job.g));
-    job.g->build_stream = nullptr;
     job.ok = true;
     *out = job.g;
     return PF_OK;
 }
 
-// The two meshes of a pair (target and source of focusr.py:134-170) assembled SIDE BY SIDE: mesh a on the ctx stream, mesh
-// b on the ctx's second stream, their halves interleaved (begin a, begin b, end a, end b).  An assembly is ~75 small
-// kernels (4-80 us each, most of them launch latency and one wave of blocks); two of them overlap almost completely.
-// Results are those of two pf_graph_build_device calls, bit for bit.  On return both graphs live on the ctx stream.
+// The two meshes of a pair (target and source of focusr.py:134-170) assembled SIDE BY SIDE on the ctx stream.  SHARED
+// LAUNCHES (pf_launch.h): the host code of every phase runs once per mesh, each into its own recorder, and what both
+// meshes ask for goes out as one launch with the mesh in blockIdx.z - an assembly is ~75 small kernels (4-80 us each, most
+// of them launch latency and one wave of blocks), and the pair pays for them about once.  Chains of the build that the
+// row statistics and the labelling rounds do not need run beside them on the ctx's second stream (MeshBuild::phase: the
+// fork; FinishJob::queue_order: the join).  Results are those of two pf_graph_build_device calls, bit for bit.
 int pf_graph_build_device2(pf_mesh* mesh_a, pf_mesh* mesh_b, pf_graph** out_a, pf_graph** out_b) {
     PF_CHECK(mesh_a && mesh_b && out_a && out_b, PF_E_ARG, "pf_graph_build_device2: NULL argument");
     PF_CHECK(mesh_a->ctx == mesh_b->ctx, PF_E_ARG, "pf_graph_build_device2: the two meshes must belong to one ctx");
@@ -1228,22 +1220,16 @@ int pf_graph_build_device2(pf_mesh* mesh_a, pf_mesh* mesh_b, pf_graph** out_a, p
         }
         return r;
     }
-    int rc = PF_OK;
+    hipStream_t st = ctx->stream;
     bool redo = false;
-    static const bool two_streams = getenv("PF_PAIR_BUILD_STREAMS") != nullptr;  // (the form of rounds 2-4, for comparisons)
-    if (!two_streams) {
-        // SHARED LAUNCHES (pf_launch.h): the host code of every phase runs once per mesh, each into its own recorder, and
-        // what both meshes ask for goes out as one launch with the mesh in blockIdx.z - half the dispatches of the two-stream
-        // form, half the host time, one stream.
+    {
         MeshBuild a, b;
         pfl::Recorder ra, rb;
         struct Unhook {
             ~Unhook() { pfl::tl_rec = nullptr; }
         } unhook;
-        hipStream_t st = ctx->stream;
-        rc = a.prepare(mesh_a, 0);
-        if (rc == PF_OK) rc = b.prepare(mesh_b, 1, true);
-        a.fork_ok = b.fork_ok = getenv("PF_BUILD_FORK") == nullptr || atoi(getenv("PF_BUILD_FORK")) != 0;
+        int rc = a.prepare(mesh_a, 0);
+        if (rc == PF_OK) rc = b.prepare(mesh_b, 1);
         for (int k = 0; k < MeshBuild::N_PHASES && rc == PF_OK; ++k) {
             pfl::tl_rec = &ra;
             rc = a.phase(k);
@@ -1268,90 +1254,33 @@ int pf_graph_build_device2(pf_mesh* mesh_a, pf_mesh* mesh_b, pf_graph** out_a, p
         }
         pfl::tl_rec = nullptr;
         pfl::flush(ra, &rb);  // (also after an error: the recorded launches are harmless, the held-back frees are due)
+        if (rc != PF_OK) {
+            // A phase may have failed between the fork onto the second stream and the join: what was forked can still read
+            // or write the temporaries and the graphs' blocks.  Both streams drain before any of them is handed out again.
+            (void)pfl::sync(ctx->stream_b);
+            (void)pfl::sync(st);
+        }
         a.release();
         b.release();
-        if (rc == PF_OK) {
-            const hipError_t e1 = hipEventRecord(ctx->ev1, st);  // (no wait for the fills: pf_timing_get reads the events)
-            if (e1 == hipSuccess) ctx->build_pending = true;
-            else rc = PF_E_HIP, pf_set_error("pf_graph_build_device2: %s", hipGetErrorString(e1));
-        }
-        if (rc == PF_OK && (a.needs_robust || b.needs_robust)) {
-            redo = true;  // (a pile of vertices in one Morton cell: the two builds once more, one after the other; below)
-        } else if (rc == PF_OK) {
-            a.g->build_stream = b.g->build_stream = nullptr;
-            a.ok = b.ok = true;
-            *out_a = a.g;
-            *out_b = b.g;
-        } else {
-            (void)hipStreamSynchronize(st);
-        }
-    } else {
-        MeshBuild a, b;
-        rc = pf_streams_join(ctx, 1);  // the second stream sees the uploads and may reuse what the first has released
-        if (rc == PF_OK) {
-            // The first halves are ~55 launches each, ~4 us of host time apiece.  Queued one build after the other, the
-            // second mesh would start when the first one's kernels are half through; queued from two threads (rounds 2-3)
-            // they start together - until the host's scheduler leaves the second thread waiting for a core for 3-9 ms,
-            // which it did in one step of six in about one process of twelve on this pool's loaded hosts (PF_DEBUG_BUILD:
-            // "worker began 3045 us after the call", "ended 9344").  So: ONE thread, the two builds phase by phase (four
-            // phases of ~15 launches): the second stream is never more than one phase behind, 0.45 ms of launching against
-            // 0.97 ms of device time.
-            static const bool dbg = getenv("PF_DEBUG_BUILD") != nullptr;
-            using clk = std::chrono::steady_clock;
-            const clk::time_point t0 = clk::now();
-            rc = a.prepare(mesh_a, 0);
-            if (rc == PF_OK) rc = b.prepare(mesh_b, 1);
-            for (int k = 0; k < MeshBuild::N_PHASES && rc == PF_OK; ++k) {
-                rc = a.phase(k);
-                if (rc == PF_OK) rc = b.phase(k);
-            }
-            if (dbg) fprintf(stderr, "pf_build2: first halves queued in %.0f us (one thread, phase by phase)\n",
-                             std::chrono::duration<double, std::micro>(clk::now() - t0).count());
-        }
-        const auto tq0 = std::chrono::steady_clock::now();
-        if (rc == PF_OK) rc = a.end();
-        const auto tq1 = std::chrono::steady_clock::now();
-        if (rc == PF_OK) rc = b.end();
-        const auto tq2 = std::chrono::steady_clock::now();
-        if (getenv("PF_DEBUG_BUILD"))
-            fprintf(stderr, "pf_build2: second halves (wait for the read-back, SELL fill queued): first mesh %.0f us, second %.0f us\n",
-                    std::chrono::duration<double, std::micro>(tq1 - tq0).count(), std::chrono::duration<double, std::micro>(tq2 - tq1).count());
-        // the temporaries go back before the join, so that the first stream may have the second one's from now on (a
-        // block is visible across streams only if it was released before the join)
-        a.release();
-        b.release();
-        // whatever happened, the first stream waits for the second before anything else is queued on it (and the graphs
-        // move to the first stream)
-        const int rj = pf_streams_join(ctx, 0);
-        if (rc == PF_OK) rc = rj;
         if (rc == PF_OK) {
             // The call does NOT wait for the SELL fills it has queued: everything that reads the graphs is ordered behind
             // them on the ctx stream, and the host fields came with the read-back.  The build's device time (pf_timing_get:
             // build_ms) is taken from the events when somebody asks.
-            const hipError_t e1 = pfl::event_record(ctx->stream, ctx->ev1);
+            const hipError_t e1 = hipEventRecord(ctx->ev1, st);
             if (e1 == hipSuccess) ctx->build_pending = true;
             else rc = PF_E_HIP, pf_set_error("pf_graph_build_device2: %s", hipGetErrorString(e1));
         }
-        if (rc == PF_OK && !(a.needs_robust || b.needs_robust) && pf_persist_enabled()) {
-            // the window structures of the resident filter kernel, queued behind the fills (collected by the first application)
-            rc = pf_window_slots_begin(a.g);
-            if (rc == PF_OK) rc = pf_window_slots_begin(b.g);
-        }
-        if (rc == PF_OK && (a.needs_robust || b.needs_robust)) {
+        if (rc != PF_OK) return rc;
+        if (a.needs_robust || b.needs_robust) {
             redo = true;  // (a pile of vertices in one Morton cell: the two builds once more, one after the other; below)
-        } else if (rc == PF_OK) {
-            a.g->build_stream = b.g->build_stream = nullptr;
+        } else {
             a.ok = b.ok = true;
             *out_a = a.g;
             *out_b = b.g;
-        } else {
-            (void)pfl::sync(ctx->stream_b);
-            (void)pfl::sync(ctx->stream);
         }
     }
     if (redo) {
-        (void)pfl::sync(ctx->stream_b);
-        (void)pfl::sync(ctx->stream);
+        (void)pfl::sync(st);
         PF_TRY(pf_graph_build_device(mesh_a, out_a));
         const int r = pf_graph_build_device(mesh_b, out_b);
         if (r != PF_OK) {
@@ -1360,7 +1289,7 @@ int pf_graph_build_device2(pf_mesh* mesh_a, pf_mesh* mesh_b, pf_graph** out_a, p
         }
         return r;
     }
-    return rc;
+    return PF_OK;
 }
 
 int pf_graph_from_matrix(pf_ctx* ctx, int64_t n, const int32_t* rowptr, const int32_t* colidx, const double* values,

@@ -3,11 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <atomic>
-#include <condition_variable>
-#include <functional>
 #include <map>
 #include <mutex>
-#include <thread>
 #include <unordered_map>
 #include <vector>
 
@@ -134,32 +131,18 @@ struct pf_ctx {
     void* pinned_scratch = nullptr;  // small read-backs land here (pinned: one DMA instead of a staged copy each)
     size_t pinned_scratch_bytes = 0;
     std::vector<hipEvent_t> event_pool;                    // created with hipEventDisableTiming
-    // allocator state.  Two streams may allocate: `stream`, and `stream_b` while a pair of meshes is assembled side by
-    // side (pf_graph_build_device2).  A cached block remembers the stream it was released on and the allocator epoch of
-    // that moment; the other stream may take it only once it has waited for the releasing stream after that release
-    // (pf_streams_join bumps the epoch and records what the waiter may now see).
-    struct FreeBlock {
-        void* p;
-        int sid;          // 0: stream, 1: stream_b
-        uint64_t epoch;   // alloc_epoch when it was released
-    };
-    std::multimap<size_t, FreeBlock> free_blocks;   // size -> block
+    // allocator state (pf_malloc / pf_free)
+    std::multimap<size_t, void*> free_blocks;   // size -> block
     std::unordered_map<void*, size_t> live_blocks;
+    std::mutex alloc_mutex;
+    // the side stream of a pair build (pf_graph_build_device2): chains of the build that run beside the others between a
+    // fork and a join.  Blocks it uses come from the one cache: taken after the fork, released after the join is queued.
     hipStream_t stream_b = nullptr;
-    std::mutex alloc_mutex;  // pf_malloc / pf_free: the second stream's job runs its first half on a thread of its own
-    // that thread: created once per ctx (a new thread's first HIP call costs ~0.3 ms of per-thread runtime set-up)
-    std::thread worker;
-    std::mutex worker_mutex;
-    std::condition_variable worker_cv;
-    std::function<void()> worker_task;
-    bool worker_busy = false, worker_stop = false;
     hipEvent_t join_ev = nullptr, fork_ev = nullptr;
     std::vector<pf_graph*> deferred;  // graphs with a download that is not queued yet ...
     std::mutex deferred_mutex;        // ... guarded: pf_host_free / pf_host_detach walk every ctx's list from whatever thread collects an array
     int64_t alloc_misses = 0;  // allocations the cache could not serve (hipMalloc: 0.1-1 ms each)
-    uint64_t alloc_epoch = 1;
-    uint64_t visible[2] = {0, 0};  // stream sid may take the OTHER stream's blocks released before this epoch
-    void* pinned_scratch_b = nullptr;  // pf_pinned_scratch of stream_b's job
+    void* pinned_scratch_b = nullptr;  // pf_pinned_scratch of the second mesh of a pair build (both read-backs are in flight at once)
     size_t pinned_scratch_b_bytes = 0;
     void* pinned_scratch_knn = nullptr;  // ... and of the KNN's result read-back (which runs inside other users of the first)
     size_t pinned_scratch_knn_bytes = 0;
@@ -171,8 +154,7 @@ inline uint64_t pf_next_uid() {
 }
 
 struct pf_graph {
-    hipStream_t build_stream = nullptr;  // while the graph is being assembled: the stream its kernels and blocks belong to
-    hipStream_t side_stream = nullptr;   // ... and, between a fork and a join of the build, the stream of its independent chain
+    hipStream_t side_stream = nullptr;  // between a fork and a join of a pair build: the stream of the graph's independent chain
     uint64_t uid = pf_next_uid();  // never reused (unlike an address): remembered facts about a PAIR of graphs are keyed by it
     pf_ctx* ctx = nullptr;
     int64_t n = 0, n_pad = 0, n_faces = 0;
@@ -246,7 +228,6 @@ struct pf_graph {
     int64_t px_gh2_total = 0, px_g1_entries = 0;  // sums over the windows: ring-2 rows, entries of ring-1 rows
     int32_t single_applications = 0;   // single-graph resident applications so far (the rings are built at the third)
     uint64_t lds_need_partner = 0;   // uid of the partner (own uid: alone) the remembered LDS need belongs to
-    uint64_t lds_need2_partner = 0;
     int64_t lds_need_value = -2, lds_need2_value = -2;
     double* persist_ring2 = nullptr; // [4][n_pad] hand-off buffers of k_cheb_resident2 (slot of ROUND r = (r + phase2) & 3)
     int32_t persist_phase2 = 0;
@@ -317,19 +298,14 @@ int pf_timing_collect(pf_ctx* c);  // pf_api.hip: fold finished spans into op_ms
 hipError_t pf_malloc(hipStream_t st, void** p, size_t bytes);
 // the ctx's pinned host block for small transfers, at least `bytes` large (valid until the next call that asks for more;
 // users synchronise with the stream before they return)
-int pf_pinned_scratch(pf_ctx* c, size_t bytes, void** out, int sid = 0);  // sid 0: ctx stream, 1: stream_b's job, 2: the KNN read-back
+int pf_pinned_scratch(pf_ctx* c, size_t bytes, void** out, int which = 0);  // which 0: ctx stream, 1: the second mesh of a pair build, 2: the KNN read-back
 // src -> dst by a copy KERNEL on `st` (one of them pinned host memory, read or written in place: no DMA engine involved);
 // sizes rounded up to 8 bytes
 int pf_copy_by_kernel(hipStream_t st, const void* src, void* dst, size_t bytes);
 int pf_downloads_release(pf_ctx* c);  // queue every download of the ctx that was held back (behind what the ctx stream holds now)
 int pf_download_cancel(pf_graph* g);  // forget the image owed to the caller's buffer / wait for the one in flight (a call is about to fail)
-// `waiter_sid` (0: stream, 1: stream_b) waits for everything queued on the other stream so far; afterwards it may reuse
-// the blocks the other stream has released, and use what the other stream has written
-int pf_streams_join(pf_ctx* c, int waiter_sid);
 hipStream_t pf_stream_b(pf_ctx* c);  // created on first use (nullptr on failure)
 hipError_t pf_create_side_stream(hipStream_t* s, bool low = false);  // low: the least priority (a third pool of queues: the copy stream)  // a stream that never shares a hardware queue with a ctx's main stream
-void pf_worker_run(pf_ctx* c, std::function<void()> task);  // starts `task` on the ctx's worker thread (one at a time)
-void pf_worker_wait(pf_ctx* c);                             // until that task has returned
 void pf_free(hipStream_t st, void* p);
 
 // SELL-64 entry layout inside a slice of `width` entries per row: entries come in PAIRS per lane, so that one
@@ -368,13 +344,13 @@ static inline int32_t pf_window_rows(int64_t n_pad) { return n_pad <= 262144 ? 1
 // 1M pair, d = 10: 133 / 19.6 - profiles/r03_knn_hierarchy.md)
 constexpr int PF_KNN_TREE_MIN_D = 7;
 int pf_knn_tree_run(pf_ctx* c);
-extern "C" {
+
+// pf_operator.hip: the split-phase forms behind the C++ Krylov driver (pf_eigs.hip)
 int pf_gram_begin(pf_graph* g, int32_t first_a, int32_t count_a, int32_t first_b, int32_t count_b, int32_t append);
 int pf_resnorms_begin(pf_graph* g, int32_t ax_first, int32_t x_first, const double* lam, int32_t count);
 int pf_small_end(pf_graph* g, double* out);
 int pf_combine2(pf_graph* g, int32_t src_first, int32_t m, const double* Y, int32_t k, int32_t dst_first, int32_t src_first2,
                 int32_t dst_first2);
-}
 
 // pf_persist.hip: a whole recurrence T_degree((c - A)/e)/rho^degree src -> dst in ONE kernel (operator in registers,
 // x in LDS, neighbouring windows hand their boundary rows over through memory)

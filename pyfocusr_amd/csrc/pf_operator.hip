@@ -28,15 +28,6 @@ inline unsigned nblk(int64_t n) { return (unsigned)((n + PF_BLOCK - 1) / PF_BLOC
 #ifndef PF_OP_BLOCK
 #define PF_OP_BLOCK 256
 #endif
-#ifndef PF_OP_NT
-#define PF_OP_NT 0
-#endif
-#if PF_OP_NT
-#define PF_STREAM_LOAD(p) __builtin_nontemporal_load(p)
-#else
-#define PF_STREAM_LOAD(p) (*(p))
-#endif
-
 // out = alpha * (shift * x - A x) - beta * prev          (A = diag + SELL off-diagonals)
 //   SpMV:            alpha = -1, shift = 0, beta = 0      -> out = A x
 //   Chebyshev k = 1: alpha = 1/e, shift = c, beta = 0
@@ -76,8 +67,8 @@ __device__ __forceinline__ void sell_op_block(const OpArgs& a, unsigned bid) {
     const int2* __restrict__ cp2 = reinterpret_cast<const int2*>(a.scol + base) + lane;
     int j = 0;
     for (; j + 2 <= pairs; j += 2) {
-        const int2 c0 = PF_STREAM_LOAD(cp2 + (int64_t)(j + 0) * PF_WAVE), c1 = PF_STREAM_LOAD(cp2 + (int64_t)(j + 1) * PF_WAVE);
-        const double2 v0 = PF_STREAM_LOAD(vp2 + (int64_t)(j + 0) * PF_WAVE), v1 = PF_STREAM_LOAD(vp2 + (int64_t)(j + 1) * PF_WAVE);
+        const int2 c0 = cp2[(int64_t)(j + 0) * PF_WAVE], c1 = cp2[(int64_t)(j + 1) * PF_WAVE];
+        const double2 v0 = vp2[(int64_t)(j + 0) * PF_WAVE], v1 = vp2[(int64_t)(j + 1) * PF_WAVE];
         const double x0 = x[c0.x], x1 = x[c0.y], x2 = x[c1.x], x3 = x[c1.y];
         acc += v0.x * x0;
         acc += v0.y * x1;
@@ -85,14 +76,14 @@ __device__ __forceinline__ void sell_op_block(const OpArgs& a, unsigned bid) {
         acc += v1.y * x3;
     }
     for (; j < pairs; ++j) {
-        const int2 c0 = PF_STREAM_LOAD(cp2 + (int64_t)j * PF_WAVE);
-        const double2 v0 = PF_STREAM_LOAD(vp2 + (int64_t)j * PF_WAVE);
+        const int2 c0 = cp2[(int64_t)j * PF_WAVE];
+        const double2 v0 = vp2[(int64_t)j * PF_WAVE];
         acc += v0.x * x[c0.x];
         acc += v0.y * x[c0.y];
     }
     if (width & 1) {
         const int64_t t = base + (int64_t)pairs * (2 * PF_WAVE) + lane;
-        acc += PF_STREAM_LOAD(a.sval + t) * x[PF_STREAM_LOAD(a.scol + t)];
+        acc += a.sval[t] * x[a.scol[t]];
     }
     double r = a.alpha * (a.shift * xi - acc);
     if (HAS_PREV) r -= a.beta * a.prev[row];
@@ -1823,6 +1814,8 @@ int pf_combine(pf_graph* g, int32_t src_first, int32_t m, const double* Y, int32
     return pf_combine2(g, src_first, m, Y, k, dst_first, -1, -1);
 }
 
+}  // extern "C"
+
 // dst = src Y and, when src_first2 >= 0, dst2 = src2 Y in the same launches (one upload of Y)
 int pf_combine2(pf_graph* g, int32_t src_first, int32_t m, const double* Y, int32_t k, int32_t dst_first, int32_t src_first2,
                 int32_t dst_first2) {
@@ -1893,6 +1886,8 @@ int pf_combine2(pf_graph* g, int32_t src_first, int32_t m, const double* Y, int3
     return PF_OK;
 }
 
+extern "C" {
+
 int pf_resnorm(pf_graph* g, int32_t ax, int32_t x, double lam, double* out) {
     PF_TRY(check_slots(g, ax, 1, "pf_resnorm"));
     PF_TRY(check_slots(g, x, 1, "pf_resnorm"));
@@ -1927,6 +1922,8 @@ int pf_gram(pf_graph* g, int32_t first_a, int32_t count_a, int32_t first_b, int3
 // pf_gram / pf_resnorms in two halves: _begin queues the kernels and a copy of the few results into a pinned block of the
 // graph's own, with an event behind it; pf_small_end waits for that event only - what the stream holds behind it (the
 // partner graph's extraction) keeps running.  One collection in flight per graph.
+}  // extern "C"
+
 static int small_begin(pf_graph* g, const double* d_src, size_t count, bool root, bool append = false) {
     PF_CHECK(append ? g->small_pending > 0 && !g->small_root && !root : g->small_pending == 0, PF_E_STATE,
              "pf_gram_begin / pf_resnorms_begin: a previous result has not been collected");
@@ -2014,6 +2011,8 @@ int pf_resnorms_begin(pf_graph* g, int32_t ax_first, int32_t x_first, const doub
     }
     return small_begin(g, g->coef, (size_t)count, true);
 }
+
+extern "C" {
 
 int pf_resnorms(pf_graph* g, int32_t ax_first, int32_t x_first, const double* lam, int32_t count, double* out) {
     PF_TRY(check_slots(g, ax_first, count, "pf_resnorms"));

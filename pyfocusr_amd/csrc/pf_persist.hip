@@ -95,11 +95,7 @@ constexpr unsigned RX_EMPTY32 = 0xFFFFDEADu;
 // a wait gives up after this many repeated fetches (~0.5 us each: ~0.1 s; a launch lasts ~0.2 ms, and every block of the
 // grid is resident before the first wait - what a wait can run into is a device shared with another tenant)
 constexpr unsigned RX_SPIN_LIMIT = 200000u;
-#ifdef RX_EXP_STAMPS
-constexpr size_t RX_LDS_LIMIT = 160 * 1024 - 512 - 1024;
-#else
 constexpr size_t RX_LDS_LIMIT = 160 * 1024 - 512;  // the kernels' static __shared__ lives in the remainder
-#endif
 
 struct RxGraph {
     const int64_t* slice_ptr;
@@ -130,24 +126,6 @@ struct RxArgs {
                            // 0: a fixed s_sleep behind the wave's rows instead
 };
 
-#ifdef RX_EXP_STAMPS  // diagnostic build only: cycle stamps of the one-step kernel's phases, per block and wave
-__device__ unsigned long long g_rx_stamps[256 * 16 * 10];
-// (accumulated in LDS by each wave's first lane, clock values cut to 32 bits: the kernel has no registers to spare)
-#define RX_STAMP(i) \
-    do { \
-        const unsigned now_ = (unsigned)__builtin_amdgcn_s_memtime(); \
-        if (lane == 0) s_st[wave][i] += now_ - st_prev; \
-        st_prev = now_; \
-    } while (0)
-#define RX_MARK(i) \
-    do { \
-        const unsigned now_ = (unsigned)__builtin_amdgcn_s_memtime(); \
-        if (lane == 0) s_st[wave][i] += now_ - st_top; \
-    } while (0)
-#else
-#define RX_STAMP(i)
-#define RX_MARK(i)
-#endif
 #ifndef RX_HOLD
 #define RX_HOLD 16
 #endif
@@ -211,8 +189,6 @@ __global__ __launch_bounds__(RX_THREADS) void k_cheb_resident(RxArgs a) {
     const int32_t win = (int32_t)(xcd * per_xcd + (blockIdx.x >> 3));  // every XCD owns one contiguous run of windows
     const int tid = threadIdx.x;
     const int lane = tid & (PF_WAVE - 1);
-    const int wave = tid >> 6;
-    (void)wave;  // (the stamps of the diagnostic build)
 
     // slot q of this wave is graph gq(q); its row of that graph's window is rt[q] (+ w * RX_THREADS)
     const int half = SW ? __builtin_amdgcn_readfirstlane(tid >> 9) : 0;
@@ -388,17 +364,8 @@ __global__ __launch_bounds__(RX_THREADS) void k_cheb_resident(RxArgs a) {
     bool early = (rt[0] & ~(PF_WAVE - 1)) < need_r[0];  // this wave owns boundary rows (its w = 0 rows)
     if (NG > 1) early = early || (rt[NG - 1] & ~(PF_WAVE - 1)) < need_r[NG - 1];
     int cur = 0;
-#ifdef RX_EXP_STAMPS
-    __shared__ unsigned s_st[16][10];
-    if (lane < 10) s_st[wave][lane] = 0;
-    unsigned st_prev = (unsigned)__builtin_amdgcn_s_memtime(), st_top = 0;
-#endif
 
     for (int32_t k = 1; k <= n_steps; ++k) {
-        RX_STAMP(5);  // loop overhead (state check, branch)
-#ifdef RX_EXP_STAMPS
-        st_top = st_prev;
-#endif
         if (early) __builtin_amdgcn_s_setprio(3);
         const unsigned step_top = (unsigned)__builtin_amdgcn_s_memrealtime();
         // (threads with four rows: the row number is "new" in every step, so that the compiler forms a row's LDS and memory
@@ -422,11 +389,7 @@ __global__ __launch_bounds__(RX_THREADS) void k_cheb_resident(RxArgs a) {
                 const int32_t wd = width[q][w];
                 const double xi = xc[q][w];  // the row's own x: last step's result, still in its register
                 double acc = rx_row_dispatch<JR>(__builtin_amdgcn_readfirstlane(wd < JR ? wd : JR), x, dg[q][w], xi, v[q][w], slp[q][w]);
-#ifndef RX_OV_PAIRS
-#define RX_OV_PAIRS 1
-#endif
                 int j = JR;
-#if RX_OV_PAIRS
                 for (; j + 1 < wd; j += 2) {  // (two entries' value, slot and x reads in flight together; fmas in entry order)
                     const int32_t o = ovoff[q][w] + (j - JR) * PF_WAVE + lane;
                     const double a0 = ov_val[o], a1 = ov_val[o + PF_WAVE];
@@ -435,7 +398,6 @@ __global__ __launch_bounds__(RX_THREADS) void k_cheb_resident(RxArgs a) {
                     acc = __builtin_fma(a0, x0, acc);
                     acc = __builtin_fma(a1, x1, acc);
                 }
-#endif
                 for (; j < wd; ++j) {
                     const int32_t o = ovoff[q][w] + (j - JR) * PF_WAVE + lane;
                     acc = __builtin_fma(ov_val[o], x[ov_slot[o]], acc);
@@ -460,12 +422,10 @@ __global__ __launch_bounds__(RX_THREADS) void k_cheb_resident(RxArgs a) {
                                            (unsigned long long)__double_as_longlong(res), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     __hip_atomic_store(ring + (int64_t)((k + 2 + g.phase) & 3) * g.n_pad + row, RX_EMPTY, __ATOMIC_RELAXED,
                                        __HIP_MEMORY_SCOPE_AGENT);
-                    RX_MARK(6 + q);  // hand-off of graph q issued
                 }
             }
             if (w == 0 && early) __builtin_amdgcn_s_setprio(0);
         }
-        RX_STAMP(0);  // rows computed, hand-off stores issued
         if (k == n_steps) break;
         // ---- the outside values of step k, straight from their owners' stores.  The owners stored them about when this
         // block stored its own, and an agent-scope store takes ~0.5 us to land: a poll issued at once would just miss it
@@ -488,7 +448,6 @@ __global__ __launch_bounds__(RX_THREADS) void k_cheb_resident(RxArgs a) {
                     __builtin_amdgcn_s_sleep(RX_HOLD);  // (every wave that fetches, once)
                 }
                 slept = true;
-                RX_STAMP(1);  // hold-back
                 const unsigned long long* p =
                     reinterpret_cast<const unsigned long long*>(g.ring) + (int64_t)((k + g.phase) & 3) * g.n_pad + ghrow[q];
                 unsigned long long bits;
@@ -504,19 +463,10 @@ __global__ __launch_bounds__(RX_THREADS) void k_cheb_resident(RxArgs a) {
                     __builtin_amdgcn_s_sleep(1);
                 }
                 xb[q][(size_t)(cur ^ 1) * xlen[q] + RB + gh_lane[q]] = __longlong_as_double((long long)bits);
-#ifdef RX_EXP_STAMPS
-                if (lane == 0) {
-                    s_st[wave][8] += spins;                          // repeats of the wave's first lane
-                }
-                if (__ballot(spins > 0) != 0 && lane == 0) s_st[wave][9] += 1;  // steps in which some lane had to repeat
-#endif
             }
         }
-        RX_STAMP(2);  // polls returned (first tries and repeats)
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's hand-offs and EMPTY stores are in memory (see header)
-        RX_STAMP(3);  // own stores drained
         __syncthreads();
-        RX_STAMP(4);  // barrier
         if (s_state != 0) {
             if (tid == 0) *a.host_abort = 1;
             return;
@@ -532,18 +482,7 @@ __global__ __launch_bounds__(RX_THREADS) void k_cheb_resident(RxArgs a) {
             __hip_atomic_store(a.report + 1, a.report_id, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
         }
     }
-#ifdef RX_EXP_STAMPS
-    if (lane == 0 && blockIdx.x < 256)
-        for (int i = 0; i < 10; ++i) g_rx_stamps[((size_t)blockIdx.x * 16 + wave) * 10 + i] = s_st[wave][i];
-#endif
 }
-
-#ifdef RX_EXP_STAMPS
-extern "C" int pf_persist_stamps(unsigned long long* out /* [256][16][10] */) {
-    PF_HIP(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_rx_stamps), sizeof(unsigned long long) * 256 * 16 * 10));
-    return PF_OK;
-}
-#endif
 
 // ---------------------------------------------------------------------------------------------------------------
 // Two recurrence steps per exchange (k_cheb_resident2).
@@ -587,32 +526,22 @@ struct Rx2Graph {
 };
 
 struct Rx2Args {
-    Rx2Graph g[2];
+    Rx2Graph g;
     uint32_t* abort_flag;
     int32_t* host_abort;
     unsigned long long* clock;  // as RxArgs::clock
-    int32_t hold;  // first fetch of a round not before this many 10 ns ticks after its phase B began; 0: a fixed s_sleep
 };
 
-#ifndef RX2_JR_PAIR
-#define RX2_JR_PAIR 8  // entries of a row kept in registers when a thread holds a row of each of two graphs
-#endif
-#define RX2_JR(ng) ((ng) == 2 ? RX2_JR_PAIR : 8)
 #ifndef RX2_GB
 #define RX2_GB 4  // entries of a ring-1 row whose LDS reads are in flight together
 #endif
 #ifndef RX2_HOLD1
-#define RX2_HOLD1 16  // one graph: first poll of a round held back by this many x 64 cycles
-#endif
-#ifndef RX2_HOLD2
-#define RX2_HOLD2 8   // two graphs: the same for the lower half's waves (they have just published; the upper half's arrive late anyway)
+#define RX2_HOLD1 16  // first poll of a round held back by this many x 64 cycles
 #endif
 
-template <int NG>
 __global__ __launch_bounds__(RX_THREADS) void k_cheb_resident2(Rx2Args a) {
 #pragma clang fp contract(off)
-    constexpr int JR = RX2_JR(NG), RB = RX_THREADS, NW = 1;
-    constexpr int PH = RX_THREADS / NG;  // threads that look after one graph's outside rows (NG == 2: the halves of the block)
+    constexpr int JR = 8, RB = RX_THREADS, PH = RX_THREADS;
     extern __shared__ __align__(16) unsigned char lds[];
     __shared__ int s_state;
     __shared__ unsigned long long s_began;
@@ -623,66 +552,50 @@ __global__ __launch_bounds__(RX_THREADS) void k_cheb_resident2(Rx2Args a) {
     const int tid = threadIdx.x;
     const int lane = tid & (PF_WAVE - 1);
     const int wave = tid >> 6;
-    const int qg = NG == 2 ? (tid >= PH ? 1 : 0) : 0;  // (wave-uniform) the graph whose outside rows this thread serves
-    const int lt = tid - qg * PH;
+    const Rx2Graph& g = a.g;
 
-    bool have[NG];
-    int32_t g1n[NG], gall[NG], need_r[NG], gwid[NG], g1p[NG], o0[NG], o1[NG];
-    int64_t row0[NG];
-    double *gval[NG], *gdiag[NG];
-    uint4* gslot8[NG];
-    unsigned short* gslotx[NG];
-    int32_t* glist[NG];
-    double v[NG][JR];
-    unsigned slp[NG][JR / 2];
-    double dg[NG], xc[NG];
-    int32_t width[NG], ovoff[NG];
-    int64_t sbase[NG];
+    double v[JR];
+    unsigned slp[JR / 2];
 
     int32_t* ovtab = reinterpret_cast<int32_t*>(lds);
-    size_t off = rx_table_bytes<NG, NW>();
-#pragma unroll
-    for (int q = 0; q < NG; ++q) {
-        const Rx2Graph& g = a.g[q];
-        have[q] = win < g.n_windows;
-        const int32_t wq = have[q] ? win : 0;
-        g1n[q] = have[q] ? g.gh_cnt[wq] : 0;
-        gall[q] = g1n[q] + (have[q] ? g.gh_cnt2[wq] : 0);
-        need_r[q] = have[q] ? ((g.need2[wq] + PF_WAVE - 1) & ~(PF_WAVE - 1)) : 0;
-        gwid[q] = have[q] ? g.g1_gw[wq] : 0;
-        g1p[q] = (g1n[q] + PF_WAVE - 1) & ~(PF_WAVE - 1);
-        row0[q] = (int64_t)wq * RB;
-        o0[q] = (int32_t)off;  // buffer 0: own | ring 1 | ring 2
-        off += have[q] ? (size_t)(RB + ((gall[q] + 1) & ~1)) * sizeof(double) : 0;
-        o1[q] = (int32_t)off;  // buffer 1: own | ring 1
-        off += have[q] ? (size_t)(RB + ((g1n[q] + 1) & ~1)) * sizeof(double) : 0;
-        gslot8[q] = reinterpret_cast<uint4*>(lds + off);  // (16-byte aligned: everything before it is a multiple of 16)
-        off += (size_t)g1p[q] * sizeof(uint4);
-        gval[q] = reinterpret_cast<double*>(lds + off);
-        off += (size_t)gwid[q] * g1p[q] * sizeof(double);
-        gdiag[q] = reinterpret_cast<double*>(lds + off);
-        off += (size_t)g1p[q] * sizeof(double);
-        glist[q] = reinterpret_cast<int32_t*>(lds + off);
-        off += (size_t)((gall[q] + 3) & ~3) * sizeof(int32_t);
-        gslotx[q] = reinterpret_cast<unsigned short*>(lds + off);
-        off += (size_t)(gwid[q] > 8 ? gwid[q] - 8 : 0) * g1p[q] * sizeof(unsigned short);
-        const int64_t row = row0[q] + tid;
-        const int64_t s = row >> 6;
-        sbase[q] = g.slice_ptr[s];
-        width[q] = __builtin_amdgcn_readfirstlane(have[q] ? (int32_t)((g.slice_ptr[s + 1] - sbase[q]) >> 6) : 0);
-        dg[q] = have[q] ? g.diag[row] : 0.0;
-        if (lane == 0) ovtab[q * 16 + wave] = width[q] > JR ? (width[q] - JR) * PF_WAVE : 0;
-    }
+    size_t off = rx_table_bytes<1, 1>();
+    const bool have = win < g.n_windows;
+    const int32_t wq = have ? win : 0;
+    const int32_t g1n = have ? g.gh_cnt[wq] : 0;
+    const int32_t gall = g1n + (have ? g.gh_cnt2[wq] : 0);
+    const int32_t need_r = have ? ((g.need2[wq] + PF_WAVE - 1) & ~(PF_WAVE - 1)) : 0;
+    const int32_t gwid = have ? g.g1_gw[wq] : 0;
+    const int32_t g1p = (g1n + PF_WAVE - 1) & ~(PF_WAVE - 1);
+    const int64_t row0 = (int64_t)wq * RB;
+    const int32_t o0 = (int32_t)off;  // buffer 0: own | ring 1 | ring 2
+    off += have ? (size_t)(RB + ((gall + 1) & ~1)) * sizeof(double) : 0;
+    const int32_t o1 = (int32_t)off;  // buffer 1: own | ring 1
+    off += have ? (size_t)(RB + ((g1n + 1) & ~1)) * sizeof(double) : 0;
+    uint4* gslot8 = reinterpret_cast<uint4*>(lds + off);  // (16-byte aligned: everything before it is a multiple of 16)
+    off += (size_t)g1p * sizeof(uint4);
+    double* gval = reinterpret_cast<double*>(lds + off);
+    off += (size_t)gwid * g1p * sizeof(double);
+    double* gdiag = reinterpret_cast<double*>(lds + off);
+    off += (size_t)g1p * sizeof(double);
+    int32_t* glist = reinterpret_cast<int32_t*>(lds + off);
+    off += (size_t)((gall + 3) & ~3) * sizeof(int32_t);
+    unsigned short* gslotx = reinterpret_cast<unsigned short*>(lds + off);
+    off += (size_t)(gwid > 8 ? gwid - 8 : 0) * g1p * sizeof(unsigned short);
+    const int64_t s = (row0 + tid) >> 6;
+    const int64_t sbase = g.slice_ptr[s];
+    const int32_t width = __builtin_amdgcn_readfirstlane(have ? (int32_t)((g.slice_ptr[s + 1] - sbase) >> 6) : 0);
+    const double dg = have ? g.diag[row0 + tid] : 0.0;
+    if (lane == 0) ovtab[wave] = width > JR ? (width - JR) * PF_WAVE : 0;
     if (tid == 0) s_state = (int)__hip_atomic_load(a.abort_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __syncthreads();
     if (tid == 0) {
         int32_t run = 0;
-        for (int i = 0; i < NG * 16; ++i) {
+        for (int i = 0; i < 16; ++i) {
             const int32_t c = ovtab[i];
             ovtab[i] = run;
             run += c;
         }
-        ovtab[NG * 16] = run;
+        ovtab[16] = run;
     }
     __syncthreads();
     if (s_state != 0) {
@@ -690,16 +603,15 @@ __global__ __launch_bounds__(RX_THREADS) void k_cheb_resident2(Rx2Args a) {
         return;
     }
     double* ov_val = reinterpret_cast<double*>(lds + off);
-    unsigned short* ov_slot = reinterpret_cast<unsigned short*>(lds + off + (size_t)ovtab[NG * 16] * sizeof(double));
+    unsigned short* ov_slot = reinterpret_cast<unsigned short*>(lds + off + (size_t)ovtab[16] * sizeof(double));
 
     // ---- own rows: entries into registers (beyond JR per row: LDS), y_0 into buffer 0
-#pragma unroll
-    for (int q = 0; q < NG; ++q) {
-        const Rx2Graph& g = a.g[q];
-        const int32_t wd = width[q];
+    const int32_t ovoff = __builtin_amdgcn_readfirstlane(ovtab[wave]);
+    double xc;
+    {
+        const int32_t wd = width;
         const int32_t pairs = wd >> 1;
-        const int64_t base = sbase[q];
-        ovoff[q] = __builtin_amdgcn_readfirstlane(ovtab[q * 16 + wave]);
+        const int64_t base = sbase;
 #pragma unroll
         for (int p = 0; p < JR / 2; ++p) {
             double2 vv = make_double2(0.0, 0.0);
@@ -708,9 +620,9 @@ __global__ __launch_bounds__(RX_THREADS) void k_cheb_resident2(Rx2Args a) {
                 vv = *reinterpret_cast<const double2*>(g.sval + base + (int64_t)p * (2 * PF_WAVE) + 2 * lane);
                 ss = *reinterpret_cast<const int2*>(g.slot + base + (int64_t)p * (2 * PF_WAVE) + 2 * lane);
             }
-            v[q][2 * p] = vv.x;
-            v[q][2 * p + 1] = vv.y;
-            slp[q][p] = (unsigned)ss.x | ((unsigned)ss.y << 16);
+            v[2 * p] = vv.x;
+            v[2 * p + 1] = vv.y;
+            slp[p] = (unsigned)ss.x | ((unsigned)ss.y << 16);
         }
         if (wd & 1) {
             const int64_t idx = base + (int64_t)pairs * (2 * PF_WAVE) + lane;
@@ -720,11 +632,11 @@ __global__ __launch_bounds__(RX_THREADS) void k_cheb_resident2(Rx2Args a) {
 #pragma unroll
                 for (int p = 0; p < JR / 2; ++p)
                     if (2 * p == wd - 1) {
-                        v[q][2 * p] = tv;
-                        slp[q][p] = ts;
+                        v[2 * p] = tv;
+                        slp[p] = ts;
                     }
             } else {
-                const int32_t o = ovoff[q] + (wd - 1 - JR) * PF_WAVE + lane;
+                const int32_t o = ovoff + (wd - 1 - JR) * PF_WAVE + lane;
                 ov_val[o] = tv;
                 ov_slot[o] = (unsigned short)ts;
             }
@@ -733,81 +645,73 @@ __global__ __launch_bounds__(RX_THREADS) void k_cheb_resident2(Rx2Args a) {
             const int64_t idx = base + (int64_t)p * (2 * PF_WAVE) + 2 * lane;
             const double2 vv = *reinterpret_cast<const double2*>(g.sval + idx);
             const int2 ss = *reinterpret_cast<const int2*>(g.slot + idx);
-            const int32_t o = ovoff[q] + (2 * p - JR) * PF_WAVE + lane;
+            const int32_t o = ovoff + (2 * p - JR) * PF_WAVE + lane;
             ov_val[o] = vv.x;
             ov_slot[o] = (unsigned short)ss.x;
             ov_val[o + PF_WAVE] = vv.y;
             ov_slot[o + PF_WAVE] = (unsigned short)ss.y;
         }
-        xc[q] = have[q] ? g.src[row0[q] + tid] : 0.0;
-        if (have[q]) reinterpret_cast<double*>(lds + o0[q])[tid] = xc[q];
+        xc = have ? g.src[row0 + tid] : 0.0;
+        if (have) reinterpret_cast<double*>(lds + o0)[tid] = xc;
     }
-    // ---- outside rows this thread serves: it fetches rows lt and lt + PH of graph qg's list and repeats the recurrence of
-    // ring-1 row lt.  That row's entries live in LDS (values entry-major, the first eight slots as one 16-byte record),
+    // ---- outside rows this thread serves: it fetches rows tid and tid + PH of the list and repeats the recurrence of
+    // ring-1 row tid.  That row's entries live in LDS (values entry-major, the first eight slots as one 16-byte record),
     // as do its diagonal and the list; its two latest values are the row's places in the two buffers.
     int32_t gwi = 0;
     bool gf0 = false, gf1 = false, grow = false;
-#pragma unroll
-    for (int q = 0; q < NG; ++q) {
-        if (qg != q || !have[q]) continue;  // (wave-uniform)
-        const Rx2Graph& g = a.g[q];
-        double* b0 = reinterpret_cast<double*>(lds + o0[q]);
+    if (have) {  // (block-uniform)
+        double* b0 = reinterpret_cast<double*>(lds + o0);
         const int64_t lbase = (int64_t)win * PF_WIN_GHOSTS;
-        gf0 = lt < gall[q];
-        gf1 = lt + PH < gall[q];
-        grow = lt < g1n[q];
+        gf0 = tid < gall;
+        gf1 = tid + PH < gall;
+        grow = tid < g1n;
         if (gf0) {
-            const int32_t r0 = g.gh_row[lbase + lt];
-            glist[q][lt] = r0;
-            b0[RB + lt] = g.src[r0];
+            const int32_t r0 = g.gh_row[lbase + tid];
+            glist[tid] = r0;
+            b0[RB + tid] = g.src[r0];
             if (grow) {
-                gwi = g.g1_w[(int64_t)win * PF_WIN_G1 + lt];
-                gdiag[q][lt] = g.diag[r0];
+                gwi = g.g1_w[(int64_t)win * PF_WIN_G1 + tid];
+                gdiag[tid] = g.diag[r0];
                 unsigned sl[8];
 #pragma unroll
                 for (int j = 0; j < 8; ++j) sl[j] = 0u;
                 for (int32_t j = 0; j < gwi; ++j) {
-                    const int64_t o = ((int64_t)win * PF_WIN_GW + j) * PF_WIN_G1 + lt;
-                    gval[q][j * g1p[q] + lt] = g.sval[g.g1_pos[o]];
+                    const int64_t o = ((int64_t)win * PF_WIN_GW + j) * PF_WIN_G1 + tid;
+                    gval[j * g1p + tid] = g.sval[g.g1_pos[o]];
                     const unsigned sj = g.g1_slot[o];
-                    if (j >= 8) gslotx[q][(j - 8) * g1p[q] + lt] = (unsigned short)sj;
+                    if (j >= 8) gslotx[(j - 8) * g1p + tid] = (unsigned short)sj;
 #pragma unroll
                     for (int jj = 0; jj < 8; ++jj)
                         if (jj == j) sl[jj] = sj;
                 }
-                gslot8[q][lt] = make_uint4(sl[0] | (sl[1] << 16), sl[2] | (sl[3] << 16), sl[4] | (sl[5] << 16), sl[6] | (sl[7] << 16));
+                gslot8[tid] = make_uint4(sl[0] | (sl[1] << 16), sl[2] | (sl[3] << 16), sl[4] | (sl[5] << 16), sl[6] | (sl[7] << 16));
             }
         }
         if (gf1) {
-            const int32_t r1 = g.gh_row[lbase + lt + PH];
-            glist[q][lt + PH] = r1;
-            b0[RB + lt + PH] = g.src[r1];
+            const int32_t r1 = g.gh_row[lbase + tid + PH];
+            glist[tid + PH] = r1;
+            b0[RB + tid + PH] = g.src[r1];
         }
     }
     __syncthreads();
 
-    int32_t n_steps = a.g[0].degree;
-    if (NG > 1 && a.g[1].degree > n_steps) n_steps = a.g[1].degree;
-    const int32_t rounds = (n_steps + 1) >> 1;
-    int32_t need_max = need_r[0];
-    if (NG > 1 && need_r[1] > need_max) need_max = need_r[1];
-    const bool early = (tid & ~(PF_WAVE - 1)) < need_max;
+    const int32_t rounds = (g.degree + 1) >> 1;
+    const bool early = (tid & ~(PF_WAVE - 1)) < need_r;
 
-    // one step of this thread's row of graph q: gathers from the buffer at LDS offset xo, y_{k-2} is what the target
-    // buffer still holds at the row's place.  (The buffer's address is hidden from the optimiser once per phase: with two
-    // fixed buffers it would keep both sets of gather addresses in registers across the loop and spill the entries.)
-    auto own_step = [&](int q, int32_t xo_in, int32_t yo_in, bool first) -> double {
-        const Rx2Graph& g = a.g[q];
+    // one step of this thread's row: gathers from the buffer at LDS offset xo, y_{k-2} is what the target buffer still
+    // holds at the row's place.  (The buffer's address is hidden from the optimiser once per phase: with two fixed
+    // buffers it would keep both sets of gather addresses in registers across the loop and spill the entries.)
+    auto own_step = [&](int32_t xo_in, int32_t yo_in, bool first) -> double {
         int32_t xo = xo_in, yo = yo_in;
         asm volatile("" : "+s"(xo), "+s"(yo));
         const double* x = reinterpret_cast<const double*>(lds + xo);
         double* y = reinterpret_cast<double*>(lds + yo);
-        const int32_t wd = width[q];
-        const double xi = xc[q];
+        const int32_t wd = width;
+        const double xi = xc;
         const double prev = y[tid];
-        double acc = rx_row_dispatch<JR>(wd < JR ? wd : JR, x, dg[q], xi, v[q], slp[q]);
+        double acc = rx_row_dispatch<JR>(wd < JR ? wd : JR, x, dg, xi, v, slp);
         for (int j = JR; j < wd; ++j) {
-            const int32_t o = ovoff[q] + (j - JR) * PF_WAVE + lane;
+            const int32_t o = ovoff + (j - JR) * PF_WAVE + lane;
             acc = __builtin_fma(ov_val[o], x[ov_slot[o]], acc);
         }
         const double u = __builtin_fma(g.shift, xi, -acc);
@@ -818,7 +722,7 @@ __global__ __launch_bounds__(RX_THREADS) void k_cheb_resident2(Rx2Args a) {
             const double wp = g.beta * prev;
             res = __builtin_fma(g.a2, u, -wp);
         }
-        xc[q] = res;
+        xc = res;
         y[tid] = res;
         return res;
     };
@@ -827,71 +731,59 @@ __global__ __launch_bounds__(RX_THREADS) void k_cheb_resident2(Rx2Args a) {
         const int32_t kA = 2 * r - 1, kB = 2 * r;
         // ---- phase A: step kA of ring 1 and of the own rows, buffer 0 -> buffer 1.  The ring-1 rows come first: their reads
         // are two dependent LDS round trips (slots, then x), which the waves without such rows cover with their own rows
+        if (have && kA < g.degree && grow) {  // ring 1 only if a phase B follows
+            int32_t xo = o0, yo = o1;
+            asm volatile("" : "+s"(xo), "+s"(yo));
+            const double* x = reinterpret_cast<const double*>(lds + xo);
+            double* y = reinterpret_cast<double*>(lds + yo);
+            int32_t ld = g1p;
+            asm volatile("" : "+s"(ld));  // (entry addresses formed here, not kept in registers across the rounds)
+            const double* gv = gval + tid;
+            const uint4 gsl = gslot8[tid];
+            const double gx = x[RB + tid];
+            const double gprev = y[RB + tid];
+            const unsigned sw[4] = {gsl.x, gsl.y, gsl.z, gsl.w};
+            double acc = gdiag[tid] * gx;
 #pragma unroll
-        for (int q = 0; q < NG; ++q) {
-            const Rx2Graph& g = a.g[q];
-            if (qg != q || !have[q] || kA >= g.degree) continue;  // (wave-uniform) ring 1 only if a phase B follows
-            if (grow) {
-                int32_t xo = o0[q], yo = o1[q];
-                asm volatile("" : "+s"(xo), "+s"(yo));
-                const double* x = reinterpret_cast<const double*>(lds + xo);
-                double* y = reinterpret_cast<double*>(lds + yo);
-                int32_t ld = g1p[q];
-                asm volatile("" : "+s"(ld));  // (entry addresses formed here, not kept in registers across the rounds)
-                const double* gv = gval[q] + lt;
-                const uint4 gsl = gslot8[q][lt];
-                const double gx = x[RB + lt];
-                const double gprev = y[RB + lt];
-                const unsigned sw[4] = {gsl.x, gsl.y, gsl.z, gsl.w};
-                double acc = gdiag[q][lt] * gx;
+            for (int h = 0; h < 8; h += RX2_GB) {  // RX2_GB entries' reads in flight together (unused places read slot 0 / entry 0)
+                double xs[RX2_GB], vs[RX2_GB];
 #pragma unroll
-                for (int h = 0; h < 8; h += RX2_GB) {  // RX2_GB entries' reads in flight together (unused places read slot 0 / entry 0)
-                    double xs[RX2_GB], vs[RX2_GB];
-#pragma unroll
-                    for (int j = 0; j < RX2_GB; ++j) {
-                        xs[j] = x[((h + j) & 1) ? (sw[(h + j) >> 1] >> 16) : (sw[(h + j) >> 1] & 0xffffu)];
-                        vs[j] = gv[(h + j < gwi ? h + j : 0) * ld];
-                    }
-#pragma unroll
-                    for (int j = 0; j < RX2_GB; ++j)
-                        if (h + j < gwi) acc = __builtin_fma(vs[j], xs[j], acc);
+                for (int j = 0; j < RX2_GB; ++j) {
+                    xs[j] = x[((h + j) & 1) ? (sw[(h + j) >> 1] >> 16) : (sw[(h + j) >> 1] & 0xffffu)];
+                    vs[j] = gv[(h + j < gwi ? h + j : 0) * ld];
                 }
-                for (int32_t j = 8; j < gwi; ++j) acc = __builtin_fma(gv[j * ld], x[gslotx[q][(j - 8) * ld + lt]], acc);
-                const double u = __builtin_fma(g.shift, gx, -acc);
-                double res;
-                if (kA == 1) {
-                    res = g.a1 * u;
-                } else {
-                    const double wp = g.beta * gprev;
-                    res = __builtin_fma(g.a2, u, -wp);
-                }
-                y[RB + lt] = res;
+#pragma unroll
+                for (int j = 0; j < RX2_GB; ++j)
+                    if (h + j < gwi) acc = __builtin_fma(vs[j], xs[j], acc);
             }
+            for (int32_t j = 8; j < gwi; ++j) acc = __builtin_fma(gv[j * ld], x[gslotx[(j - 8) * ld + tid]], acc);
+            const double u = __builtin_fma(g.shift, gx, -acc);
+            double res;
+            if (kA == 1) {
+                res = g.a1 * u;
+            } else {
+                const double wp = g.beta * gprev;
+                res = __builtin_fma(g.a2, u, -wp);
+            }
+            y[RB + tid] = res;
         }
-#pragma unroll
-        for (int q = 0; q < NG; ++q) {
-            const Rx2Graph& g = a.g[q];
-            if (!have[q] || kA > g.degree) continue;  // (block-uniform)
-            const double res = own_step(q, o0[q], o1[q], kA == 1);
+        if (have && kA <= g.degree) {  // (block-uniform)
+            const double res = own_step(o0, o1, kA == 1);
             if (kA == g.degree) {  // an odd degree ends here
-                (g.dst + row0[q])[tid] = res;
-                if (tid < need_r[q])
-                    __hip_atomic_store(reinterpret_cast<unsigned long long*>(g.ring) + ((int64_t)((r + 2 + g.phase) & 3) * g.n_pad + row0[q]) + tid,
+                (g.dst + row0)[tid] = res;
+                if (tid < need_r)
+                    __hip_atomic_store(reinterpret_cast<unsigned long long*>(g.ring) + ((int64_t)((r + 2 + g.phase) & 3) * g.n_pad + row0) + tid,
                                        RX_EMPTY, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
         }
         __syncthreads();
         // ---- phase B: step kB of the own rows, buffer 1 -> buffer 0; leading rows published first
-        const unsigned b_top = (unsigned)__builtin_amdgcn_s_memrealtime();
         if (early) __builtin_amdgcn_s_setprio(3);
-#pragma unroll
-        for (int q = 0; q < NG; ++q) {
-            const Rx2Graph& g = a.g[q];
-            if (!have[q] || kB > g.degree) continue;  // (block-uniform)
-            const double res = own_step(q, o1[q], o0[q], false);
-            if (kB == g.degree) (g.dst + row0[q])[tid] = res;
-            if (tid < need_r[q]) {  // (wave-uniform)
-                unsigned long long* ring = reinterpret_cast<unsigned long long*>(g.ring) + row0[q];  // (uniform bases + the thread's index)
+        if (have && kB <= g.degree) {  // (block-uniform)
+            const double res = own_step(o1, o0, false);
+            if (kB == g.degree) (g.dst + row0)[tid] = res;
+            if (tid < need_r) {  // (wave-uniform)
+                unsigned long long* ring = reinterpret_cast<unsigned long long*>(g.ring) + row0;  // (uniform bases + the thread's index)
                 if (kB < g.degree)
                     __hip_atomic_store(ring + (int64_t)((r + g.phase) & 3) * g.n_pad + tid, (unsigned long long)__double_as_longlong(res),
                                        __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -902,41 +794,30 @@ __global__ __launch_bounds__(RX_THREADS) void k_cheb_resident2(Rx2Args a) {
         if (early) __builtin_amdgcn_s_setprio(0);
         if (r == rounds) break;
         // ---- rings 1 and 2 of step kB, straight from their owners' stores (two per thread in flight)
-#pragma unroll
-        for (int q = 0; q < NG; ++q) {
-            const Rx2Graph& g = a.g[q];
-            if (qg != q || !have[q] || kB >= g.degree) continue;  // (wave-uniform)
-            if (gf0) {
-                if (a.hold > 0) {
-                    while ((int)((unsigned)a.hold - ((unsigned)__builtin_amdgcn_s_memrealtime() - b_top)) > 6) __builtin_amdgcn_s_sleep(1);
-                    while ((unsigned)__builtin_amdgcn_s_memrealtime() - b_top < (unsigned)a.hold) {
-                    }
-                } else if (q == 0 && (NG == 1 ? RX2_HOLD1 : RX2_HOLD2) > 0) {
-                    __builtin_amdgcn_s_sleep(NG == 1 ? RX2_HOLD1 : RX2_HOLD2);
+        if (have && kB < g.degree && gf0) {  // (wave-uniform)
+            if (RX2_HOLD1 > 0) __builtin_amdgcn_s_sleep(RX2_HOLD1);
+            const unsigned long long* p0 = reinterpret_cast<const unsigned long long*>(g.ring) + (int64_t)((r + g.phase) & 3) * g.n_pad;
+            const int32_t ghr0 = glist[tid];
+            const unsigned long long* p1 = p0 + (gf1 ? glist[tid + PH] : ghr0);
+            p0 += ghr0;
+            unsigned long long v0 = __hip_atomic_load(p0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            unsigned long long v1 = __hip_atomic_load(p1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            unsigned spins = 0;
+            while (v0 == RX_EMPTY || v1 == RX_EMPTY) {
+                ++spins;
+                if (spins > RX_SPIN_LIMIT ||
+                    ((spins & 63u) == 0u && __hip_atomic_load(a.abort_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u)) {
+                    __hip_atomic_store(a.abort_flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    s_state = 1;
+                    break;
                 }
-                const unsigned long long* p0 = reinterpret_cast<const unsigned long long*>(g.ring) + (int64_t)((r + g.phase) & 3) * g.n_pad;
-                const int32_t ghr0 = glist[q][lt];
-                const unsigned long long* p1 = p0 + (gf1 ? glist[q][lt + PH] : ghr0);
-                p0 += ghr0;
-                unsigned long long v0 = __hip_atomic_load(p0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                unsigned long long v1 = __hip_atomic_load(p1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                unsigned spins = 0;
-                while (v0 == RX_EMPTY || v1 == RX_EMPTY) {
-                    ++spins;
-                    if (spins > RX_SPIN_LIMIT ||
-                        ((spins & 63u) == 0u && __hip_atomic_load(a.abort_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u)) {
-                        __hip_atomic_store(a.abort_flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        s_state = 1;
-                        break;
-                    }
-                    __builtin_amdgcn_s_sleep(1);
-                    if (v0 == RX_EMPTY) v0 = __hip_atomic_load(p0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    if (v1 == RX_EMPTY) v1 = __hip_atomic_load(p1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
-                double* b0 = reinterpret_cast<double*>(lds + o0[q]);
-                b0[RB + lt] = __longlong_as_double((long long)v0);
-                if (gf1) b0[RB + lt + PH] = __longlong_as_double((long long)v1);
+                __builtin_amdgcn_s_sleep(1);
+                if (v0 == RX_EMPTY) v0 = __hip_atomic_load(p0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (v1 == RX_EMPTY) v1 = __hip_atomic_load(p1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
+            double* b0 = reinterpret_cast<double*>(lds + o0);
+            b0[RB + tid] = __longlong_as_double((long long)v0);
+            if (gf1) b0[RB + tid + PH] = __longlong_as_double((long long)v1);
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
@@ -1048,10 +929,9 @@ int device_grid(int device) {
                 return;
             }
         }
-        for (int ng = 1; ng <= 3; ++ng) {
-            const void* fn = ng == 1   ? reinterpret_cast<const void*>(k_cheb_resident2<1>)
-                             : ng == 2 ? reinterpret_cast<const void*>(k_cheb_resident2<2>)
-                                       : reinterpret_cast<const void*>(k_cheb_resident<2, 1, rx_jr(2, 1), true>);
+        const void* more[2] = {reinterpret_cast<const void*>(k_cheb_resident2),
+                               reinterpret_cast<const void*>(k_cheb_resident<2, 1, rx_jr(2, 1), true>)};
+        for (const void* fn : more) {
             int per_cu = 0;
             if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)RX_LDS_LIMIT) != hipSuccess ||
                 hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, RX_THREADS, RX_LDS_LIMIT) != hipSuccess || per_cu < 1) {
@@ -1064,47 +944,39 @@ int device_grid(int device) {
     return f.grid;
 }
 
-// -1 undecided (environment PF_PERSIST_S2 = 0 / 1 / 2), 0 off, 1 single-graph launches (default), 2 paired launches too.
-// Measured on MI355X at 250k rows (profiles/r03_two_step_ablation.md): one graph 1.41 -> 1.24 us per step; a pair 1.85 ->
-// 2.08: with two graphs per block the step is bound by LDS issue and vector ALU work, not by the hand-off, and the
-// repeated ring-1 rows (20 LDS reads each against 10 of an own row) cost more than the saved hand-off.
+// -1 undecided (environment PF_PERSIST_S2 = 0 / 1), 0 off, 1 single-graph launches (default).  Pairs always take one
+// step per exchange.  Measured on MI355X at 250k rows (profiles/r03_two_step_ablation.md): one graph 1.41 -> 1.24 us per
+// step; a pair 1.85 -> 2.08 (a paired form of the kernel, since removed): with two graphs per block the step is bound by
+// LDS issue and vector ALU work, not by the hand-off, and the repeated ring-1 rows (20 LDS reads each against 10 of an own
+// row) cost more than the saved hand-off.
 std::atomic<int> g_last_hold{0};  // the hold-back of the latest one-step resident launch (pf_persist_state)
 std::atomic<int> g_two_step{-1};
 int two_step_level() {
     int v = g_two_step.load();
     if (v < 0) {
         const char* e = getenv("PF_PERSIST_S2");
-        v = e ? (e[0] == '0' ? 0 : (e[0] == '2' ? 2 : 1)) : 1;
+        v = (e && e[0] == '0') ? 0 : 1;
         g_two_step.store(v);
     }
     return v;
 }
-bool two_step_enabled() { return two_step_level() >= 1; }
 
-// LDS bytes of the fullest window of k_cheb_resident2 (layout as in the kernel); -1 if the graph(s) cannot use it
-int64_t lds_need2(pf_graph* ga, pf_graph* gb) {
-    const int jr = RX2_JR(gb ? 2 : 1);
-    pf_graph* gs[2] = {ga, gb};
-    const int ng = gb ? 2 : 1;
+// LDS bytes of the fullest window of k_cheb_resident2 (layout as in the kernel); -1 if the graph cannot use it
+int64_t lds_need2(pf_graph* g) {
+    const int jr = 8;
     const int64_t RB = RX_THREADS;
-    const int64_t ph = RX_THREADS / ng;
-    const int64_t wa = ga->n_pad / RB, wb = gb ? gb->n_pad / RB : 0;
+    if (g->px2_state != 1 || g->win_rows != RB || g->h_slice_ptr.empty() || (int64_t)g->h_px_gh_cnt.size() * RB != g->n_pad) return -1;
     int64_t worst = 0;
-    for (int64_t w = 0; w < std::max(wa, wb); ++w) {
-        int64_t need = ((ng * 16 + 1) * 4 + 15) & ~15, ov = 0;
-        for (int q = 0; q < ng; ++q) {
-            pf_graph* g = gs[q];
-            if (g->px2_state != 1 || g->win_rows != RB || g->h_slice_ptr.empty() || (int64_t)g->h_px_gh_cnt.size() * RB != g->n_pad) return -1;
-            if (w >= g->n_pad / RB) continue;
-            const int64_t g1 = g->h_px_gh_cnt[(size_t)w], g2 = g->h_px_gh_cnt2[(size_t)w], gw = g->h_px_g1_gw[(size_t)w];
-            if (g1 > ph || g1 + g2 > 2 * ph) return -1;  // a thread repeats one ring-1 row and fetches two outside rows
-            const int64_t g1p = (g1 + PF_WAVE - 1) & ~(int64_t)(PF_WAVE - 1);
-            need += (RB + ((g1 + g2 + 1) & ~1)) * 8 + (RB + ((g1 + 1) & ~1)) * 8 + g1p * 16 + gw * g1p * 8 + g1p * 8 +
-                    ((g1 + g2 + 3) & ~3) * 4 + (gw > 8 ? gw - 8 : 0) * g1p * 2;
-            for (int64_t s = w * (RB / PF_WAVE); s < (w + 1) * (RB / PF_WAVE); ++s) {
-                const int64_t width = (g->h_slice_ptr[(size_t)s + 1] - g->h_slice_ptr[(size_t)s]) / PF_WAVE;
-                if (width > jr) ov += (width - jr) * PF_WAVE;
-            }
+    for (int64_t w = 0; w < g->n_pad / RB; ++w) {
+        int64_t need = ((16 + 1) * 4 + 15) & ~15, ov = 0;
+        const int64_t g1 = g->h_px_gh_cnt[(size_t)w], g2 = g->h_px_gh_cnt2[(size_t)w], gw = g->h_px_g1_gw[(size_t)w];
+        if (g1 > RB || g1 + g2 > 2 * RB) return -1;  // a thread repeats one ring-1 row and fetches two outside rows
+        const int64_t g1p = (g1 + PF_WAVE - 1) & ~(int64_t)(PF_WAVE - 1);
+        need += (RB + ((g1 + g2 + 1) & ~1)) * 8 + (RB + ((g1 + 1) & ~1)) * 8 + g1p * 16 + gw * g1p * 8 + g1p * 8 +
+                ((g1 + g2 + 3) & ~3) * 4 + (gw > 8 ? gw - 8 : 0) * g1p * 2;
+        for (int64_t s = w * (RB / PF_WAVE); s < (w + 1) * (RB / PF_WAVE); ++s) {
+            const int64_t width = (g->h_slice_ptr[(size_t)s + 1] - g->h_slice_ptr[(size_t)s]) / PF_WAVE;
+            if (width > jr) ov += (width - jr) * PF_WAVE;
         }
         need += ov * 10 + 16;
         worst = std::max(worst, need);
@@ -1112,77 +984,59 @@ int64_t lds_need2(pf_graph* ga, pf_graph* gb) {
     return worst;
 }
 
-// two steps per exchange, if both graphs and the sizes allow it: *done = 1 when launched
-// When a block first asks for the outside values of a round (see hold_ticks below): here for the two-step kernel, counted from the start of its phase B (environment PF_PERSIST_HOLD2)
-int hold_ticks2(int ng, int windows) {
-    if (const char* e = getenv("PF_PERSIST_HOLD2")) return atoi(e);
-    (void)ng;
-    (void)windows;
-    return 0;
-}
-
-int persist_cheb2(const pf_persist_args* a, const pf_persist_args* b, int64_t grid, int* done, double* lds_bytes) {
+// two steps per exchange for a single graph, if the graph and its sizes allow it: *done = 1 when launched
+int persist_cheb2(const pf_persist_args* a, int64_t grid, int* done, double* lds_bytes) {
     *done = 0;
-    pf_graph* ga = a->g;
-    pf_graph* gb = b ? b->g : nullptr;
-    pf_ctx* ctx = ga->ctx;
-    if (two_step_level() < (gb ? 2 : 1) || ga->win_rows != RX_THREADS) return PF_OK;
+    pf_graph* g = a->g;
+    pf_ctx* ctx = g->ctx;
+    if (two_step_level() < 1 || g->win_rows != RX_THREADS) return PF_OK;
     // the second-ring structures cost ~0.1 ms to build (a kernel and a read-back): a graph pays that at its THIRD
     // single-graph application, not for the one or two a paired solve leaves over when its partner converges first
-    if (!gb && ga->px2_state < 0 && ++ga->single_applications < 3) return PF_OK;
-    PF_TRY(pf_window_rings_prepare(ga));
-    if (gb) PF_TRY(pf_window_rings_prepare(gb));
-    if (ga->px2_state != 1 || (gb && gb->px2_state != 1)) return PF_OK;
-    if (ga->lds_need2_partner != (gb ? gb->uid : ga->uid) || ga->lds_need2_value == -2) {
-        ga->lds_need2_value = lds_need2(ga, gb);
-        ga->lds_need2_partner = gb ? gb->uid : ga->uid;
-    }
-    const int64_t need = ga->lds_need2_value;
+    if (g->px2_state < 0 && ++g->single_applications < 3) return PF_OK;
+    PF_TRY(pf_window_rings_prepare(g));
+    if (g->px2_state != 1) return PF_OK;
+    if (g->lds_need2_value == -2) g->lds_need2_value = lds_need2(g);
+    const int64_t need = g->lds_need2_value;
     if (need < 0 || (size_t)need > RX_LDS_LIMIT) return PF_OK;
     OwnerGuard own(ctx);
     if (!own.ok) return PF_OK;
     hipStream_t st = ctx->stream;
     PF_TRY(pf_persist_sync_ensure(ctx));
     const uint64_t epoch = g_abort_epoch.load();
-    const pf_persist_args* in[2] = {a, b};
-    const int ng = gb ? 2 : 1;
-    Rx2Args args{};
-    for (int q = 0; q < ng; ++q) {
-        pf_graph* g = in[q]->g;
-        if (!g->persist_ring2) {
-            PF_HIP(pf_malloc(st, (void**)&g->persist_ring2, sizeof(double) * 4 * (size_t)g->n_pad));
-            g->persist_epoch2 = 0;
-        }
-        if (g->persist_epoch2 != epoch) {
-            PF_HIP(hipMemsetD32Async((hipDeviceptr_t)g->persist_ring2, (int)RX_EMPTY32, (size_t)8 * (size_t)g->n_pad, st));
-            g->persist_epoch2 = epoch;
-            g->persist_phase2 = 0;
-        }
-        Rx2Graph& p = args.g[q];
-        p.slice_ptr = g->slice_ptr;
-        p.slot = g->px_slot;
-        p.gh_cnt = g->px_gh_cnt;
-        p.gh_cnt2 = g->px_gh_cnt2;
-        p.gh_row = g->px_gh_row;
-        p.need2 = g->px_need2;
-        p.g1_w = g->px_g1_w;
-        p.g1_pos = g->px_g1_pos;
-        p.g1_slot = g->px_g1_slot;
-        p.g1_gw = g->px_g1_gw;
-        p.sval = in[q]->vals;
-        p.diag = g->diag;
-        p.src = in[q]->src;
-        p.dst = in[q]->dst;
-        p.ring = g->persist_ring2;
-        p.n_pad = g->n_pad;
-        p.n_windows = (int32_t)(g->n_pad / g->win_rows);
-        p.degree = in[q]->degree;
-        p.phase = g->persist_phase2;
-        p.a1 = 1.0 / (in[q]->e * in[q]->rho);
-        p.a2 = 2.0 / (in[q]->e * in[q]->rho);
-        p.shift = in[q]->c;
-        p.beta = 1.0 / (in[q]->rho * in[q]->rho);
+    if (!g->persist_ring2) {
+        PF_HIP(pf_malloc(st, (void**)&g->persist_ring2, sizeof(double) * 4 * (size_t)g->n_pad));
+        g->persist_epoch2 = 0;
     }
+    if (g->persist_epoch2 != epoch) {
+        PF_HIP(hipMemsetD32Async((hipDeviceptr_t)g->persist_ring2, (int)RX_EMPTY32, (size_t)8 * (size_t)g->n_pad, st));
+        g->persist_epoch2 = epoch;
+        g->persist_phase2 = 0;
+    }
+    Rx2Args args{};
+    Rx2Graph& p = args.g;
+    p.slice_ptr = g->slice_ptr;
+    p.slot = g->px_slot;
+    p.gh_cnt = g->px_gh_cnt;
+    p.gh_cnt2 = g->px_gh_cnt2;
+    p.gh_row = g->px_gh_row;
+    p.need2 = g->px_need2;
+    p.g1_w = g->px_g1_w;
+    p.g1_pos = g->px_g1_pos;
+    p.g1_slot = g->px_g1_slot;
+    p.g1_gw = g->px_g1_gw;
+    p.sval = a->vals;
+    p.diag = g->diag;
+    p.src = a->src;
+    p.dst = a->dst;
+    p.ring = g->persist_ring2;
+    p.n_pad = g->n_pad;
+    p.n_windows = (int32_t)(g->n_pad / g->win_rows);
+    p.degree = a->degree;
+    p.phase = g->persist_phase2;
+    p.a1 = 1.0 / (a->e * a->rho);
+    p.a2 = 2.0 / (a->e * a->rho);
+    p.shift = a->c;
+    p.beta = 1.0 / (a->rho * a->rho);
     args.abort_flag = ctx->persist_sync;
     args.host_abort = ctx->persist_abort;
     args.clock = reinterpret_cast<unsigned long long*>(ctx->persist_sync + 8);
@@ -1190,9 +1044,7 @@ int persist_cheb2(const pf_persist_args* a, const pf_persist_args* b, int64_t gr
         g_test_aborts.fetch_sub(1);
         PF_HIP(hipMemsetAsync(ctx->persist_sync, 1, sizeof(uint32_t), st));
     }
-    args.hold = hold_ticks2(ng, (int)grid);
-    if (ng == 2) k_cheb_resident2<2><<<dim3((unsigned)grid), dim3(RX_THREADS), (size_t)need, st>>>(args);
-    else k_cheb_resident2<1><<<dim3((unsigned)grid), dim3(RX_THREADS), (size_t)need, st>>>(args);
+    k_cheb_resident2<<<dim3((unsigned)grid), dim3(RX_THREADS), (size_t)need, st>>>(args);
     const hipError_t err = hipGetLastError();
     if (err != hipSuccess) {
         g_two_step.store(0);  // one step per exchange from now on
@@ -1202,17 +1054,14 @@ int persist_cheb2(const pf_persist_args* a, const pf_persist_args* b, int64_t gr
     PF_TRY(persist_launched(ctx));
     g_launches.fetch_add(1);
     g_launches2.fetch_add(1);
-    for (int q = 0; q < ng; ++q) {
-        pf_graph* g = in[q]->g;
-        const int32_t d = in[q]->degree, rounds = (d + 1) / 2;
-        g->persist_phase2 = (g->persist_phase2 + rounds) & 3;
-        // LDS bytes: per step and own row the gathered x (8 per stored entry) and the result (8); per round the ring-1 rows'
-        // entries (value 8 + slot 2 + gathered x 8 each) and results (8), and the fetched rows of both rings (8)
-        if (lds_bytes)
-            *lds_bytes += (double)d * (8.0 * (double)g->sell_entries + 8.0 * (double)g->n_pad) +
-                          (double)(d / 2) * (18.0 * (double)g->px_g1_entries + 8.0 * (double)g->px_gh_total) +
-                          (double)((d - 1) / 2) * 8.0 * (double)(g->px_gh_total + g->px_gh2_total);
-    }
+    const int32_t d = a->degree, rounds = (d + 1) / 2;
+    g->persist_phase2 = (g->persist_phase2 + rounds) & 3;
+    // LDS bytes: per step and own row the gathered x (8 per stored entry) and the result (8); per round the ring-1 rows'
+    // entries (value 8 + slot 2 + gathered x 8 each) and results (8), and the fetched rows of both rings (8)
+    if (lds_bytes)
+        *lds_bytes += (double)d * (8.0 * (double)g->sell_entries + 8.0 * (double)g->n_pad) +
+                      (double)(d / 2) * (18.0 * (double)g->px_g1_entries + 8.0 * (double)g->px_gh_total) +
+                      (double)((d - 1) / 2) * 8.0 * (double)(g->px_gh_total + g->px_gh2_total);
     *done = 1;
     return PF_OK;
 }
@@ -1253,9 +1102,9 @@ int pf_persist_set(int on) {
 
 extern "C" int pf_persist_enable(int on) { return pf_persist_set(on); }
 
-// 1: two recurrence steps per exchange where a graph allows it (default), 0: one (k_cheb_resident)
+// 1: two recurrence steps per exchange where a single graph allows it (default), 0: one (k_cheb_resident)
 extern "C" int pf_persist_two_step(int level) {
-    g_two_step.store(level <= 0 ? 0 : (level >= 2 ? 2 : 1));
+    g_two_step.store(level <= 0 ? 0 : 1);
     return PF_OK;
 }
 
@@ -1511,8 +1360,8 @@ int pf_persist_cheb(const pf_persist_args* a, const pf_persist_args* b, int* don
     const int64_t wa = ga->n_pad / ga->win_rows, wb = gb ? gb->n_pad / gb->win_rows : 0;
     const int64_t grid = (std::max(wa, wb) + 7) & ~(int64_t)7;
     if (grid > dev_grid) return PF_OK;
-    if (nw == 1) {
-        PF_TRY(persist_cheb2(a, b, grid, done, lds_bytes));
+    if (nw == 1 && !gb) {
+        PF_TRY(persist_cheb2(a, grid, done, lds_bytes));
         if (*done) return PF_OK;
     }
     PF_TRY(pf_window_slots_prepare(ga));

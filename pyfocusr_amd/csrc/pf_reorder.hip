@@ -341,7 +341,7 @@ struct k_order_rank {
 // g->mrank[original] = m, g->order_bbox.  The assembler renumbers points and faces with it and builds everything in that
 // space; pf_compute_order then only refines the order inside windows.
 int pf_morton_order(pf_graph* g, const double* d_pts, int32_t* d_overflow) {
-    hipStream_t st = g->build_stream ? g->build_stream : g->ctx->stream;
+    hipStream_t st = g->ctx->stream;
     const int64_t n = g->n;
     const int in = (int)n;
     unsigned *k0 = nullptr, *k1 = nullptr;
@@ -411,8 +411,8 @@ int pf_morton_order(pf_graph* g, const double* d_pts, int32_t* d_overflow) {
 // m-space; d_pts: the points in that order): boundary rows first, then by degree; g->perm_m / g->iperm_m (solver <-> m),
 // their compositions with morder in g->perm / g->iperm (solver <-> original), g->smooth.
 static int order_in_windows(pf_graph* g, const double* d_pts) {
-    hipStream_t st = g->build_stream ? g->build_stream : g->ctx->stream;  // blocks are taken and released on this one ...
-    hipStream_t ls = g->side_stream ? g->side_stream : st;                // ... the kernels may run on the build's side stream
+    hipStream_t st = g->ctx->stream;                        // blocks are taken and released on this one ...
+    hipStream_t ls = g->side_stream ? g->side_stream : st;  // ... the kernels may run on the build's side stream
     const int64_t n = g->n;
     const int32_t win_rows = g->win_rows;
     unsigned *bflag = nullptr, *k0 = nullptr, *k1 = nullptr;
@@ -467,7 +467,7 @@ static int order_in_windows(pf_graph* g, const double* d_pts) {
 // mesh assembled in m-space.
 int pf_compute_order(pf_graph* g, const double* d_pts, int32_t* d_overflow) {
     if (g->morder) return order_in_windows(g, d_pts);
-    hipStream_t st = g->build_stream ? g->build_stream : g->ctx->stream;
+    hipStream_t st = g->ctx->stream;
     const int64_t n = g->n;
     const int in = (int)n;
     unsigned long long* bbox = nullptr;

@@ -3,6 +3,7 @@ shells, VTK reader, mesh generator) against the oracle and the golden fixtures. 
 compute happens here; the device is replaced by the numpy test double in tests/_numpy_ops.py."""
 import os
 import re
+import subprocess
 import sys
 
 import numpy as np
@@ -37,6 +38,10 @@ def test_library_exports_every_declared_symbol():
     for name in declared:
         assert getattr(lib, name) is not None
     assert lib.pf_version() == 1
+    # ... and the header is the whole exported surface: every unmangled pf_ function of the library is declared there
+    nm = subprocess.run(["nm", "-D", "--defined-only", _hip.LIB_PATH], check=True, capture_output=True, text=True).stdout
+    exported = {f[2] for f in (line.split() for line in nm.splitlines()) if len(f) == 3 and f[2].startswith("pf_")}
+    assert exported and sorted(exported - set(declared)) == []
 
 
 def test_product_fails_loudly_without_gpu_or_library(monkeypatch):

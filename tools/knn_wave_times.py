@@ -21,7 +21,6 @@ timers = dict(assembly=0.0, eigensolve=0.0, eigsort=0.0, knn=0.0, matvecs=0)
 np.random.seed(0)
 bench.hot_path_step([ctx, ctx], meshes[0], meshes[1], k, 5000, timers)
 lib = _hip.load_library()
-lib.pf_knn_wave_stats.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_double)]
 ctx.knn_count(True)  # the next step's search is the counting instantiation
 for rep in range(3):
     ctx.knn_count(True)
