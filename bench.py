@@ -9,10 +9,17 @@ One "step" = one pass of the hot path over one synthetic mesh pair (BASELINE.jso
     1-NN of every source vertex among the target vertices (d = k)
 metric value = eigenpairs per second = (2 k) / step time, whole job (sum over ranks).
 
+A plain run does only what that figure needs: set-up, warm-up, the timed steps, --dump-outputs, the
+line (with the roofline entries of the resident kernel and of the assembly, read off the timed
+steps).  --full adds everything that takes runs of its own, after the timed steps: the streaming
+kernel's and the 1-NN's roofline entries, the device copy rate, the bundled 15k pair, the single-
+graph solve, the pair with scan defects, C5 on one GPU, the measured CPU baseline with the parity
+at full size, and the C4 split pair below.
+
 N > 1 ranks: every rank owns an independent mesh pair (the unit that shards with no data-path
-collective: template-to-many-targets pipelines) -> weak scaling.  With exactly 2 ranks the C4
-layout is measured in addition (one pair split target/source over the two GPUs, RCCL all-gather
-of the spectral coordinates, query-sharded KNN) and reported under "split_pair".
+collective: template-to-many-targets pipelines) -> weak scaling.  With exactly 2 ranks and --full
+the C4 layout is measured in addition (one pair split target/source over the two GPUs, RCCL
+all-gather of the spectral coordinates, query-sharded KNN) and reported under "split_pair".
 """
 import argparse
 import json
@@ -466,11 +473,14 @@ def main():
     ap.add_argument("--vertices", dest="n", type=int, default=250000, help="vertices per mesh")
     ap.add_argument("--k", type=int, default=5)
     ap.add_argument("--samples", type=int, default=5000, help="n_coords_spectral_ordering (focusr.py:37)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check what takes runs of its own: extra roofline entries, "
+                         "the other workloads, the CPU baseline with the parity at full size, the C4 split pair (2 ranks)")
     ap.add_argument("--cpu-eigs-runs", type=int, default=3, help="timed scipy eigs runs per mesh of the CPU baseline (median)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: without the CPU baseline and its parity")
     ap.add_argument("--no-extras", action="store_true",
-                    help="only the headline workload (no bundled-15k-pair measurement): keeps rocprofv3 kernel statistics "
-                         "to the 250k launches")
+                    help="with --full: without the extra steps, roofline entries and workloads (a plain run has none of "
+                         "them: rocprofv3 kernel statistics stay with the 250k launches)")
     ap.add_argument("--row-partition", type=int, default=0, metavar="S",
                     help="opt-in extra at N > 1: additionally solve ONE mesh with its rows split over all ranks, ghost "
                          "zones of depth S (BASELINE config C5 layout); reported under 'row_partitioned'")
@@ -490,6 +500,8 @@ def main():
                     help="after the timed steps, write what the last one computed (rank 0's pair: eigenvalues, eigenvectors, "
                          "spectral weights, correspondences) as DIR/<name>.npy, float64, at most 64 MB in all")
     args = ap.parse_args()
+    extras = args.full and not args.no_extras  # the untimed extra steps, roofline entries and workloads
+    cpu_leg = args.full and not args.no_cpu_baseline  # the oracle on the CPU (~75 s of a --full run)
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -604,9 +616,9 @@ def main():
 
     # The kernel that DOES stream the operators through HBM (one step per launch, k_sell_op2): the path of graphs the
     # resident kernel does not cover.  One untimed extra step with the resident kernel switched off gives its HBM
-    # roofline entry in the same run.
+    # roofline entry in the same run (--full).
     stream_tm = None
-    if rank == 0 and not args.no_extras:
+    if rank == 0 and extras:
         _hip.persist_enable(False)
         try:
             extra = dict(assembly=0.0, eigensolve=0.0, eigsort=0.0, knn=0.0, matvecs=0)
@@ -806,8 +818,8 @@ def main():
             "traffic_source": PMC_SUMMARY if asm_traffic is not None else None,
             "note": "both meshes of the pair; wall time of the stage (the two builds share their launches: pf_launch.h)"}
         try:
-            if args.no_extras:
-                raise LookupError("skipped with --no-extras (one extra untimed step)")
+            if not extras:
+                raise LookupError("needs --full without --no-extras (one extra untimed step)")
             ctx.knn_count(True)
             np.random.seed(99)
             extra = dict(assembly=0.0, eigensolve=0.0, eigsort=0.0, knn=0.0, matvecs=0)
@@ -834,11 +846,11 @@ def main():
             out["host_call_ms_per_step"] = {k: v / args.steps for k, v in call_ms.items()}
         if roofline_stream is not None:
             out["roofline_streaming_kernel"] = roofline_stream
-        if not args.no_extras:
+        if extras:
             out["roofline"]["achievable_hbm_copy_GBps"] = device_copy_gbs(torch, torch.device("cuda", local))
         if rowp is not None:
             out["row_partitioned"] = rowp
-        if world == 1 and not args.no_extras:
+        if world == 1 and extras:
             c2 = bundled_15k_pair(ctx, 5)
             if c2 is not None:
                 out["bundled_15k_pair"] = c2
@@ -848,7 +860,7 @@ def main():
                 out["single_graph_solve"] = dict(error="%s: %s" % (type(exc).__name__, exc))
                 failed.append("single_graph_solve")
             try:
-                out["messy_250k_pair"] = messy_250k_pair(ctx, n=args.n, k=args.k, samples=args.samples, check_cpu=not args.no_cpu_baseline)
+                out["messy_250k_pair"] = messy_250k_pair(ctx, n=args.n, k=args.k, samples=args.samples, check_cpu=cpu_leg)
                 out["messy_250k_pair"]["ratio_to_clean_pair"] = out["messy_250k_pair"]["ms"] / out["ms_per_step"]
             except Exception as exc:  # noqa: BLE001
                 out["messy_250k_pair"] = dict(error="%s: %s" % (type(exc).__name__, exc))
@@ -858,7 +870,7 @@ def main():
             except Exception as exc:  # noqa: BLE001 - an extra: recorded, and the exit status says so
                 out["c5_1m_k10"] = dict(error="%s: %s" % (type(exc).__name__, exc))
                 failed.append("c5_1m_k10")
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and cpu_leg:
             vt, vs, w, vals_t, vals_s = coords  # last timed step; the coordinate arrays are built here, outside the timed region
             coords = (vt[:, :args.k] * w[None, :], vs[:, :args.k] * w[None, :])
             out["cpu_baseline"], out["parity_at_full_size"] = cpu_baseline((mesh_t, mesh_s), args.k, coords, (vals_t, vals_s), idx,
@@ -866,11 +878,11 @@ def main():
             out["speedup_vs_cpu_baseline"] = out["value"] / out["cpu_baseline"]["value"]
     else:
         out = {}
-    # BASELINE config C4 (N = 2 only), measured AFTER the headline figures are in hand and under a watchdog: this is the
-    # one place where the ranks talk to each other on the data path, and a collective that never completes must not
+    # BASELINE config C4 (N = 2 and --full only), measured AFTER the headline figures are in hand and under a watchdog: this
+    # is the one place where the ranks talk to each other on the data path, and a collective that never completes must not
     # cost the headline line (the watchdog prints it, with the failure named, and ends the ranks).
     split = None
-    if world == 2:
+    if world == 2 and args.full:
         import threading
 
         done = threading.Event()

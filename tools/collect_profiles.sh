@@ -1,7 +1,7 @@
 #!/bin/bash
 # The measurement set behind profiles/r03_<tag>_*: run on the GPU box (gpurun), results land in gpurun_out/final/.
 #   bash tools/collect_profiles.sh
-# 1. python bench.py (the full line: headline + extras + measured CPU baseline)
+# 1. python bench.py --full (the full line: headline + extras + measured CPU baseline)
 # 2. rocprofv3 kernel stats / gaps / timeline of the headline workload
 # 3. the same kernel stats with the resident path off (PF_PERSIST=0 in the environment of the rocprofv3 command itself):
 #    the streaming kernel k_sell_op2
@@ -12,7 +12,7 @@ root=$(cd "$(dirname "$0")/.." && pwd)
 out=$root/gpurun_out/final
 rm -rf $out && mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
-python3 $root/bench.py > $out/bench.json 2> $out/bench.err
+python3 $root/bench.py --full > $out/bench.json 2> $out/bench.err
 echo "bench done" > $out/progress.txt
 args="--steps 4 --warmup 2 --no-extras --no-cpu-baseline"
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- python3 $root/bench.py $args > $out/bench_under_rocprof.json 2> $out/rocprof.err
