@@ -448,6 +448,18 @@ int pf_surface_create(pf_ctx* ctx, const double* points, int64_t n, const int32_
 void pf_surface_free(pf_surface* s);
 int pf_surface_closest(pf_surface* s, const double* qry, int64_t n_qry, double* out_pts, int32_t* out_face,
                        double* out_d2);
+/* Surface distances of many queries (whole meshes: every vertex of one mesh against the surface of another).  Same
+ * exact minimum and tie rule as pf_surface_closest, so out_d2 and out_face equal its outputs bit for bit; no closest
+ * points.  The queries are Morton-sorted on the device and searched in packets of 16 neighbours (4 for fewer than
+ * 65536 queries), each chunk of triangles loaded once per packet.
+ *   pf_surface_distance  qry [n_qry][3] f64 (host), n_qry >= 1 (else PF_E_ARG) -> out_d2 [n_qry] exact squared
+ *                        distances, out_face [n_qry] face index (a query with a non-finite coordinate: NaN and -1);
+ *                        stats [6] = n_finite | n_nan | sum d | sum d^2 | max d | argmax (as double; -1 if none) over
+ *                        the queries with a finite d = sqrt(d2), n_nan counting the others, argmax the lowest query
+ *                        index of the largest d2; sums in a fixed order (two calls give identical bits).  Each output
+ *                        may be NULL. */
+int pf_surface_distance(pf_surface* s, const double* qry, int64_t n_qry, double* out_d2, int32_t* out_face,
+                        double* stats);
 
 /* ---- Coherent Point Drift pieces ("next" row f4) ------------------------------------------------------------
  * The reference registers the spectral coordinates with the third-party cycpd package (focusr.py:297-334).

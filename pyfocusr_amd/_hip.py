@@ -169,6 +169,7 @@ SIGNATURES = {
     "pf_surface_create": (C.c_int, [C.c_void_p, _f64p, C.c_int64, _i32p, C.c_int64, C.c_int32, C.POINTER(C.c_void_p)]),
     "pf_surface_free": (None, [C.c_void_p]),
     "pf_surface_closest": (C.c_int, [C.c_void_p, _f64p, C.c_int64, _f64p, _i32p, _f64p]),
+    "pf_surface_distance": (C.c_int, [C.c_void_p, _f64p, C.c_int64, _f64p, _i32p, _f64p]),
     "pf_cpd_create": (C.c_int, [C.c_void_p, _f64p, C.c_int64, _f64p, C.c_int64, C.c_int32, C.POINTER(C.c_void_p)]),
     "pf_cpd_free": (None, [C.c_void_p]),
     "pf_cpd_estep": (C.c_int, [C.c_void_p, _f64p, C.c_double, C.c_double, _f64p, _f64p, _f64p]),
@@ -621,6 +622,23 @@ class DeviceSurface(object):
         d2 = np.empty(len(q), dtype=np.float64)
         _check(self._lib.pf_surface_closest(self._h, _f64(q), len(q), _f64(pts), face.ctypes.data_as(_i32p), _f64(d2)))
         return pts, face, d2
+
+    def distance(self, queries, per_point=True):
+        """(squared distance (q,) f64, face (q,) i32, stats dict) of every query to the surface (`pf_surface_distance`:
+        many queries, no closest points).  A query with a non-finite coordinate gives NaN and face -1.  stats:
+        n_finite, n_nan, sum_d, sum_d2, max_d, argmax (-1 if none) over d = sqrt(d2).  per_point=False downloads the
+        stats only and returns (None, None, stats)."""
+        q = _c_f64(queries)
+        if q.ndim != 2 or q.shape[1] != 3 or q.shape[0] == 0:
+            raise ValueError("queries must be a non-empty (n, 3) array")
+        d2 = np.empty(len(q), dtype=np.float64) if per_point else None
+        face = np.empty(len(q), dtype=np.int32) if per_point else None
+        st = np.empty(6, dtype=np.float64)
+        _check(self._lib.pf_surface_distance(self._h, _f64(q), len(q), _f64(d2) if per_point else None,
+                                             face.ctypes.data_as(_i32p) if per_point else None, _f64(st)))
+        stats = {"n_finite": int(st[0]), "n_nan": int(st[1]), "sum_d": float(st[2]), "sum_d2": float(st[3]),
+                 "max_d": float(st[4]), "argmax": int(st[5])}
+        return d2, face, stats
 
     def close(self):
         if getattr(self, "_h", None):

@@ -370,6 +370,251 @@ __global__ __launch_bounds__(PF_CLOSEST_WAVES* PF_WAVE) void k_closest(const dou
     }
 }
 
+// ---- many-query distances (pf_surface_distance) ------------------------------------------------------------------
+// Queries are Morton-sorted in their own bounding box and cut into packets of 16 consecutive ones (4 when there are
+// fewer than 16 x 4096 queries), one packet per wave.  The wave walks the same super-chunk / chunk hierarchy as
+// k_closest, but a chunk is loaded ONCE per packet: its 64 triangles are staged in LDS (one coalesced load per lane)
+// and the lanes of each query share them out, reading from LDS by broadcast.  A triangle whose own box is farther than
+// the query's bound is skipped before the exact test.  Exactness: every exact test is the one of k_closest (same
+// closest_on_triangle / better, same PF_BOX_SLACK); the packet's box test (box of the queries against a chunk box) is
+// never larger than the point-box test of any query inside it, and a triangle's box never farther than the triangle,
+// so nothing the per-query search would test is skipped, and the lanes of a query merge with the same tie rule.
+
+__global__ __launch_bounds__(PF_BLOCK) void k_qry_keys(const double* __restrict__ qry, int64_t n, Box3 bb,
+                                                       unsigned* __restrict__ keys, int32_t* __restrict__ vals) {
+    const int64_t i = (int64_t)blockIdx.x * PF_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    unsigned code = 0;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        double u = bb.ext[a] > 0.0 ? (qry[3 * i + a] - bb.lo[a]) / bb.ext[a] : 0.0;
+        u = u < 0.0 ? 0.0 : (u > 1.0 ? 1.0 : u);
+        if (!(u == u)) u = 0.0;  // NaN coordinates: key 0
+        code |= spread10((unsigned)(u * 1023.0)) << a;
+    }
+    keys[i] = code;
+    vals[i] = (int32_t)i;
+}
+
+// squared distance between two boxes (0 if they overlap); never larger than box_dist2 of any point of the first box
+__device__ __forceinline__ double boxbox_dist2(const double lo[3], const double hi[3], const double* __restrict__ bx) {
+    double s = 0.0;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const double d = fmax(fmax(bx[a] - hi[a], lo[a] - bx[3 + a]), 0.0);
+        s += d * d;
+    }
+    return s;
+}
+
+__device__ __forceinline__ double wave_max(double v) {
+    for (int off = PF_WAVE / 2; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off, PF_WAVE));
+    return v;
+}
+
+__device__ __forceinline__ double wave_sum(double v) {  // fixed butterfly: the same order on every run
+    for (int off = PF_WAVE / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, PF_WAVE);
+    return v;
+}
+
+// the larger distance wins; lowest query index on ties; idx < 0 = none
+__device__ __forceinline__ bool later_max(double d2, int64_t idx, double bd2, int64_t bidx) {
+    return idx >= 0 && (bidx < 0 || d2 > bd2 || (d2 == bd2 && idx < bidx));
+}
+
+constexpr int PF_DIST_STATS = 6;  // n_finite | n_nan | sum d | sum d^2 | max d | argmax
+
+// one wave (= one block) per packet of PACKET sorted queries; lane = query (lane % PACKET) x triangle subset
+// (lane / PACKET): each of a query's 64 / PACKET lanes tests every (64 / PACKET)-th triangle of a chunk.  Larger
+// packets share each chunk load among more queries; smaller ones give more waves when there are few queries.
+template <int PACKET>
+__global__ __launch_bounds__(PF_WAVE) void k_distance(const double* __restrict__ tri, const int32_t* __restrict__ tri_orig,
+                                                      const double* __restrict__ box, const double* __restrict__ sbox,
+                                                      int64_t n_tri, int64_t n_chunks, int64_t n_super,
+                                                      const double* __restrict__ qry, const int32_t* __restrict__ perm,
+                                                      int64_t n_qry, int32_t per_face, double* __restrict__ out_d2,
+                                                      int32_t* __restrict__ out_face, double* __restrict__ partial) {
+    __shared__ double s_tri[9][PF_TRI_CHUNK];  // 4.5 KiB: one chunk, SoA as in HBM
+    __shared__ int32_t s_orig[PF_TRI_CHUNK];
+    constexpr int PF_DIST_PACKET = PACKET, PF_DIST_SUB = PF_WAVE / PACKET;
+    static_assert(PF_WAVE % PACKET == 0, "a packet divides the wave");
+    const int lane = threadIdx.x, sub = lane / PF_DIST_PACKET;
+    const int64_t i = (int64_t)blockIdx.x * PF_DIST_PACKET + (lane % PF_DIST_PACKET);
+    const bool live = i < n_qry;
+    const int64_t qi = live ? perm[i] : -1;  // the caller's index of this lane's query
+    const double inf = std::numeric_limits<double>::infinity();
+    double p[3] = {0.0, 0.0, 0.0};
+    if (live) p[0] = qry[3 * qi], p[1] = qry[3 * qi + 1], p[2] = qry[3 * qi + 2];
+    const bool ok = live && std::isfinite(p[0]) && std::isfinite(p[1]) && std::isfinite(p[2]);
+
+    Best best;
+    best.d2 = inf, best.orig = 0x7fffffff;
+    // the query's bound: the least distance its PF_DIST_SUB lanes have found
+    auto query_min = [&](double v) {
+        for (int off = PF_DIST_PACKET; off < PF_WAVE; off <<= 1) v = fmin(v, __shfl_xor(v, off, PF_WAVE));
+        return v;
+    };
+    if (__ballot(ok)) {
+        // the packet's box
+        double lo[3], hi[3];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            lo[a] = ok ? p[a] : inf, hi[a] = ok ? p[a] : -inf;
+            for (int off = PF_WAVE / 2; off > 0; off >>= 1) {
+                lo[a] = fmin(lo[a], __shfl_xor(lo[a], off, PF_WAVE));
+                hi[a] = fmax(hi[a], __shfl_xor(hi[a], off, PF_WAVE));
+            }
+        }
+        double qbest = inf;
+        auto scan = [&](int64_t c) {  // stage chunk c in LDS, test its triangles against every query
+            const int64_t s = c * PF_TRI_CHUNK + lane;
+            const int cnt = (int)(n_tri - c * PF_TRI_CHUNK < PF_TRI_CHUNK ? n_tri - c * PF_TRI_CHUNK : PF_TRI_CHUNK);
+            __syncthreads();  // the previous chunk's reads are done
+            if (lane < cnt) {
+#pragma unroll
+                for (int k = 0; k < 9; ++k) s_tri[k][lane] = tri[(int64_t)k * n_tri + s];
+                s_orig[lane] = tri_orig[s];
+            }
+            __syncthreads();
+            if (ok) {
+                for (int t = sub; t < cnt; t += PF_DIST_SUB) {
+                    const double a[3] = {s_tri[0][t], s_tri[1][t], s_tri[2][t]}, b[3] = {s_tri[3][t], s_tri[4][t], s_tri[5][t]},
+                                 cc[3] = {s_tri[6][t], s_tri[7][t], s_tri[8][t]};
+                    // the triangle's own box first: it is never farther than the triangle (the chunk-box argument)
+                    double tb = 0.0;
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) {
+                        const double d = fmax(fmax(fmin(fmin(a[k], b[k]), cc[k]) - p[k], p[k] - fmax(fmax(a[k], b[k]), cc[k])), 0.0);
+                        tb += d * d;
+                    }
+                    if (tb > fmin(best.d2, qbest) * PF_BOX_SLACK) continue;
+                    double q[3];
+                    closest_on_triangle(p, a, b, cc, q);
+                    const double dx = p[0] - q[0], dy = p[1] - q[1], dz = p[2] - q[2];
+                    const double d2 = dx * dx + dy * dy + dz * dz;
+                    const int32_t o = s_orig[t];
+                    if (better(d2, o, best.d2, best.orig)) best.d2 = d2, best.orig = o;  // NaN distances never win
+                }
+            }
+            qbest = query_min(best.d2);
+        };
+        // does any query's own point-box test (k_closest's) keep chunk c?
+        auto wanted = [&](int64_t c) { return __ballot(ok && box_dist2(p, box + 6 * c) <= qbest * PF_BOX_SLACK) != 0; };
+        auto wave_argmin = [&](double& d, int64_t& k) {
+            for (int off = PF_WAVE / 2; off > 0; off >>= 1) {
+                const double od = __shfl_xor(d, off, PF_WAVE);
+                const int64_t ok2 = __shfl_xor(k, off, PF_WAVE);
+                if (od < d || (od == d && ok2 < k)) d = od, k = ok2;
+            }
+        };
+
+        // (1) seed: the chunk nearest to the packet's centre (nearest super-chunk, then nearest chunk inside it)
+        const double ctr[3] = {0.5 * (lo[0] + hi[0]), 0.5 * (lo[1] + hi[1]), 0.5 * (lo[2] + hi[2])};
+        double nd = inf;
+        int64_t ns = n_super;
+        for (int64_t s = lane; s < n_super; s += PF_WAVE) {
+            const double d = box_dist2(ctr, sbox + 6 * s);
+            if (d < nd) nd = d, ns = s;
+        }
+        wave_argmin(nd, ns);
+        int64_t c0 = n_chunks;
+        if (ns < n_super) {
+            c0 = ns * PF_WAVE + lane;
+            nd = c0 < n_chunks ? box_dist2(ctr, box + 6 * c0) : inf;
+            if (!(nd < inf)) c0 = n_chunks;
+            wave_argmin(nd, c0);
+        }
+        if (c0 < n_chunks) scan(c0);
+        double bound = wave_max(ok ? qbest : -inf);  // the packet's bound: its worst query
+
+        // (2) every chunk whose box is within the bound of the packet's box and of some query
+        for (int64_t sb = 0; sb < n_super; sb += PF_WAVE) {
+            const int64_t s = sb + lane;
+            unsigned long long smask = __ballot(s < n_super && boxbox_dist2(lo, hi, sbox + 6 * s) <= bound * PF_BOX_SLACK);
+            while (smask) {
+                const int64_t ss = sb + __ffsll((long long)smask) - 1;
+                smask &= smask - 1;
+                if (boxbox_dist2(lo, hi, sbox + 6 * ss) > bound * PF_BOX_SLACK) continue;  // the bound has shrunk
+                const int64_t c = ss * PF_WAVE + lane;
+                unsigned long long mask = __ballot(c < n_chunks && c != c0 && boxbox_dist2(lo, hi, box + 6 * c) <= bound * PF_BOX_SLACK);
+                while (mask) {
+                    const int64_t cc = ss * PF_WAVE + __ffsll((long long)mask) - 1;
+                    mask &= mask - 1;
+                    if (boxbox_dist2(lo, hi, box + 6 * cc) > bound * PF_BOX_SLACK || !wanted(cc)) continue;
+                    scan(cc);
+                    bound = wave_max(ok ? qbest : -inf);
+                }
+            }
+        }
+    }
+
+    // the query's winner over its lanes (smallest distance, lowest triangle index), outputs in the caller's order
+    for (int off = PF_DIST_PACKET; off < PF_WAVE; off <<= 1) {
+        const double od = __shfl_xor(best.d2, off, PF_WAVE);
+        const int32_t oo = __shfl_xor(best.orig, off, PF_WAVE);
+        if (better(od, oo, best.d2, best.orig)) best.d2 = od, best.orig = oo;
+    }
+    const bool found = ok && best.orig != 0x7fffffff;
+    const double d2 = found ? best.d2 : (ok ? inf : __longlong_as_double(0x7ff8000000000000ll));
+    const bool mine = live && sub == 0;  // one lane per query writes and counts
+    if (mine) {
+        if (out_d2) out_d2[qi] = d2;
+        if (out_face) out_face[qi] = found ? best.orig / per_face : -1;
+    }
+    // the packet's partial statistics
+    const bool fin = mine && std::isfinite(d2);
+    const double d = fin ? sqrt(d2) : 0.0;
+    double md2 = fin ? d2 : -inf;
+    int64_t mi = fin ? qi : -1;
+    for (int off = PF_WAVE / 2; off > 0; off >>= 1) {
+        const double od = __shfl_xor(md2, off, PF_WAVE);
+        const int64_t oi = __shfl_xor(mi, off, PF_WAVE);
+        if (later_max(od, oi, md2, mi)) md2 = od, mi = oi;
+    }
+    const double n_fin = wave_sum(fin ? 1.0 : 0.0), n_bad = wave_sum(mine && !fin ? 1.0 : 0.0);
+    const double sd = wave_sum(d), sdd = wave_sum(d * d);
+    if (lane == 0) {
+        double* w = partial + (int64_t)PF_DIST_STATS * blockIdx.x;
+        w[0] = n_fin, w[1] = n_bad, w[2] = sd, w[3] = sdd, w[4] = md2, w[5] = (double)mi;
+    }
+}
+
+// one block: the packets' partials in a fixed order (strided sequential sums per thread, then a fixed tree)
+__global__ __launch_bounds__(PF_BLOCK) void k_distance_stats(const double* __restrict__ partial, int64_t n_part,
+                                                             double* __restrict__ stats) {
+    __shared__ double s_v[4][PF_BLOCK];
+    __shared__ double s_m[PF_BLOCK];
+    __shared__ int64_t s_i[PF_BLOCK];
+    const int t = threadIdx.x;
+    double v[4] = {0.0, 0.0, 0.0, 0.0}, m = -std::numeric_limits<double>::infinity();
+    int64_t mi = -1;
+    for (int64_t w = t; w < n_part; w += PF_BLOCK) {
+        const double* x = partial + (int64_t)PF_DIST_STATS * w;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[k] += x[k];
+        const int64_t xi = (int64_t)x[5];
+        if (later_max(x[4], xi, m, mi)) m = x[4], mi = xi;
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) s_v[k][t] = v[k];
+    s_m[t] = m, s_i[t] = mi;
+    __syncthreads();
+    for (int h = PF_BLOCK / 2; h > 0; h >>= 1) {
+        if (t < h) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) s_v[k][t] += s_v[k][t + h];
+            if (later_max(s_m[t + h], s_i[t + h], s_m[t], s_i[t])) s_m[t] = s_m[t + h], s_i[t] = s_i[t + h];
+        }
+        __syncthreads();
+    }
+    if (t == 0) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) stats[k] = s_v[k][0];
+        stats[4] = s_i[0] >= 0 ? sqrt(s_m[0]) : __longlong_as_double(0x7ff8000000000000ll);
+        stats[5] = (double)s_i[0];
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -492,6 +737,80 @@ int pf_surface_closest(pf_surface* s, const double* qry, int64_t n_qry, double* 
     pf_free(st, d_face);
     if (e != hipSuccess) {
         pf_set_error("pf_surface_closest: %s", hipGetErrorString(e));
+        return PF_E_HIP;
+    }
+    return PF_OK;
+}
+
+int pf_surface_distance(pf_surface* s, const double* qry, int64_t n_qry, double* out_d2, int32_t* out_face, double* stats) {
+    PF_CHECK(s && qry, PF_E_ARG, "pf_surface_distance: NULL argument");
+    PF_CHECK(n_qry >= 1 && n_qry < ((int64_t)1 << 31), PF_E_ARG, "pf_surface_distance: n_qry = %lld out of range", (long long)n_qry);
+    Box3 bb;  // Morton box of the finite queries
+    for (int a = 0; a < 3; ++a) {
+        double lo = std::numeric_limits<double>::infinity(), hi = -lo;
+        for (int64_t i = 0; i < n_qry; ++i) {
+            const double x = qry[3 * i + a];
+            if (!std::isfinite(x)) continue;
+            if (x < lo) lo = x;
+            if (x > hi) hi = x;
+        }
+        bb.lo[a] = lo;
+        bb.ext[a] = hi - lo;
+        if (!(bb.ext[a] > 0.0) || !std::isfinite(bb.ext[a])) bb.ext[a] = 0.0;
+    }
+    PF_HIP(hipSetDevice(s->ctx->device));
+    hipStream_t st = s->ctx->stream;
+    // 16 queries per wave once that gives >= 4096 waves (4 per SIMD), else 4 (measured: profiles/surface_distance.md)
+    const bool big = n_qry >= (int64_t)16 * 4096;
+    const int64_t n_pack = big ? (n_qry + 15) / 16 : (n_qry + 3) / 4;
+    double *d_q = nullptr, *d_d2 = nullptr, *d_part = nullptr, *d_stats = nullptr;
+    int32_t* d_face = nullptr;
+    unsigned *k0 = nullptr, *k1 = nullptr;
+    int32_t *v0 = nullptr, *v1 = nullptr;
+    void* tmp = nullptr;
+    size_t need = 0;
+    hipError_t e = hipSuccess;
+    do {
+        if ((e = pf_malloc(st, (void**)&d_q, sizeof(double) * 3 * n_qry)) != hipSuccess) break;
+        if ((e = pf_malloc(st, (void**)&k0, sizeof(unsigned) * n_qry)) != hipSuccess) break;
+        if ((e = pf_malloc(st, (void**)&k1, sizeof(unsigned) * n_qry)) != hipSuccess) break;
+        if ((e = pf_malloc(st, (void**)&v0, sizeof(int32_t) * n_qry)) != hipSuccess) break;
+        if ((e = pf_malloc(st, (void**)&v1, sizeof(int32_t) * n_qry)) != hipSuccess) break;
+        if (out_d2 && (e = pf_malloc(st, (void**)&d_d2, sizeof(double) * n_qry)) != hipSuccess) break;
+        if (out_face && (e = pf_malloc(st, (void**)&d_face, sizeof(int32_t) * n_qry)) != hipSuccess) break;
+        if ((e = pf_malloc(st, (void**)&d_part, sizeof(double) * PF_DIST_STATS * n_pack)) != hipSuccess) break;
+        if ((e = pf_malloc(st, (void**)&d_stats, sizeof(double) * PF_DIST_STATS)) != hipSuccess) break;
+        if ((e = hipMemcpyAsync(d_q, qry, sizeof(double) * 3 * n_qry, hipMemcpyHostToDevice, st)) != hipSuccess) break;
+        k_qry_keys<<<nblk(n_qry), PF_BLOCK, 0, st>>>(d_q, n_qry, bb, k0, v0);
+        if ((e = hipGetLastError()) != hipSuccess) break;
+        if ((e = hipcub::DeviceRadixSort::SortPairs(nullptr, need, k0, k1, v0, v1, (int)n_qry, 0, 30, st)) != hipSuccess) break;
+        if ((e = pf_malloc(st, &tmp, need)) != hipSuccess) break;
+        if ((e = hipcub::DeviceRadixSort::SortPairs(tmp, need, k0, k1, v0, v1, (int)n_qry, 0, 30, st)) != hipSuccess) break;
+        if (big)
+            k_distance<16><<<(unsigned)n_pack, PF_WAVE, 0, st>>>(s->tri, s->tri_orig, s->box, s->sbox, s->n_tri, s->n_chunks, s->n_super,
+                                                                 d_q, v1, n_qry, s->vpf - 2, d_d2, d_face, d_part);
+        else
+            k_distance<4><<<(unsigned)n_pack, PF_WAVE, 0, st>>>(s->tri, s->tri_orig, s->box, s->sbox, s->n_tri, s->n_chunks, s->n_super,
+                                                                d_q, v1, n_qry, s->vpf - 2, d_d2, d_face, d_part);
+        k_distance_stats<<<1, PF_BLOCK, 0, st>>>(d_part, n_pack, d_stats);
+        if ((e = hipGetLastError()) != hipSuccess) break;
+        if (out_d2 && (e = hipMemcpyAsync(out_d2, d_d2, sizeof(double) * n_qry, hipMemcpyDeviceToHost, st)) != hipSuccess) break;
+        if (out_face && (e = hipMemcpyAsync(out_face, d_face, sizeof(int32_t) * n_qry, hipMemcpyDeviceToHost, st)) != hipSuccess) break;
+        if (stats && (e = hipMemcpyAsync(stats, d_stats, sizeof(double) * PF_DIST_STATS, hipMemcpyDeviceToHost, st)) != hipSuccess) break;
+        e = hipStreamSynchronize(st);
+    } while (0);
+    pf_free(st, d_q);
+    pf_free(st, k0);
+    pf_free(st, k1);
+    pf_free(st, v0);
+    pf_free(st, v1);
+    pf_free(st, tmp);
+    pf_free(st, d_d2);
+    pf_free(st, d_face);
+    pf_free(st, d_part);
+    pf_free(st, d_stats);
+    if (e != hipSuccess) {
+        pf_set_error("pf_surface_distance: %s", hipGetErrorString(e));
         return PF_E_HIP;
     }
     return PF_OK;

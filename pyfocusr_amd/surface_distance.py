@@ -1,0 +1,118 @@
+"""Exact surface distances between meshes: per-point distances, ASSD, RMS, Hausdorff and its 95th percentile.
+
+The reference sketches a registration check (`pyfocusr/test.py`, `get_all_pairwise_surface_errors`) around a
+`get_surface_distance_metrics` it never defines.  Here the distance of every vertex of one mesh to the surface of the
+other is the exact minimum over all triangles (polygons fan-triangulated), computed on the MI355X by
+`pf_surface_distance` (`_hip.DeviceSurface.distance`): the same arithmetic and tie rule as the ICP search, so the
+squared distances equal a brute-force scan bit for bit.  The summary of the downloaded distances is host work
+(`summarize_distances`, which needs no device).
+"""
+import numpy as np
+
+from . import _hip
+from . import vtk_functions
+
+
+def _mesh_arrays(mesh):
+    """(points (n,3) f64, faces (F,v) i32) of a `PolyMesh`, a vtkPolyData or a `(points, faces)` pair, checked before
+    anything touches the device."""
+    if isinstance(mesh, (tuple, list)) and len(mesh) == 2:
+        pts, faces = mesh
+    else:
+        pts, faces = vtk_functions.mesh_arrays(mesh)
+    pts = np.ascontiguousarray(pts, dtype=np.float64)
+    faces = np.asarray(faces)
+    if pts.ndim != 2 or pts.shape[1] != 3 or pts.shape[0] == 0:
+        raise ValueError("mesh points must be a non-empty (n, 3) array")
+    if faces.ndim != 2 or faces.shape[0] == 0 or faces.shape[1] < 3:
+        raise ValueError("mesh faces must be a non-empty (F, verts_per_face >= 3) array")
+    return pts, np.ascontiguousarray(faces, dtype=np.int32)
+
+
+def _query_array(points):
+    q = np.ascontiguousarray(points, dtype=np.float64)
+    if q.ndim != 2 or q.shape[1] != 3 or q.shape[0] == 0:
+        raise ValueError("query points must be a non-empty (n, 3) array")
+    return q
+
+
+def point_to_surface_distances(points, mesh, ctx=None):
+    """(d (n,) f64, face (n,) i32): the distance of every point to the surface of `mesh` and the face that attains it
+    (lowest face index on exact ties).  A point with a non-finite coordinate gives NaN and -1.  `mesh` may also be a
+    `_hip.DeviceSurface` built earlier, which is then reused and left open."""
+    q = _query_array(points)
+    if hasattr(mesh, "distance"):  # a DeviceSurface
+        d2, face, _ = mesh.distance(q)
+        return np.sqrt(d2), face
+    pts, faces = _mesh_arrays(mesh)
+    surface = _hip.DeviceSurface(pts, faces, ctx=ctx)
+    try:
+        d2, face, _ = surface.distance(q)
+    finally:
+        surface.close()
+    return np.sqrt(d2), face
+
+
+def _direction(d, tag):
+    d = np.asarray(d, dtype=np.float64).ravel()
+    fin = np.isfinite(d)
+    n = int(fin.sum())
+    out = {"n_" + tag: n, "n_nan_" + tag: int(d.size - n)}
+    if n == 0:
+        out.update({"mean_" + tag: np.nan, "rms_" + tag: np.nan, "max_" + tag: np.nan, "max_%s_vertex" % tag: -1,
+                    "p95_" + tag: np.nan, "_sum": 0.0})
+        return out
+    df = d[fin]
+    s = float(np.sum(df))
+    v = int(np.argmax(np.where(fin, d, -np.inf)))  # lowest index on ties
+    out.update({"mean_" + tag: s / n, "rms_" + tag: float(np.sqrt(np.sum(df * df) / n)), "max_" + tag: float(d[v]),
+                "max_%s_vertex" % tag: v, "p95_" + tag: float(np.percentile(df, 95)), "_sum": s})
+    return out
+
+
+def summarize_distances(d_a_to_b, d_b_to_a=None):
+    """Metrics of per-point distances (pure numpy, no device).  Non-finite distances are counted (`n_nan_*`) and left
+    out.  Per direction `t` (`a_to_b`, and `b_to_a` if given): `n_t`, `n_nan_t`, `mean_t`, `rms_t`, `max_t`,
+    `max_t_vertex` (the point attaining it, lowest index on ties), `p95_t`.  With both directions also `assd`
+    (mean over the points of both meshes), `hausdorff` (max of both maxima) and `hausdorff_95` (max of both 95th
+    percentiles)."""
+    ab = _direction(d_a_to_b, "a_to_b")
+    s_ab = ab.pop("_sum")
+    if d_b_to_a is None:
+        return ab
+    ba = _direction(d_b_to_a, "b_to_a")
+    s_ba = ba.pop("_sum")
+    out = dict(ab, **ba)
+    n = ab["n_a_to_b"] + ba["n_b_to_a"]
+    out["assd"] = (s_ab + s_ba) / n if n else np.nan
+    out["hausdorff"] = float(np.nanmax([ab["max_a_to_b"], ba["max_b_to_a"]])) if n else np.nan
+    out["hausdorff_95"] = float(np.nanmax([ab["p95_a_to_b"], ba["p95_b_to_a"]])) if n else np.nan
+    return out
+
+
+def surface_distance_metrics(mesh_a, mesh_b, symmetric=True, ctx=None, surface_a=None, surface_b=None):
+    """Distances from the vertices of `mesh_a` to the surface of `mesh_b` (and, if `symmetric`, from `mesh_b`'s
+    vertices to `mesh_a`'s surface), summarised by `summarize_distances`: `mean_a_to_b`, `rms_a_to_b`, `max_a_to_b`,
+    `max_a_to_b_vertex`, `p95_a_to_b`, the same for `b_to_a`, `assd`, `hausdorff`, `hausdorff_95`.
+
+    Meshes: `PolyMesh`, vtkPolyData or `(points, faces)`; quads and larger polygons are fan-triangulated.
+    `surface_a` / `surface_b`: `_hip.DeviceSurface` objects already built from the same meshes, reused and left open
+    (many pairs over one set of meshes build each surface once)."""
+    pts_a, faces_a = _mesh_arrays(mesh_a)
+    pts_b, faces_b = _mesh_arrays(mesh_b)
+    built = []
+    try:
+        if surface_b is None:
+            surface_b = _hip.DeviceSurface(pts_b, faces_b, ctx=ctx)
+            built.append(surface_b)
+        d_ab = np.sqrt(surface_b.distance(pts_a)[0])
+        d_ba = None
+        if symmetric:
+            if surface_a is None:
+                surface_a = _hip.DeviceSurface(pts_a, faces_a, ctx=ctx)
+                built.append(surface_a)
+            d_ba = np.sqrt(surface_a.distance(pts_b)[0])
+    finally:
+        for s in built:
+            s.close()
+    return summarize_distances(d_ab, d_ba)
