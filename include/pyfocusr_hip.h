@@ -460,6 +460,25 @@ int pf_surface_closest(pf_surface* s, const double* qry, int64_t n_qry, double* 
  *                        may be NULL. */
 int pf_surface_distance(pf_surface* s, const double* qry, int64_t n_qry, double* out_d2, int32_t* out_face,
                         double* stats);
+/* Signed surface distances (angle-weighted pseudonormals, Baerentzen & Aanaes 2005).  sd = sign((p - c) . n) sqrt(d2)
+ * with c the closest point on the winning triangle and n the pseudonormal of the feature c lies on: the unit face
+ * normal (interior; right-hand rule of the face's vertex order), the sum of the unit normals of the edge's triangles
+ * (edge; fan diagonals are edges), sum of corner angle x unit normal (vertex).  sd > 0 on the side the face normals
+ * point to: on an outward-oriented closed mesh inside is negative.  Sums in a fixed order, no floating-point atomics.
+ *   pf_surface_prepare_signed   the host points [n][3] f64 and faces [n_faces][verts_per_face] i32 given to
+ *                               pf_surface_create again (that call keeps no copy) -> device copies, face normals, edge and
+ *                               vertex pseudonormals; topology [4] (may be NULL) = edges | boundary edges (one triangle) |
+ *                               non-manifold edges (three or more) | inconsistent edges (two triangles that traverse it in
+ *                               the same direction), counted over the fan triangles' edges.  A second call rebuilds.
+ *   pf_surface_signed_distance  qry [n_qry][3] f64 (host), n_qry >= 1 -> out_sd [n_qry] (|sd| = sqrt(out_d2 of
+ *                               pf_surface_distance) bit for bit; +0.0 at distance 0; NaN for a non-finite query),
+ *                               out_face [n_qry] (= pf_surface_distance's), out_feature [n_qry] 0 face | 1 edge | 2 vertex
+ *                               (-1 with face -1), n_ambiguous: queries with d2 > 0 whose (p - c) . n is 0 (e.g. a zero
+ *                               pseudonormal of degenerate triangles), returned as +sqrt(d2).  Each output may be NULL.
+ *                               PF_E_ARG before pf_surface_prepare_signed. */
+int pf_surface_prepare_signed(pf_surface* s, const double* points, const int32_t* faces, int64_t* topology);
+int pf_surface_signed_distance(pf_surface* s, const double* qry, int64_t n_qry, double* out_sd, int32_t* out_face,
+                               int32_t* out_feature, int64_t* n_ambiguous);
 
 /* ---- Coherent Point Drift pieces ("next" row f4) ------------------------------------------------------------
  * The reference registers the spectral coordinates with the third-party cycpd package (focusr.py:297-334).

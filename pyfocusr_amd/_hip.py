@@ -170,6 +170,8 @@ SIGNATURES = {
     "pf_surface_free": (None, [C.c_void_p]),
     "pf_surface_closest": (C.c_int, [C.c_void_p, _f64p, C.c_int64, _f64p, _i32p, _f64p]),
     "pf_surface_distance": (C.c_int, [C.c_void_p, _f64p, C.c_int64, _f64p, _i32p, _f64p]),
+    "pf_surface_prepare_signed": (C.c_int, [C.c_void_p, _f64p, _i32p, _i64p]),
+    "pf_surface_signed_distance": (C.c_int, [C.c_void_p, _f64p, C.c_int64, _f64p, _i32p, _i32p, _i64p]),
     "pf_cpd_create": (C.c_int, [C.c_void_p, _f64p, C.c_int64, _f64p, C.c_int64, C.c_int32, C.POINTER(C.c_void_p)]),
     "pf_cpd_free": (None, [C.c_void_p]),
     "pf_cpd_estep": (C.c_int, [C.c_void_p, _f64p, C.c_double, C.c_double, _f64p, _f64p, _f64p]),
@@ -595,6 +597,12 @@ class DeviceMesh(object):
             pass
 
 
+def _fan_triangles(faces):
+    """(F,v) polygons -> (F*(v-2), 3) triangles (0,j+1,j+2), face-major, as the device fan-triangulates them."""
+    v = faces.shape[1]
+    return np.stack([faces[:, [0, j + 1, j + 2]] for j in range(v - 2)], axis=1).reshape(-1, 3)
+
+
 class DeviceSurface(object):
     """Triangle soup of one mesh in HBM (Morton-sorted, chunk boxes) for exact closest-point queries
     (`pf_surface_*`): the search inside the ICP pre-alignment."""
@@ -611,8 +619,48 @@ class DeviceSurface(object):
                                            f.shape[1], C.byref(h)))
         self._h = h
         self.n, self.n_faces = pts.shape[0], f.shape[0]
+        self.points, self.faces = pts, f  # host arrays, for pf_surface_prepare_signed and topology()
+        self._topology = None  # edge counts once the signed structure is built
         _live_graphs.add(self)
         self.ctx._children.add(self)
+
+    def _prepare_signed(self):
+        if self._topology is None:
+            t = np.zeros(4, dtype=np.int64)
+            _check(self._lib.pf_surface_prepare_signed(self._h, _f64(self.points), self.faces.ctypes.data_as(_i32p),
+                                                       t.ctypes.data_as(_i64p)))
+            self._topology = t
+        return self._topology
+
+    def topology(self):
+        """Edges of the fan triangles (built on the device with the signed structure): `n_edges`,
+        `n_boundary_edges` (one triangle), `n_nonmanifold_edges` (three or more), `n_inconsistent_edges` (two
+        triangles that traverse it in the same direction), `closed` (no boundary edge), and the signed `volume`
+        (sum of det / 6 over the triangles, host numpy): negative when the faces point inward."""
+        t = self._prepare_signed()
+        tri = _fan_triangles(self.faces)
+        a, b, c = self.points[tri[:, 0]], self.points[tri[:, 1]], self.points[tri[:, 2]]
+        volume = float(np.sum(np.einsum("ij,ij->i", a, np.cross(b, c)))) / 6.0
+        return {"n_edges": int(t[0]), "n_boundary_edges": int(t[1]), "n_nonmanifold_edges": int(t[2]),
+                "n_inconsistent_edges": int(t[3]), "closed": bool(t[1] == 0), "volume": volume}
+
+    def signed_distance(self, queries):
+        """(sd (q,) f64, face (q,) i32, feature (q,) i32, n_ambiguous int) of every query (`pf_surface_signed_distance`):
+        |sd| is sqrt of `distance`'s d2 bit for bit and face its face; sd > 0 on the side the face normals point to
+        (outside of an outward-oriented closed mesh).  feature: 0 face, 1 edge, 2 vertex the closest point lies on (-1
+        for a non-finite query, which gives NaN).  n_ambiguous: queries off the surface with a zero pseudonormal
+        component (returned positive).  Builds the signed structure on first use."""
+        q = _c_f64(queries)
+        if q.ndim != 2 or q.shape[1] != 3 or q.shape[0] == 0:
+            raise ValueError("queries must be a non-empty (n, 3) array")
+        self._prepare_signed()
+        sd = np.empty(len(q), dtype=np.float64)
+        face = np.empty(len(q), dtype=np.int32)
+        feature = np.empty(len(q), dtype=np.int32)
+        amb = C.c_int64(0)
+        _check(self._lib.pf_surface_signed_distance(self._h, _f64(q), len(q), _f64(sd), face.ctypes.data_as(_i32p),
+                                                    feature.ctypes.data_as(_i32p), C.byref(amb)))
+        return sd, face, feature, int(amb.value)
 
     def closest(self, queries):
         """(points (q,3) f64, face (q,) i32, squared distance (q,) f64) of the closest surface point of each query."""

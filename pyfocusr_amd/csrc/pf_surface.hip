@@ -20,6 +20,9 @@
 //           per step on that chain of dependent loads.
 // The arithmetic of closest_on_triangle is Ericson's region walk, operation for operation the one in
 // oracle/icp_port.py (compiled with -ffp-contract=off), so points and distances are bit-identical to it.
+// Signed distances (pf_surface_prepare_signed / pf_surface_signed_distance, at the end of the file) add
+// angle-weighted pseudonormals, built once per surface on request, and one per-query kernel after the unchanged
+// k_distance search that names the feature (face, edge, vertex) of the winning triangle the closest point lies on.
 #include <hipcub/hipcub.hpp>
 
 #include <cmath>
@@ -36,6 +39,12 @@ struct pf_surface {
     double* box = nullptr;       // [n_chunks][6] lo xyz, hi xyz
     double* sbox = nullptr;      // [n_super][6] boxes of 64 consecutive chunks
     int64_t n_super = 0;
+    // signed distances (pf_surface_prepare_signed; NULL until then)
+    double* pts = nullptr;       // [n_points][3]
+    int32_t* faces = nullptr;    // [n_faces][vpf]
+    double* tnrm = nullptr;      // [n_tri][3] unit face normal of triangle (face * (vpf-2) + fan position)
+    double* enrm = nullptr;      // [n_tri][3 edge slots][3] edge pseudonormal; slot j = edge (corner j, corner j+1)
+    double* vnrm = nullptr;      // [n_points][3] angle-weighted vertex pseudonormal
 };
 
 namespace {
@@ -200,6 +209,63 @@ __device__ __forceinline__ void closest_on_triangle(const double p[3], const dou
     const double v = vb * denom, w = vc * denom;
 #pragma unroll
     for (int k = 0; k < 3; ++k) out[k] = (a[k] + ab[k] * v) + ac[k] * w;
+}
+
+// closest_on_triangle, same operations in the same order, that also names the Voronoi region of the result:
+// 0 1 2 = corner a b c, 3 = edge ab, 4 = edge bc, 5 = edge ca, 6 = interior (PF_REGION_*)
+enum { PF_REGION_EDGE_AB = 3, PF_REGION_EDGE_BC = 4, PF_REGION_EDGE_CA = 5, PF_REGION_FACE = 6 };
+__device__ __forceinline__ int closest_on_triangle_region(const double p[3], const double a[3], const double b[3], const double c[3],
+                                                          double out[3]) {
+    double ab[3], ac[3], ap[3], bp[3], cp[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        ab[k] = b[k] - a[k];
+        ac[k] = c[k] - a[k];
+        ap[k] = p[k] - a[k];
+        bp[k] = p[k] - b[k];
+        cp[k] = p[k] - c[k];
+    }
+    const double d1 = dot3(ab, ap), d2 = dot3(ac, ap);
+    if (d1 <= 0.0 && d2 <= 0.0) {
+        out[0] = a[0], out[1] = a[1], out[2] = a[2];
+        return 0;
+    }
+    const double d3 = dot3(ab, bp), d4 = dot3(ac, bp);
+    if (d3 >= 0.0 && d4 <= d3) {
+        out[0] = b[0], out[1] = b[1], out[2] = b[2];
+        return 1;
+    }
+    const double vc = d1 * d4 - d3 * d2;
+    if (vc <= 0.0 && d1 >= 0.0 && d3 <= 0.0) {
+        const double v = d1 / (d1 - d3);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) out[k] = a[k] + v * ab[k];
+        return PF_REGION_EDGE_AB;
+    }
+    const double d5 = dot3(ab, cp), d6 = dot3(ac, cp);
+    if (d6 >= 0.0 && d5 <= d6) {
+        out[0] = c[0], out[1] = c[1], out[2] = c[2];
+        return 2;
+    }
+    const double vb = d5 * d2 - d1 * d6;
+    if (vb <= 0.0 && d2 >= 0.0 && d6 <= 0.0) {
+        const double w = d2 / (d2 - d6);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) out[k] = a[k] + w * ac[k];
+        return PF_REGION_EDGE_CA;
+    }
+    const double va = d3 * d6 - d5 * d4;
+    if (va <= 0.0 && (d4 - d3) >= 0.0 && (d5 - d6) >= 0.0) {
+        const double w = (d4 - d3) / ((d4 - d3) + (d5 - d6));
+#pragma unroll
+        for (int k = 0; k < 3; ++k) out[k] = b[k] + w * (c[k] - b[k]);
+        return PF_REGION_EDGE_BC;
+    }
+    const double denom = 1.0 / (va + vb + vc);
+    const double v = vb * denom, w = vc * denom;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) out[k] = (a[k] + ab[k] * v) + ac[k] * w;
+    return PF_REGION_FACE;
 }
 
 __device__ __forceinline__ double box_dist2(const double p[3], const double* __restrict__ bx) {
@@ -615,6 +681,234 @@ __global__ __launch_bounds__(PF_BLOCK) void k_distance_stats(const double* __res
     }
 }
 
+// ---- signed distances (pf_surface_prepare_signed, pf_surface_signed_distance) -----------------------------------
+// Angle-weighted pseudonormals (Baerentzen & Aanaes 2005) of the fan triangles: the sign of (p - c) . n over the
+// feature (interior, edge, corner) of the winning triangle that the closest point c lies on is the exact inside /
+// outside sign on a closed, consistently oriented mesh.  Fan diagonals are edges like any other.  Every sum runs in a
+// fixed order (triangle order for an edge, sorted (vertex, half-edge) order for a vertex): no floating-point atomics.
+
+// per triangle: unit normal (zero for a zero-area or non-finite triangle), corner angles atan2(|u x v|, u . v) (zero
+// there too); per half-edge h = 3t + j (corner j -> corner j+1): the key (min << nb | max) of its edge, and its corner's
+// vertex (for the vertex sums)
+__global__ __launch_bounds__(PF_BLOCK) void k_tri_normals(const double* __restrict__ pts, const int32_t* __restrict__ faces,
+                                                          int32_t vpf, int64_t n_tri, int nb, double* __restrict__ tnrm,
+                                                          double* __restrict__ tang, unsigned long long* __restrict__ ekey,
+                                                          unsigned* __restrict__ vkey, int32_t* __restrict__ hval) {
+    const int64_t t = (int64_t)blockIdx.x * PF_BLOCK + threadIdx.x;
+    if (t >= n_tri) return;
+    int32_t v[3];
+    tri_vertices(faces, vpf, t, v);
+    double x[3][3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+        for (int a = 0; a < 3; ++a) x[c][a] = pts[3 * (int64_t)v[c] + a];
+    const double u[3] = {x[1][0] - x[0][0], x[1][1] - x[0][1], x[1][2] - x[0][2]};
+    const double w[3] = {x[2][0] - x[0][0], x[2][1] - x[0][1], x[2][2] - x[0][2]};
+    const double cr[3] = {u[1] * w[2] - u[2] * w[1], u[2] * w[0] - u[0] * w[2], u[0] * w[1] - u[1] * w[0]};
+    const double len = sqrt(dot3(cr, cr));
+    const bool area = len > 0.0 && std::isfinite(len);
+#pragma unroll
+    for (int a = 0; a < 3; ++a) tnrm[3 * t + a] = area ? cr[a] / len : 0.0;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        const int j1 = j == 2 ? 0 : j + 1, j2 = j == 0 ? 2 : j - 1;
+        const double e1[3] = {x[j1][0] - x[j][0], x[j1][1] - x[j][1], x[j1][2] - x[j][2]};
+        const double e2[3] = {x[j2][0] - x[j][0], x[j2][1] - x[j][1], x[j2][2] - x[j][2]};
+        const double c[3] = {e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0]};
+        tang[3 * t + j] = area ? atan2(sqrt(dot3(c, c)), dot3(e1, e2)) : 0.0;
+        const unsigned lo = (unsigned)min(v[j], v[j1]), hi = (unsigned)max(v[j], v[j1]);
+        ekey[3 * t + j] = ((unsigned long long)lo << nb) | hi;
+        vkey[3 * t + j] = (unsigned)v[j];
+        hval[3 * t + j] = (int32_t)(3 * t + j);
+    }
+}
+
+// one thread per edge (the first half-edge of each run of equal keys; runs are in triangle order, the sort being
+// stable): the sum of its triangles' normals, stored for each of its half-edges; counts edges | boundary | non-manifold
+// | inconsistent (two triangles that traverse it in the same direction)
+__global__ __launch_bounds__(PF_BLOCK) void k_edge_normals(const unsigned long long* __restrict__ ekey, const int32_t* __restrict__ hedge,
+                                                           int64_t n_half, const int32_t* __restrict__ faces, int32_t vpf,
+                                                           const double* __restrict__ tnrm, double* __restrict__ enrm,
+                                                           unsigned long long* __restrict__ counts) {
+    const int64_t i = (int64_t)blockIdx.x * PF_BLOCK + threadIdx.x;
+    if (i >= n_half || (i > 0 && ekey[i - 1] == ekey[i])) return;
+    const unsigned long long key = ekey[i];
+    int64_t end = i;
+    double s[3] = {0.0, 0.0, 0.0};
+    for (; end < n_half && ekey[end] == key; ++end) {
+        const int64_t t = hedge[end] / 3;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) s[a] += tnrm[3 * t + a];
+    }
+    for (int64_t k = i; k < end; ++k)
+#pragma unroll
+        for (int a = 0; a < 3; ++a) enrm[3 * (int64_t)hedge[k] + a] = s[a];
+    const int64_t m = end - i;
+    atomicAdd(&counts[0], 1ull);  // integer counts: the same on every run
+    if (m == 1) atomicAdd(&counts[1], 1ull);
+    if (m > 2) atomicAdd(&counts[2], 1ull);
+    if (m == 2) {
+        bool fwd[2];
+        for (int k = 0; k < 2; ++k) {
+            const int32_t h = hedge[i + k];
+            int32_t v[3];
+            tri_vertices(faces, vpf, h / 3, v);
+            const int j = h % 3;
+            fwd[k] = v[j] < v[j == 2 ? 0 : j + 1];
+        }
+        if (fwd[0] == fwd[1]) atomicAdd(&counts[3], 1ull);
+    }
+}
+
+// one thread per vertex: sum of corner angle x unit normal over its corners, in sorted (vertex, half-edge) order
+__global__ __launch_bounds__(PF_BLOCK) void k_vertex_normals(const unsigned* __restrict__ vkey, const int32_t* __restrict__ hedge,
+                                                             int64_t n_half, int64_t n_points, const double* __restrict__ tnrm,
+                                                             const double* __restrict__ tang, double* __restrict__ vnrm) {
+    const int64_t v = (int64_t)blockIdx.x * PF_BLOCK + threadIdx.x;
+    if (v >= n_points) return;
+    int64_t lo = 0, hi = n_half;  // first position with key >= v
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (vkey[mid] < (unsigned)v) lo = mid + 1;
+        else hi = mid;
+    }
+    double s[3] = {0.0, 0.0, 0.0};
+    for (; lo < n_half && vkey[lo] == (unsigned)v; ++lo) {
+        const int32_t h = hedge[lo];
+        const double ang = tang[h];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) s[a] += ang * tnrm[3 * (int64_t)(h / 3) + a];
+    }
+#pragma unroll
+    for (int a = 0; a < 3; ++a) vnrm[3 * v + a] = s[a];
+}
+
+// one thread per query, after k_distance: the fan triangles of the winning face are evaluated again with the same
+// arithmetic and tie rule, which gives the search's winner, its closest point and its region; the sign is that of
+// (p - c) . pseudonormal of the region's feature, the magnitude sqrt of the search's own d2
+__global__ __launch_bounds__(PF_BLOCK) void k_signed(const double* __restrict__ pts, const int32_t* __restrict__ faces, int32_t vpf,
+                                                     const double* __restrict__ tnrm, const double* __restrict__ enrm,
+                                                     const double* __restrict__ vnrm, const double* __restrict__ qry, int64_t n_qry,
+                                                     const double* __restrict__ d2s, const int32_t* __restrict__ face,
+                                                     double* __restrict__ out_sd, int32_t* __restrict__ out_feature,
+                                                     unsigned long long* __restrict__ n_ambiguous) {
+    const int64_t i = (int64_t)blockIdx.x * PF_BLOCK + threadIdx.x;
+    if (i >= n_qry) return;
+    const double p[3] = {qry[3 * i], qry[3 * i + 1], qry[3 * i + 2]};
+    const double d2 = d2s[i];
+    const int32_t f = face[i];
+    if (f < 0) {  // a non-finite query (NaN) or no finite triangle (+inf)
+        out_sd[i] = sqrt(d2);
+        out_feature[i] = -1;
+        return;
+    }
+    const int32_t per = vpf - 2;
+    double bd2 = std::numeric_limits<double>::infinity(), bq[3] = {0.0, 0.0, 0.0};
+    int32_t bt = 0x7fffffff, bv[3] = {0, 0, 0};
+    int breg = PF_REGION_FACE;
+    for (int32_t j = 0; j < per; ++j) {
+        const int32_t t = f * per + j;
+        int32_t v[3];
+        tri_vertices(faces, vpf, t, v);
+        const double a[3] = {pts[3 * (int64_t)v[0]], pts[3 * (int64_t)v[0] + 1], pts[3 * (int64_t)v[0] + 2]};
+        const double b[3] = {pts[3 * (int64_t)v[1]], pts[3 * (int64_t)v[1] + 1], pts[3 * (int64_t)v[1] + 2]};
+        const double c[3] = {pts[3 * (int64_t)v[2]], pts[3 * (int64_t)v[2] + 1], pts[3 * (int64_t)v[2] + 2]};
+        double q[3];
+        const int reg = closest_on_triangle_region(p, a, b, c, q);
+        const double dx = p[0] - q[0], dy = p[1] - q[1], dz = p[2] - q[2];
+        const double e2 = dx * dx + dy * dy + dz * dz;
+        if (better(e2, t, bd2, bt)) {
+            bd2 = e2, bt = t, breg = reg;
+            bq[0] = q[0], bq[1] = q[1], bq[2] = q[2];
+            bv[0] = v[0], bv[1] = v[1], bv[2] = v[2];
+        }
+    }
+    double n[3] = {0.0, 0.0, 0.0};
+    int feature = 0;
+    if (bt != 0x7fffffff) {
+        const double* src;
+        if (breg == PF_REGION_FACE) {
+            src = tnrm + 3 * (int64_t)bt;
+        } else if (breg >= PF_REGION_EDGE_AB) {
+            src = enrm + 9 * (int64_t)bt + 3 * (breg - PF_REGION_EDGE_AB);
+            feature = 1;
+        } else {
+            src = vnrm + 3 * (int64_t)bv[breg];
+            feature = 2;
+        }
+        n[0] = src[0], n[1] = src[1], n[2] = src[2];
+    }
+    const double s = (p[0] - bq[0]) * n[0] + (p[1] - bq[1]) * n[1] + (p[2] - bq[2]) * n[2];
+    const double d = sqrt(d2);
+    double sd = d;
+    if (d2 == 0.0) sd = 0.0;
+    else if (s < 0.0) sd = -d;
+    else if (!(s > 0.0)) atomicAdd(n_ambiguous, 1ull);  // zero (or NaN) pseudonormal component: + and counted
+    out_sd[i] = sd;
+    out_feature[i] = feature;
+}
+
+Box3 query_box(const double* qry, int64_t n_qry) {  // Morton box of the finite queries
+    Box3 bb;
+    for (int a = 0; a < 3; ++a) {
+        double lo = std::numeric_limits<double>::infinity(), hi = -lo;
+        for (int64_t i = 0; i < n_qry; ++i) {
+            const double x = qry[3 * i + a];
+            if (!std::isfinite(x)) continue;
+            if (x < lo) lo = x;
+            if (x > hi) hi = x;
+        }
+        bb.lo[a] = lo;
+        bb.ext[a] = hi - lo;
+        if (!(bb.ext[a] > 0.0) || !std::isfinite(bb.ext[a])) bb.ext[a] = 0.0;
+    }
+    return bb;
+}
+
+// the search of pf_surface_distance on queries already in HBM (d_q): Morton sort, k_distance, the fixed-order
+// statistics.  d_d2 / d_face may be NULL; d_stats [PF_DIST_STATS] may not.
+hipError_t distance_search(pf_surface* s, hipStream_t st, const double* d_q, int64_t n_qry, const Box3& bb, double* d_d2,
+                           int32_t* d_face, double* d_stats) {
+    // 16 queries per wave once that gives >= 4096 waves (4 per SIMD), else 4 (measured: profiles/surface_distance.md)
+    const bool big = n_qry >= (int64_t)16 * 4096;
+    const int64_t n_pack = big ? (n_qry + 15) / 16 : (n_qry + 3) / 4;
+    double* d_part = nullptr;
+    unsigned *k0 = nullptr, *k1 = nullptr;
+    int32_t *v0 = nullptr, *v1 = nullptr;
+    void* tmp = nullptr;
+    size_t need = 0;
+    hipError_t e = hipSuccess;
+    do {
+        if ((e = pf_malloc(st, (void**)&k0, sizeof(unsigned) * n_qry)) != hipSuccess) break;
+        if ((e = pf_malloc(st, (void**)&k1, sizeof(unsigned) * n_qry)) != hipSuccess) break;
+        if ((e = pf_malloc(st, (void**)&v0, sizeof(int32_t) * n_qry)) != hipSuccess) break;
+        if ((e = pf_malloc(st, (void**)&v1, sizeof(int32_t) * n_qry)) != hipSuccess) break;
+        if ((e = pf_malloc(st, (void**)&d_part, sizeof(double) * PF_DIST_STATS * n_pack)) != hipSuccess) break;
+        k_qry_keys<<<nblk(n_qry), PF_BLOCK, 0, st>>>(d_q, n_qry, bb, k0, v0);
+        if ((e = hipGetLastError()) != hipSuccess) break;
+        if ((e = hipcub::DeviceRadixSort::SortPairs(nullptr, need, k0, k1, v0, v1, (int)n_qry, 0, 30, st)) != hipSuccess) break;
+        if ((e = pf_malloc(st, &tmp, need)) != hipSuccess) break;
+        if ((e = hipcub::DeviceRadixSort::SortPairs(tmp, need, k0, k1, v0, v1, (int)n_qry, 0, 30, st)) != hipSuccess) break;
+        if (big)
+            k_distance<16><<<(unsigned)n_pack, PF_WAVE, 0, st>>>(s->tri, s->tri_orig, s->box, s->sbox, s->n_tri, s->n_chunks, s->n_super,
+                                                                 d_q, v1, n_qry, s->vpf - 2, d_d2, d_face, d_part);
+        else
+            k_distance<4><<<(unsigned)n_pack, PF_WAVE, 0, st>>>(s->tri, s->tri_orig, s->box, s->sbox, s->n_tri, s->n_chunks, s->n_super,
+                                                                d_q, v1, n_qry, s->vpf - 2, d_d2, d_face, d_part);
+        k_distance_stats<<<1, PF_BLOCK, 0, st>>>(d_part, n_pack, d_stats);
+        e = hipGetLastError();
+    } while (0);
+    // the cache hands these blocks out again only to work queued behind the kernels above
+    pf_free(st, k0);
+    pf_free(st, k1);
+    pf_free(st, v0);
+    pf_free(st, v1);
+    pf_free(st, tmp);
+    pf_free(st, d_part);
+    return e;
+}
+
 }  // namespace
 
 extern "C" {
@@ -628,6 +922,11 @@ void pf_surface_free(pf_surface* s) {
     pf_free(st, s->tri_orig);
     pf_free(st, s->box);
     pf_free(st, s->sbox);
+    pf_free(st, s->pts);
+    pf_free(st, s->faces);
+    pf_free(st, s->tnrm);
+    pf_free(st, s->enrm);
+    pf_free(st, s->vnrm);
     delete s;
 }
 
@@ -745,74 +1044,157 @@ int pf_surface_closest(pf_surface* s, const double* qry, int64_t n_qry, double* 
 int pf_surface_distance(pf_surface* s, const double* qry, int64_t n_qry, double* out_d2, int32_t* out_face, double* stats) {
     PF_CHECK(s && qry, PF_E_ARG, "pf_surface_distance: NULL argument");
     PF_CHECK(n_qry >= 1 && n_qry < ((int64_t)1 << 31), PF_E_ARG, "pf_surface_distance: n_qry = %lld out of range", (long long)n_qry);
-    Box3 bb;  // Morton box of the finite queries
-    for (int a = 0; a < 3; ++a) {
-        double lo = std::numeric_limits<double>::infinity(), hi = -lo;
-        for (int64_t i = 0; i < n_qry; ++i) {
-            const double x = qry[3 * i + a];
-            if (!std::isfinite(x)) continue;
-            if (x < lo) lo = x;
-            if (x > hi) hi = x;
-        }
-        bb.lo[a] = lo;
-        bb.ext[a] = hi - lo;
-        if (!(bb.ext[a] > 0.0) || !std::isfinite(bb.ext[a])) bb.ext[a] = 0.0;
-    }
+    const Box3 bb = query_box(qry, n_qry);
     PF_HIP(hipSetDevice(s->ctx->device));
     hipStream_t st = s->ctx->stream;
-    // 16 queries per wave once that gives >= 4096 waves (4 per SIMD), else 4 (measured: profiles/surface_distance.md)
-    const bool big = n_qry >= (int64_t)16 * 4096;
-    const int64_t n_pack = big ? (n_qry + 15) / 16 : (n_qry + 3) / 4;
-    double *d_q = nullptr, *d_d2 = nullptr, *d_part = nullptr, *d_stats = nullptr;
+    double *d_q = nullptr, *d_d2 = nullptr, *d_stats = nullptr;
     int32_t* d_face = nullptr;
-    unsigned *k0 = nullptr, *k1 = nullptr;
-    int32_t *v0 = nullptr, *v1 = nullptr;
-    void* tmp = nullptr;
-    size_t need = 0;
     hipError_t e = hipSuccess;
     do {
         if ((e = pf_malloc(st, (void**)&d_q, sizeof(double) * 3 * n_qry)) != hipSuccess) break;
-        if ((e = pf_malloc(st, (void**)&k0, sizeof(unsigned) * n_qry)) != hipSuccess) break;
-        if ((e = pf_malloc(st, (void**)&k1, sizeof(unsigned) * n_qry)) != hipSuccess) break;
-        if ((e = pf_malloc(st, (void**)&v0, sizeof(int32_t) * n_qry)) != hipSuccess) break;
-        if ((e = pf_malloc(st, (void**)&v1, sizeof(int32_t) * n_qry)) != hipSuccess) break;
         if (out_d2 && (e = pf_malloc(st, (void**)&d_d2, sizeof(double) * n_qry)) != hipSuccess) break;
         if (out_face && (e = pf_malloc(st, (void**)&d_face, sizeof(int32_t) * n_qry)) != hipSuccess) break;
-        if ((e = pf_malloc(st, (void**)&d_part, sizeof(double) * PF_DIST_STATS * n_pack)) != hipSuccess) break;
         if ((e = pf_malloc(st, (void**)&d_stats, sizeof(double) * PF_DIST_STATS)) != hipSuccess) break;
         if ((e = hipMemcpyAsync(d_q, qry, sizeof(double) * 3 * n_qry, hipMemcpyHostToDevice, st)) != hipSuccess) break;
-        k_qry_keys<<<nblk(n_qry), PF_BLOCK, 0, st>>>(d_q, n_qry, bb, k0, v0);
-        if ((e = hipGetLastError()) != hipSuccess) break;
-        if ((e = hipcub::DeviceRadixSort::SortPairs(nullptr, need, k0, k1, v0, v1, (int)n_qry, 0, 30, st)) != hipSuccess) break;
-        if ((e = pf_malloc(st, &tmp, need)) != hipSuccess) break;
-        if ((e = hipcub::DeviceRadixSort::SortPairs(tmp, need, k0, k1, v0, v1, (int)n_qry, 0, 30, st)) != hipSuccess) break;
-        if (big)
-            k_distance<16><<<(unsigned)n_pack, PF_WAVE, 0, st>>>(s->tri, s->tri_orig, s->box, s->sbox, s->n_tri, s->n_chunks, s->n_super,
-                                                                 d_q, v1, n_qry, s->vpf - 2, d_d2, d_face, d_part);
-        else
-            k_distance<4><<<(unsigned)n_pack, PF_WAVE, 0, st>>>(s->tri, s->tri_orig, s->box, s->sbox, s->n_tri, s->n_chunks, s->n_super,
-                                                                d_q, v1, n_qry, s->vpf - 2, d_d2, d_face, d_part);
-        k_distance_stats<<<1, PF_BLOCK, 0, st>>>(d_part, n_pack, d_stats);
-        if ((e = hipGetLastError()) != hipSuccess) break;
+        if ((e = distance_search(s, st, d_q, n_qry, bb, d_d2, d_face, d_stats)) != hipSuccess) break;
         if (out_d2 && (e = hipMemcpyAsync(out_d2, d_d2, sizeof(double) * n_qry, hipMemcpyDeviceToHost, st)) != hipSuccess) break;
         if (out_face && (e = hipMemcpyAsync(out_face, d_face, sizeof(int32_t) * n_qry, hipMemcpyDeviceToHost, st)) != hipSuccess) break;
         if (stats && (e = hipMemcpyAsync(stats, d_stats, sizeof(double) * PF_DIST_STATS, hipMemcpyDeviceToHost, st)) != hipSuccess) break;
         e = hipStreamSynchronize(st);
     } while (0);
     pf_free(st, d_q);
-    pf_free(st, k0);
-    pf_free(st, k1);
-    pf_free(st, v0);
-    pf_free(st, v1);
-    pf_free(st, tmp);
     pf_free(st, d_d2);
     pf_free(st, d_face);
-    pf_free(st, d_part);
     pf_free(st, d_stats);
     if (e != hipSuccess) {
         pf_set_error("pf_surface_distance: %s", hipGetErrorString(e));
         return PF_E_HIP;
     }
+    return PF_OK;
+}
+
+int pf_surface_prepare_signed(pf_surface* s, const double* points, const int32_t* faces, int64_t* topology) {
+    PF_CHECK(s && points && faces, PF_E_ARG, "pf_surface_prepare_signed: NULL argument");
+    const int64_t n = s->n_points, T = s->n_tri, H = 3 * T, nf = s->n_faces * s->vpf;
+    PF_CHECK(H < ((int64_t)1 << 31), PF_E_ARG, "pf_surface_prepare_signed: %lld half-edges out of range", (long long)H);
+    for (int64_t i = 0; i < nf; ++i)  // the same arrays as at pf_surface_create, or at least indices within them
+        PF_CHECK(faces[i] >= 0 && faces[i] < n, PF_E_ARG, "pf_surface_prepare_signed: face %lld references vertex %d of %lld",
+                 (long long)(i / s->vpf), faces[i], (long long)n);
+    int nb = 1;  // bits of a vertex index
+    while (nb < 31 && ((int64_t)1 << nb) < n) ++nb;
+    PF_HIP(hipSetDevice(s->ctx->device));
+    hipStream_t st = s->ctx->stream;
+    // a second call builds afresh from the arrays it is given
+    pf_free(st, s->pts), pf_free(st, s->faces), pf_free(st, s->tnrm), pf_free(st, s->enrm), pf_free(st, s->vnrm);
+    s->pts = s->tnrm = s->enrm = s->vnrm = nullptr;
+    s->faces = nullptr;
+    double* tang = nullptr;
+    unsigned long long *ek0 = nullptr, *ek1 = nullptr, *cnt = nullptr;
+    unsigned *vk0 = nullptr, *vk1 = nullptr;
+    int32_t *h0 = nullptr, *h1 = nullptr;
+    void* tmp = nullptr;
+    size_t need_e = 0, need_v = 0;
+    unsigned long long counts[4] = {0, 0, 0, 0};
+    hipError_t e = hipSuccess;
+    do {
+        if ((e = pf_malloc(st, (void**)&s->pts, sizeof(double) * 3 * n)) != hipSuccess) break;
+        if ((e = pf_malloc(st, (void**)&s->faces, sizeof(int32_t) * nf)) != hipSuccess) break;
+        if ((e = pf_malloc(st, (void**)&s->tnrm, sizeof(double) * 3 * T)) != hipSuccess) break;
+        if ((e = pf_malloc(st, (void**)&s->enrm, sizeof(double) * 3 * H)) != hipSuccess) break;
+        if ((e = pf_malloc(st, (void**)&s->vnrm, sizeof(double) * 3 * n)) != hipSuccess) break;
+        if ((e = pf_malloc(st, (void**)&tang, sizeof(double) * H)) != hipSuccess) break;
+        if ((e = pf_malloc(st, (void**)&ek0, sizeof(unsigned long long) * H)) != hipSuccess) break;
+        if ((e = pf_malloc(st, (void**)&ek1, sizeof(unsigned long long) * H)) != hipSuccess) break;
+        if ((e = pf_malloc(st, (void**)&vk0, sizeof(unsigned) * H)) != hipSuccess) break;
+        if ((e = pf_malloc(st, (void**)&vk1, sizeof(unsigned) * H)) != hipSuccess) break;
+        if ((e = pf_malloc(st, (void**)&h0, sizeof(int32_t) * H)) != hipSuccess) break;
+        if ((e = pf_malloc(st, (void**)&h1, sizeof(int32_t) * H)) != hipSuccess) break;
+        if ((e = pf_malloc(st, (void**)&cnt, sizeof(unsigned long long) * 4)) != hipSuccess) break;
+        if ((e = hipMemcpyAsync(s->pts, points, sizeof(double) * 3 * n, hipMemcpyHostToDevice, st)) != hipSuccess) break;
+        if ((e = hipMemcpyAsync(s->faces, faces, sizeof(int32_t) * nf, hipMemcpyHostToDevice, st)) != hipSuccess) break;
+        if ((e = hipMemsetAsync(cnt, 0, sizeof(unsigned long long) * 4, st)) != hipSuccess) break;
+        k_tri_normals<<<nblk(T), PF_BLOCK, 0, st>>>(s->pts, s->faces, s->vpf, T, nb, s->tnrm, tang, ek0, vk0, h0);
+        if ((e = hipGetLastError()) != hipSuccess) break;
+        // both sorts are stable and start from half-edge order: equal keys stay in triangle order
+        if ((e = hipcub::DeviceRadixSort::SortPairs(nullptr, need_e, ek0, ek1, h0, h1, (int)H, 0, 2 * nb, st)) != hipSuccess) break;
+        if ((e = hipcub::DeviceRadixSort::SortPairs(nullptr, need_v, vk0, vk1, h0, h1, (int)H, 0, nb, st)) != hipSuccess) break;
+        if ((e = pf_malloc(st, &tmp, need_e > need_v ? need_e : need_v)) != hipSuccess) break;
+        if ((e = hipcub::DeviceRadixSort::SortPairs(tmp, need_e, ek0, ek1, h0, h1, (int)H, 0, 2 * nb, st)) != hipSuccess) break;
+        k_edge_normals<<<nblk(H), PF_BLOCK, 0, st>>>(ek1, h1, H, s->faces, s->vpf, s->tnrm, s->enrm, cnt);
+        if ((e = hipGetLastError()) != hipSuccess) break;
+        if ((e = hipcub::DeviceRadixSort::SortPairs(tmp, need_v, vk0, vk1, h0, h1, (int)H, 0, nb, st)) != hipSuccess) break;
+        k_vertex_normals<<<nblk(n), PF_BLOCK, 0, st>>>(vk1, h1, H, n, s->tnrm, tang, s->vnrm);
+        if ((e = hipGetLastError()) != hipSuccess) break;
+        if ((e = hipMemcpyAsync(counts, cnt, sizeof(counts), hipMemcpyDeviceToHost, st)) != hipSuccess) break;
+        e = hipStreamSynchronize(st);  // the host arrays may go away after the call
+    } while (0);
+    pf_free(st, tang);
+    pf_free(st, ek0);
+    pf_free(st, ek1);
+    pf_free(st, vk0);
+    pf_free(st, vk1);
+    pf_free(st, h0);
+    pf_free(st, h1);
+    pf_free(st, cnt);
+    pf_free(st, tmp);
+    if (e != hipSuccess) {
+        pf_free(st, s->pts), pf_free(st, s->faces), pf_free(st, s->tnrm), pf_free(st, s->enrm), pf_free(st, s->vnrm);
+        s->pts = s->tnrm = s->enrm = s->vnrm = nullptr;
+        s->faces = nullptr;
+        pf_set_error("pf_surface_prepare_signed: %s", hipGetErrorString(e));
+        return PF_E_HIP;
+    }
+    if (topology)
+        for (int k = 0; k < 4; ++k) topology[k] = (int64_t)counts[k];
+    return PF_OK;
+}
+
+int pf_surface_signed_distance(pf_surface* s, const double* qry, int64_t n_qry, double* out_sd, int32_t* out_face,
+                               int32_t* out_feature, int64_t* n_ambiguous) {
+    PF_CHECK(s && qry, PF_E_ARG, "pf_surface_signed_distance: NULL argument");
+    PF_CHECK(n_qry >= 1 && n_qry < ((int64_t)1 << 31), PF_E_ARG, "pf_surface_signed_distance: n_qry = %lld out of range",
+             (long long)n_qry);
+    PF_CHECK(s->vnrm, PF_E_ARG, "pf_surface_signed_distance: pf_surface_prepare_signed has not been called");
+    const Box3 bb = query_box(qry, n_qry);
+    PF_HIP(hipSetDevice(s->ctx->device));
+    hipStream_t st = s->ctx->stream;
+    double *d_q = nullptr, *d_d2 = nullptr, *d_stats = nullptr, *d_sd = nullptr;
+    int32_t *d_face = nullptr, *d_feat = nullptr;
+    unsigned long long* d_amb = nullptr;
+    unsigned long long amb = 0;
+    hipError_t e = hipSuccess;
+    do {
+        if ((e = pf_malloc(st, (void**)&d_q, sizeof(double) * 3 * n_qry)) != hipSuccess) break;
+        if ((e = pf_malloc(st, (void**)&d_d2, sizeof(double) * n_qry)) != hipSuccess) break;
+        if ((e = pf_malloc(st, (void**)&d_face, sizeof(int32_t) * n_qry)) != hipSuccess) break;
+        if ((e = pf_malloc(st, (void**)&d_stats, sizeof(double) * PF_DIST_STATS)) != hipSuccess) break;
+        if ((e = pf_malloc(st, (void**)&d_sd, sizeof(double) * n_qry)) != hipSuccess) break;
+        if ((e = pf_malloc(st, (void**)&d_feat, sizeof(int32_t) * n_qry)) != hipSuccess) break;
+        if ((e = pf_malloc(st, (void**)&d_amb, sizeof(unsigned long long))) != hipSuccess) break;
+        if ((e = hipMemcpyAsync(d_q, qry, sizeof(double) * 3 * n_qry, hipMemcpyHostToDevice, st)) != hipSuccess) break;
+        if ((e = hipMemsetAsync(d_amb, 0, sizeof(unsigned long long), st)) != hipSuccess) break;
+        if ((e = distance_search(s, st, d_q, n_qry, bb, d_d2, d_face, d_stats)) != hipSuccess) break;
+        k_signed<<<nblk(n_qry), PF_BLOCK, 0, st>>>(s->pts, s->faces, s->vpf, s->tnrm, s->enrm, s->vnrm, d_q, n_qry, d_d2, d_face,
+                                                   d_sd, d_feat, d_amb);
+        if ((e = hipGetLastError()) != hipSuccess) break;
+        if (out_sd && (e = hipMemcpyAsync(out_sd, d_sd, sizeof(double) * n_qry, hipMemcpyDeviceToHost, st)) != hipSuccess) break;
+        if (out_face && (e = hipMemcpyAsync(out_face, d_face, sizeof(int32_t) * n_qry, hipMemcpyDeviceToHost, st)) != hipSuccess) break;
+        if (out_feature && (e = hipMemcpyAsync(out_feature, d_feat, sizeof(int32_t) * n_qry, hipMemcpyDeviceToHost, st)) != hipSuccess) break;
+        if ((e = hipMemcpyAsync(&amb, d_amb, sizeof(amb), hipMemcpyDeviceToHost, st)) != hipSuccess) break;
+        e = hipStreamSynchronize(st);
+    } while (0);
+    pf_free(st, d_q);
+    pf_free(st, d_d2);
+    pf_free(st, d_face);
+    pf_free(st, d_stats);
+    pf_free(st, d_sd);
+    pf_free(st, d_feat);
+    pf_free(st, d_amb);
+    if (e != hipSuccess) {
+        pf_set_error("pf_surface_signed_distance: %s", hipGetErrorString(e));
+        return PF_E_HIP;
+    }
+    if (n_ambiguous) *n_ambiguous = (int64_t)amb;
     return PF_OK;
 }
 

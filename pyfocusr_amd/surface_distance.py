@@ -6,6 +6,11 @@ other is the exact minimum over all triangles (polygons fan-triangulated), compu
 `pf_surface_distance` (`_hip.DeviceSurface.distance`): the same arithmetic and tie rule as the ICP search, so the
 squared distances equal a brute-force scan bit for bit.  The summary of the downloaded distances is host work
 (`summarize_distances`, which needs no device).
+
+Signed distances (`pf_surface_signed_distance`, `_hip.DeviceSurface.signed_distance`) add the side: the sign of
+(p - c) . n with n the angle-weighted pseudonormal of the face, edge or vertex the closest point c lies on.  On a
+closed, consistently oriented mesh with outward faces, inside is negative (as in VTK's vtkImplicitPolyDataDistance);
+the magnitude is the unsigned distance bit for bit.
 """
 import numpy as np
 
@@ -90,29 +95,106 @@ def summarize_distances(d_a_to_b, d_b_to_a=None):
     return out
 
 
-def surface_distance_metrics(mesh_a, mesh_b, symmetric=True, ctx=None, surface_a=None, surface_b=None):
+def signed_point_to_surface_distances(points, mesh, ctx=None, check_orientation=True):
+    """(sd (n,) f64, face (n,) i32): the signed distance of every point to the surface of `mesh` (negative on the side
+    opposite to the face normals: inside an outward-oriented closed mesh) and the face that attains it.  |sd| and face
+    equal `point_to_surface_distances` bit for bit; NaN and -1 for a point with a non-finite coordinate.  `mesh` may
+    also be a `_hip.DeviceSurface`, reused and left open.  With `check_orientation` a mesh whose triangles disagree
+    on their orientation (inconsistent edges) or that has edges in three or more triangles raises ValueError: the sign
+    means nothing there.  Open boundaries are allowed (the sign then follows the face normals nearby)."""
+    q = _query_array(points)
+    built = None
+    if hasattr(mesh, "signed_distance"):  # a DeviceSurface
+        surface = mesh
+    else:
+        pts, faces = _mesh_arrays(mesh)
+        surface = built = _hip.DeviceSurface(pts, faces, ctx=ctx)
+    try:
+        if check_orientation:
+            t = surface.topology()
+            if t["n_inconsistent_edges"] or t["n_nonmanifold_edges"]:
+                raise ValueError("signed distances need a consistently oriented manifold surface: %d inconsistent and %d "
+                                 "non-manifold edges (check_orientation=False to compute them anyway)"
+                                 % (t["n_inconsistent_edges"], t["n_nonmanifold_edges"]))
+        sd, face, _, _ = surface.signed_distance(q)
+    finally:
+        if built is not None:
+            built.close()
+    return sd, face
+
+
+def summarize_signed_distances(sd):
+    """Summary of signed distances (pure numpy, no device): `n` (finite values), `n_nan` (the others, left out),
+    `mean_signed` (the bias), `std_signed`, `min_signed` / `min_signed_vertex` (deepest inside), `max_signed` /
+    `max_signed_vertex` (farthest outside; lowest index on ties), `n_inside` (sd < 0), `n_outside` (sd > 0), `n_on`
+    (sd == 0)."""
+    sd = np.asarray(sd, dtype=np.float64).ravel()
+    fin = np.isfinite(sd)
+    n = int(fin.sum())
+    out = {"n": n, "n_nan": int(sd.size - n)}
+    if n == 0:
+        out.update({"mean_signed": np.nan, "std_signed": np.nan, "min_signed": np.nan, "min_signed_vertex": -1,
+                    "max_signed": np.nan, "max_signed_vertex": -1, "n_inside": 0, "n_outside": 0, "n_on": 0})
+        return out
+    f = sd[fin]
+    lo = int(np.argmin(np.where(fin, sd, np.inf)))  # first index on ties
+    hi = int(np.argmax(np.where(fin, sd, -np.inf)))
+    out.update({"mean_signed": float(np.mean(f)), "std_signed": float(np.std(f)), "min_signed": float(sd[lo]),
+                "min_signed_vertex": lo, "max_signed": float(sd[hi]), "max_signed_vertex": hi,
+                "n_inside": int(np.sum(f < 0)), "n_outside": int(np.sum(f > 0)), "n_on": int(np.sum(f == 0))})
+    return out
+
+
+def signed_distances_on_mesh(mesh, other, name="signed_distance", ctx=None):
+    """Signed distances of `mesh`'s vertices to the surface of `other` (`signed_point_to_surface_distances`, orientation
+    checked), stored on `mesh` as the point-data array `name` (`set_mesh_scalars`; written by `write_vtk_mesh` with
+    17 digits, so they read back exactly).  Returns the distances."""
+    pts, _ = _mesh_arrays(mesh)
+    sd, _ = signed_point_to_surface_distances(pts, other, ctx=ctx)
+    vtk_functions.set_mesh_scalars(mesh, sd, name=name)
+    return sd
+
+
+def surface_distance_metrics(mesh_a, mesh_b, symmetric=True, ctx=None, surface_a=None, surface_b=None, signed=False):
     """Distances from the vertices of `mesh_a` to the surface of `mesh_b` (and, if `symmetric`, from `mesh_b`'s
     vertices to `mesh_a`'s surface), summarised by `summarize_distances`: `mean_a_to_b`, `rms_a_to_b`, `max_a_to_b`,
     `max_a_to_b_vertex`, `p95_a_to_b`, the same for `b_to_a`, `assd`, `hausdorff`, `hausdorff_95`.
 
     Meshes: `PolyMesh`, vtkPolyData or `(points, faces)`; quads and larger polygons are fan-triangulated.
     `surface_a` / `surface_b`: `_hip.DeviceSurface` objects already built from the same meshes, reused and left open
-    (many pairs over one set of meshes build each surface once)."""
+    (many pairs over one set of meshes build each surface once).
+
+    `signed=True` adds `summarize_signed_distances` of each direction, its keys suffixed `_a_to_b` / `_b_to_a`
+    (`mean_signed_a_to_b` is the bias of `mesh_a` against `mesh_b`'s surface; negative = inside it).  Orientation is
+    not checked here; `topology()` of a surface tells whether its signs mean anything."""
     pts_a, faces_a = _mesh_arrays(mesh_a)
     pts_b, faces_b = _mesh_arrays(mesh_b)
     built = []
+    sd_ab = sd_ba = None
     try:
         if surface_b is None:
             surface_b = _hip.DeviceSurface(pts_b, faces_b, ctx=ctx)
             built.append(surface_b)
-        d_ab = np.sqrt(surface_b.distance(pts_a)[0])
+        if signed:  # |sd| is the unsigned distance bit for bit: one search per direction
+            sd_ab = surface_b.signed_distance(pts_a)[0]
+            d_ab = np.abs(sd_ab)
+        else:
+            d_ab = np.sqrt(surface_b.distance(pts_a)[0])
         d_ba = None
         if symmetric:
             if surface_a is None:
                 surface_a = _hip.DeviceSurface(pts_a, faces_a, ctx=ctx)
                 built.append(surface_a)
-            d_ba = np.sqrt(surface_a.distance(pts_b)[0])
+            if signed:
+                sd_ba = surface_a.signed_distance(pts_b)[0]
+                d_ba = np.abs(sd_ba)
+            else:
+                d_ba = np.sqrt(surface_a.distance(pts_b)[0])
     finally:
         for s in built:
             s.close()
-    return summarize_distances(d_ab, d_ba)
+    out = summarize_distances(d_ab, d_ba)
+    for tag, sd in (("a_to_b", sd_ab), ("b_to_a", sd_ba)):
+        if sd is not None:
+            out.update({"%s_%s" % (k, tag): v for k, v in summarize_signed_distances(sd).items()})
+    return out
