@@ -479,6 +479,26 @@ int pf_surface_distance(pf_surface* s, const double* qry, int64_t n_qry, double*
 int pf_surface_prepare_signed(pf_surface* s, const double* points, const int32_t* faces, int64_t* topology);
 int pf_surface_signed_distance(pf_surface* s, const double* qry, int64_t n_qry, double* out_sd, int32_t* out_face,
                                int32_t* out_feature, int64_t* n_ambiguous);
+/* Generalized winding numbers (Jacobson et al. 2013; hierarchical evaluation after Barill et al. 2018).
+ * w(q) = (1 / 4 pi) sum_t Omega_t(q) over the fan triangles, Omega the signed solid angle (Van Oosterom & Strackee):
+ * Omega = 2 atan2(a . (b x c), |a||b||c| + (a . b)|c| + (b . c)|a| + (c . a)|b|) with a, b, c the corners minus q; a
+ * triangle with a corner exactly at q gives 0.  w is 1 inside and 0 outside a closed outward-oriented mesh (reversed
+ * faces subtract), varies smoothly across holes and needs no normals, edges or manifoldness.  Works on the structure
+ * pf_surface_create built (no host arrays again).  Sums in a fixed order, no floating-point atomics: two calls give
+ * identical bits.  Against a host evaluation only a tolerance holds (summation order, FMA and atan2 differ).
+ *   pf_surface_prepare_winding  per chunk of 64 triangles and per super-chunk of 64 chunks the dipole data: N = sum of
+ *                               1/2 (b - a) x (c - a), A = sum of areas, the area-weighted centroid (the box centre if
+ *                               A = 0), r = max |corner - centroid|.  A second call does nothing.
+ *   pf_surface_winding          qry [n_qry][3] f64 (host), n_qry >= 1 -> out_w [n_qry], out_bound [n_qry]; each may be NULL.
+ *                               beta <= 0: every triangle through the exact term; out_bound is 0.  beta > 1: a cluster
+ *                               (super-chunk, then chunk) whose centroid is at d >= beta r from every finite query of a
+ *                               packet of 8 neighbouring queries contributes N . (p - q) / (4 pi d^3) instead of its
+ *                               triangles, and A r / (2 pi (d - r)^3) to out_bound: |out_w - w| <= out_bound up to the
+ *                               rounding of the sums.  0 < beta <= 1 (q may lie inside the ball), NaN or +inf: PF_E_ARG.
+ *                               A query with a non-finite coordinate gives NaN in both outputs.  PF_E_ARG for n_qry < 1
+ *                               or before pf_surface_prepare_winding. */
+int pf_surface_prepare_winding(pf_surface* s);
+int pf_surface_winding(pf_surface* s, const double* qry, int64_t n_qry, double beta, double* out_w, double* out_bound);
 
 /* ---- Coherent Point Drift pieces ("next" row f4) ------------------------------------------------------------
  * The reference registers the spectral coordinates with the third-party cycpd package (focusr.py:297-334).

@@ -11,8 +11,9 @@ from .assignment import euclidean_assignment
 from .eigsort import eigsort
 from .focusr import *  # noqa: F401,F403
 from .graph import *  # noqa: F401,F403
-from .surface_distance import (point_to_surface_distances, signed_distances_on_mesh, signed_point_to_surface_distances,
-                               summarize_distances, summarize_signed_distances, surface_distance_metrics)
+from .surface_distance import (point_to_surface_distances, points_inside, signed_distances_on_mesh,
+                               signed_point_to_surface_distances, summarize_distances, summarize_signed_distances,
+                               surface_distance_metrics, winding_numbers)
 from .test import get_all_pairwise_surface_errors
 from .vtk_functions import PolyMesh, read_vtk_mesh, write_vtk_mesh
 

@@ -172,6 +172,8 @@ SIGNATURES = {
     "pf_surface_distance": (C.c_int, [C.c_void_p, _f64p, C.c_int64, _f64p, _i32p, _f64p]),
     "pf_surface_prepare_signed": (C.c_int, [C.c_void_p, _f64p, _i32p, _i64p]),
     "pf_surface_signed_distance": (C.c_int, [C.c_void_p, _f64p, C.c_int64, _f64p, _i32p, _i32p, _i64p]),
+    "pf_surface_prepare_winding": (C.c_int, [C.c_void_p]),
+    "pf_surface_winding": (C.c_int, [C.c_void_p, _f64p, C.c_int64, C.c_double, _f64p, _f64p]),
     "pf_cpd_create": (C.c_int, [C.c_void_p, _f64p, C.c_int64, _f64p, C.c_int64, C.c_int32, C.POINTER(C.c_void_p)]),
     "pf_cpd_free": (None, [C.c_void_p]),
     "pf_cpd_estep": (C.c_int, [C.c_void_p, _f64p, C.c_double, C.c_double, _f64p, _f64p, _f64p]),
@@ -621,6 +623,7 @@ class DeviceSurface(object):
         self.n, self.n_faces = pts.shape[0], f.shape[0]
         self.points, self.faces = pts, f  # host arrays, for pf_surface_prepare_signed and topology()
         self._topology = None  # edge counts once the signed structure is built
+        self._winding_ready = False  # the dipole data of pf_surface_prepare_winding
         _live_graphs.add(self)
         self.ctx._children.add(self)
 
@@ -661,6 +664,23 @@ class DeviceSurface(object):
         _check(self._lib.pf_surface_signed_distance(self._h, _f64(q), len(q), _f64(sd), face.ctypes.data_as(_i32p),
                                                     feature.ctypes.data_as(_i32p), C.byref(amb)))
         return sd, face, feature, int(amb.value)
+
+    def winding_number(self, queries, beta=0.0):
+        """(w (q,) f64, bound (q,) f64): the generalized winding number of every query (`pf_surface_winding`): 1 inside and
+        0 outside an outward-oriented closed mesh, smooth across holes; NaN for a non-finite query.  `beta <= 0`: every
+        triangle exactly, bound 0.  `beta > 1`: clusters of triangles at least `beta` radii away contribute their dipole
+        term, and `bound` is a rigorous bound of |w - exact w|.  Two calls give identical bits.  Builds the dipole data on
+        first use."""
+        q = _c_f64(queries)
+        if q.ndim != 2 or q.shape[1] != 3 or q.shape[0] == 0:
+            raise ValueError("queries must be a non-empty (n, 3) array")
+        if not self._winding_ready:
+            _check(self._lib.pf_surface_prepare_winding(self._h))
+            self._winding_ready = True
+        w = np.empty(len(q), dtype=np.float64)
+        bound = np.empty(len(q), dtype=np.float64)
+        _check(self._lib.pf_surface_winding(self._h, _f64(q), len(q), float(beta), _f64(w), _f64(bound)))
+        return w, bound
 
     def closest(self, queries):
         """(points (q,3) f64, face (q,) i32, squared distance (q,) f64) of the closest surface point of each query."""

@@ -23,6 +23,8 @@
 // Signed distances (pf_surface_prepare_signed / pf_surface_signed_distance, at the end of the file) add
 // angle-weighted pseudonormals, built once per surface on request, and one per-query kernel after the unchanged
 // k_distance search that names the feature (face, edge, vertex) of the winning triangle the closest point lies on.
+// Generalized winding numbers (pf_surface_prepare_winding / pf_surface_winding, the last device section) sum the solid
+// angles of all triangles over the same chunks, exactly or with far clusters replaced by their dipoles.
 #include <hipcub/hipcub.hpp>
 
 #include <cmath>
@@ -45,6 +47,9 @@ struct pf_surface {
     double* tnrm = nullptr;      // [n_tri][3] unit face normal of triangle (face * (vpf-2) + fan position)
     double* enrm = nullptr;      // [n_tri][3 edge slots][3] edge pseudonormal; slot j = edge (corner j, corner j+1)
     double* vnrm = nullptr;      // [n_points][3] angle-weighted vertex pseudonormal
+    // winding numbers (pf_surface_prepare_winding; NULL until then)
+    double* dip = nullptr;       // [n_chunks][8] dipole of a chunk: Nx Ny Nz | A | centroid xyz | radius
+    double* sdip = nullptr;      // [n_super][8] the same per super-chunk
 };
 
 namespace {
@@ -909,6 +914,218 @@ hipError_t distance_search(pf_surface* s, hipStream_t st, const double* d_q, int
     return e;
 }
 
+// ---- generalized winding numbers (pf_surface_prepare_winding, pf_surface_winding) -------------------------------
+// w(q) = (1 / 4 pi) sum_t Omega_t(q), the signed solid angles of all triangles seen from q (Jacobson et al. 2013): 1
+// inside and 0 outside a closed outward-oriented mesh, smooth across holes, no normals, edges or manifoldness needed.
+// Nothing can be culled: every triangle contributes to every query.
+//   prepare  per chunk and per super-chunk the dipole data of its triangles: N = sum 1/2 (b - a) x (c - a), A = sum
+//            area, the area-weighted centroid (the box centre if A = 0), r = max |corner - centroid|.
+//   query    queries Morton-sorted (k_qry_keys), ONE WAVE PER PACKET of PF_WIND_PACKET neighbouring queries.  A
+//            chunk's 64 triangles are loaded once per packet, one triangle per lane; the lane evaluates its triangle
+//            against each query of the packet (coordinates broadcast through scalar registers) and adds the term to
+//            that query's accumulator in its own registers; one butterfly per query at the very end.  One atan2 per
+//            (triangle, query).  f64 throughout.
+//   beta > 1 Barill et al. 2018, two levels: a super-chunk, then a chunk, whose centroid is at d >= beta r from EVERY
+//            finite query of the packet contributes N . (p - q) / (4 pi d^3) and the bound A r / (2 pi (d - r)^3) on
+//            what that drops (derived in DESIGN.md 5); otherwise it is opened for the whole packet (lane = chunk, then lane =
+//            triangle).  Opening more than a single query would need only makes that query more exact.
+// Reproducible: run to run, bit for bit (a lane adds its terms in chunk order, the butterfly is fixed, no atomics; the
+// packet a query falls in depends only on the query set).  Not against numpy: summation order, FMA contraction and the
+// device's atan2 / sqrt differ from libm, so the tests compare with a derived tolerance, not bit for bit.
+
+constexpr int PF_WIND_PACKET = 8;  // queries per wave: 8 accumulators (+ 8 bounds) per lane, the term unrolled 8 times
+constexpr int PF_DIPOLE = 8;       // Nx Ny Nz | A | px py pz | r
+
+__device__ __forceinline__ double lane_bcast(double v, int l) {  // l uniform: the value lands in scalar registers
+    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
+}
+
+// half the signed solid angle of triangle (a, b, c), corners relative to the query (Van Oosterom & Strackee 1983);
+// positive where the normal (b - a) x (c - a) points away from the query; 0 with a corner at the query
+__device__ __forceinline__ double half_solid_angle(const double a[3], const double b[3], const double c[3]) {
+#pragma clang fp contract(fast)
+    const double la = sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]);
+    const double lb = sqrt(b[0] * b[0] + b[1] * b[1] + b[2] * b[2]);
+    const double lc = sqrt(c[0] * c[0] + c[1] * c[1] + c[2] * c[2]);
+    const double det = a[0] * (b[1] * c[2] - b[2] * c[1]) + a[1] * (b[2] * c[0] - b[0] * c[2]) + a[2] * (b[0] * c[1] - b[1] * c[0]);
+    const double ab = a[0] * b[0] + a[1] * b[1] + a[2] * b[2];
+    const double bc = b[0] * c[0] + b[1] * c[1] + b[2] * c[2];
+    const double ca = c[0] * a[0] + c[1] * a[1] + c[2] * a[2];
+    const double den = la * lb * lc + ab * lc + bc * la + ca * lb;
+    return (la == 0.0 || lb == 0.0 || lc == 0.0) ? 0.0 : atan2(det, den);
+}
+
+// one wave per chunk, one triangle per lane; sums by the fixed butterfly
+__global__ __launch_bounds__(PF_WAVE) void k_chunk_dipoles(const double* __restrict__ tri, int64_t n_tri, const double* __restrict__ box,
+                                                           double* __restrict__ dip) {
+    const int64_t c = blockIdx.x;
+    const int lane = threadIdx.x;
+    const int64_t s = c * PF_TRI_CHUNK + lane;
+    const bool have = s < n_tri;
+    double x[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) x[k] = have ? tri[(int64_t)k * n_tri + s] : 0.0;
+    const double u[3] = {x[3] - x[0], x[4] - x[1], x[5] - x[2]}, v[3] = {x[6] - x[0], x[7] - x[1], x[8] - x[2]};
+    const double n[3] = {0.5 * (u[1] * v[2] - u[2] * v[1]), 0.5 * (u[2] * v[0] - u[0] * v[2]), 0.5 * (u[0] * v[1] - u[1] * v[0])};
+    const double area = sqrt(dot3(n, n));
+    const double N[3] = {wave_sum(n[0]), wave_sum(n[1]), wave_sum(n[2])};
+    const double A = wave_sum(area);
+    double p[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const double m = wave_sum(area * ((x[a] + x[3 + a] + x[6 + a]) / 3.0));
+        p[a] = A > 0.0 ? m / A : 0.5 * (box[6 * c + a] + box[6 * c + 3 + a]);
+    }
+    double r2 = 0.0;
+    if (have) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const double d[3] = {x[3 * k] - p[0], x[3 * k + 1] - p[1], x[3 * k + 2] - p[2]};
+            r2 = fmax(r2, dot3(d, d));
+        }
+    }
+    r2 = wave_max(r2);
+    if (lane == 0) {
+        double* o = dip + PF_DIPOLE * c;
+        o[0] = N[0], o[1] = N[1], o[2] = N[2], o[3] = A, o[4] = p[0], o[5] = p[1], o[6] = p[2], o[7] = sqrt(r2);
+    }
+}
+
+// one wave per super-chunk: its chunks' sums, one chunk per lane, then the radius over all its triangles' corners
+__global__ __launch_bounds__(PF_WAVE) void k_super_dipoles(const double* __restrict__ tri, int64_t n_tri, const double* __restrict__ dip,
+                                                           int64_t n_chunks, const double* __restrict__ sbox, double* __restrict__ sdip) {
+    const int64_t ss = blockIdx.x;
+    const int lane = threadIdx.x;
+    const int64_t c = ss * PF_WAVE + lane;
+    const bool have = c < n_chunks;
+    double d[PF_DIPOLE];
+#pragma unroll
+    for (int k = 0; k < PF_DIPOLE; ++k) d[k] = have ? dip[PF_DIPOLE * c + k] : 0.0;
+    const double N[3] = {wave_sum(d[0]), wave_sum(d[1]), wave_sum(d[2])};
+    const double A = wave_sum(d[3]);
+    double p[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const double m = wave_sum(d[3] * d[4 + a]);
+        p[a] = A > 0.0 ? m / A : 0.5 * (sbox[6 * ss + a] + sbox[6 * ss + 3 + a]);
+    }
+    double r2 = 0.0;
+    const int64_t end = (ss + 1) * PF_WAVE * PF_TRI_CHUNK < n_tri ? (ss + 1) * PF_WAVE * PF_TRI_CHUNK : n_tri;
+    for (int64_t s = ss * PF_WAVE * PF_TRI_CHUNK + lane; s < end; s += PF_WAVE) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const double e[3] = {tri[(int64_t)(3 * k) * n_tri + s] - p[0], tri[(int64_t)(3 * k + 1) * n_tri + s] - p[1],
+                                 tri[(int64_t)(3 * k + 2) * n_tri + s] - p[2]};
+            r2 = fmax(r2, dot3(e, e));
+        }
+    }
+    r2 = wave_max(r2);
+    if (lane == 0) {
+        double* o = sdip + PF_DIPOLE * ss;
+        o[0] = N[0], o[1] = N[1], o[2] = N[2], o[3] = A, o[4] = p[0], o[5] = p[1], o[6] = p[2], o[7] = sqrt(r2);
+    }
+}
+
+// one wave (= one block) per packet of PF_WIND_PACKET sorted queries.  acc[j] holds this lane's share of sum Omega / 2 of
+// query j, bnd[j] of its bound; HIER = false never touches the dipoles and leaves the bound 0.
+template <bool HIER>
+__global__ __launch_bounds__(PF_WAVE) void k_winding(const double* __restrict__ tri, int64_t n_tri, int64_t n_chunks, int64_t n_super,
+                                                     const double* __restrict__ dip, const double* __restrict__ sdip,
+                                                     const double* __restrict__ qry, const int32_t* __restrict__ perm, int64_t n_qry,
+                                                     double beta, double* __restrict__ out_w, double* __restrict__ out_bound) {
+#pragma clang fp contract(fast)
+    constexpr int P = PF_WIND_PACKET;
+    const int lane = threadIdx.x;
+    const int64_t i = (int64_t)blockIdx.x * P + lane;
+    const bool live = lane < P && i < n_qry;
+    const int64_t qi = live ? perm[i] : -1;  // the caller's index of this lane's query
+    double p[3] = {0.0, 0.0, 0.0};
+    if (live) p[0] = qry[3 * qi], p[1] = qry[3 * qi + 1], p[2] = qry[3 * qi + 2];
+    const bool ok = live && std::isfinite(p[0]) && std::isfinite(p[1]) && std::isfinite(p[2]);
+    if (!ok) p[0] = p[1] = p[2] = 0.0;  // a dead slot computes on the origin and is never written
+    const unsigned long long okmask = __ballot(ok);
+    double q[P][3], acc[P], bnd[P];
+#pragma unroll
+    for (int j = 0; j < P; ++j) {
+        q[j][0] = lane_bcast(p[0], j), q[j][1] = lane_bcast(p[1], j), q[j][2] = lane_bcast(p[2], j);
+        acc[j] = 0.0, bnd[j] = 0.0;
+    }
+
+    auto scan = [&](int64_t c) {  // chunk c: one triangle per lane against every query of the packet
+        const int64_t s = c * PF_TRI_CHUNK + lane;
+        const bool have = s < n_tri;
+        const int64_t sc = have ? s : n_tri - 1;
+        double x[9];
+#pragma unroll
+        for (int k = 0; k < 9; ++k) x[k] = tri[(int64_t)k * n_tri + sc];
+#pragma unroll
+        for (int j = 0; j < P; ++j) {
+            const double a[3] = {x[0] - q[j][0], x[1] - q[j][1], x[2] - q[j][2]};
+            const double b[3] = {x[3] - q[j][0], x[4] - q[j][1], x[5] - q[j][2]};
+            const double cc[3] = {x[6] - q[j][0], x[7] - q[j][1], x[8] - q[j][2]};
+            const double h = half_solid_angle(a, b, cc);
+            acc[j] += have ? h : 0.0;
+        }
+    };
+    // cluster data d of this lane (if have): is it far from every finite query of the packet?  If so its dipole term
+    // and bound are added for each query.  Returns whether the lane's cluster has to be opened.
+    auto cluster = [&](bool have, const double* __restrict__ d) {
+        double v[PF_DIPOLE];
+#pragma unroll
+        for (int k = 0; k < PF_DIPOLE; ++k) v[k] = have ? d[k] : 0.0;
+        const double br = beta * v[7];
+        bool far = have;
+#pragma unroll
+        for (int j = 0; j < P; ++j) {
+            const double e[3] = {v[4] - q[j][0], v[5] - q[j][1], v[6] - q[j][2]};
+            const double d2 = e[0] * e[0] + e[1] * e[1] + e[2] * e[2];
+            far = far && (!((okmask >> j) & 1ull) || (d2 >= br * br && d2 > 0.0));
+        }
+        if (far) {
+#pragma unroll
+            for (int j = 0; j < P; ++j) {
+                const double e[3] = {v[4] - q[j][0], v[5] - q[j][1], v[6] - q[j][2]};
+                const double d2 = e[0] * e[0] + e[1] * e[1] + e[2] * e[2];
+                const double dd = sqrt(d2), gap = dd - v[7];
+                acc[j] += 0.5 * (v[0] * e[0] + v[1] * e[1] + v[2] * e[2]) / (d2 * dd);
+                bnd[j] += v[3] * v[7] / (6.283185307179586 * (gap * gap * gap));
+            }
+        }
+        return have && !far;
+    };
+
+    if (HIER) {
+        for (int64_t sb = 0; sb < n_super; sb += PF_WAVE) {
+            const int64_t s = sb + lane;
+            unsigned long long smask = __ballot(cluster(s < n_super, sdip + PF_DIPOLE * (s < n_super ? s : 0)));
+            while (smask) {
+                const int64_t ss = sb + __ffsll((long long)smask) - 1;
+                smask &= smask - 1;
+                const int64_t c = ss * PF_WAVE + lane;
+                unsigned long long mask = __ballot(cluster(c < n_chunks, dip + PF_DIPOLE * (c < n_chunks ? c : 0)));
+                while (mask) {
+                    scan(ss * PF_WAVE + __ffsll((long long)mask) - 1);
+                    mask &= mask - 1;
+                }
+            }
+        }
+    } else {
+        for (int64_t c = 0; c < n_chunks; ++c) scan(c);
+    }
+
+    double w = 0.0, b = 0.0;
+#pragma unroll
+    for (int j = 0; j < P; ++j) {
+        const double sw = wave_sum(acc[j]), sb = HIER ? wave_sum(bnd[j]) : 0.0;
+        if (lane == j) w = sw / 6.283185307179586, b = sb;
+    }
+    if (live) {
+        const double nan = __longlong_as_double(0x7ff8000000000000ll);
+        if (out_w) out_w[qi] = ok ? w : nan;
+        if (out_bound) out_bound[qi] = ok ? b : nan;
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -927,6 +1144,8 @@ void pf_surface_free(pf_surface* s) {
     pf_free(st, s->tnrm);
     pf_free(st, s->enrm);
     pf_free(st, s->vnrm);
+    pf_free(st, s->dip);
+    pf_free(st, s->sdip);
     delete s;
 }
 
@@ -1195,6 +1414,88 @@ int pf_surface_signed_distance(pf_surface* s, const double* qry, int64_t n_qry, 
         return PF_E_HIP;
     }
     if (n_ambiguous) *n_ambiguous = (int64_t)amb;
+    return PF_OK;
+}
+
+int pf_surface_prepare_winding(pf_surface* s) {
+    PF_CHECK(s, PF_E_ARG, "pf_surface_prepare_winding: NULL argument");
+    if (s->dip) return PF_OK;  // built once: the triangles never change
+    PF_HIP(hipSetDevice(s->ctx->device));
+    hipStream_t st = s->ctx->stream;
+    double *dip = nullptr, *sdip = nullptr;
+    hipError_t e = hipSuccess;
+    do {
+        if ((e = pf_malloc(st, (void**)&dip, sizeof(double) * PF_DIPOLE * s->n_chunks)) != hipSuccess) break;
+        if ((e = pf_malloc(st, (void**)&sdip, sizeof(double) * PF_DIPOLE * s->n_super)) != hipSuccess) break;
+        k_chunk_dipoles<<<(unsigned)s->n_chunks, PF_WAVE, 0, st>>>(s->tri, s->n_tri, s->box, dip);
+        k_super_dipoles<<<(unsigned)s->n_super, PF_WAVE, 0, st>>>(s->tri, s->n_tri, dip, s->n_chunks, s->sbox, sdip);
+        if ((e = hipGetLastError()) != hipSuccess) break;
+        e = hipStreamSynchronize(st);
+    } while (0);
+    if (e != hipSuccess) {
+        pf_free(st, dip);
+        pf_free(st, sdip);
+        pf_set_error("pf_surface_prepare_winding: %s", hipGetErrorString(e));
+        return PF_E_HIP;
+    }
+    s->dip = dip, s->sdip = sdip;
+    return PF_OK;
+}
+
+int pf_surface_winding(pf_surface* s, const double* qry, int64_t n_qry, double beta, double* out_w, double* out_bound) {
+    PF_CHECK(s && qry, PF_E_ARG, "pf_surface_winding: NULL argument");
+    PF_CHECK(n_qry >= 1 && n_qry < ((int64_t)1 << 31), PF_E_ARG, "pf_surface_winding: n_qry = %lld out of range", (long long)n_qry);
+    PF_CHECK(s->dip, PF_E_ARG, "pf_surface_winding: pf_surface_prepare_winding has not been called");
+    // beta <= 0: exact.  A query may lie inside a cluster's ball for beta <= 1, where the dropped part has no bound.
+    PF_CHECK(beta <= 0.0 || (beta > 1.0 && std::isfinite(beta)), PF_E_ARG,
+             "pf_surface_winding: beta = %g: use beta <= 0 (exact) or a finite beta > 1", beta);
+    const Box3 bb = query_box(qry, n_qry);
+    PF_HIP(hipSetDevice(s->ctx->device));
+    hipStream_t st = s->ctx->stream;
+    const int64_t n_pack = (n_qry + PF_WIND_PACKET - 1) / PF_WIND_PACKET;
+    double *d_q = nullptr, *d_w = nullptr, *d_b = nullptr;
+    unsigned *k0 = nullptr, *k1 = nullptr;
+    int32_t *v0 = nullptr, *v1 = nullptr;
+    void* tmp = nullptr;
+    size_t need = 0;
+    hipError_t e = hipSuccess;
+    do {
+        if ((e = pf_malloc(st, (void**)&d_q, sizeof(double) * 3 * n_qry)) != hipSuccess) break;
+        if (out_w && (e = pf_malloc(st, (void**)&d_w, sizeof(double) * n_qry)) != hipSuccess) break;
+        if (out_bound && (e = pf_malloc(st, (void**)&d_b, sizeof(double) * n_qry)) != hipSuccess) break;
+        if ((e = pf_malloc(st, (void**)&k0, sizeof(unsigned) * n_qry)) != hipSuccess) break;
+        if ((e = pf_malloc(st, (void**)&k1, sizeof(unsigned) * n_qry)) != hipSuccess) break;
+        if ((e = pf_malloc(st, (void**)&v0, sizeof(int32_t) * n_qry)) != hipSuccess) break;
+        if ((e = pf_malloc(st, (void**)&v1, sizeof(int32_t) * n_qry)) != hipSuccess) break;
+        if ((e = hipMemcpyAsync(d_q, qry, sizeof(double) * 3 * n_qry, hipMemcpyHostToDevice, st)) != hipSuccess) break;
+        k_qry_keys<<<nblk(n_qry), PF_BLOCK, 0, st>>>(d_q, n_qry, bb, k0, v0);
+        if ((e = hipGetLastError()) != hipSuccess) break;
+        if ((e = hipcub::DeviceRadixSort::SortPairs(nullptr, need, k0, k1, v0, v1, (int)n_qry, 0, 30, st)) != hipSuccess) break;
+        if ((e = pf_malloc(st, &tmp, need)) != hipSuccess) break;
+        if ((e = hipcub::DeviceRadixSort::SortPairs(tmp, need, k0, k1, v0, v1, (int)n_qry, 0, 30, st)) != hipSuccess) break;
+        if (beta > 0.0)
+            k_winding<true><<<(unsigned)n_pack, PF_WAVE, 0, st>>>(s->tri, s->n_tri, s->n_chunks, s->n_super, s->dip, s->sdip, d_q, v1,
+                                                                  n_qry, beta, d_w, d_b);
+        else
+            k_winding<false><<<(unsigned)n_pack, PF_WAVE, 0, st>>>(s->tri, s->n_tri, s->n_chunks, s->n_super, s->dip, s->sdip, d_q, v1,
+                                                                   n_qry, 0.0, d_w, d_b);
+        if ((e = hipGetLastError()) != hipSuccess) break;
+        if (out_w && (e = hipMemcpyAsync(out_w, d_w, sizeof(double) * n_qry, hipMemcpyDeviceToHost, st)) != hipSuccess) break;
+        if (out_bound && (e = hipMemcpyAsync(out_bound, d_b, sizeof(double) * n_qry, hipMemcpyDeviceToHost, st)) != hipSuccess) break;
+        e = hipStreamSynchronize(st);
+    } while (0);
+    pf_free(st, d_q);
+    pf_free(st, d_w);
+    pf_free(st, d_b);
+    pf_free(st, k0);
+    pf_free(st, k1);
+    pf_free(st, v0);
+    pf_free(st, v1);
+    pf_free(st, tmp);
+    if (e != hipSuccess) {
+        pf_set_error("pf_surface_winding: %s", hipGetErrorString(e));
+        return PF_E_HIP;
+    }
     return PF_OK;
 }
 

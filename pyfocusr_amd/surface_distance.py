@@ -11,6 +11,11 @@ Signed distances (`pf_surface_signed_distance`, `_hip.DeviceSurface.signed_dista
 (p - c) . n with n the angle-weighted pseudonormal of the face, edge or vertex the closest point c lies on.  On a
 closed, consistently oriented mesh with outward faces, inside is negative (as in VTK's vtkImplicitPolyDataDistance);
 the magnitude is the unsigned distance bit for bit.
+
+Generalized winding numbers (`pf_surface_winding`, `_hip.DeviceSurface.winding_number`): w = the signed solid angles
+of all triangles seen from the point, over 4 pi.  1 inside and 0 outside a closed outward-oriented mesh, smooth across
+holes, no normals or manifoldness needed: `winding_numbers`, `points_inside`, and the signs of `sign="winding"` for
+meshes that are open or non-manifold, where the pseudonormal sign flips near every boundary loop.
 """
 import numpy as np
 
@@ -95,14 +100,72 @@ def summarize_distances(d_a_to_b, d_b_to_a=None):
     return out
 
 
-def signed_point_to_surface_distances(points, mesh, ctx=None, check_orientation=True):
+_SIGNS = ("pseudonormal", "winding")
+
+
+def _check_sign(sign):
+    if sign not in _SIGNS:
+        raise ValueError("sign must be one of %r, not %r" % (_SIGNS, sign))
+
+
+def winding_numbers(points, mesh, ctx=None, beta=0.0):
+    """w (n,) f64: the generalized winding number of `mesh` at every point: the signed solid angles of all triangles
+    (polygons fan-triangulated) seen from the point, over 4 pi.  1 inside and 0 outside a closed mesh with outward faces
+    (reversed faces subtract), in between near holes; NaN for a point with a non-finite coordinate.  `beta <= 0`
+    evaluates every triangle exactly; `beta > 1` replaces clusters of triangles at least `beta` cluster radii away by
+    their dipole (`_hip.DeviceSurface.winding_number` also returns the bound on what that changes).  `mesh` may also be
+    a `_hip.DeviceSurface` built earlier, which is then reused and left open."""
+    q = _query_array(points)
+    beta = float(beta)
+    if 0.0 < beta <= 1.0 or beta != beta or beta == np.inf:
+        raise ValueError("beta must be <= 0 (exact) or a finite value > 1, not %r" % beta)
+    if hasattr(mesh, "winding_number"):  # a DeviceSurface
+        return mesh.winding_number(q, beta=beta)[0]
+    pts, faces = _mesh_arrays(mesh)
+    surface = _hip.DeviceSurface(pts, faces, ctx=ctx)
+    try:
+        return surface.winding_number(q, beta=beta)[0]
+    finally:
+        surface.close()
+
+
+def points_inside(points, mesh, ctx=None, threshold=0.5):
+    """bool (n,): `winding_numbers(points, mesh) > threshold`; False for a point with a non-finite coordinate.  On an
+    open mesh w falls off smoothly across a hole, and 0.5 is the level that closes it the way the surface continues."""
+    w = winding_numbers(points, mesh, ctx=ctx)
+    with np.errstate(invalid="ignore"):
+        return w > threshold
+
+
+def _signed_on_surface(surface, q, sign):
+    """(sd, face) of the queries against an open DeviceSurface."""
+    if sign == "pseudonormal":
+        sd, face, _, _ = surface.signed_distance(q)
+        return sd, face
+    d2, face, _ = surface.distance(q)
+    w, _ = surface.winding_number(q)
+    d = np.sqrt(d2)
+    with np.errstate(invalid="ignore"):
+        sd = np.where((w > 0.5) & (d > 0.0), -d, d)  # +0.0 at distance 0; NaN stays NaN
+    return sd, face
+
+
+def signed_point_to_surface_distances(points, mesh, ctx=None, check_orientation=True, sign="pseudonormal"):
     """(sd (n,) f64, face (n,) i32): the signed distance of every point to the surface of `mesh` (negative on the side
     opposite to the face normals: inside an outward-oriented closed mesh) and the face that attains it.  |sd| and face
     equal `point_to_surface_distances` bit for bit; NaN and -1 for a point with a non-finite coordinate.  `mesh` may
-    also be a `_hip.DeviceSurface`, reused and left open.  With `check_orientation` a mesh whose triangles disagree
-    on their orientation (inconsistent edges) or that has edges in three or more triangles raises ValueError: the sign
-    means nothing there.  Open boundaries are allowed (the sign then follows the face normals nearby)."""
+    also be a `_hip.DeviceSurface`, reused and left open.
+
+    `sign="pseudonormal"`: the side of the angle-weighted pseudonormal at the closest point.  With `check_orientation`
+    a mesh whose triangles disagree on their orientation (inconsistent edges) or that has edges in three or more
+    triangles raises ValueError: the sign means nothing there.  Open boundaries are allowed (the sign then follows
+    the face normals nearby, and flips near every boundary loop).
+
+    `sign="winding"`: negative where the generalized winding number (`winding_numbers`, exact mode) exceeds 0.5,
+    positive otherwise, +0.0 at distance 0.  Meant for open and non-manifold meshes; with `check_orientation` only
+    inconsistent edges raise (a reversed face subtracts its solid angle instead of adding it)."""
     q = _query_array(points)
+    _check_sign(sign)
     built = None
     if hasattr(mesh, "signed_distance"):  # a DeviceSurface
         surface = mesh
@@ -112,11 +175,15 @@ def signed_point_to_surface_distances(points, mesh, ctx=None, check_orientation=
     try:
         if check_orientation:
             t = surface.topology()
-            if t["n_inconsistent_edges"] or t["n_nonmanifold_edges"]:
+            if sign == "winding":
+                if t["n_inconsistent_edges"]:
+                    raise ValueError("winding-number signs need consistently oriented faces: %d inconsistent edges "
+                                     "(check_orientation=False to compute them anyway)" % t["n_inconsistent_edges"])
+            elif t["n_inconsistent_edges"] or t["n_nonmanifold_edges"]:
                 raise ValueError("signed distances need a consistently oriented manifold surface: %d inconsistent and %d "
                                  "non-manifold edges (check_orientation=False to compute them anyway)"
                                  % (t["n_inconsistent_edges"], t["n_nonmanifold_edges"]))
-        sd, face, _, _ = surface.signed_distance(q)
+        sd, face = _signed_on_surface(surface, q, sign)
     finally:
         if built is not None:
             built.close()
@@ -145,17 +212,19 @@ def summarize_signed_distances(sd):
     return out
 
 
-def signed_distances_on_mesh(mesh, other, name="signed_distance", ctx=None):
+def signed_distances_on_mesh(mesh, other, name="signed_distance", ctx=None, sign="pseudonormal"):
     """Signed distances of `mesh`'s vertices to the surface of `other` (`signed_point_to_surface_distances`, orientation
-    checked), stored on `mesh` as the point-data array `name` (`set_mesh_scalars`; written by `write_vtk_mesh` with
-    17 digits, so they read back exactly).  Returns the distances."""
+    checked, `sign` as there), stored on `mesh` as the point-data array `name` (`set_mesh_scalars`; written by
+    `write_vtk_mesh` with 17 digits, so they read back exactly).  Returns the distances."""
     pts, _ = _mesh_arrays(mesh)
-    sd, _ = signed_point_to_surface_distances(pts, other, ctx=ctx)
+    _check_sign(sign)
+    sd, _ = signed_point_to_surface_distances(pts, other, ctx=ctx, sign=sign)
     vtk_functions.set_mesh_scalars(mesh, sd, name=name)
     return sd
 
 
-def surface_distance_metrics(mesh_a, mesh_b, symmetric=True, ctx=None, surface_a=None, surface_b=None, signed=False):
+def surface_distance_metrics(mesh_a, mesh_b, symmetric=True, ctx=None, surface_a=None, surface_b=None, signed=False,
+                             sign="pseudonormal"):
     """Distances from the vertices of `mesh_a` to the surface of `mesh_b` (and, if `symmetric`, from `mesh_b`'s
     vertices to `mesh_a`'s surface), summarised by `summarize_distances`: `mean_a_to_b`, `rms_a_to_b`, `max_a_to_b`,
     `max_a_to_b_vertex`, `p95_a_to_b`, the same for `b_to_a`, `assd`, `hausdorff`, `hausdorff_95`.
@@ -166,9 +235,12 @@ def surface_distance_metrics(mesh_a, mesh_b, symmetric=True, ctx=None, surface_a
 
     `signed=True` adds `summarize_signed_distances` of each direction, its keys suffixed `_a_to_b` / `_b_to_a`
     (`mean_signed_a_to_b` is the bias of `mesh_a` against `mesh_b`'s surface; negative = inside it).  Orientation is
-    not checked here; `topology()` of a surface tells whether its signs mean anything."""
+    not checked here; `topology()` of a surface tells whether its signs mean anything.  `sign="winding"` takes the
+    signs from the generalized winding number instead (`signed_point_to_surface_distances`): the choice for open or
+    non-manifold meshes; the unsigned entries are the same either way."""
     pts_a, faces_a = _mesh_arrays(mesh_a)
     pts_b, faces_b = _mesh_arrays(mesh_b)
+    _check_sign(sign)
     built = []
     sd_ab = sd_ba = None
     try:
@@ -176,7 +248,7 @@ def surface_distance_metrics(mesh_a, mesh_b, symmetric=True, ctx=None, surface_a
             surface_b = _hip.DeviceSurface(pts_b, faces_b, ctx=ctx)
             built.append(surface_b)
         if signed:  # |sd| is the unsigned distance bit for bit: one search per direction
-            sd_ab = surface_b.signed_distance(pts_a)[0]
+            sd_ab = _signed_on_surface(surface_b, pts_a, sign)[0]
             d_ab = np.abs(sd_ab)
         else:
             d_ab = np.sqrt(surface_b.distance(pts_a)[0])
@@ -186,7 +258,7 @@ def surface_distance_metrics(mesh_a, mesh_b, symmetric=True, ctx=None, surface_a
                 surface_a = _hip.DeviceSurface(pts_a, faces_a, ctx=ctx)
                 built.append(surface_a)
             if signed:
-                sd_ba = surface_a.signed_distance(pts_b)[0]
+                sd_ba = _signed_on_surface(surface_a, pts_b, sign)[0]
                 d_ba = np.abs(sd_ba)
             else:
                 d_ba = np.sqrt(surface_a.distance(pts_b)[0])
