@@ -1,30 +1,37 @@
-// Closest point on a triangulated surface — the search inside the ICP pre-alignment
-// (reference: vtk_functions.py:12-29 -> vtkIterativeClosestPointTransform, whose inner loop asks a
-// vtkCellLocator for the closest surface point of <= 1000 landmarks, 100 times).
+// Queries against a triangulated surface: closest points, many-query distances, signed distances, winding numbers.
+// All four work on one structure, built once per surface (pf_surface_create): the triangles (polygons
+// fan-triangulated) are sorted along a Morton curve of their centroids (hipCUB radix sort) and cut into chunks of 64
+// consecutive ones, each with its bounding box; coordinates are stored SoA so that a wave reads 64 consecutive triangles
+// coalesced.  64 consecutive chunks form a super-chunk with its own box (two levels are enough: 500k triangles = 7813
+// chunks = 123 super-chunks, two per lane).  In the order of the file:
 //
-// Exact search, no approximation: the answer is the minimum over ALL triangles of the exact
-// point-triangle distance (ties: lowest triangle index), the same as a brute-force scan.  Pruning
-// only removes triangles that provably cannot win:
-//   build   triangles (polygons fan-triangulated) are sorted along a Morton curve of their centroids
-//           (hipCUB radix sort) and cut into chunks of 64 consecutive ones, each with its bounding box;
-//           coordinates are stored SoA so that a wave reads 64 consecutive triangles coalesced.
-//           64 consecutive chunks form a super-chunk with its own box (two levels are enough: 500k
-//           triangles = 7813 chunks = 123 super-chunks, two per lane).
-//   query   ONE BLOCK (4 waves) PER QUERY POINT.  (1) the nearest super-chunk, then the nearest chunk inside it, by
-//           point-box distance (one box per lane); that chunk is scanned first and yields an upper bound.
-//           (2) one ballot over the super-chunk boxes, then per surviving super-chunk one ballot over its
-//           64 chunk boxes; the surviving chunks are dealt round-robin to the 4 waves, which scan them one
-//           triangle per lane, 4 chunks per step (loads issued together), re-deriving the bound after
-//           every step.  Measured on a 250k pair: 41 chunk scans per landmark on average but 420 for the
-//           farthest one, and the kernel lasts as long as its slowest query — hence 4 waves x 4 chunks
-//           per step on that chain of dependent loads.
+// Closest point (pf_surface_closest, k_closest) - the search inside the ICP pre-alignment (reference:
+// vtk_functions.py:12-29 -> vtkIterativeClosestPointTransform, whose inner loop asks a vtkCellLocator for the closest
+// surface point of <= 1000 landmarks, 100 times).  Exact, no approximation: the answer is the minimum
+// over ALL triangles of the exact point-triangle distance (ties: lowest triangle index), the same as a brute-force scan;
+// pruning only removes triangles that provably cannot win.  ONE BLOCK (4 waves) PER QUERY POINT.  (1) the nearest
+// super-chunk, then the nearest chunk inside it, by point-box distance (one box per lane, nearest_chunk); that chunk is
+// scanned first and yields an upper bound.  (2) one ballot over the super-chunk boxes, then per surviving super-chunk
+// one ballot over its 64 chunk boxes; the surviving chunks are dealt round-robin to the 4 waves, which scan them one
+// triangle per lane, 4 chunks per step (loads issued together), re-deriving the bound after every step.  Measured on a
+// 250k pair: 41 chunk scans per landmark on average but 420 for the farthest one, and the kernel lasts as long as its
+// slowest query - hence 4 waves x 4 chunks per step on that chain of dependent loads.
 // The arithmetic of closest_on_triangle is Ericson's region walk, operation for operation the one in
-// oracle/icp_port.py (compiled with -ffp-contract=off), so points and distances are bit-identical to it.
-// Signed distances (pf_surface_prepare_signed / pf_surface_signed_distance, at the end of the file) add
-// angle-weighted pseudonormals, built once per surface on request, and one per-query kernel after the unchanged
-// k_distance search that names the feature (face, edge, vertex) of the winning triangle the closest point lies on.
-// Generalized winding numbers (pf_surface_prepare_winding / pf_surface_winding, the last device section) sum the solid
-// angles of all triangles over the same chunks, exactly or with far clusters replaced by their dipoles.
+// oracle/icp_port.py (compiled with -ffp-contract=off), so points and distances are bit-identical to it.  There is one
+// body of it; every exact test of the file goes through it.
+//
+// Many-query distances (pf_surface_distance, k_distance): the queries are Morton-sorted too and walk the same
+// hierarchy one packet of neighbouring queries per wave, with the same exact tests and tie rule as k_closest.
+//
+// Signed distances (pf_surface_prepare_signed / pf_surface_signed_distance): angle-weighted pseudonormals, built once
+// per surface on request, and one per-query kernel after the unchanged k_distance search that names the feature (face,
+// edge, vertex) of the winning triangle the closest point lies on.
+//
+// Generalized winding numbers (pf_surface_prepare_winding / pf_surface_winding): the solid angles of all triangles,
+// summed over the same chunks, exactly or with far clusters replaced by their dipoles.
+//
+// Each section's own comment has the details.  The entry points (extern "C", at the end) keep their device scratch in a
+// Scratch, and sort along the Morton curve through morton_order.
 #include <hipcub/hipcub.hpp>
 
 #include <cmath>
@@ -71,6 +78,45 @@ __device__ __forceinline__ unsigned spread10(unsigned v) {
     return v;
 }
 
+// 30-bit Morton key of a point in box bb: 10 bits per axis, x lowest; outside the box clamps, NaN and a flat axis give 0.
+// The point comes as coord(axis), so that an axis is loaded where it is used (registers: as few as the loops this replaces).
+template <class Coord>
+__device__ __forceinline__ unsigned morton_key(Coord coord, const Box3& bb) {
+    unsigned code = 0;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        double u = bb.ext[a] > 0.0 ? (coord(a) - bb.lo[a]) / bb.ext[a] : 0.0;
+        u = u < 0.0 ? 0.0 : (u > 1.0 ? 1.0 : u);
+        if (!(u == u)) u = 0.0;  // the clamp lets NaN through
+        code |= spread10((unsigned)(u * 1023.0)) << a;
+    }
+    return code;
+}
+
+__device__ __forceinline__ double wave_min(double v) {
+    for (int off = PF_WAVE / 2; off > 0; off >>= 1) v = fmin(v, __shfl_xor(v, off, PF_WAVE));
+    return v;
+}
+
+__device__ __forceinline__ double wave_max(double v) {
+    for (int off = PF_WAVE / 2; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off, PF_WAVE));
+    return v;
+}
+
+__device__ __forceinline__ double wave_sum(double v) {  // fixed butterfly: the same order on every run
+    for (int off = PF_WAVE / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, PF_WAVE);
+    return v;
+}
+
+// the least d of the wave and its index, in every lane; lowest index on ties
+__device__ __forceinline__ void wave_argmin(double& d, int64_t& i) {
+    for (int off = PF_WAVE / 2; off > 0; off >>= 1) {
+        const double od = __shfl_xor(d, off, PF_WAVE);
+        const int64_t oi = __shfl_xor(i, off, PF_WAVE);
+        if (od < d || (od == d && oi < i)) d = od, i = oi;
+    }
+}
+
 __device__ __forceinline__ void tri_vertices(const int32_t* __restrict__ faces, int32_t vpf, int64_t t, int32_t v[3]) {
     const int32_t per = vpf - 2;
     const int64_t f = t / per;
@@ -87,17 +133,17 @@ __global__ __launch_bounds__(PF_BLOCK) void k_tri_keys(const double* __restrict_
     if (t >= n_tri) return;
     int32_t v[3];
     tri_vertices(faces, vpf, t, v);
-    unsigned code = 0;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const double c = (pts[3 * (int64_t)v[0] + a] + pts[3 * (int64_t)v[1] + a] + pts[3 * (int64_t)v[2] + a]) / 3.0;
-        double u = bb.ext[a] > 0.0 ? (c - bb.lo[a]) / bb.ext[a] : 0.0;
-        u = u < 0.0 ? 0.0 : (u > 1.0 ? 1.0 : u);  // also maps NaN to 0
-        if (!(u == u)) u = 0.0;
-        code |= spread10((unsigned)(u * 1023.0)) << a;
-    }
-    keys[t] = code;
+    const auto centroid = [&](int a) { return (pts[3 * (int64_t)v[0] + a] + pts[3 * (int64_t)v[1] + a] + pts[3 * (int64_t)v[2] + a]) / 3.0; };
+    keys[t] = morton_key(centroid, bb);
     vals[t] = (int32_t)t;
+}
+
+__global__ __launch_bounds__(PF_BLOCK) void k_qry_keys(const double* __restrict__ qry, int64_t n, Box3 bb,
+                                                       unsigned* __restrict__ keys, int32_t* __restrict__ vals) {
+    const int64_t i = (int64_t)blockIdx.x * PF_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    keys[i] = morton_key([&](int a) { return qry[3 * i + a]; }, bb);
+    vals[i] = (int32_t)i;
 }
 
 __global__ __launch_bounds__(PF_BLOCK) void k_tri_gather(const double* __restrict__ pts, const int32_t* __restrict__ faces,
@@ -162,65 +208,12 @@ __global__ __launch_bounds__(PF_WAVE) void k_super_boxes(const double* __restric
 
 __device__ __forceinline__ double dot3(const double a[3], const double b[3]) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
 
-// Ericson, Real-Time Collision Detection 5.1.5; same operation order as oracle/icp_port.py.
-__device__ __forceinline__ void closest_on_triangle(const double p[3], const double a[3], const double b[3], const double c[3],
-                                                    double out[3]) {
-    double ab[3], ac[3], ap[3], bp[3], cp[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        ab[k] = b[k] - a[k];
-        ac[k] = c[k] - a[k];
-        ap[k] = p[k] - a[k];
-        bp[k] = p[k] - b[k];
-        cp[k] = p[k] - c[k];
-    }
-    const double d1 = dot3(ab, ap), d2 = dot3(ac, ap);
-    if (d1 <= 0.0 && d2 <= 0.0) {
-        out[0] = a[0], out[1] = a[1], out[2] = a[2];
-        return;
-    }
-    const double d3 = dot3(ab, bp), d4 = dot3(ac, bp);
-    if (d3 >= 0.0 && d4 <= d3) {
-        out[0] = b[0], out[1] = b[1], out[2] = b[2];
-        return;
-    }
-    const double vc = d1 * d4 - d3 * d2;
-    if (vc <= 0.0 && d1 >= 0.0 && d3 <= 0.0) {
-        const double v = d1 / (d1 - d3);
-#pragma unroll
-        for (int k = 0; k < 3; ++k) out[k] = a[k] + v * ab[k];
-        return;
-    }
-    const double d5 = dot3(ab, cp), d6 = dot3(ac, cp);
-    if (d6 >= 0.0 && d5 <= d6) {
-        out[0] = c[0], out[1] = c[1], out[2] = c[2];
-        return;
-    }
-    const double vb = d5 * d2 - d1 * d6;
-    if (vb <= 0.0 && d2 >= 0.0 && d6 <= 0.0) {
-        const double w = d2 / (d2 - d6);
-#pragma unroll
-        for (int k = 0; k < 3; ++k) out[k] = a[k] + w * ac[k];
-        return;
-    }
-    const double va = d3 * d6 - d5 * d4;
-    if (va <= 0.0 && (d4 - d3) >= 0.0 && (d5 - d6) >= 0.0) {
-        const double w = (d4 - d3) / ((d4 - d3) + (d5 - d6));
-#pragma unroll
-        for (int k = 0; k < 3; ++k) out[k] = b[k] + w * (c[k] - b[k]);
-        return;
-    }
-    const double denom = 1.0 / (va + vb + vc);
-    const double v = vb * denom, w = vc * denom;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) out[k] = (a[k] + ab[k] * v) + ac[k] * w;
-}
-
-// closest_on_triangle, same operations in the same order, that also names the Voronoi region of the result:
-// 0 1 2 = corner a b c, 3 = edge ab, 4 = edge bc, 5 = edge ca, 6 = interior (PF_REGION_*)
+// Ericson, Real-Time Collision Detection 5.1.5; same operation order as oracle/icp_port.py.  Returns the Voronoi region
+// of the result: 0 1 2 = corner a b c, 3 = edge ab, 4 = edge bc, 5 = edge ca, 6 = interior (PF_REGION_*); only k_signed
+// asks for it.
 enum { PF_REGION_EDGE_AB = 3, PF_REGION_EDGE_BC = 4, PF_REGION_EDGE_CA = 5, PF_REGION_FACE = 6 };
-__device__ __forceinline__ int closest_on_triangle_region(const double p[3], const double a[3], const double b[3], const double c[3],
-                                                          double out[3]) {
+__device__ __forceinline__ int closest_on_triangle(const double p[3], const double a[3], const double b[3], const double c[3],
+                                                   double out[3]) {
     double ab[3], ac[3], ap[3], bp[3], cp[3];
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
@@ -284,6 +277,29 @@ __device__ __forceinline__ double box_dist2(const double p[3], const double* __r
     return s;
 }
 
+// The chunk nearest to p, for a whole wave: the nearest super-chunk, then the nearest chunk inside it, by box distance
+// (one box per lane), lowest index on ties; n_chunks when there is none (a NaN point, no finite box).  Every lane
+// returns the same.
+__device__ __forceinline__ int64_t nearest_chunk(const double p[3], const double* __restrict__ box, const double* __restrict__ sbox,
+                                                 int64_t n_chunks, int64_t n_super, int lane) {
+    const double inf = std::numeric_limits<double>::infinity();
+    double nd = inf;
+    int64_t ns = n_super;  // sentinel: none
+    for (int64_t s = lane; s < n_super; s += PF_WAVE) {
+        const double d = box_dist2(p, sbox + 6 * s);
+        if (d < nd) nd = d, ns = s;
+    }
+    wave_argmin(nd, ns);
+    int64_t c0 = n_chunks;
+    if (ns < n_super) {
+        c0 = ns * PF_WAVE + lane;
+        nd = c0 < n_chunks ? box_dist2(p, box + 6 * c0) : inf;
+        if (!(nd < inf)) c0 = n_chunks;
+        wave_argmin(nd, c0);
+    }
+    return c0;
+}
+
 struct Best {
     double d2;
     int32_t orig;  // triangle index (tie-break: lowest)
@@ -325,15 +341,10 @@ __device__ __forceinline__ void scan_chunks(const double* __restrict__ tri, cons
     }
 }
 
-__device__ __forceinline__ double wave_min(double v) {
-    for (int off = PF_WAVE / 2; off > 0; off >>= 1) v = fmin(v, __shfl_xor(v, off, PF_WAVE));
-    return v;
-}
-
 constexpr double PF_BOX_SLACK = 1.0 + 1e-9;  // the box test must never reject on a rounding error
 
-// one block (PF_CLOSEST_WAVES waves) per query point
-constexpr int PF_CLOSEST_WAVES = 4;  // waves per query point (8 measured slower: 0.29 vs 0.25 ms per 1000 landmarks)
+// one block of PF_CLOSEST_WAVES waves per query point (8 waves measured slower: 0.29 vs 0.25 ms per 1000 landmarks)
+constexpr int PF_CLOSEST_WAVES = 4;
 
 __global__ __launch_bounds__(PF_CLOSEST_WAVES* PF_WAVE) void k_closest(const double* __restrict__ tri, const int32_t* __restrict__ tri_orig,
                                                       const double* __restrict__ box, const double* __restrict__ sbox,
@@ -350,28 +361,8 @@ __global__ __launch_bounds__(PF_CLOSEST_WAVES* PF_WAVE) void k_closest(const dou
     const double p[3] = {qry[3 * qi], qry[3 * qi + 1], qry[3 * qi + 2]};
     const double inf = std::numeric_limits<double>::infinity();
 
-    // (1) nearest super-chunk, nearest chunk inside it (by box distance; lowest index on ties) — every wave, same result
-    auto wave_argmin = [&](double& d, int64_t& i) {
-        for (int off = PF_WAVE / 2; off > 0; off >>= 1) {
-            const double od = __shfl_xor(d, off, PF_WAVE);
-            const int64_t oi = __shfl_xor(i, off, PF_WAVE);
-            if (od < d || (od == d && oi < i)) d = od, i = oi;
-        }
-    };
-    double nd = inf;
-    int64_t ns = n_super;  // sentinel: none
-    for (int64_t s = lane; s < n_super; s += PF_WAVE) {
-        const double d = box_dist2(p, sbox + 6 * s);
-        if (d < nd) nd = d, ns = s;
-    }
-    wave_argmin(nd, ns);
-    int64_t c0 = n_chunks;
-    if (ns < n_super) {
-        c0 = ns * PF_WAVE + lane;
-        nd = c0 < n_chunks ? box_dist2(p, box + 6 * c0) : inf;
-        if (!(nd < inf)) c0 = n_chunks;
-        wave_argmin(nd, c0);
-    }
+    // (1) the chunk nearest to the query - every wave, same result
+    const int64_t c0 = nearest_chunk(p, box, sbox, n_chunks, n_super, lane);
     Best best;
     best.d2 = inf, best.orig = 0x7fffffff, best.pt[0] = best.pt[1] = best.pt[2] = 0.0;
     if (c0 < n_chunks) {
@@ -382,8 +373,8 @@ __global__ __launch_bounds__(PF_CLOSEST_WAVES* PF_WAVE) void k_closest(const dou
 
     // (2) every chunk whose box is within the bound, super-chunk by super-chunk; of a super-chunk's surviving
     // chunks, wave w takes those at positions w, w+4, ... and scans NB of them per step
-    const unsigned long long mine = (NW == 8 ? 0x0101010101010101ull : 0x1111111111111111ull) << wave;
-    static_assert(NW == 4 || NW == 8, "chunk positions are dealt to 4 or 8 waves");
+    static_assert(NW == 4, "the mask deals chunk positions to 4 waves");
+    const unsigned long long mine = 0x1111111111111111ull << wave;
     for (int64_t sb = 0; sb < n_super; sb += PF_WAVE) {
         const int64_t s = sb + lane;
         unsigned long long smask = __ballot(s < n_super && box_dist2(p, sbox + 6 * s) <= bound * PF_BOX_SLACK);
@@ -451,22 +442,6 @@ __global__ __launch_bounds__(PF_CLOSEST_WAVES* PF_WAVE) void k_closest(const dou
 // never larger than the point-box test of any query inside it, and a triangle's box never farther than the triangle,
 // so nothing the per-query search would test is skipped, and the lanes of a query merge with the same tie rule.
 
-__global__ __launch_bounds__(PF_BLOCK) void k_qry_keys(const double* __restrict__ qry, int64_t n, Box3 bb,
-                                                       unsigned* __restrict__ keys, int32_t* __restrict__ vals) {
-    const int64_t i = (int64_t)blockIdx.x * PF_BLOCK + threadIdx.x;
-    if (i >= n) return;
-    unsigned code = 0;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        double u = bb.ext[a] > 0.0 ? (qry[3 * i + a] - bb.lo[a]) / bb.ext[a] : 0.0;
-        u = u < 0.0 ? 0.0 : (u > 1.0 ? 1.0 : u);
-        if (!(u == u)) u = 0.0;  // NaN coordinates: key 0
-        code |= spread10((unsigned)(u * 1023.0)) << a;
-    }
-    keys[i] = code;
-    vals[i] = (int32_t)i;
-}
-
 // squared distance between two boxes (0 if they overlap); never larger than box_dist2 of any point of the first box
 __device__ __forceinline__ double boxbox_dist2(const double lo[3], const double hi[3], const double* __restrict__ bx) {
     double s = 0.0;
@@ -476,16 +451,6 @@ __device__ __forceinline__ double boxbox_dist2(const double lo[3], const double 
         s += d * d;
     }
     return s;
-}
-
-__device__ __forceinline__ double wave_max(double v) {
-    for (int off = PF_WAVE / 2; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off, PF_WAVE));
-    return v;
-}
-
-__device__ __forceinline__ double wave_sum(double v) {  // fixed butterfly: the same order on every run
-    for (int off = PF_WAVE / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, PF_WAVE);
-    return v;
 }
 
 // the larger distance wins; lowest query index on ties; idx < 0 = none
@@ -507,10 +472,10 @@ __global__ __launch_bounds__(PF_WAVE) void k_distance(const double* __restrict__
                                                       int32_t* __restrict__ out_face, double* __restrict__ partial) {
     __shared__ double s_tri[9][PF_TRI_CHUNK];  // 4.5 KiB: one chunk, SoA as in HBM
     __shared__ int32_t s_orig[PF_TRI_CHUNK];
-    constexpr int PF_DIST_PACKET = PACKET, PF_DIST_SUB = PF_WAVE / PACKET;
+    constexpr int SUB = PF_WAVE / PACKET;  // lanes per query
     static_assert(PF_WAVE % PACKET == 0, "a packet divides the wave");
-    const int lane = threadIdx.x, sub = lane / PF_DIST_PACKET;
-    const int64_t i = (int64_t)blockIdx.x * PF_DIST_PACKET + (lane % PF_DIST_PACKET);
+    const int lane = threadIdx.x, sub = lane / PACKET;
+    const int64_t i = (int64_t)blockIdx.x * PACKET + (lane % PACKET);
     const bool live = i < n_qry;
     const int64_t qi = live ? perm[i] : -1;  // the caller's index of this lane's query
     const double inf = std::numeric_limits<double>::infinity();
@@ -520,9 +485,9 @@ __global__ __launch_bounds__(PF_WAVE) void k_distance(const double* __restrict__
 
     Best best;
     best.d2 = inf, best.orig = 0x7fffffff;
-    // the query's bound: the least distance its PF_DIST_SUB lanes have found
+    // the query's bound: the least distance its SUB lanes have found
     auto query_min = [&](double v) {
-        for (int off = PF_DIST_PACKET; off < PF_WAVE; off <<= 1) v = fmin(v, __shfl_xor(v, off, PF_WAVE));
+        for (int off = PACKET; off < PF_WAVE; off <<= 1) v = fmin(v, __shfl_xor(v, off, PF_WAVE));
         return v;
     };
     if (__ballot(ok)) {
@@ -548,7 +513,7 @@ __global__ __launch_bounds__(PF_WAVE) void k_distance(const double* __restrict__
             }
             __syncthreads();
             if (ok) {
-                for (int t = sub; t < cnt; t += PF_DIST_SUB) {
+                for (int t = sub; t < cnt; t += SUB) {
                     const double a[3] = {s_tri[0][t], s_tri[1][t], s_tri[2][t]}, b[3] = {s_tri[3][t], s_tri[4][t], s_tri[5][t]},
                                  cc[3] = {s_tri[6][t], s_tri[7][t], s_tri[8][t]};
                     // the triangle's own box first: it is never farther than the triangle (the chunk-box argument)
@@ -571,30 +536,10 @@ __global__ __launch_bounds__(PF_WAVE) void k_distance(const double* __restrict__
         };
         // does any query's own point-box test (k_closest's) keep chunk c?
         auto wanted = [&](int64_t c) { return __ballot(ok && box_dist2(p, box + 6 * c) <= qbest * PF_BOX_SLACK) != 0; };
-        auto wave_argmin = [&](double& d, int64_t& k) {
-            for (int off = PF_WAVE / 2; off > 0; off >>= 1) {
-                const double od = __shfl_xor(d, off, PF_WAVE);
-                const int64_t ok2 = __shfl_xor(k, off, PF_WAVE);
-                if (od < d || (od == d && ok2 < k)) d = od, k = ok2;
-            }
-        };
 
-        // (1) seed: the chunk nearest to the packet's centre (nearest super-chunk, then nearest chunk inside it)
+        // (1) seed: the chunk nearest to the packet's centre
         const double ctr[3] = {0.5 * (lo[0] + hi[0]), 0.5 * (lo[1] + hi[1]), 0.5 * (lo[2] + hi[2])};
-        double nd = inf;
-        int64_t ns = n_super;
-        for (int64_t s = lane; s < n_super; s += PF_WAVE) {
-            const double d = box_dist2(ctr, sbox + 6 * s);
-            if (d < nd) nd = d, ns = s;
-        }
-        wave_argmin(nd, ns);
-        int64_t c0 = n_chunks;
-        if (ns < n_super) {
-            c0 = ns * PF_WAVE + lane;
-            nd = c0 < n_chunks ? box_dist2(ctr, box + 6 * c0) : inf;
-            if (!(nd < inf)) c0 = n_chunks;
-            wave_argmin(nd, c0);
-        }
+        const int64_t c0 = nearest_chunk(ctr, box, sbox, n_chunks, n_super, lane);
         if (c0 < n_chunks) scan(c0);
         double bound = wave_max(ok ? qbest : -inf);  // the packet's bound: its worst query
 
@@ -620,7 +565,7 @@ __global__ __launch_bounds__(PF_WAVE) void k_distance(const double* __restrict__
     }
 
     // the query's winner over its lanes (smallest distance, lowest triangle index), outputs in the caller's order
-    for (int off = PF_DIST_PACKET; off < PF_WAVE; off <<= 1) {
+    for (int off = PACKET; off < PF_WAVE; off <<= 1) {
         const double od = __shfl_xor(best.d2, off, PF_WAVE);
         const int32_t oo = __shfl_xor(best.orig, off, PF_WAVE);
         if (better(od, oo, best.d2, best.orig)) best.d2 = od, best.orig = oo;
@@ -820,7 +765,7 @@ __global__ __launch_bounds__(PF_BLOCK) void k_signed(const double* __restrict__ 
         const double b[3] = {pts[3 * (int64_t)v[1]], pts[3 * (int64_t)v[1] + 1], pts[3 * (int64_t)v[1] + 2]};
         const double c[3] = {pts[3 * (int64_t)v[2]], pts[3 * (int64_t)v[2] + 1], pts[3 * (int64_t)v[2] + 2]};
         double q[3];
-        const int reg = closest_on_triangle_region(p, a, b, c, q);
+        const int reg = closest_on_triangle(p, a, b, c, q);
         const double dx = p[0] - q[0], dy = p[1] - q[1], dz = p[2] - q[2];
         const double e2 = dx * dx + dy * dy + dz * dz;
         if (better(e2, t, bd2, bt)) {
@@ -852,66 +797,6 @@ __global__ __launch_bounds__(PF_BLOCK) void k_signed(const double* __restrict__ 
     else if (!(s > 0.0)) atomicAdd(n_ambiguous, 1ull);  // zero (or NaN) pseudonormal component: + and counted
     out_sd[i] = sd;
     out_feature[i] = feature;
-}
-
-Box3 query_box(const double* qry, int64_t n_qry) {  // Morton box of the finite queries
-    Box3 bb;
-    for (int a = 0; a < 3; ++a) {
-        double lo = std::numeric_limits<double>::infinity(), hi = -lo;
-        for (int64_t i = 0; i < n_qry; ++i) {
-            const double x = qry[3 * i + a];
-            if (!std::isfinite(x)) continue;
-            if (x < lo) lo = x;
-            if (x > hi) hi = x;
-        }
-        bb.lo[a] = lo;
-        bb.ext[a] = hi - lo;
-        if (!(bb.ext[a] > 0.0) || !std::isfinite(bb.ext[a])) bb.ext[a] = 0.0;
-    }
-    return bb;
-}
-
-// the search of pf_surface_distance on queries already in HBM (d_q): Morton sort, k_distance, the fixed-order
-// statistics.  d_d2 / d_face may be NULL; d_stats [PF_DIST_STATS] may not.
-hipError_t distance_search(pf_surface* s, hipStream_t st, const double* d_q, int64_t n_qry, const Box3& bb, double* d_d2,
-                           int32_t* d_face, double* d_stats) {
-    // 16 queries per wave once that gives >= 4096 waves (4 per SIMD), else 4 (measured: profiles/surface_distance.md)
-    const bool big = n_qry >= (int64_t)16 * 4096;
-    const int64_t n_pack = big ? (n_qry + 15) / 16 : (n_qry + 3) / 4;
-    double* d_part = nullptr;
-    unsigned *k0 = nullptr, *k1 = nullptr;
-    int32_t *v0 = nullptr, *v1 = nullptr;
-    void* tmp = nullptr;
-    size_t need = 0;
-    hipError_t e = hipSuccess;
-    do {
-        if ((e = pf_malloc(st, (void**)&k0, sizeof(unsigned) * n_qry)) != hipSuccess) break;
-        if ((e = pf_malloc(st, (void**)&k1, sizeof(unsigned) * n_qry)) != hipSuccess) break;
-        if ((e = pf_malloc(st, (void**)&v0, sizeof(int32_t) * n_qry)) != hipSuccess) break;
-        if ((e = pf_malloc(st, (void**)&v1, sizeof(int32_t) * n_qry)) != hipSuccess) break;
-        if ((e = pf_malloc(st, (void**)&d_part, sizeof(double) * PF_DIST_STATS * n_pack)) != hipSuccess) break;
-        k_qry_keys<<<nblk(n_qry), PF_BLOCK, 0, st>>>(d_q, n_qry, bb, k0, v0);
-        if ((e = hipGetLastError()) != hipSuccess) break;
-        if ((e = hipcub::DeviceRadixSort::SortPairs(nullptr, need, k0, k1, v0, v1, (int)n_qry, 0, 30, st)) != hipSuccess) break;
-        if ((e = pf_malloc(st, &tmp, need)) != hipSuccess) break;
-        if ((e = hipcub::DeviceRadixSort::SortPairs(tmp, need, k0, k1, v0, v1, (int)n_qry, 0, 30, st)) != hipSuccess) break;
-        if (big)
-            k_distance<16><<<(unsigned)n_pack, PF_WAVE, 0, st>>>(s->tri, s->tri_orig, s->box, s->sbox, s->n_tri, s->n_chunks, s->n_super,
-                                                                 d_q, v1, n_qry, s->vpf - 2, d_d2, d_face, d_part);
-        else
-            k_distance<4><<<(unsigned)n_pack, PF_WAVE, 0, st>>>(s->tri, s->tri_orig, s->box, s->sbox, s->n_tri, s->n_chunks, s->n_super,
-                                                                d_q, v1, n_qry, s->vpf - 2, d_d2, d_face, d_part);
-        k_distance_stats<<<1, PF_BLOCK, 0, st>>>(d_part, n_pack, d_stats);
-        e = hipGetLastError();
-    } while (0);
-    // the cache hands these blocks out again only to work queued behind the kernels above
-    pf_free(st, k0);
-    pf_free(st, k1);
-    pf_free(st, v0);
-    pf_free(st, v1);
-    pf_free(st, tmp);
-    pf_free(st, d_part);
-    return e;
 }
 
 // ---- generalized winding numbers (pf_surface_prepare_winding, pf_surface_winding) -------------------------------
@@ -1126,6 +1011,128 @@ __global__ __launch_bounds__(PF_WAVE) void k_winding(const double* __restrict__ 
     }
 }
 
+// ---- host side ---------------------------------------------------------------------------------------------------------
+
+// The device side of one call: scratch blocks from the ctx's cache, all given back when the call's scope ends (after
+// whatever synchronise the call made: as late as the blocks can matter), and the stream work itself.  The first failure is
+// kept in err and turns everything that follows into a no-op, so a call is written without branches: ok() before its
+// kernels, err at the end.
+struct Scratch {
+    const hipStream_t st;
+    hipError_t err = hipSuccess;
+    std::vector<void*> blocks;
+
+    explicit Scratch(hipStream_t stream) : st(stream) {}
+    Scratch(const Scratch&) = delete;
+    Scratch& operator=(const Scratch&) = delete;
+    ~Scratch() {
+        for (void* p : blocks) pf_free(st, p);
+    }
+    bool ok() const { return err == hipSuccess; }
+    void note(hipError_t e) {
+        if (ok()) err = e;
+    }
+    template <class T>
+    T* keep(size_t count) {  // a block that outlives the call: the caller owns it, also after a failure
+        void* p = nullptr;
+        if (ok()) err = pf_malloc(st, &p, sizeof(T) * count);
+        return (T*)p;
+    }
+    template <class T>
+    T* get(size_t count) {
+        T* p = keep<T>(count);
+        if (p) blocks.push_back(p);
+        return p;
+    }
+    template <class T>
+    void upload(T* dst, const T* src, size_t count) {
+        if (ok()) err = hipMemcpyAsync(dst, src, sizeof(T) * count, hipMemcpyHostToDevice, st);
+    }
+    template <class T>
+    void download(T* dst, const T* src, size_t count) {  // dst == NULL: the caller did not ask for it
+        if (ok() && dst) err = hipMemcpyAsync(dst, src, sizeof(T) * count, hipMemcpyDeviceToHost, st);
+    }
+    void zero(void* p, size_t bytes) {
+        if (ok()) err = hipMemsetAsync(p, 0, bytes, st);
+    }
+    void launched() { note(hipGetLastError()); }  // after the kernels of an ok() block
+    void sync() {
+        if (ok()) err = hipStreamSynchronize(st);
+    }
+};
+
+// The box the Morton keys of n points are taken in.  finite_only leaves every non-finite coordinate out (queries);
+// without it only NaN is left out and an infinite coordinate flattens its axis (the vertices of a surface, as ever: the
+// order of the triangles decides the order of the winding sums).
+Box3 point_box(const double* pts, int64_t n, bool finite_only) {
+    Box3 bb;
+    for (int a = 0; a < 3; ++a) {
+        double lo = std::numeric_limits<double>::infinity(), hi = -lo;
+        for (int64_t i = 0; i < n; ++i) {
+            const double x = pts[3 * i + a];
+            if (finite_only && !std::isfinite(x)) continue;
+            if (x < lo) lo = x;
+            if (x > hi) hi = x;
+        }
+        bb.lo[a] = lo;
+        bb.ext[a] = hi - lo;
+        if (!(bb.ext[a] > 0.0) || !std::isfinite(bb.ext[a])) bb.ext[a] = 0.0;
+    }
+    return bb;
+}
+
+// The order of n items along the Morton curve in box bb, as a device permutation (sorted position -> item; stable): the
+// centroids of the fan triangles of (d_pts, d_faces, vpf), or with d_faces == NULL the points d_pts themselves.  Keys,
+// values and the sort's temporary are scratch of sc; NULL after a failure.
+const int32_t* morton_order(Scratch& sc, const double* d_pts, const int32_t* d_faces, int32_t vpf, int64_t n, const Box3& bb) {
+    unsigned *k0 = sc.get<unsigned>(n), *k1 = sc.get<unsigned>(n);
+    int32_t *v0 = sc.get<int32_t>(n), *v1 = sc.get<int32_t>(n);
+    size_t need = 0;
+    if (sc.ok()) {
+        if (d_faces)
+            k_tri_keys<<<nblk(n), PF_BLOCK, 0, sc.st>>>(d_pts, d_faces, vpf, n, bb, k0, v0);
+        else
+            k_qry_keys<<<nblk(n), PF_BLOCK, 0, sc.st>>>(d_pts, n, bb, k0, v0);
+        sc.launched();
+    }
+    if (sc.ok()) sc.note(hipcub::DeviceRadixSort::SortPairs(nullptr, need, k0, k1, v0, v1, (int)n, 0, 30, sc.st));
+    void* tmp = sc.get<char>(need);
+    if (sc.ok()) sc.note(hipcub::DeviceRadixSort::SortPairs(tmp, need, k0, k1, v0, v1, (int)n, 0, 30, sc.st));
+    return sc.ok() ? v1 : nullptr;
+}
+
+// the search of pf_surface_distance on queries already in HBM (d_q): Morton sort, k_distance, the fixed-order
+// statistics.  d_d2 / d_face may be NULL; d_stats [PF_DIST_STATS] may not.
+hipError_t distance_search(pf_surface* s, hipStream_t st, const double* d_q, int64_t n_qry, const Box3& bb, double* d_d2,
+                           int32_t* d_face, double* d_stats) {
+    // 16 queries per wave once that gives >= 4096 waves (4 per SIMD), else 4 (measured: profiles/surface_distance.md)
+    const bool big = n_qry >= (int64_t)16 * 4096;
+    const int64_t n_pack = big ? (n_qry + 15) / 16 : (n_qry + 3) / 4;
+    // no synchronise here: the scratch goes back at enqueue time, and the cache hands these blocks out again only to work
+    // queued behind the kernels below
+    Scratch sc(st);
+    const int32_t* perm = morton_order(sc, d_q, nullptr, 0, n_qry, bb);
+    double* d_part = sc.get<double>(PF_DIST_STATS * n_pack);
+    if (sc.ok()) {
+        if (big)
+            k_distance<16><<<(unsigned)n_pack, PF_WAVE, 0, st>>>(s->tri, s->tri_orig, s->box, s->sbox, s->n_tri, s->n_chunks, s->n_super,
+                                                                 d_q, perm, n_qry, s->vpf - 2, d_d2, d_face, d_part);
+        else
+            k_distance<4><<<(unsigned)n_pack, PF_WAVE, 0, st>>>(s->tri, s->tri_orig, s->box, s->sbox, s->n_tri, s->n_chunks, s->n_super,
+                                                                d_q, perm, n_qry, s->vpf - 2, d_d2, d_face, d_part);
+        k_distance_stats<<<1, PF_BLOCK, 0, st>>>(d_part, n_pack, d_stats);
+        sc.launched();
+    }
+    return sc.err;
+}
+
+// the per-surface arrays of the signed distances: gone, as before pf_surface_prepare_signed
+void release_signed(pf_surface* s, hipStream_t st) {
+    pf_free(st, s->pts), pf_free(st, s->faces), pf_free(st, s->tnrm), pf_free(st, s->enrm), pf_free(st, s->vnrm);
+    s->pts = s->tnrm = s->enrm = s->vnrm = nullptr;
+    s->faces = nullptr;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1158,18 +1165,7 @@ int pf_surface_create(pf_ctx* ctx, const double* pts, int64_t n, const int32_t* 
     for (int64_t i = 0; i < n_faces * vpf; ++i)
         PF_CHECK(faces[i] >= 0 && faces[i] < n, PF_E_ARG, "pf_surface_create: face %lld references vertex %d of %lld",
                  (long long)(i / vpf), faces[i], (long long)n);
-    Box3 bb;
-    for (int a = 0; a < 3; ++a) {
-        double lo = std::numeric_limits<double>::infinity(), hi = -lo;
-        for (int64_t i = 0; i < n; ++i) {
-            const double x = pts[3 * i + a];
-            if (x < lo) lo = x;
-            if (x > hi) hi = x;
-        }
-        bb.lo[a] = lo;
-        bb.ext[a] = hi - lo;
-        if (!(bb.ext[a] > 0.0) || !std::isfinite(bb.ext[a])) bb.ext[a] = 0.0;
-    }
+    const Box3 bb = point_box(pts, n, false);
     PF_HIP(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     pf_surface* s = new pf_surface();
@@ -1179,44 +1175,27 @@ int pf_surface_create(pf_ctx* ctx, const double* pts, int64_t n, const int32_t* 
     s->n_chunks = (s->n_tri + PF_TRI_CHUNK - 1) / PF_TRI_CHUNK;
     s->n_super = (s->n_chunks + PF_WAVE - 1) / PF_WAVE;
     const int64_t T = s->n_tri;
-    double* d_pts = nullptr;
-    int32_t* d_faces = nullptr;
-    unsigned *k0 = nullptr, *k1 = nullptr;
-    int32_t *v0 = nullptr, *v1 = nullptr;
-    void* tmp = nullptr;
-    size_t need = 0;
-    hipError_t e = hipSuccess;
-    do {
-        if ((e = pf_malloc(st, (void**)&d_pts, sizeof(double) * 3 * n)) != hipSuccess) break;
-        if ((e = pf_malloc(st, (void**)&d_faces, sizeof(int32_t) * n_faces * vpf)) != hipSuccess) break;
-        if ((e = pf_malloc(st, (void**)&k0, sizeof(unsigned) * T)) != hipSuccess) break;
-        if ((e = pf_malloc(st, (void**)&k1, sizeof(unsigned) * T)) != hipSuccess) break;
-        if ((e = pf_malloc(st, (void**)&v0, sizeof(int32_t) * T)) != hipSuccess) break;
-        if ((e = pf_malloc(st, (void**)&v1, sizeof(int32_t) * T)) != hipSuccess) break;
-        if ((e = pf_malloc(st, (void**)&s->tri, sizeof(double) * 9 * T)) != hipSuccess) break;
-        if ((e = pf_malloc(st, (void**)&s->tri_orig, sizeof(int32_t) * T)) != hipSuccess) break;
-        if ((e = pf_malloc(st, (void**)&s->box, sizeof(double) * 6 * s->n_chunks)) != hipSuccess) break;
-        if ((e = pf_malloc(st, (void**)&s->sbox, sizeof(double) * 6 * s->n_super)) != hipSuccess) break;
-        if ((e = hipMemcpyAsync(d_pts, pts, sizeof(double) * 3 * n, hipMemcpyHostToDevice, st)) != hipSuccess) break;
-        if ((e = hipMemcpyAsync(d_faces, faces, sizeof(int32_t) * n_faces * vpf, hipMemcpyHostToDevice, st)) != hipSuccess) break;
-        k_tri_keys<<<nblk(T), PF_BLOCK, 0, st>>>(d_pts, d_faces, vpf, T, bb, k0, v0);
-        if ((e = hipGetLastError()) != hipSuccess) break;
-        if ((e = hipcub::DeviceRadixSort::SortPairs(nullptr, need, k0, k1, v0, v1, (int)T, 0, 30, st)) != hipSuccess) break;
-        if ((e = pf_malloc(st, &tmp, need)) != hipSuccess) break;
-        if ((e = hipcub::DeviceRadixSort::SortPairs(tmp, need, k0, k1, v0, v1, (int)T, 0, 30, st)) != hipSuccess) break;
-        k_tri_gather<<<nblk(T), PF_BLOCK, 0, st>>>(d_pts, d_faces, vpf, T, v1, s->tri, s->tri_orig);
-        k_chunk_boxes<<<(unsigned)s->n_chunks, PF_WAVE, 0, st>>>(s->tri, T, s->box);
-        k_super_boxes<<<(unsigned)s->n_super, PF_WAVE, 0, st>>>(s->box, s->n_chunks, s->sbox);
-        if ((e = hipGetLastError()) != hipSuccess) break;
-        e = hipStreamSynchronize(st);  // the host arrays may go away after the call
-    } while (0);
-    pf_free(st, d_pts);
-    pf_free(st, d_faces);
-    pf_free(st, k0);
-    pf_free(st, k1);
-    pf_free(st, v0);
-    pf_free(st, v1);
-    pf_free(st, tmp);
+    hipError_t e;
+    {
+        Scratch sc(st);
+        double* d_pts = sc.get<double>(3 * n);
+        int32_t* d_faces = sc.get<int32_t>(n_faces * vpf);
+        s->tri = sc.keep<double>(9 * T);
+        s->tri_orig = sc.keep<int32_t>(T);
+        s->box = sc.keep<double>(6 * s->n_chunks);
+        s->sbox = sc.keep<double>(6 * s->n_super);
+        sc.upload(d_pts, pts, 3 * n);
+        sc.upload(d_faces, faces, n_faces * vpf);
+        const int32_t* order = morton_order(sc, d_pts, d_faces, vpf, T, bb);
+        if (sc.ok()) {
+            k_tri_gather<<<nblk(T), PF_BLOCK, 0, st>>>(d_pts, d_faces, vpf, T, order, s->tri, s->tri_orig);
+            k_chunk_boxes<<<(unsigned)s->n_chunks, PF_WAVE, 0, st>>>(s->tri, T, s->box);
+            k_super_boxes<<<(unsigned)s->n_super, PF_WAVE, 0, st>>>(s->box, s->n_chunks, s->sbox);
+            sc.launched();
+        }
+        sc.sync();  // the host arrays may go away after the call
+        e = sc.err;
+    }
     if (e != hipSuccess) {
         pf_set_error("pf_surface_create: %s", hipGetErrorString(e));
         pf_surface_free(s);
@@ -1232,29 +1211,21 @@ int pf_surface_closest(pf_surface* s, const double* qry, int64_t n_qry, double* 
     if (n_qry == 0) return PF_OK;
     PF_HIP(hipSetDevice(s->ctx->device));
     hipStream_t st = s->ctx->stream;
-    double *d_q = nullptr, *d_pt = nullptr, *d_d2 = nullptr;
-    int32_t* d_face = nullptr;
-    hipError_t e = hipSuccess;
-    do {
-        if ((e = pf_malloc(st, (void**)&d_q, sizeof(double) * 3 * n_qry)) != hipSuccess) break;
-        if ((e = pf_malloc(st, (void**)&d_pt, sizeof(double) * 3 * n_qry)) != hipSuccess) break;
-        if ((e = pf_malloc(st, (void**)&d_d2, sizeof(double) * n_qry)) != hipSuccess) break;
-        if ((e = pf_malloc(st, (void**)&d_face, sizeof(int32_t) * n_qry)) != hipSuccess) break;
-        if ((e = hipMemcpyAsync(d_q, qry, sizeof(double) * 3 * n_qry, hipMemcpyHostToDevice, st)) != hipSuccess) break;
-        k_closest<<<(unsigned)n_qry, PF_CLOSEST_WAVES * PF_WAVE, 0, st>>>(s->tri, s->tri_orig, s->box, s->sbox, s->n_tri, s->n_chunks, s->n_super, d_q, n_qry,
-                                               s->vpf - 2, d_pt, d_face, d_d2);
-        if ((e = hipGetLastError()) != hipSuccess) break;
-        if (out_pts && (e = hipMemcpyAsync(out_pts, d_pt, sizeof(double) * 3 * n_qry, hipMemcpyDeviceToHost, st)) != hipSuccess) break;
-        if (out_face && (e = hipMemcpyAsync(out_face, d_face, sizeof(int32_t) * n_qry, hipMemcpyDeviceToHost, st)) != hipSuccess) break;
-        if (out_d2 && (e = hipMemcpyAsync(out_d2, d_d2, sizeof(double) * n_qry, hipMemcpyDeviceToHost, st)) != hipSuccess) break;
-        e = hipStreamSynchronize(st);
-    } while (0);
-    pf_free(st, d_q);
-    pf_free(st, d_pt);
-    pf_free(st, d_d2);
-    pf_free(st, d_face);
-    if (e != hipSuccess) {
-        pf_set_error("pf_surface_closest: %s", hipGetErrorString(e));
+    Scratch sc(st);
+    double *d_q = sc.get<double>(3 * n_qry), *d_pt = sc.get<double>(3 * n_qry), *d_d2 = sc.get<double>(n_qry);
+    int32_t* d_face = sc.get<int32_t>(n_qry);
+    sc.upload(d_q, qry, 3 * n_qry);
+    if (sc.ok()) {
+        k_closest<<<(unsigned)n_qry, PF_CLOSEST_WAVES * PF_WAVE, 0, st>>>(s->tri, s->tri_orig, s->box, s->sbox, s->n_tri, s->n_chunks,
+                                                                          s->n_super, d_q, n_qry, s->vpf - 2, d_pt, d_face, d_d2);
+        sc.launched();
+    }
+    sc.download(out_pts, d_pt, 3 * n_qry);
+    sc.download(out_face, d_face, n_qry);
+    sc.download(out_d2, d_d2, n_qry);
+    sc.sync();
+    if (!sc.ok()) {
+        pf_set_error("pf_surface_closest: %s", hipGetErrorString(sc.err));
         return PF_E_HIP;
     }
     return PF_OK;
@@ -1263,30 +1234,22 @@ int pf_surface_closest(pf_surface* s, const double* qry, int64_t n_qry, double* 
 int pf_surface_distance(pf_surface* s, const double* qry, int64_t n_qry, double* out_d2, int32_t* out_face, double* stats) {
     PF_CHECK(s && qry, PF_E_ARG, "pf_surface_distance: NULL argument");
     PF_CHECK(n_qry >= 1 && n_qry < ((int64_t)1 << 31), PF_E_ARG, "pf_surface_distance: n_qry = %lld out of range", (long long)n_qry);
-    const Box3 bb = query_box(qry, n_qry);
+    const Box3 bb = point_box(qry, n_qry, true);
     PF_HIP(hipSetDevice(s->ctx->device));
     hipStream_t st = s->ctx->stream;
-    double *d_q = nullptr, *d_d2 = nullptr, *d_stats = nullptr;
-    int32_t* d_face = nullptr;
-    hipError_t e = hipSuccess;
-    do {
-        if ((e = pf_malloc(st, (void**)&d_q, sizeof(double) * 3 * n_qry)) != hipSuccess) break;
-        if (out_d2 && (e = pf_malloc(st, (void**)&d_d2, sizeof(double) * n_qry)) != hipSuccess) break;
-        if (out_face && (e = pf_malloc(st, (void**)&d_face, sizeof(int32_t) * n_qry)) != hipSuccess) break;
-        if ((e = pf_malloc(st, (void**)&d_stats, sizeof(double) * PF_DIST_STATS)) != hipSuccess) break;
-        if ((e = hipMemcpyAsync(d_q, qry, sizeof(double) * 3 * n_qry, hipMemcpyHostToDevice, st)) != hipSuccess) break;
-        if ((e = distance_search(s, st, d_q, n_qry, bb, d_d2, d_face, d_stats)) != hipSuccess) break;
-        if (out_d2 && (e = hipMemcpyAsync(out_d2, d_d2, sizeof(double) * n_qry, hipMemcpyDeviceToHost, st)) != hipSuccess) break;
-        if (out_face && (e = hipMemcpyAsync(out_face, d_face, sizeof(int32_t) * n_qry, hipMemcpyDeviceToHost, st)) != hipSuccess) break;
-        if (stats && (e = hipMemcpyAsync(stats, d_stats, sizeof(double) * PF_DIST_STATS, hipMemcpyDeviceToHost, st)) != hipSuccess) break;
-        e = hipStreamSynchronize(st);
-    } while (0);
-    pf_free(st, d_q);
-    pf_free(st, d_d2);
-    pf_free(st, d_face);
-    pf_free(st, d_stats);
-    if (e != hipSuccess) {
-        pf_set_error("pf_surface_distance: %s", hipGetErrorString(e));
+    Scratch sc(st);
+    double* d_q = sc.get<double>(3 * n_qry);
+    double* d_d2 = out_d2 ? sc.get<double>(n_qry) : nullptr;
+    int32_t* d_face = out_face ? sc.get<int32_t>(n_qry) : nullptr;
+    double* d_stats = sc.get<double>(PF_DIST_STATS);
+    sc.upload(d_q, qry, 3 * n_qry);
+    if (sc.ok()) sc.note(distance_search(s, st, d_q, n_qry, bb, d_d2, d_face, d_stats));
+    sc.download(out_d2, d_d2, n_qry);
+    sc.download(out_face, d_face, n_qry);
+    sc.download(stats, d_stats, PF_DIST_STATS);
+    sc.sync();
+    if (!sc.ok()) {
+        pf_set_error("pf_surface_distance: %s", hipGetErrorString(sc.err));
         return PF_E_HIP;
     }
     return PF_OK;
@@ -1303,63 +1266,50 @@ int pf_surface_prepare_signed(pf_surface* s, const double* points, const int32_t
     while (nb < 31 && ((int64_t)1 << nb) < n) ++nb;
     PF_HIP(hipSetDevice(s->ctx->device));
     hipStream_t st = s->ctx->stream;
-    // a second call builds afresh from the arrays it is given
-    pf_free(st, s->pts), pf_free(st, s->faces), pf_free(st, s->tnrm), pf_free(st, s->enrm), pf_free(st, s->vnrm);
-    s->pts = s->tnrm = s->enrm = s->vnrm = nullptr;
-    s->faces = nullptr;
-    double* tang = nullptr;
-    unsigned long long *ek0 = nullptr, *ek1 = nullptr, *cnt = nullptr;
-    unsigned *vk0 = nullptr, *vk1 = nullptr;
-    int32_t *h0 = nullptr, *h1 = nullptr;
-    void* tmp = nullptr;
-    size_t need_e = 0, need_v = 0;
+    release_signed(s, st);  // a second call builds afresh from the arrays it is given
     unsigned long long counts[4] = {0, 0, 0, 0};
-    hipError_t e = hipSuccess;
-    do {
-        if ((e = pf_malloc(st, (void**)&s->pts, sizeof(double) * 3 * n)) != hipSuccess) break;
-        if ((e = pf_malloc(st, (void**)&s->faces, sizeof(int32_t) * nf)) != hipSuccess) break;
-        if ((e = pf_malloc(st, (void**)&s->tnrm, sizeof(double) * 3 * T)) != hipSuccess) break;
-        if ((e = pf_malloc(st, (void**)&s->enrm, sizeof(double) * 3 * H)) != hipSuccess) break;
-        if ((e = pf_malloc(st, (void**)&s->vnrm, sizeof(double) * 3 * n)) != hipSuccess) break;
-        if ((e = pf_malloc(st, (void**)&tang, sizeof(double) * H)) != hipSuccess) break;
-        if ((e = pf_malloc(st, (void**)&ek0, sizeof(unsigned long long) * H)) != hipSuccess) break;
-        if ((e = pf_malloc(st, (void**)&ek1, sizeof(unsigned long long) * H)) != hipSuccess) break;
-        if ((e = pf_malloc(st, (void**)&vk0, sizeof(unsigned) * H)) != hipSuccess) break;
-        if ((e = pf_malloc(st, (void**)&vk1, sizeof(unsigned) * H)) != hipSuccess) break;
-        if ((e = pf_malloc(st, (void**)&h0, sizeof(int32_t) * H)) != hipSuccess) break;
-        if ((e = pf_malloc(st, (void**)&h1, sizeof(int32_t) * H)) != hipSuccess) break;
-        if ((e = pf_malloc(st, (void**)&cnt, sizeof(unsigned long long) * 4)) != hipSuccess) break;
-        if ((e = hipMemcpyAsync(s->pts, points, sizeof(double) * 3 * n, hipMemcpyHostToDevice, st)) != hipSuccess) break;
-        if ((e = hipMemcpyAsync(s->faces, faces, sizeof(int32_t) * nf, hipMemcpyHostToDevice, st)) != hipSuccess) break;
-        if ((e = hipMemsetAsync(cnt, 0, sizeof(unsigned long long) * 4, st)) != hipSuccess) break;
-        k_tri_normals<<<nblk(T), PF_BLOCK, 0, st>>>(s->pts, s->faces, s->vpf, T, nb, s->tnrm, tang, ek0, vk0, h0);
-        if ((e = hipGetLastError()) != hipSuccess) break;
-        // both sorts are stable and start from half-edge order: equal keys stay in triangle order
-        if ((e = hipcub::DeviceRadixSort::SortPairs(nullptr, need_e, ek0, ek1, h0, h1, (int)H, 0, 2 * nb, st)) != hipSuccess) break;
-        if ((e = hipcub::DeviceRadixSort::SortPairs(nullptr, need_v, vk0, vk1, h0, h1, (int)H, 0, nb, st)) != hipSuccess) break;
-        if ((e = pf_malloc(st, &tmp, need_e > need_v ? need_e : need_v)) != hipSuccess) break;
-        if ((e = hipcub::DeviceRadixSort::SortPairs(tmp, need_e, ek0, ek1, h0, h1, (int)H, 0, 2 * nb, st)) != hipSuccess) break;
-        k_edge_normals<<<nblk(H), PF_BLOCK, 0, st>>>(ek1, h1, H, s->faces, s->vpf, s->tnrm, s->enrm, cnt);
-        if ((e = hipGetLastError()) != hipSuccess) break;
-        if ((e = hipcub::DeviceRadixSort::SortPairs(tmp, need_v, vk0, vk1, h0, h1, (int)H, 0, nb, st)) != hipSuccess) break;
-        k_vertex_normals<<<nblk(n), PF_BLOCK, 0, st>>>(vk1, h1, H, n, s->tnrm, tang, s->vnrm);
-        if ((e = hipGetLastError()) != hipSuccess) break;
-        if ((e = hipMemcpyAsync(counts, cnt, sizeof(counts), hipMemcpyDeviceToHost, st)) != hipSuccess) break;
-        e = hipStreamSynchronize(st);  // the host arrays may go away after the call
-    } while (0);
-    pf_free(st, tang);
-    pf_free(st, ek0);
-    pf_free(st, ek1);
-    pf_free(st, vk0);
-    pf_free(st, vk1);
-    pf_free(st, h0);
-    pf_free(st, h1);
-    pf_free(st, cnt);
-    pf_free(st, tmp);
+    hipError_t e;
+    {
+        Scratch sc(st);
+        s->pts = sc.keep<double>(3 * n);
+        s->faces = sc.keep<int32_t>(nf);
+        s->tnrm = sc.keep<double>(3 * T);
+        s->enrm = sc.keep<double>(3 * H);
+        s->vnrm = sc.keep<double>(3 * n);
+        double* tang = sc.get<double>(H);
+        unsigned long long *ek0 = sc.get<unsigned long long>(H), *ek1 = sc.get<unsigned long long>(H);
+        unsigned *vk0 = sc.get<unsigned>(H), *vk1 = sc.get<unsigned>(H);
+        int32_t *h0 = sc.get<int32_t>(H), *h1 = sc.get<int32_t>(H);
+        unsigned long long* cnt = sc.get<unsigned long long>(4);
+        sc.upload(s->pts, points, 3 * n);
+        sc.upload(s->faces, faces, nf);
+        sc.zero(cnt, sizeof(unsigned long long) * 4);
+        if (sc.ok()) {
+            k_tri_normals<<<nblk(T), PF_BLOCK, 0, st>>>(s->pts, s->faces, s->vpf, T, nb, s->tnrm, tang, ek0, vk0, h0);
+            sc.launched();
+        }
+        // both sorts are stable and start from half-edge order: equal keys stay in triangle order.  They share the value
+        // arrays and the temporary, so the vertex sort runs after k_edge_normals has read the edge sort's h1.
+        size_t need_e = 0, need_v = 0;
+        if (sc.ok()) sc.note(hipcub::DeviceRadixSort::SortPairs(nullptr, need_e, ek0, ek1, h0, h1, (int)H, 0, 2 * nb, st));
+        if (sc.ok()) sc.note(hipcub::DeviceRadixSort::SortPairs(nullptr, need_v, vk0, vk1, h0, h1, (int)H, 0, nb, st));
+        void* tmp = sc.get<char>(need_e > need_v ? need_e : need_v);
+        if (sc.ok()) sc.note(hipcub::DeviceRadixSort::SortPairs(tmp, need_e, ek0, ek1, h0, h1, (int)H, 0, 2 * nb, st));
+        if (sc.ok()) {
+            k_edge_normals<<<nblk(H), PF_BLOCK, 0, st>>>(ek1, h1, H, s->faces, s->vpf, s->tnrm, s->enrm, cnt);
+            sc.launched();
+        }
+        if (sc.ok()) sc.note(hipcub::DeviceRadixSort::SortPairs(tmp, need_v, vk0, vk1, h0, h1, (int)H, 0, nb, st));
+        if (sc.ok()) {
+            k_vertex_normals<<<nblk(n), PF_BLOCK, 0, st>>>(vk1, h1, H, n, s->tnrm, tang, s->vnrm);
+            sc.launched();
+        }
+        sc.download(counts, cnt, 4);
+        sc.sync();  // the host arrays may go away after the call
+        e = sc.err;
+    }
     if (e != hipSuccess) {
-        pf_free(st, s->pts), pf_free(st, s->faces), pf_free(st, s->tnrm), pf_free(st, s->enrm), pf_free(st, s->vnrm);
-        s->pts = s->tnrm = s->enrm = s->vnrm = nullptr;
-        s->faces = nullptr;
+        release_signed(s, st);
         pf_set_error("pf_surface_prepare_signed: %s", hipGetErrorString(e));
         return PF_E_HIP;
     }
@@ -1374,43 +1324,31 @@ int pf_surface_signed_distance(pf_surface* s, const double* qry, int64_t n_qry, 
     PF_CHECK(n_qry >= 1 && n_qry < ((int64_t)1 << 31), PF_E_ARG, "pf_surface_signed_distance: n_qry = %lld out of range",
              (long long)n_qry);
     PF_CHECK(s->vnrm, PF_E_ARG, "pf_surface_signed_distance: pf_surface_prepare_signed has not been called");
-    const Box3 bb = query_box(qry, n_qry);
+    const Box3 bb = point_box(qry, n_qry, true);
     PF_HIP(hipSetDevice(s->ctx->device));
     hipStream_t st = s->ctx->stream;
-    double *d_q = nullptr, *d_d2 = nullptr, *d_stats = nullptr, *d_sd = nullptr;
-    int32_t *d_face = nullptr, *d_feat = nullptr;
-    unsigned long long* d_amb = nullptr;
+    Scratch sc(st);
+    double *d_q = sc.get<double>(3 * n_qry), *d_d2 = sc.get<double>(n_qry);
+    int32_t* d_face = sc.get<int32_t>(n_qry);
+    double *d_stats = sc.get<double>(PF_DIST_STATS), *d_sd = sc.get<double>(n_qry);
+    int32_t* d_feat = sc.get<int32_t>(n_qry);
+    unsigned long long* d_amb = sc.get<unsigned long long>(1);
     unsigned long long amb = 0;
-    hipError_t e = hipSuccess;
-    do {
-        if ((e = pf_malloc(st, (void**)&d_q, sizeof(double) * 3 * n_qry)) != hipSuccess) break;
-        if ((e = pf_malloc(st, (void**)&d_d2, sizeof(double) * n_qry)) != hipSuccess) break;
-        if ((e = pf_malloc(st, (void**)&d_face, sizeof(int32_t) * n_qry)) != hipSuccess) break;
-        if ((e = pf_malloc(st, (void**)&d_stats, sizeof(double) * PF_DIST_STATS)) != hipSuccess) break;
-        if ((e = pf_malloc(st, (void**)&d_sd, sizeof(double) * n_qry)) != hipSuccess) break;
-        if ((e = pf_malloc(st, (void**)&d_feat, sizeof(int32_t) * n_qry)) != hipSuccess) break;
-        if ((e = pf_malloc(st, (void**)&d_amb, sizeof(unsigned long long))) != hipSuccess) break;
-        if ((e = hipMemcpyAsync(d_q, qry, sizeof(double) * 3 * n_qry, hipMemcpyHostToDevice, st)) != hipSuccess) break;
-        if ((e = hipMemsetAsync(d_amb, 0, sizeof(unsigned long long), st)) != hipSuccess) break;
-        if ((e = distance_search(s, st, d_q, n_qry, bb, d_d2, d_face, d_stats)) != hipSuccess) break;
+    sc.upload(d_q, qry, 3 * n_qry);
+    sc.zero(d_amb, sizeof(unsigned long long));
+    if (sc.ok()) sc.note(distance_search(s, st, d_q, n_qry, bb, d_d2, d_face, d_stats));
+    if (sc.ok()) {
         k_signed<<<nblk(n_qry), PF_BLOCK, 0, st>>>(s->pts, s->faces, s->vpf, s->tnrm, s->enrm, s->vnrm, d_q, n_qry, d_d2, d_face,
                                                    d_sd, d_feat, d_amb);
-        if ((e = hipGetLastError()) != hipSuccess) break;
-        if (out_sd && (e = hipMemcpyAsync(out_sd, d_sd, sizeof(double) * n_qry, hipMemcpyDeviceToHost, st)) != hipSuccess) break;
-        if (out_face && (e = hipMemcpyAsync(out_face, d_face, sizeof(int32_t) * n_qry, hipMemcpyDeviceToHost, st)) != hipSuccess) break;
-        if (out_feature && (e = hipMemcpyAsync(out_feature, d_feat, sizeof(int32_t) * n_qry, hipMemcpyDeviceToHost, st)) != hipSuccess) break;
-        if ((e = hipMemcpyAsync(&amb, d_amb, sizeof(amb), hipMemcpyDeviceToHost, st)) != hipSuccess) break;
-        e = hipStreamSynchronize(st);
-    } while (0);
-    pf_free(st, d_q);
-    pf_free(st, d_d2);
-    pf_free(st, d_face);
-    pf_free(st, d_stats);
-    pf_free(st, d_sd);
-    pf_free(st, d_feat);
-    pf_free(st, d_amb);
-    if (e != hipSuccess) {
-        pf_set_error("pf_surface_signed_distance: %s", hipGetErrorString(e));
+        sc.launched();
+    }
+    sc.download(out_sd, d_sd, n_qry);
+    sc.download(out_face, d_face, n_qry);
+    sc.download(out_feature, d_feat, n_qry);
+    sc.download(&amb, d_amb, 1);
+    sc.sync();
+    if (!sc.ok()) {
+        pf_set_error("pf_surface_signed_distance: %s", hipGetErrorString(sc.err));
         return PF_E_HIP;
     }
     if (n_ambiguous) *n_ambiguous = (int64_t)amb;
@@ -1422,20 +1360,18 @@ int pf_surface_prepare_winding(pf_surface* s) {
     if (s->dip) return PF_OK;  // built once: the triangles never change
     PF_HIP(hipSetDevice(s->ctx->device));
     hipStream_t st = s->ctx->stream;
-    double *dip = nullptr, *sdip = nullptr;
-    hipError_t e = hipSuccess;
-    do {
-        if ((e = pf_malloc(st, (void**)&dip, sizeof(double) * PF_DIPOLE * s->n_chunks)) != hipSuccess) break;
-        if ((e = pf_malloc(st, (void**)&sdip, sizeof(double) * PF_DIPOLE * s->n_super)) != hipSuccess) break;
+    Scratch sc(st);  // no scratch, two blocks to keep: published only when everything worked
+    double *dip = sc.keep<double>(PF_DIPOLE * s->n_chunks), *sdip = sc.keep<double>(PF_DIPOLE * s->n_super);
+    if (sc.ok()) {
         k_chunk_dipoles<<<(unsigned)s->n_chunks, PF_WAVE, 0, st>>>(s->tri, s->n_tri, s->box, dip);
         k_super_dipoles<<<(unsigned)s->n_super, PF_WAVE, 0, st>>>(s->tri, s->n_tri, dip, s->n_chunks, s->sbox, sdip);
-        if ((e = hipGetLastError()) != hipSuccess) break;
-        e = hipStreamSynchronize(st);
-    } while (0);
-    if (e != hipSuccess) {
+        sc.launched();
+    }
+    sc.sync();
+    if (!sc.ok()) {
         pf_free(st, dip);
         pf_free(st, sdip);
-        pf_set_error("pf_surface_prepare_winding: %s", hipGetErrorString(e));
+        pf_set_error("pf_surface_prepare_winding: %s", hipGetErrorString(sc.err));
         return PF_E_HIP;
     }
     s->dip = dip, s->sdip = sdip;
@@ -1449,51 +1385,30 @@ int pf_surface_winding(pf_surface* s, const double* qry, int64_t n_qry, double b
     // beta <= 0: exact.  A query may lie inside a cluster's ball for beta <= 1, where the dropped part has no bound.
     PF_CHECK(beta <= 0.0 || (beta > 1.0 && std::isfinite(beta)), PF_E_ARG,
              "pf_surface_winding: beta = %g: use beta <= 0 (exact) or a finite beta > 1", beta);
-    const Box3 bb = query_box(qry, n_qry);
+    const Box3 bb = point_box(qry, n_qry, true);
     PF_HIP(hipSetDevice(s->ctx->device));
     hipStream_t st = s->ctx->stream;
     const int64_t n_pack = (n_qry + PF_WIND_PACKET - 1) / PF_WIND_PACKET;
-    double *d_q = nullptr, *d_w = nullptr, *d_b = nullptr;
-    unsigned *k0 = nullptr, *k1 = nullptr;
-    int32_t *v0 = nullptr, *v1 = nullptr;
-    void* tmp = nullptr;
-    size_t need = 0;
-    hipError_t e = hipSuccess;
-    do {
-        if ((e = pf_malloc(st, (void**)&d_q, sizeof(double) * 3 * n_qry)) != hipSuccess) break;
-        if (out_w && (e = pf_malloc(st, (void**)&d_w, sizeof(double) * n_qry)) != hipSuccess) break;
-        if (out_bound && (e = pf_malloc(st, (void**)&d_b, sizeof(double) * n_qry)) != hipSuccess) break;
-        if ((e = pf_malloc(st, (void**)&k0, sizeof(unsigned) * n_qry)) != hipSuccess) break;
-        if ((e = pf_malloc(st, (void**)&k1, sizeof(unsigned) * n_qry)) != hipSuccess) break;
-        if ((e = pf_malloc(st, (void**)&v0, sizeof(int32_t) * n_qry)) != hipSuccess) break;
-        if ((e = pf_malloc(st, (void**)&v1, sizeof(int32_t) * n_qry)) != hipSuccess) break;
-        if ((e = hipMemcpyAsync(d_q, qry, sizeof(double) * 3 * n_qry, hipMemcpyHostToDevice, st)) != hipSuccess) break;
-        k_qry_keys<<<nblk(n_qry), PF_BLOCK, 0, st>>>(d_q, n_qry, bb, k0, v0);
-        if ((e = hipGetLastError()) != hipSuccess) break;
-        if ((e = hipcub::DeviceRadixSort::SortPairs(nullptr, need, k0, k1, v0, v1, (int)n_qry, 0, 30, st)) != hipSuccess) break;
-        if ((e = pf_malloc(st, &tmp, need)) != hipSuccess) break;
-        if ((e = hipcub::DeviceRadixSort::SortPairs(tmp, need, k0, k1, v0, v1, (int)n_qry, 0, 30, st)) != hipSuccess) break;
+    Scratch sc(st);
+    double* d_q = sc.get<double>(3 * n_qry);
+    double* d_w = out_w ? sc.get<double>(n_qry) : nullptr;
+    double* d_b = out_bound ? sc.get<double>(n_qry) : nullptr;
+    sc.upload(d_q, qry, 3 * n_qry);
+    const int32_t* perm = morton_order(sc, d_q, nullptr, 0, n_qry, bb);
+    if (sc.ok()) {
         if (beta > 0.0)
-            k_winding<true><<<(unsigned)n_pack, PF_WAVE, 0, st>>>(s->tri, s->n_tri, s->n_chunks, s->n_super, s->dip, s->sdip, d_q, v1,
+            k_winding<true><<<(unsigned)n_pack, PF_WAVE, 0, st>>>(s->tri, s->n_tri, s->n_chunks, s->n_super, s->dip, s->sdip, d_q, perm,
                                                                   n_qry, beta, d_w, d_b);
         else
-            k_winding<false><<<(unsigned)n_pack, PF_WAVE, 0, st>>>(s->tri, s->n_tri, s->n_chunks, s->n_super, s->dip, s->sdip, d_q, v1,
+            k_winding<false><<<(unsigned)n_pack, PF_WAVE, 0, st>>>(s->tri, s->n_tri, s->n_chunks, s->n_super, s->dip, s->sdip, d_q, perm,
                                                                    n_qry, 0.0, d_w, d_b);
-        if ((e = hipGetLastError()) != hipSuccess) break;
-        if (out_w && (e = hipMemcpyAsync(out_w, d_w, sizeof(double) * n_qry, hipMemcpyDeviceToHost, st)) != hipSuccess) break;
-        if (out_bound && (e = hipMemcpyAsync(out_bound, d_b, sizeof(double) * n_qry, hipMemcpyDeviceToHost, st)) != hipSuccess) break;
-        e = hipStreamSynchronize(st);
-    } while (0);
-    pf_free(st, d_q);
-    pf_free(st, d_w);
-    pf_free(st, d_b);
-    pf_free(st, k0);
-    pf_free(st, k1);
-    pf_free(st, v0);
-    pf_free(st, v1);
-    pf_free(st, tmp);
-    if (e != hipSuccess) {
-        pf_set_error("pf_surface_winding: %s", hipGetErrorString(e));
+        sc.launched();
+    }
+    sc.download(out_w, d_w, n_qry);
+    sc.download(out_bound, d_b, n_qry);
+    sc.sync();
+    if (!sc.ok()) {
+        pf_set_error("pf_surface_winding: %s", hipGetErrorString(sc.err));
         return PF_E_HIP;
     }
     return PF_OK;
