@@ -499,6 +499,31 @@ int pf_surface_signed_distance(pf_surface* s, const double* qry, int64_t n_qry, 
  *                               or before pf_surface_prepare_winding. */
 int pf_surface_prepare_winding(pf_surface* s);
 int pf_surface_winding(pf_surface* s, const double* qry, int64_t n_qry, double beta, double* out_w, double* out_bound);
+/* Ray casting: first hit, barycentric coordinates and crossing count of many rays o + t d against the fan triangles,
+ * on the structure pf_surface_create built.  One exact test in f64 without FMA (Moeller-Trumbore; d is not normalised,
+ * so t is in units of |d|):
+ *   e1 = b - a, e2 = c - a, p = d x e2, det = e1 . p, tv = o - a, u = (tv . p) / det, q = tv x e1, v = (d . q) / det,
+ *   t = (e2 . q) / det;  a triangle is accepted when det != 0, u >= 0, v >= 0, u + v <= 1, t_min <= t <= t_max (both ends
+ *   inclusive) and facing allows it: 0 any side, +1 only det > 0 (the ray meets the side the face normal points to),
+ *   -1 only det < 0.  NaN triangles never pass; zero-area triangles have det = 0.
+ * The result of a ray is that of this test over ALL fan triangles, bit for bit (box pruning only skips triangles the test
+ * cannot accept: the argument is in pf_surface.hip).  The test is not watertight: a ray exactly through an edge or a vertex
+ * may be accepted by several triangles or by none.
+ *   pf_surface_raycast         origins, dirs [n_rays][3] f64 (host), n_rays >= 1 -> out_t [n_rays] the least accepted t
+ *                              (ties: lowest fan-triangle index), out_face [n_rays] that triangle's face, out_uv
+ *                              [n_rays][2] its (u, v): the hit point is a + u e1 + v e2; out_count [n_rays] the number of
+ *                              accepted triangles in [t_min, t_max].  A miss gives +inf, -1, NaN uv, count 0; a ray with a
+ *                              non-finite origin or direction component or a zero direction gives NaN, -1, NaN uv, count 0.
+ *                              Each output may be NULL; without out_count the search narrows the interval to the best t
+ *                              found.  PF_E_ARG for n_rays < 1, NaN t_min / t_max, t_min > t_max, facing outside {-1, 0, 1}.
+ *                              The rays are Morton-sorted by origin on the device and traced in packets of 16 neighbours (4
+ *                              for fewer than 65536 rays); two calls give identical bits.
+ *   pf_surface_vertex_normals  out [n][3]: the angle-weighted vertex pseudonormals (sum of corner angle x unit normal) as
+ *                              pf_surface_prepare_signed stored them, not normalised (zero for an unreferenced vertex).
+ *                              PF_E_ARG before pf_surface_prepare_signed. */
+int pf_surface_raycast(pf_surface* s, const double* origins, const double* dirs, int64_t n_rays, double t_min, double t_max,
+                       int32_t facing, double* out_t, int32_t* out_face, double* out_uv, int32_t* out_count);
+int pf_surface_vertex_normals(pf_surface* s, double* out);
 
 /* ---- Coherent Point Drift pieces ("next" row f4) ------------------------------------------------------------
  * The reference registers the spectral coordinates with the third-party cycpd package (focusr.py:297-334).

@@ -11,6 +11,8 @@ from .assignment import euclidean_assignment
 from .eigsort import eigsort
 from .focusr import *  # noqa: F401,F403
 from .graph import *  # noqa: F401,F403
+from .ray_casting import (hit_points, ray_crossings, ray_mesh_intersections, thickness_along_normals,
+                          vertex_normals)
 from .surface_distance import (point_to_surface_distances, points_inside, signed_distances_on_mesh,
                                signed_point_to_surface_distances, summarize_distances, summarize_signed_distances,
                                surface_distance_metrics, winding_numbers)

@@ -174,6 +174,9 @@ SIGNATURES = {
     "pf_surface_signed_distance": (C.c_int, [C.c_void_p, _f64p, C.c_int64, _f64p, _i32p, _i32p, _i64p]),
     "pf_surface_prepare_winding": (C.c_int, [C.c_void_p]),
     "pf_surface_winding": (C.c_int, [C.c_void_p, _f64p, C.c_int64, C.c_double, _f64p, _f64p]),
+    "pf_surface_raycast": (C.c_int, [C.c_void_p, _f64p, _f64p, C.c_int64, C.c_double, C.c_double, C.c_int32, _f64p, _i32p, _f64p,
+                                     _i32p]),
+    "pf_surface_vertex_normals": (C.c_int, [C.c_void_p, _f64p]),
     "pf_cpd_create": (C.c_int, [C.c_void_p, _f64p, C.c_int64, _f64p, C.c_int64, C.c_int32, C.POINTER(C.c_void_p)]),
     "pf_cpd_free": (None, [C.c_void_p]),
     "pf_cpd_estep": (C.c_int, [C.c_void_p, _f64p, C.c_double, C.c_double, _f64p, _f64p, _f64p]),
@@ -681,6 +684,34 @@ class DeviceSurface(object):
         bound = np.empty(len(q), dtype=np.float64)
         _check(self._lib.pf_surface_winding(self._h, _f64(q), len(q), float(beta), _f64(w), _f64(bound)))
         return w, bound
+
+    def raycast(self, origins, directions, t_min=0.0, t_max=np.inf, facing=0, count=False):
+        """(t (r,) f64, face (r,) i32, uv (r,2) f64[, count (r,) i32]) of every ray origin + t direction
+        (`pf_surface_raycast`): the least t in [t_min, t_max] (inclusive; in units of |direction|) at which the exact
+        Moeller-Trumbore test accepts a fan triangle (ties: lowest triangle index), that triangle's face and barycentric
+        (u, v) (hit point a + u (b - a) + v (c - a)), and with `count` the number of accepted triangles in the interval.
+        `facing`: 0 any side, 1 only faces whose normal points against the ray (det > 0), -1 only the others.  A miss gives
+        +inf, -1, NaN; a ray with a non-finite component or a zero direction NaN, -1, NaN, count 0.  Equal to a brute-force
+        loop over all triangles bit for bit; two calls give identical bits."""
+        o, d = _c_f64(origins), _c_f64(directions)
+        if o.ndim != 2 or o.shape[1] != 3 or o.shape[0] == 0 or d.shape != o.shape:
+            raise ValueError("origins and directions must be non-empty (n, 3) arrays of the same length")
+        t = np.empty(len(o), dtype=np.float64)
+        face = np.empty(len(o), dtype=np.int32)
+        uv = np.empty((len(o), 2), dtype=np.float64)
+        n_hit = np.empty(len(o), dtype=np.int32) if count else None
+        _check(self._lib.pf_surface_raycast(self._h, _f64(o), _f64(d), len(o), float(t_min), float(t_max), int(facing), _f64(t),
+                                            face.ctypes.data_as(_i32p), _f64(uv),
+                                            n_hit.ctypes.data_as(_i32p) if count else None))
+        return (t, face, uv, n_hit) if count else (t, face, uv)
+
+    def vertex_normals(self):
+        """(n, 3) f64: the angle-weighted vertex pseudonormals as the device stores them (`pf_surface_vertex_normals`), not
+        normalised; zero for a vertex no face references.  Builds the signed structure on first use."""
+        self._prepare_signed()
+        out = np.empty((self.n, 3), dtype=np.float64)
+        _check(self._lib.pf_surface_vertex_normals(self._h, _f64(out)))
+        return out
 
     def closest(self, queries):
         """(points (q,3) f64, face (q,) i32, squared distance (q,) f64) of the closest surface point of each query."""

@@ -1,5 +1,5 @@
-// Queries against a triangulated surface: closest points, many-query distances, signed distances, winding numbers.
-// All four work on one structure, built once per surface (pf_surface_create): the triangles (polygons
+// Queries against a triangulated surface: closest points, many-query distances, signed distances, winding numbers,
+// ray casting.  All five work on one structure, built once per surface (pf_surface_create): the triangles (polygons
 // fan-triangulated) are sorted along a Morton curve of their centroids (hipCUB radix sort) and cut into chunks of 64
 // consecutive ones, each with its bounding box; coordinates are stored SoA so that a wave reads 64 consecutive triangles
 // coalesced.  64 consecutive chunks form a super-chunk with its own box (two levels are enough: 500k triangles = 7813
@@ -29,6 +29,10 @@
 //
 // Generalized winding numbers (pf_surface_prepare_winding / pf_surface_winding): the solid angles of all triangles,
 // summed over the same chunks, exactly or with far clusters replaced by their dipoles.
+//
+// Ray casting (pf_surface_raycast, k_raycast): first hit, barycentric coordinates and crossing count of many rays, by
+// one exact FP64 Moeller-Trumbore test over the same boxes; pf_surface_vertex_normals hands out the vertex pseudonormals
+// of the signed structure as ray directions.
 //
 // Each section's own comment has the details.  The entry points (extern "C", at the end) keep their device scratch in a
 // Scratch, and sort along the Morton curve through morton_order.
@@ -1011,6 +1015,244 @@ __global__ __launch_bounds__(PF_WAVE) void k_winding(const double* __restrict__ 
     }
 }
 
+// ---- ray casting (pf_surface_raycast) -----------------------------------------------------------------------------
+// For every ray o + t d: the least t in [t_min, t_max] at which it meets a fan triangle (ties: lowest triangle index),
+// that triangle's face and barycentric (u, v), and the number of triangles it meets in the interval.  d is not
+// normalised: t is in units of |d|.
+//
+// The exact test, ray_triangle, is Moeller-Trumbore in FP64, ONE body that every decision goes through, written out
+// operation by operation (no FMA: -ffp-contract=off; true divisions by det) so that a numpy restatement rounds the same:
+//   e1 = b - a, e2 = c - a, p = d x e2, det = e1 . p, tv = o - a, u = (tv . p) / det, q = tv x e1, v = (d . q) / det,
+//   t = (e2 . q) / det;  accepted when det != 0, u >= 0, v >= 0, u + v <= 1, t_min <= t <= t_max (both inclusive) and
+//   facing allows the side: 0 any, +1 only det > 0 (the ray meets the side the face normal points to), -1 only det < 0.
+// A NaN anywhere fails a comparison, so a NaN triangle never passes; a zero-area triangle has det = 0 in exact
+// arithmetic.  NOT watertight: a ray exactly through an edge or a vertex may be accepted by both neighbours or by
+// neither (u, v and u + v are rounded per triangle), and that is left as it is: the result is defined as what this
+// test says over ALL triangles, the same as a brute-force loop.
+//
+// Traversal.  Rays are Morton-sorted by origin in the box of the finite origins; one wave per packet of 16 neighbouring
+// rays (4 when there are fewer than 16 x 4096 rays: the same rule and reason as k_distance, small sets still fill the
+// GPU).  Lane = ray (lane % PACKET) x triangle subset (lane / PACKET).  The packet's rays sit in LDS (origin,
+// direction and the ray's current upper end t_hi), so that in a box ballot lane = box and every lane runs through the
+// packet's rays by broadcast.  One ballot over the super-chunk boxes, per surviving super-chunk one over its 64 chunk
+// boxes; at both levels the survivors are taken nearest first (least entry parameter over the packet) so that t_hi
+// shrinks early, and the rest of a level is dropped once its least entry parameter exceeds every ray's t_hi.  A chunk
+// some ray still wants is staged in LDS once per packet, as in k_distance, and each ray's lanes share its triangles out.
+// COUNT = true (out_count requested) never shrinks t_hi below t_max: every chunk is scanned at most once per packet
+// and every triangle of it tested by exactly one lane of each ray that wants the chunk, so the count is exact, and the
+// same launch still yields the first hit.
+//
+// Pruning never changes a result: ray_box keeps every box that holds a triangle which ray_triangle accepts for that
+// ray with t in [t_lo, t_hi].  The accepted t, u, v are rounded values, so the point o + t d may lie outside the
+// triangle, hence outside its box, by a rounding error; the slab test therefore runs on the box widened on every side by
+//   w = PF_RAY_SLACK * m,  m = max over the axes of max(|lo - o|, |hi - o|)   (the box's farthest face from the origin).
+// Argument.  Let x = (u, v, t) be the accepted values, sigma = |det| / (|d| |e1| |e2|) (the sine of the triangle's angle
+// at a times the cosine between the ray and the normal), and L = |e1| + |e2| + |tv| + |t||d|.  Each of the four triple
+// products is computed with an error of at most 10 eps times the product of the lengths of its three vectors (two
+// roundings per cross-product component, three per dot, one per difference of the inputs).  x solves [e1 e2 -d] x = tv
+// by Cramer's rule, and from x_i = N_i / det with those errors, |u|, |v| <= 1 and the division's own rounding, the
+// residual r = (o + t d) - (a + u e1 + v e2) obeys |r| <= 64 eps L / sigma.  a + u e1 + v e2 is a point of the triangle
+// (u, v >= 0, u + v <= 1 + eps), so o + t d lies within 64 eps L / sigma + eps L of the chunk's box.  No corner of that box
+// is farther from o than sqrt(3) m: |tv| and |t||d| - |r| are at most that, |e1| and |e2| at most twice that, so
+// L <= 11 m and |r| <= 704 eps m / sigma.  The slab arithmetic itself ((lo - o) - w, then one division per face; min, max and
+// the comparison are exact) moves a bound by at most 4 eps m.  With PF_RAY_SLACK = 2^-20 the widened, rounded slabs
+// contain o + t d on every axis, so their intersection with [t_lo, t_hi] contains t and the box is kept, whenever
+//   704 eps / sigma + 5 eps <= 2^-20,  i.e.  sigma >= 8.2e-8:
+// every triangle-ray pair except a ray within 1e-7 rad of the triangle's plane or a needle with an angle below that.
+// No box test can do without such a condition: for a ray IN the plane of a triangle all four triple products are pure
+// rounding noise and the exact test may accept at any distance from the triangle.  (Overflow and underflow aside.)
+// An axis with d = +0.0 or -0.0 has no slab parameters (0 * inf): there the origin is tested against the widened slab.
+// A reciprocal of d is not used: it overflows for a subnormal d and turns a zero numerator into NaN.  NaN (an empty
+// box of NaN triangles, an infinite corner) is ignored by fmin / fmax and by the outside test, which keeps the box.
+//
+// gfx950, -Rpass-analysis=kernel-resource-usage: 16-ray packets 94 VGPRs (96 with COUNT), 5 waves per SIMD, 5760 bytes
+// of LDS; 4-ray packets 100 (102) VGPRs, 4 waves per SIMD, 5088 bytes; no scratch, no spill in any of the four.
+
+constexpr double PF_RAY_SLACK = 1.0 / 1048576.0;  // 2^-20: see the argument above
+
+// Moeller-Trumbore, operation for operation as in tests/_ray_ref.py.  t, u, v are set when it returns true.
+__device__ __forceinline__ bool ray_triangle(const double o[3], const double d[3], const double a[3], const double b[3],
+                                             const double c[3], double t_min, double t_max, int32_t facing, double& t, double& u,
+                                             double& v) {
+    const double e1[3] = {b[0] - a[0], b[1] - a[1], b[2] - a[2]};
+    const double e2[3] = {c[0] - a[0], c[1] - a[1], c[2] - a[2]};
+    const double p[3] = {d[1] * e2[2] - d[2] * e2[1], d[2] * e2[0] - d[0] * e2[2], d[0] * e2[1] - d[1] * e2[0]};
+    const double det = e1[0] * p[0] + e1[1] * p[1] + e1[2] * p[2];
+    if (det == 0.0 || (facing > 0 && !(det > 0.0)) || (facing < 0 && !(det < 0.0))) return false;
+    const double tv[3] = {o[0] - a[0], o[1] - a[1], o[2] - a[2]};
+    u = (tv[0] * p[0] + tv[1] * p[1] + tv[2] * p[2]) / det;
+    if (!(u >= 0.0)) return false;  // also a NaN det
+    const double q[3] = {tv[1] * e1[2] - tv[2] * e1[1], tv[2] * e1[0] - tv[0] * e1[2], tv[0] * e1[1] - tv[1] * e1[0]};
+    v = (d[0] * q[0] + d[1] * q[1] + d[2] * q[2]) / det;
+    if (!(v >= 0.0) || !(u + v <= 1.0)) return false;
+    t = (e2[0] * q[0] + e2[1] * q[1] + e2[2] * q[2]) / det;
+    return t_min <= t && t <= t_max;
+}
+
+// Can the ray meet, with t in [t_lo, t_hi], a triangle inside box bx (lo xyz, hi xyz)?  Never false for a triangle that
+// ray_triangle accepts (the section comment); near = where the ray enters the widened box, at least t_lo.
+__device__ __forceinline__ bool ray_box(const double o[3], const double d[3], double t_lo, double t_hi, const double* __restrict__ bx,
+                                        double& near) {
+    double lo[3], hi[3], m = 0.0;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        lo[a] = bx[a] - o[a], hi[a] = bx[3 + a] - o[a];
+        m = fmax(m, fmax(fabs(lo[a]), fabs(hi[a])));
+    }
+    const double w = PF_RAY_SLACK * m;
+    double tn = t_lo, tf = t_hi;
+    bool outside = false;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const double nl = lo[a] - w, nh = hi[a] + w;
+        if (d[a] == 0.0) {  // +0.0 and -0.0: the ray stays at o on this axis
+            outside = outside || nl > 0.0 || nh < 0.0;
+        } else {
+            const double t1 = nl / d[a], t2 = nh / d[a];
+            tn = fmax(tn, fmin(t1, t2));
+            tf = fmin(tf, fmax(t1, t2));
+        }
+    }
+    near = tn;
+    return !outside && tn <= tf;
+}
+
+struct Hit {
+    double t;
+    int32_t orig;  // triangle index (tie-break: lowest)
+    double u, v;
+};
+
+// one wave (= one block) per packet of PACKET sorted rays; lane = ray (lane % PACKET) x triangle subset (lane / PACKET)
+template <int PACKET, bool COUNT>
+__global__ __launch_bounds__(PF_WAVE) void k_raycast(const double* __restrict__ tri, const int32_t* __restrict__ tri_orig,
+                                                     const double* __restrict__ box, const double* __restrict__ sbox, int64_t n_tri,
+                                                     int64_t n_chunks, int64_t n_super, const double* __restrict__ org,
+                                                     const double* __restrict__ dir, const int32_t* __restrict__ perm, int64_t n_rays,
+                                                     double t_min, double t_max, int32_t facing, int32_t per_face,
+                                                     double* __restrict__ out_t, int32_t* __restrict__ out_face,
+                                                     double* __restrict__ out_uv, int32_t* __restrict__ out_count) {
+    __shared__ double s_tri[9][PF_TRI_CHUNK];  // one chunk, SoA as in HBM
+    __shared__ int32_t s_orig[PF_TRI_CHUNK];
+    __shared__ double s_ray[7][PACKET];  // ox oy oz dx dy dz t_hi of the packet's rays
+    constexpr int SUB = PF_WAVE / PACKET;  // lanes per ray
+    static_assert(PF_WAVE % PACKET == 0, "a packet divides the wave");
+    const int lane = threadIdx.x, slot = lane % PACKET, sub = lane / PACKET;
+    const int64_t i = (int64_t)blockIdx.x * PACKET + slot;
+    const bool live = i < n_rays;
+    const int64_t ri = live ? perm[i] : -1;  // the caller's index of this lane's ray
+    const double inf = std::numeric_limits<double>::infinity(), nan = __longlong_as_double(0x7ff8000000000000ll);
+    double o[3] = {0.0, 0.0, 0.0}, d[3] = {0.0, 0.0, 0.0};
+    if (live) {
+#pragma unroll
+        for (int a = 0; a < 3; ++a) o[a] = org[3 * ri + a], d[a] = dir[3 * ri + a];
+    }
+    bool ok = live && (d[0] != 0.0 || d[1] != 0.0 || d[2] != 0.0);
+#pragma unroll
+    for (int a = 0; a < 3; ++a) ok = ok && std::isfinite(o[a]) && std::isfinite(d[a]);
+    // a dead slot (past the end, non-finite, zero direction) is a ray at the origin with an empty interval
+    if (!ok) o[0] = o[1] = o[2] = d[0] = d[1] = d[2] = 0.0;
+    double t_hi = ok ? t_max : -inf;  // the ray's upper end: min(t_max, its least accepted t) unless COUNT
+    if (sub == 0) {
+#pragma unroll
+        for (int a = 0; a < 3; ++a) s_ray[a][slot] = o[a], s_ray[3 + a][slot] = d[a];
+        s_ray[6][slot] = t_hi;
+    }
+    __syncthreads();
+
+    Hit best;
+    best.t = inf, best.orig = 0x7fffffff, best.u = best.v = nan;
+    int32_t count = 0;
+
+    // lane = box: the least entry parameter over the packet's rays that may meet box bx; false if none may
+    auto packet_box = [&](const double* __restrict__ bx, double& near) {
+        bool any = false;
+        near = inf;
+        for (int j = 0; j < PACKET; ++j) {
+            const double ro[3] = {s_ray[0][j], s_ray[1][j], s_ray[2][j]}, rd[3] = {s_ray[3][j], s_ray[4][j], s_ray[5][j]};
+            double tn;
+            if (ray_box(ro, rd, t_min, s_ray[6][j], bx, tn)) any = true, near = fmin(near, tn);
+        }
+        return any;
+    };
+    // stage chunk c in LDS and test its triangles against every ray that may meet its box; true if any ray did
+    auto scan = [&](int64_t c) {
+        double tn;
+        const bool want = ok && ray_box(o, d, t_min, t_hi, box + 6 * c, tn);
+        if (!__ballot(want)) return;
+        const int64_t s = c * PF_TRI_CHUNK + lane;
+        const int cnt = (int)(n_tri - c * PF_TRI_CHUNK < PF_TRI_CHUNK ? n_tri - c * PF_TRI_CHUNK : PF_TRI_CHUNK);
+        __syncthreads();  // the previous chunk's reads are done
+        if (lane < cnt) {
+#pragma unroll
+            for (int k = 0; k < 9; ++k) s_tri[k][lane] = tri[(int64_t)k * n_tri + s];
+            s_orig[lane] = tri_orig[s];
+        }
+        __syncthreads();
+        if (want) {
+            for (int k = sub; k < cnt; k += SUB) {
+                const double a[3] = {s_tri[0][k], s_tri[1][k], s_tri[2][k]}, b[3] = {s_tri[3][k], s_tri[4][k], s_tri[5][k]},
+                             cc[3] = {s_tri[6][k], s_tri[7][k], s_tri[8][k]};
+                double t, u, v;
+                if (!ray_triangle(o, d, a, b, cc, t_min, t_hi, facing, t, u, v)) continue;
+                ++count;
+                const int32_t og = s_orig[k];
+                if (better(t, og, best.t, best.orig)) best.t = t, best.orig = og, best.u = u, best.v = v;
+            }
+        }
+        if (!COUNT) {  // the ray's new upper end: the least t its SUB lanes have found (t == t_hi may still win the tie)
+            double q = best.t;
+            for (int off = PACKET; off < PF_WAVE; off <<= 1) q = fmin(q, __shfl_xor(q, off, PF_WAVE));
+            if (ok) t_hi = fmin(t_max, q);
+            if (sub == 0) s_ray[6][slot] = t_hi;
+            __syncthreads();
+        }
+    };
+    // Of the lanes with keep set, the one with the least near (lowest lane on ties), or -1; near > bound for it means the
+    // same for all that remain.  The chosen lane is cleared.
+    auto take = [&](bool& keep, double near) {
+        double k = keep ? near : inf;
+        int64_t l = keep ? lane : PF_WAVE + lane;  // a kept lane wins a tie at +inf against the others
+        wave_argmin(k, l);
+        if (l >= PF_WAVE) return -1;
+        if (l == lane) keep = false;
+        return (int)l;
+    };
+
+    double bound = wave_max(t_hi);  // the packet's upper end: that of its farthest-reaching ray
+    for (int64_t sb = 0; sb < n_super && bound >= t_min; sb += PF_WAVE) {
+        const int64_t s = sb + lane;
+        double snear = inf;
+        bool skeep = s < n_super && packet_box(sbox + 6 * s, snear);
+        for (int sl = take(skeep, snear); sl >= 0; sl = take(skeep, snear)) {
+            if (__shfl(snear, sl, PF_WAVE) > bound) break;  // t_hi has shrunk since the ballot: nothing left reaches in
+            const int64_t c = (sb + sl) * PF_WAVE + lane;
+            double cnear = inf;
+            bool ckeep = c < n_chunks && packet_box(box + 6 * c, cnear);
+            for (int cl = take(ckeep, cnear); cl >= 0; cl = take(ckeep, cnear)) {
+                if (__shfl(cnear, cl, PF_WAVE) > bound) break;
+                scan((sb + sl) * PF_WAVE + cl);
+                bound = wave_max(t_hi);
+            }
+        }
+    }
+
+    // the ray's winner over its lanes (least t, lowest triangle index) and its count, outputs in the caller's order
+    for (int off = PACKET; off < PF_WAVE; off <<= 1) {
+        const double ot = __shfl_xor(best.t, off, PF_WAVE), ou = __shfl_xor(best.u, off, PF_WAVE), ov = __shfl_xor(best.v, off, PF_WAVE);
+        const int32_t oo = __shfl_xor(best.orig, off, PF_WAVE);
+        if (better(ot, oo, best.t, best.orig)) best.t = ot, best.orig = oo, best.u = ou, best.v = ov;
+        count += __shfl_xor(count, off, PF_WAVE);
+    }
+    if (live && sub == 0) {
+        const bool found = ok && best.orig != 0x7fffffff;
+        if (out_t) out_t[ri] = found ? best.t : (ok ? inf : nan);
+        if (out_face) out_face[ri] = found ? best.orig / per_face : -1;
+        if (out_uv) out_uv[2 * ri] = found ? best.u : nan, out_uv[2 * ri + 1] = found ? best.v : nan;
+        if (out_count) out_count[ri] = count;
+    }
+}
+
 // ---- host side ---------------------------------------------------------------------------------------------------------
 
 // The device side of one call: scratch blocks from the ctx's cache, all given back when the call's scope ends (after
@@ -1409,6 +1651,64 @@ int pf_surface_winding(pf_surface* s, const double* qry, int64_t n_qry, double b
     sc.sync();
     if (!sc.ok()) {
         pf_set_error("pf_surface_winding: %s", hipGetErrorString(sc.err));
+        return PF_E_HIP;
+    }
+    return PF_OK;
+}
+
+int pf_surface_raycast(pf_surface* s, const double* origins, const double* dirs, int64_t n_rays, double t_min, double t_max,
+                       int32_t facing, double* out_t, int32_t* out_face, double* out_uv, int32_t* out_count) {
+    PF_CHECK(s && origins && dirs, PF_E_ARG, "pf_surface_raycast: NULL argument");
+    PF_CHECK(n_rays >= 1 && n_rays < ((int64_t)1 << 31), PF_E_ARG, "pf_surface_raycast: n_rays = %lld out of range", (long long)n_rays);
+    PF_CHECK(t_min <= t_max, PF_E_ARG, "pf_surface_raycast: the interval [%g, %g] is empty or NaN", t_min, t_max);
+    PF_CHECK(facing >= -1 && facing <= 1, PF_E_ARG, "pf_surface_raycast: facing = %d: use -1 (back), 0 (any) or 1 (front)", facing);
+    const Box3 bb = point_box(origins, n_rays, true);
+    PF_HIP(hipSetDevice(s->ctx->device));
+    hipStream_t st = s->ctx->stream;
+    // the packet rule of distance_search: 16 rays per wave once that gives >= 4096 waves, else 4
+    const bool big = n_rays >= (int64_t)16 * 4096;
+    const unsigned n_pack = (unsigned)(big ? (n_rays + 15) / 16 : (n_rays + 3) / 4);
+    Scratch sc(st);
+    double *d_o = sc.get<double>(3 * n_rays), *d_d = sc.get<double>(3 * n_rays);
+    double* d_t = out_t ? sc.get<double>(n_rays) : nullptr;
+    int32_t* d_face = out_face ? sc.get<int32_t>(n_rays) : nullptr;
+    double* d_uv = out_uv ? sc.get<double>(2 * n_rays) : nullptr;
+    int32_t* d_cnt = out_count ? sc.get<int32_t>(n_rays) : nullptr;
+    sc.upload(d_o, origins, 3 * n_rays);
+    sc.upload(d_d, dirs, 3 * n_rays);
+    const int32_t* perm = morton_order(sc, d_o, nullptr, 0, n_rays, bb);
+    if (sc.ok()) {
+        const auto launch = [&](auto kernel) {
+            kernel<<<n_pack, PF_WAVE, 0, st>>>(s->tri, s->tri_orig, s->box, s->sbox, s->n_tri, s->n_chunks, s->n_super, d_o, d_d, perm,
+                                               n_rays, t_min, t_max, facing, s->vpf - 2, d_t, d_face, d_uv, d_cnt);
+        };
+        if (big)
+            out_count ? launch(k_raycast<16, true>) : launch(k_raycast<16, false>);
+        else
+            out_count ? launch(k_raycast<4, true>) : launch(k_raycast<4, false>);
+        sc.launched();
+    }
+    sc.download(out_t, d_t, n_rays);
+    sc.download(out_face, d_face, n_rays);
+    sc.download(out_uv, d_uv, 2 * n_rays);
+    sc.download(out_count, d_cnt, n_rays);
+    sc.sync();
+    if (!sc.ok()) {
+        pf_set_error("pf_surface_raycast: %s", hipGetErrorString(sc.err));
+        return PF_E_HIP;
+    }
+    return PF_OK;
+}
+
+int pf_surface_vertex_normals(pf_surface* s, double* out) {
+    PF_CHECK(s && out, PF_E_ARG, "pf_surface_vertex_normals: NULL argument");
+    PF_CHECK(s->vnrm, PF_E_ARG, "pf_surface_vertex_normals: pf_surface_prepare_signed has not been called");
+    PF_HIP(hipSetDevice(s->ctx->device));
+    Scratch sc(s->ctx->stream);
+    sc.download(out, s->vnrm, 3 * s->n_points);
+    sc.sync();
+    if (!sc.ok()) {
+        pf_set_error("pf_surface_vertex_normals: %s", hipGetErrorString(sc.err));
         return PF_E_HIP;
     }
     return PF_OK;
