@@ -525,6 +525,38 @@ int pf_surface_raycast(pf_surface* s, const double* origins, const double* dirs,
                        int32_t facing, double* out_t, int32_t* out_face, double* out_uv, int32_t* out_count);
 int pf_surface_vertex_normals(pf_surface* s, double* out);
 
+/* ---- closest point on a surface embedded in d dimensions (sub-vertex correspondences) ---------------------
+ * FOCUSR matches a source vertex to the nearest target VERTEX in spectral coordinates (focusr.py:351-353).  The target
+ * is a triangulated surface in the same d-dimensional space; this is the closest point ON it: a fan triangle and
+ * barycentric weights.  1 <= d <= 16 (the limit of pf_knn_upload and pf_assign).  Polygons are fan-triangulated
+ * (0,j+1,j+2).  Exact: the minimum over ALL fan triangles of the exact point-triangle squared distance, lowest
+ * fan-triangle index on exact ties; a triangle whose distance is NaN (a degenerate one, through the divisions of the walk)
+ * never wins.  The arithmetic is the region walk of pf_surface_closest with every dot product summed left to right over
+ * coordinates 0 .. d-1 without FMA, the closest point formed per coordinate by the region's formula and d2 the sum of the
+ * squared coordinate differences, left to right: a host loop in the same order gives the same bits, and at d = 3 out_d2
+ * and out_face equal pf_surface_closest's.  No floating-point atomics: two calls give identical bits.
+ *   pf_surface_nd_create   coords [n][d] f64, faces [n_faces][verts_per_face] i32 (host) -> device search structure.
+ *                          PF_E_ARG for d outside 1..16, n < 1, no faces, verts_per_face outside 3..16, a vertex id
+ *                          outside 0..n-1.
+ *   pf_surface_nd_closest  qry [n_qry][d] f64 (host), n_qry >= 1 (else PF_E_ARG) -> out_face [n_qry] the face of the
+ *                          winning fan triangle, out_verts [n_qry][3] its vertex ids in its corner order (a, b, c),
+ *                          out_bary [n_qry][3] the weights of the region the walk ended in: (1,0,0) (0,1,0) (0,0,1) at a
+ *                          corner, (1-v, v, 0) on ab, (1-w, 0, w) on ca, (0, 1-w, w) on bc, ((1-v)-w, v, w) inside;
+ *                          out_d2 [n_qry] the squared distance.  A query with a non-finite coordinate, or a surface
+ *                          without a triangle of finite distance, gives -1, (-1,-1,-1), NaN weights, NaN.  Each output
+ *                          may be NULL.  exhaustive != 0 tests every triangle against every query (no box pruning): the
+ *                          same bits, the device-side yardstick of the pruned search.
+ *   pf_surface_nd_last_search  of the last pf_surface_nd_closest on s: chunks of 64 triangles staged, summed over the
+ *                          packets of 8 neighbouring queries; the number of packets; the chunks of the surface.  Each
+ *                          may be NULL. */
+typedef struct pf_surface_nd pf_surface_nd;
+int pf_surface_nd_create(pf_ctx* ctx, const double* coords, int64_t n, int32_t d, const int32_t* faces, int64_t n_faces,
+                         int32_t verts_per_face, pf_surface_nd** out);
+void pf_surface_nd_free(pf_surface_nd* s);
+int pf_surface_nd_closest(pf_surface_nd* s, const double* qry, int64_t n_qry, int32_t* out_face, int32_t* out_verts,
+                          double* out_bary, double* out_d2, int32_t exhaustive);
+int pf_surface_nd_last_search(pf_surface_nd* s, int64_t* chunks_opened, int64_t* packets, int64_t* n_chunks);
+
 /* ---- Coherent Point Drift pieces ("next" row f4) ------------------------------------------------------------
  * The reference registers the spectral coordinates with the third-party cycpd package (focusr.py:297-334).
  * These are the two O(M*N) operations of its EM iteration, matrix-free (P and G are never stored):

@@ -177,6 +177,11 @@ SIGNATURES = {
     "pf_surface_raycast": (C.c_int, [C.c_void_p, _f64p, _f64p, C.c_int64, C.c_double, C.c_double, C.c_int32, _f64p, _i32p, _f64p,
                                      _i32p]),
     "pf_surface_vertex_normals": (C.c_int, [C.c_void_p, _f64p]),
+    "pf_surface_nd_create": (C.c_int, [C.c_void_p, _f64p, C.c_int64, C.c_int32, _i32p, C.c_int64, C.c_int32,
+                                       C.POINTER(C.c_void_p)]),
+    "pf_surface_nd_free": (None, [C.c_void_p]),
+    "pf_surface_nd_closest": (C.c_int, [C.c_void_p, _f64p, C.c_int64, _i32p, _i32p, _f64p, _f64p, C.c_int32]),
+    "pf_surface_nd_last_search": (C.c_int, [C.c_void_p, _i64p, _i64p, _i64p]),
     "pf_cpd_create": (C.c_int, [C.c_void_p, _f64p, C.c_int64, _f64p, C.c_int64, C.c_int32, C.POINTER(C.c_void_p)]),
     "pf_cpd_free": (None, [C.c_void_p]),
     "pf_cpd_estep": (C.c_int, [C.c_void_p, _f64p, C.c_double, C.c_double, _f64p, _f64p, _f64p]),
@@ -743,6 +748,73 @@ class DeviceSurface(object):
         if getattr(self, "_h", None):
             self._lib.pf_surface_free(self._h)
             self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+
+class DeviceSurfaceND(object):
+    """Triangulated surface embedded in d dimensions (1 <= d <= 16) in HBM, for exact closest-point queries that return
+    the face, its corners and barycentric weights (`pf_surface_nd_*`): sub-vertex correspondences in spectral
+    coordinates.  `close()` frees it; usable as a context manager."""
+
+    MAX_DIM = 16
+
+    def __init__(self, coords, faces, ctx=None):
+        x = _c_f64(coords)
+        f = np.ascontiguousarray(faces, dtype=np.int32)
+        if x.ndim != 2 or x.shape[0] == 0 or not 1 <= x.shape[1] <= self.MAX_DIM:
+            raise ValueError("coords must be a non-empty (n, d) array with 1 <= d <= %d" % self.MAX_DIM)
+        if f.ndim != 2 or f.shape[0] == 0 or f.shape[1] < 3:
+            raise ValueError("faces must be a non-empty (F, verts_per_face >= 3) array")
+        self.ctx = ctx if ctx is not None else default_context()
+        self._lib = self.ctx._lib
+        h = C.c_void_p()
+        _check(self._lib.pf_surface_nd_create(self.ctx._h, _f64(x), x.shape[0], x.shape[1], f.ctypes.data_as(_i32p), f.shape[0],
+                                              f.shape[1], C.byref(h)))
+        self._h = h
+        self.n, self.d, self.n_faces = x.shape[0], x.shape[1], f.shape[0]
+        _live_graphs.add(self)
+        self.ctx._children.add(self)
+
+    def closest(self, queries, exhaustive=False):
+        """(face (q,) i32, vertices (q,3) i32, bary (q,3) f64, d2 (q,) f64) of the closest surface point of every query
+        (`pf_surface_nd_closest`): the face of the winning fan triangle, that triangle's corners, the weights of the
+        closest point on them, the squared distance.  A query with a non-finite coordinate (or a surface without a
+        triangle of finite distance) gives -1, (-1,-1,-1), NaN, NaN.  Equal to a brute-force loop over all triangles bit
+        for bit; `exhaustive` runs that loop on the device."""
+        q = _c_f64(queries)
+        if q.ndim != 2 or q.shape[0] == 0 or q.shape[1] != self.d:
+            raise ValueError("queries must be a non-empty (n, %d) array" % self.d)
+        face = np.empty(len(q), dtype=np.int32)
+        verts = np.empty((len(q), 3), dtype=np.int32)
+        bary = np.empty((len(q), 3), dtype=np.float64)
+        d2 = np.empty(len(q), dtype=np.float64)
+        _check(self._lib.pf_surface_nd_closest(self._h, _f64(q), len(q), face.ctypes.data_as(_i32p), verts.ctypes.data_as(_i32p),
+                                               _f64(bary), _f64(d2), 1 if exhaustive else 0))
+        return face, verts, bary, d2
+
+    def last_search(self):
+        """{chunks_opened, packets, n_chunks} of the last `closest`: chunks of 64 triangles staged, summed over the
+        packets of 8 neighbouring queries; the packets; the chunks the surface has."""
+        v = [C.c_int64(0) for _ in range(3)]
+        _check(self._lib.pf_surface_nd_last_search(self._h, *[C.byref(x) for x in v]))
+        return {"chunks_opened": int(v[0].value), "packets": int(v[1].value), "n_chunks": int(v[2].value)}
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.pf_surface_nd_free(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
 
     def __del__(self):
         try:

@@ -308,6 +308,54 @@ hipStream_t pf_stream_b(pf_ctx* c);  // created on first use (nullptr on failure
 hipError_t pf_create_side_stream(hipStream_t* s, bool low = false);  // low: the least priority (a third pool of queues: the copy stream)  // a stream that never shares a hardware queue with a ctx's main stream
 void pf_free(hipStream_t st, void* p);
 
+// The device side of one call: scratch blocks from the ctx's cache, all given back when the call's scope ends (after
+// whatever synchronise the call made: as late as the blocks can matter), and the stream work itself.  The first failure is
+// kept in err and turns everything that follows into a no-op, so a call is written without branches: ok() before its
+// kernels, err at the end.
+struct Scratch {
+    const hipStream_t st;
+    hipError_t err = hipSuccess;
+    std::vector<void*> blocks;
+
+    explicit Scratch(hipStream_t stream) : st(stream) {}
+    Scratch(const Scratch&) = delete;
+    Scratch& operator=(const Scratch&) = delete;
+    ~Scratch() {
+        for (void* p : blocks) pf_free(st, p);
+    }
+    bool ok() const { return err == hipSuccess; }
+    void note(hipError_t e) {
+        if (ok()) err = e;
+    }
+    template <class T>
+    T* keep(size_t count) {  // a block that outlives the call: the caller owns it, also after a failure
+        void* p = nullptr;
+        if (ok()) err = pf_malloc(st, &p, sizeof(T) * count);
+        return (T*)p;
+    }
+    template <class T>
+    T* get(size_t count) {
+        T* p = keep<T>(count);
+        if (p) blocks.push_back(p);
+        return p;
+    }
+    template <class T>
+    void upload(T* dst, const T* src, size_t count) {
+        if (ok()) err = hipMemcpyAsync(dst, src, sizeof(T) * count, hipMemcpyHostToDevice, st);
+    }
+    template <class T>
+    void download(T* dst, const T* src, size_t count) {  // dst == NULL: the caller did not ask for it
+        if (ok() && dst) err = hipMemcpyAsync(dst, src, sizeof(T) * count, hipMemcpyDeviceToHost, st);
+    }
+    void zero(void* p, size_t bytes) {
+        if (ok()) err = hipMemsetAsync(p, 0, bytes, st);
+    }
+    void launched() { note(hipGetLastError()); }  // after the kernels of an ok() block
+    void sync() {
+        if (ok()) err = hipStreamSynchronize(st);
+    }
+};
+
 // SELL-64 entry layout inside a slice of `width` entries per row: entries come in PAIRS per lane, so that one
 // lane reads two values with one 16-byte load and two column indices with one 8-byte load (the widest
 // coalesced access: 1 KiB of values per wave instruction); a slice of odd width keeps its last entry in a

@@ -1255,54 +1255,6 @@ __global__ __launch_bounds__(PF_WAVE) void k_raycast(const double* __restrict__ 
 
 // ---- host side ---------------------------------------------------------------------------------------------------------
 
-// The device side of one call: scratch blocks from the ctx's cache, all given back when the call's scope ends (after
-// whatever synchronise the call made: as late as the blocks can matter), and the stream work itself.  The first failure is
-// kept in err and turns everything that follows into a no-op, so a call is written without branches: ok() before its
-// kernels, err at the end.
-struct Scratch {
-    const hipStream_t st;
-    hipError_t err = hipSuccess;
-    std::vector<void*> blocks;
-
-    explicit Scratch(hipStream_t stream) : st(stream) {}
-    Scratch(const Scratch&) = delete;
-    Scratch& operator=(const Scratch&) = delete;
-    ~Scratch() {
-        for (void* p : blocks) pf_free(st, p);
-    }
-    bool ok() const { return err == hipSuccess; }
-    void note(hipError_t e) {
-        if (ok()) err = e;
-    }
-    template <class T>
-    T* keep(size_t count) {  // a block that outlives the call: the caller owns it, also after a failure
-        void* p = nullptr;
-        if (ok()) err = pf_malloc(st, &p, sizeof(T) * count);
-        return (T*)p;
-    }
-    template <class T>
-    T* get(size_t count) {
-        T* p = keep<T>(count);
-        if (p) blocks.push_back(p);
-        return p;
-    }
-    template <class T>
-    void upload(T* dst, const T* src, size_t count) {
-        if (ok()) err = hipMemcpyAsync(dst, src, sizeof(T) * count, hipMemcpyHostToDevice, st);
-    }
-    template <class T>
-    void download(T* dst, const T* src, size_t count) {  // dst == NULL: the caller did not ask for it
-        if (ok() && dst) err = hipMemcpyAsync(dst, src, sizeof(T) * count, hipMemcpyDeviceToHost, st);
-    }
-    void zero(void* p, size_t bytes) {
-        if (ok()) err = hipMemsetAsync(p, 0, bytes, st);
-    }
-    void launched() { note(hipGetLastError()); }  // after the kernels of an ok() block
-    void sync() {
-        if (ok()) err = hipStreamSynchronize(st);
-    }
-};
-
 // The box the Morton keys of n points are taken in.  finite_only leaves every non-finite coordinate out (queries);
 // without it only NaN is left out and an infinite coordinate flattens its axis (the vertices of a surface, as ever: the
 // order of the triangles decides the order of the winding sums).

@@ -24,10 +24,11 @@ import numpy as np
 
 from . import _hip
 from .assignment import euclidean_assignment
+from .correspondence import closest_points_on_embedded_surface, interpolate_on_surface
 from .eigsort import eigsort
 from .graph import Graph, compute_spectra, spectral_knn
 from .main import print_header
-from .vtk_functions import PolyMesh, apply_transform, icp_transform, set_mesh_scalars, vtk_deep_copy
+from .vtk_functions import PolyMesh, apply_transform, icp_transform, mesh_arrays, set_mesh_scalars, vtk_deep_copy
 
 from . import cpd as _native_cpd
 
@@ -85,6 +86,7 @@ class Focusr(object):
         verbose=False,
         registration=None,
         ctx=None,
+        return_surface_final_points=False,
     ):
         self.verbose = verbose
         self._ctx = ctx if ctx is not None else _hip.default_context()
@@ -116,6 +118,7 @@ class Focusr(object):
         self.projection_smooth_iterations = projection_smooth_iterations
         self.final_correspondence_type = final_correspondence_type
         self.return_transformed_mesh = return_transformed_mesh
+        self.return_surface_final_points = return_surface_final_points
 
         for kind in (initial_correspondence_type, final_correspondence_type):
             if kind not in ("kd", "hungarian"):
@@ -293,6 +296,30 @@ class Focusr(object):
         else:
             self.get_kd_correspondence(self.smoothed_target_coords, self.source_projected_on_target)
 
+    def get_surface_correspondence(self, target_pts, spectral_pts):
+        """The closest point ON the target surface embedded at `target_pts` (n_target, d) for every row of
+        `spectral_pts` (n_source, d), 1 <= d <= 16: face, corners, barycentric weights, squared distance
+        (`closest_points_on_embedded_surface`).  Leaves `corresponding_target_idx_for_each_source_pt` alone."""
+        _, faces = mesh_arrays(self.graph_target.vtk_mesh)
+        found = closest_points_on_embedded_surface(spectral_pts, target_pts, faces, ctx=self._ctx)
+        self.corresponding_target_face_for_each_source_pt = found["face"]
+        self.corresponding_target_vertices_for_each_source_pt = found["vertices"]
+        self.corresponding_target_bary_for_each_source_pt = found["bary"]
+        self.surface_correspondence_d2 = found["d2"]
+
+    def get_surface_final_node_locations(self):
+        """Every source point goes to its closest point on the target SURFACE: after smoothing the projection
+        `source_projected_on_target` is searched against the smoothed target surface (d = 3), without smoothing the
+        source's spectral coordinates against the target's spectral surface; the weights found there interpolate the
+        target's own points.  Unlike the 3-vertex average the result lies on a target triangle."""
+        if self.smoothed_target_coords is not None:
+            self.get_surface_correspondence(self.smoothed_target_coords, self.source_projected_on_target)
+        else:
+            self.get_surface_correspondence(self.target_spectral_coords, self.source_spectral_coords)
+        self.surface_transformed_points = interpolate_on_surface(
+            self.graph_target.points, self.corresponding_target_vertices_for_each_source_pt,
+            self.corresponding_target_bary_for_each_source_pt)
+
     def get_weighted_final_node_locations(self, n_closest_pts=3):
         """focusr.py:401-426: every source point goes to the inverse-distance-weighted average of the
         `n_closest_pts` target vertices nearest to its projection (a coincident vertex wins outright).
@@ -338,6 +365,9 @@ class Focusr(object):
         """focusr.py:603-613."""
         self.weighted_avg_transformed_mesh = self._source_mesh_with_points(self.weighted_avg_transformed_points)
 
+    def get_source_mesh_transformed_surface(self):
+        self.surface_transformed_mesh = self._source_mesh_with_points(self.surface_transformed_points)
+
     # ------------------------------------------------------------------ mesh scalars for visualisation (focusr.py:572-599)
     def set_transformed_source_scalars_to_corresp_target_idx(self):
         for mesh in (getattr(self, "weighted_avg_transformed_mesh", None), getattr(self, "nearest_neighbour_transformed_mesh", None)):
@@ -368,6 +398,8 @@ class Focusr(object):
         """focusr.py:433-453: mean of each source vertex and its image on the target."""
         if align_type == "nearest":
             moved = self.graph_target.points[self.corresponding_target_idx_for_each_source_pt, :]
+        elif align_type == "surface":
+            moved = self.surface_transformed_points
         else:
             moved = self.weighted_avg_transformed_points
         self.average_mesh = self._source_mesh_with_points((moved + self.graph_source.points) / 2)
@@ -432,6 +464,10 @@ class Focusr(object):
                 self.get_source_mesh_transformed_weighted_avg()
             if self.return_nearest_final_points is True:
                 self.get_source_mesh_transformed_nearest_neighbour()
+        if self.return_surface_final_points is True:
+            self.get_surface_final_node_locations()
+            if self.return_transformed_mesh is True:
+                self.get_source_mesh_transformed_surface()
 
     def _n_unique_correspondences(self):
         """len(np.unique(idx)) (focusr.py:543-554) without the sort: target indices are small non-negative ints."""
