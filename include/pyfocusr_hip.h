@@ -120,6 +120,30 @@ int pf_graph_build_device2(pf_mesh* mesh_a, pf_mesh* mesh_b, pf_graph** out_a, p
  * operator); deg/l_diag hold the diagonal; rows without off-diagonal entries count as isolated. */
 int pf_graph_from_matrix(pf_ctx* ctx, int64_t n, const int32_t* rowptr, const int32_t* colidx, const double* values,
                          pf_graph** out);
+/* The cotangent Laplace-Beltrami operator of a resident triangle mesh (the reference has none: an extra).
+ *   w_ij = 1/2 sum over the faces containing the undirected edge (i,j) of cot(angle opposite it), cot = (u.v)/|u x v| at
+ *          the corner with edge vectors u, v; terms in ascending face index; (i,j) and (j,i) hold the same bits; negative
+ *          weights (obtuse angles) are kept
+ *   d_i  = sum_j w_ij left to right in column order;  m_i = 1/3 sum of the incident faces' areas (|u x v|/2 at the face's
+ *          first corner) in ascending face index: the lumped barycentric mass (mass_kind 0, the only one)
+ * No floating-point atomics: two builds give identical bits.  The graph's operator is the symmetric
+ *   S = M^-1/2 (D - W) M^-1/2:  S_ij = -w_ij / (sqrt(m_i) sqrt(m_j)),  S_ii = d_i / m_i
+ * (spectrum of the generalised problem (D - W) phi = lambda M phi, eigenvectors M^1/2 phi) stored as for
+ * pf_graph_from_matrix: PF_OP_RW and PF_OP_SYM both apply S, is_symmetric = 1, pf_graph_download gives the structure with
+ * w = -S_ij, deg = l_diag = S_ii; pf_graph_info.spectral_bound is the Gershgorin bound max_i sum_j |S_ij| (not <= 2).  A
+ * vertex in no face (m_i = 0) has an empty row, counts in n_isolated and stays 0 in every eigenvector.
+ * pf_lock_null_vectors locks sqrt(m) restricted to each component.  Rows stay in the caller's numbering (no m-space).
+ * Errors: verts_per_face != 3 or a face index out of range PF_E_ARG; a face that repeats a vertex or has |u x v| == 0 (or
+ * non-finite) PF_E_DEGENERATE.  Runs on the ctx stream; pf_timing.build_ms is its device time. */
+int pf_graph_build_cotan(pf_mesh* mesh, int32_t mass_kind /* 0 = barycentric */, pf_graph** out);
+/* hi = max_i sum_j |S_ij| (diagonal included), total_area = sum of the faces' areas (fixed order); each may be NULL */
+int pf_graph_cotan_info(pf_graph* g, double* hi, double* total_area);
+/* w[nnz_w] = w_ij in the CSR order of pf_graph_download, diag[n] = d_i, mass[n] = m_i; each may be NULL */
+int pf_graph_cotan_download(pf_graph* g, double* w, double* diag, double* mass);
+/* out = M^-1 (D - W) x for a host block x[n][ncols] (row-major, 1 <= ncols <= 8): out_i = (sum_j w_ij (x_i - x_j)) / m_i,
+ * the row left to right; 0 where m_i == 0.  Applied to the points it is the mean-curvature normal (|.| = 2 H). */
+int pf_cotan_apply(pf_graph* g, const double* x, int32_t ncols, double* out);
+/* (the three calls above return PF_E_ARG for a graph that pf_graph_build_cotan did not build) */
 void pf_graph_free(pf_graph* g);
 int pf_graph_get_info(pf_graph* g, pf_graph_info* out);
 /* CSR(W): rowptr[n+1], colidx[nnz_w], w[nnz_w]; l_offdiag[nnz_w] = -w/(deg_i+1e-8);
@@ -137,7 +161,7 @@ int pf_ws_copy(pf_graph* g, int32_t src, int32_t dst, int32_t count);
 int pf_start_vector(pf_graph* g, int32_t slot, uint64_t seed);
 int pf_mask_isolated(pf_graph* g, int32_t slot);                          /* x[i] = 0 where deg_i == 0 */
 /* unit-norm null vectors of `op`, one per component with >= 2 vertices, into slots
- * [0, n_components): 1_C for PF_OP_RW, sqrt(deg+1e-8) on C for PF_OP_SYM. */
+ * [0, n_components): 1_C for PF_OP_RW, sqrt(deg+1e-8) on C for PF_OP_SYM; sqrt(m) on C for a cotangent graph. */
 int pf_lock_null_vectors(pf_graph* g, int32_t op, int32_t* n_locked);
 
 /* ---- eigensolver kernels (replace scipy eigs/ARPACK+SuperLU at graph.py:372) ------------- */

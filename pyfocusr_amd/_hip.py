@@ -81,6 +81,10 @@ SIGNATURES = {
     "pf_graph_build_device": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
     "pf_graph_build_device2": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "pf_graph_from_matrix": (C.c_int, [C.c_void_p, C.c_int64, _i32p, _i32p, _f64p, C.POINTER(C.c_void_p)]),
+    "pf_graph_build_cotan": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p)]),
+    "pf_graph_cotan_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "pf_graph_cotan_download": (C.c_int, [C.c_void_p, _f64p, _f64p, _f64p]),
+    "pf_cotan_apply": (C.c_int, [C.c_void_p, _f64p, C.c_int32, _f64p]),
     "pf_graph_free": (None, [C.c_void_p]),
     "pf_graph_get_info": (C.c_int, [C.c_void_p, C.POINTER(GraphInfo)]),
     "pf_graph_download": (C.c_int, [C.c_void_p, _i32p, _i32p, _f64p, _f64p, _f64p, _f64p, _i32p]),
@@ -940,9 +944,22 @@ class DeviceLaplacian(object):
     """Device-resident graph of one mesh: CSR(W), deg, SELL-64 operators, workspace.
     Also the `ops` object the Krylov driver (`_krylov.filtered_eigs`) drives."""
 
-    def __init__(self, points=None, faces=None, ctx=None, device_mesh=None, matrix=None, _handle=None):
+    cotangent = False  # True: built by pf_graph_build_cotan - the operator is S = M^-1/2 (D - W) M^-1/2 of the cotangent weights
+
+    def __init__(self, points=None, faces=None, ctx=None, device_mesh=None, matrix=None, _handle=None, cotangent=False):
         h = C.c_void_p()
-        if _handle is not None:  # (ctx, pf_graph*) of a graph the library has already built (build_pair)
+        if cotangent:
+            if matrix is not None or _handle is not None:
+                raise ValueError("cotangent=True needs a mesh (points and faces, or device_mesh)")
+            mesh = device_mesh if device_mesh is not None else DeviceMesh(points, faces, ctx=ctx)
+            self.ctx = mesh.ctx
+            self._lib = self.ctx._lib
+            try:
+                _check(self._lib.pf_graph_build_cotan(mesh._h, 0, C.byref(h)))
+            finally:
+                if device_mesh is None:
+                    mesh.close()
+        elif _handle is not None:  # (ctx, pf_graph*) of a graph the library has already built (build_pair)
             self.ctx, h = _handle
             self._lib = self.ctx._lib
         elif matrix is not None:  # (rowptr, colidx, values) of a general CSR matrix, canonical format
@@ -984,6 +1001,13 @@ class DeviceLaplacian(object):
         self.op = PF_OP_SYM if self.symmetric else PF_OP_RW
         self.has_points = matrix is None
         self._rows = []
+        if cotangent:
+            self.cotangent = True
+            hi, area = C.c_double(), C.c_double()
+            _check(self._lib.pf_graph_cotan_info(h, C.byref(hi), C.byref(area)))
+            self.hi, self.total_area = float(hi.value), float(area.value)
+            self.spectral_bound = self.hi
+            self.mass = self.cotan_download(w=False, diag=False)["mass"]
 
     @classmethod
     def build_pair(cls, mesh_a, mesh_b):
@@ -1022,6 +1046,26 @@ class DeviceLaplacian(object):
         if labels:
             out["labels"] = lab
         return out
+
+    def cotan_download(self, w=True, diag=True, mass=True):
+        """`pf_graph_cotan_download`: the cotangent weights w_ij (CSR order of `download()`), d_i and m_i of a cotangent graph."""
+        out = {}
+        if w:
+            out["w"] = np.empty(self.nnz_w)
+        if diag:
+            out["diag"] = np.empty(self.n)
+        if mass:
+            out["mass"] = np.empty(self.n)
+        _check(self._lib.pf_graph_cotan_download(self._h, *[_f64(out[k]) if k in out else None for k in ("w", "diag", "mass")]))
+        return out
+
+    def cotan_apply(self, x):
+        """`pf_cotan_apply`: M^-1 (D - W) x for x of shape (n,) or (n, ncols <= 8)."""
+        v = _c_f64(x)
+        v2 = v.reshape(self.n, -1)
+        out = np.empty_like(v2)
+        _check(self._lib.pf_cotan_apply(self._h, _f64(v2), v2.shape[1], _f64(out)))
+        return out[:, 0] if v.ndim == 1 else out
 
     # ---- ops interface ------------------------------------------------------------------------
     def ws_ensure(self, n_slots):

@@ -853,14 +853,6 @@ int finish_graph(pf_graph* g, const double* d_pts, bool numeric_symmetry, const 
 
 }  // namespace
 
-struct pf_mesh {
-    pf_ctx* ctx = nullptr;
-    double* pts = nullptr;    // [n][3]
-    int32_t* faces = nullptr; // [n_faces][vpf]
-    int64_t n = 0, n_faces = 0;
-    int32_t vpf = 0;
-};
-
 namespace {
 
 // The assembly of one mesh in two halves around its one synchronisation (see FinishJob)
@@ -1060,6 +1052,18 @@ struct MeshBuild {
 
 }  // namespace
 
+int pf_graph_finish_general(pf_graph* g, const double* d_pts) {
+    pf_ctx* ctx = g->ctx;
+    hipStream_t st = ctx->stream;
+    PF_TRY(finish_graph(g, d_pts, true));
+    PF_HIP(pfl::event_record(st, ctx->ev1));
+    PF_HIP(pfl::sync(st));
+    float ms = 0.f;
+    PF_HIP(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+    ctx->build_ms = ms;
+    return PF_OK;
+}
+
 extern "C" {
 
 void pf_graph_free(pf_graph* g) {
@@ -1083,6 +1087,10 @@ void pf_graph_free(pf_graph* g) {
     pf_free(st, g->persist_ring2);
     pf_free(st, g->final_vecs);
     pf_free(st, g->pts);
+    pf_free(st, g->cot_w);
+    pf_free(st, g->cot_diag);
+    pf_free(st, g->cot_mass);
+    pf_free(st, g->cot_sqrtm);
     pf_window_slots_free(g);
     pf_free(st, g->rowptr);
     pf_free(st, g->col);
@@ -1365,12 +1373,7 @@ int pf_graph_from_matrix(pf_ctx* ctx, int64_t n, const int32_t* rowptr, const in
     PF_TRY(dev_alloc(st, &g->w, g->nnz_w));
     pfl::launch<k_csr_split>(dim3(nblk(n)), dim3(PF_BLOCK), 0, st, rp, ci, va, g->rowptr, n, g->col, g->w, g->deg, g->g, g->sg);
     PF_HIP(hipGetLastError());
-    PF_TRY(finish_graph(g, nullptr, true));
-    PF_HIP(pfl::event_record(st, ctx->ev1));
-    PF_HIP(pfl::sync(st));
-    float ms = 0.f;
-    PF_HIP(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
-    ctx->build_ms = ms;
+    PF_TRY(pf_graph_finish_general(g, nullptr));
     guard.ok = true;
     *out = g;
     return PF_OK;

@@ -287,6 +287,23 @@ struct pf_graph {
     double* pts = nullptr;  // [n][3] the mesh's points (graphs built from a mesh): pf_point_rows
     bool deg_block = false; // g and sg live in deg's allocation (mesh path: one memset for the three)
     double spectral_bound = 2.0; // proven upper bound of the operator's spectrum (2: Gershgorin; less for closed triangle meshes)
+    // cotangent graphs (pf_cotan.hip): the operator stored above is S = M^-1/2 (D - W) M^-1/2 on the unit_g path (w = -S_ij,
+    // deg = S_ii, g = sg = 1); the cotangent matrices themselves stay beside it, CSR order, the caller's vertex numbers
+    int32_t is_cotan = 0;
+    double* cot_w = nullptr;     // [nnz_w] w_ij = 1/2 sum of the cotangents opposite (i, j)
+    double* cot_diag = nullptr;  // [n] d_i = sum_j w_ij
+    double* cot_mass = nullptr;  // [n] m_i = 1/3 sum of the incident faces' areas (0: the vertex is in no face)
+    double* cot_sqrtm = nullptr; // [n] sqrt(m_i): S's null vector on a component
+    double cot_hi = 0.0;         // Gershgorin bound of S: max_i sum_j |S_ij|, diagonal included
+    double cot_area = 0.0;       // sum of the faces' areas
+};
+
+struct pf_mesh {
+    pf_ctx* ctx = nullptr;
+    double* pts = nullptr;    // [n][3]
+    int32_t* faces = nullptr; // [n_faces][vpf]
+    int64_t n = 0, n_faces = 0;
+    int32_t vpf = 0;
 };
 
 // Caching device allocator, one cache per ctx (pf_api.hip).  Every use of a block is enqueued on
@@ -368,6 +385,11 @@ __host__ __device__ static inline int64_t pf_sell_index(int64_t base, int32_t wi
 
 static inline double* pf_slot(pf_graph* g, int32_t s) { return g->ws + (int64_t)s * g->n_pad; }
 static inline double* pf_tmp(pf_graph* g, int which) { return g->ws + (int64_t)(g->n_slots + which) * g->n_pad; }
+
+// pf_assemble.hip: everything of a build that follows CSR(W), deg, g, sg on the device (pf_graph_from_matrix,
+// pf_graph_build_cotan): numeric symmetry, row statistics, component labels, the solver's renumbering (along the Morton
+// curve of d_pts when given), the SELL-64 storage; closes the ctx's build timer (ev0 recorded by the caller) and waits.
+int pf_graph_finish_general(pf_graph* g, const double* d_pts);
 
 // pf_scan.hip
 int pf_exclusive_scan_i32(hipStream_t st, const int32_t* in, int32_t* out, int64_t n);

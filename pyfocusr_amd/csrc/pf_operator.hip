@@ -667,14 +667,16 @@ __global__ __launch_bounds__(PF_BLOCK) void k_permute_out(const double* __restri
 __global__ __launch_bounds__(PF_BLOCK) void k_null_vector(double* __restrict__ x, const int32_t* __restrict__ label,
                                                           const int32_t* __restrict__ rowptr,
                                                           const double* __restrict__ deg, const int32_t* __restrict__ perm,
-                                                          int64_t n_pad, int32_t root, int32_t sym) {
+                                                          int64_t n_pad, int32_t root, int32_t sym,
+                                                          const double* __restrict__ weight) {
     // null vector of the iterated operator on one component: 1_C for L = G (D - W) and for a general matrix with zero
-    // row sums (G = I: sym == 0 is passed), G^-1/2 1_C = sqrt(deg + 1e-8) 1_C for S = G^1/2 (D - W) G^1/2 of a mesh graph
+    // row sums (G = I: sym == 0 is passed), G^-1/2 1_C = sqrt(deg + 1e-8) 1_C for S = G^1/2 (D - W) G^1/2 of a mesh graph;
+    // `weight` (cotangent graphs: sqrt(m), the null vector of M^-1/2 (D - W) M^-1/2) replaces both
     const int64_t r = (int64_t)blockIdx.x * PF_BLOCK + threadIdx.x;
     if (r >= n_pad) return;
     const int32_t i = perm[r];
     double v = 0.0;
-    if (i >= 0 && label[i] == root && rowptr[i + 1] > rowptr[i]) v = sym ? sqrt(deg[i] + 1e-8) : 1.0;
+    if (i >= 0 && label[i] == root && rowptr[i + 1] > rowptr[i]) v = weight ? weight[i] : (sym ? sqrt(deg[i] + 1e-8) : 1.0);
     x[r] = v;
 }
 
@@ -1290,7 +1292,7 @@ int pf_lock_null_vectors(pf_graph* g, int32_t op, int32_t* n_locked) {
     PF_TRY(pf_reduce_ensure(g, 1));
     for (int32_t c = 0; c < nc; ++c) {
         k_null_vector<<<nblk(g->n_pad), PF_BLOCK, 0, st>>>(pf_slot(g, c), g->label, g->rowptr, g->deg, g->perm_m, g->n_pad,
-                                                          g->roots[c], op == PF_OP_SYM && !g->unit_g);
+                                                          g->roots[c], op == PF_OP_SYM && !g->unit_g, g->is_cotan ? g->cot_sqrtm : nullptr);
         PF_HIP(hipGetLastError());
         // normalised with the norm still on the device (the same 1 / sqrt as on the host: the same bits; a component has at
         // least two vertices, so the norm is positive) - no wait at the head of a solve
@@ -2345,7 +2347,8 @@ int pf_mean_filter(pf_graph* g, const double* values, int32_t ncols, int32_t ite
         const size_t entries = (size_t)(g->sell_entries + g->n_pad);
         PF_HIP(pf_malloc(st, (void**)&g->mf_col, sizeof(int32_t) * entries));
         PF_HIP(pf_malloc(st, (void**)&g->mf_val, sizeof(double) * entries));
-        k_fill_mean_filter<<<nblk(g->n_pad), PF_BLOCK, 0, st>>>(g->rowptr, g->col, g->w, g->deg, g->perm_m, g->iperm_m, g->morder, g->n_pad,
+        // (a cotangent graph filters with its cotangent weights: g->w / g->deg hold the entries of S there)
+        k_fill_mean_filter<<<nblk(g->n_pad), PF_BLOCK, 0, st>>>(g->rowptr, g->col, g->is_cotan ? g->cot_w : g->w, g->is_cotan ? g->cot_diag : g->deg, g->perm_m, g->iperm_m, g->morder, g->n_pad,
                                                                 g->slice_ptr, g->mf_col, g->mf_val);
         PF_HIP(hipGetLastError());
     }

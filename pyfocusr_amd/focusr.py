@@ -87,8 +87,10 @@ class Focusr(object):
         registration=None,
         ctx=None,
         return_surface_final_points=False,
+        laplacian="inverse_length",
     ):
         self.verbose = verbose
+        self.laplacian = laplacian  # "inverse_length" (the reference's) or "cotangent" (Laplace-Beltrami), for both graphs
         self._ctx = ctx if ctx is not None else _hip.default_context()
         self.registration = registration
         print("Starting Focusr")
@@ -155,6 +157,7 @@ class Focusr(object):
             norm_node_features_std=norm_node_features_std,
             norm_node_features_cap_std=norm_node_features_cap_std,
             norm_node_features_0_1=norm_node_features_0_1,
+            laplacian=laplacian,
         )
         # focusr.py:134-170 builds target then source; the two spectra are independent, so their
         # Chebyshev recurrences run in lockstep, two graphs per kernel launch.

@@ -23,6 +23,10 @@ largest-|entry| positive (A5); `get_list_rand_idxs(force_randomization=True)`
 uses `np.random.shuffle` (A7).  Extra node features (curvature, point-data
 arrays; graph.py:85-119,166-175,191-210) need VTK and are outside the hot path:
 non-empty feature lists raise `NotImplementedError`.
+
+An extra the reference does not have: `Graph(..., laplacian="cotangent")` replaces the inverse-edge-length
+random-walk Laplacian by the cotangent Laplace-Beltrami operator M^-1 (D - W) with lumped barycentric mass
+(`pf_graph_build_cotan`; see `laplace_beltrami.py`).  The default, `"inverse_length"`, is the reference's operator.
 """
 import os
 
@@ -34,6 +38,8 @@ from ._krylov import MIN_EIG_VAL, drive, drive_pair, filtered_eigs_gen
 from .vtk_functions import mesh_arrays, vtk_deep_copy  # noqa: F401
 
 __all__ = ["Graph", "recursive_eig", "compute_spectra", "spectral_knn"]
+
+LAPLACIANS = ("inverse_length", "cotangent")
 
 
 class _DeviceBackedCSR(sparse.csr_matrix):
@@ -71,7 +77,11 @@ class Graph(object):
         norm_node_features_0_1=True,
         ctx=None,
         verbose=True,
+        laplacian="inverse_length",
     ):
+        if laplacian not in LAPLACIANS:
+            raise ValueError("laplacian must be one of %r, got %r" % (LAPLACIANS, laplacian))
+        self.laplacian = laplacian
         # Inputs (graph.py:36-55)
         self.vtk_mesh = vtk_mesh
         self.n_spectral_features = n_spectral_features
@@ -121,6 +131,7 @@ class Graph(object):
 
     # ------------------------------------------------------------------ eigenvectors: host array + device-resident twin
     _eig_pending = False  # (class default: shells made with Graph.__new__ - parallel.py, bench.py - have no download in flight)
+    laplacian = "inverse_length"
     _eig_vecs = None
     _final_map = None
 
@@ -183,7 +194,12 @@ class Graph(object):
         """The `DeviceLaplacian` of this mesh (built on first use)."""
         if self._device is None:
             resident = getattr(self.vtk_mesh, "_pf_device_mesh", None)  # inputs already in HBM (bench, pipelines)
-            if resident is not None:
+            if self.laplacian == "cotangent":
+                if resident is not None:
+                    self._device = _hip.DeviceLaplacian(device_mesh=resident, cotangent=True)
+                else:
+                    self._device = _hip.DeviceLaplacian(self.points, self._faces, ctx=self._ctx, cotangent=True)
+            elif resident is not None:
                 self._device = _hip.DeviceLaplacian(device_mesh=resident)
             else:
                 self._device = _hip.DeviceLaplacian(self.points, self._faces, ctx=self._ctx)
@@ -191,8 +207,17 @@ class Graph(object):
 
     def _host_arrays(self):
         if self._host is None:
-            self._host = self.device.download()
+            h = self.device.download()
+            if self.laplacian == "cotangent":  # (the device's w / deg are the entries of S there: the cotangent matrices instead)
+                c = self.device.cotan_download()
+                h = dict(rowptr=h["rowptr"], colidx=h["colidx"], w=c["w"], deg=c["diag"], mass=c["mass"])
+            self._host = h
         return self._host
+
+    @property
+    def mass(self):
+        """Lumped barycentric vertex areas m_i of a cotangent graph (None for the inverse-length Laplacian)."""
+        return self.device.mass if self.laplacian == "cotangent" else None
 
     def _geom(self):
         if self._geometry is None:
@@ -245,6 +270,9 @@ class Graph(object):
     def get_degree_matrix(self):
         h = self._host_arrays()
         self.degree_matrix = sparse.diags(h["deg"])
+        if self.laplacian == "cotangent":  # G = M^-1 there (0 on vertices in no face)
+            self.degree_matrix_inv = sparse.diags(_inv_or_zero(h["mass"]))
+            return
         self.degree_matrix_inv = sparse.diags((h["deg"] + 1e-8) ** -1)
 
     def get_G_matrix(self, p_function="exp"):
@@ -257,6 +285,13 @@ class Graph(object):
             self.get_G_matrix()
         h = self._host_arrays()
         n = self.n_points
+        if self.laplacian == "cotangent":  # M^-1 (D - W); its device graph holds the symmetric twin S (see recursive_eig)
+            W = sparse.csr_matrix((h["w"], h["colidx"], h["rowptr"]), shape=(n, n))
+            L = _DeviceBackedCSR(sparse.csr_matrix(sparse.diags(_inv_or_zero(h["mass"])) @ (sparse.diags(h["deg"]) - W)))
+            L.sort_indices()
+            L._pf_device = self.device
+            self.laplacian_matrix = L
+            return
         rowptr = h["rowptr"].astype(np.int64)
         cnt = np.diff(rowptr)
         has_diag = cnt > 0  # scipy drops the explicit zero diagonal of isolated vertices
@@ -284,6 +319,23 @@ class Graph(object):
         dev = self.device
         if self.verbose:
             print("Beginning Eigen Decomposition")
+        if self.laplacian == "cotangent":
+            # S through the general-matrix driver (hi from the device, cut as `_device_from_matrix` / `recursive_eig` set it),
+            # the reference's widening rule and > 1e-10 filter inside `_device_eigs`; then phi = M^-1/2 u on the host
+            k = self.n_spectral_features
+            vals, vecs, stats = _device_eigs(dev, k=k + 1, n_k_needed=k, k_buffer=1, minmax=False, verbose=self.verbose,
+                                             wait=True, **_cotan_solver_kw(dev, k))
+            vecs = _cotan_vectors(dev.mass, vecs, unit=False)
+            if self.norm_eig_vecs is True and vecs.shape[1]:
+                lo = vecs.min(axis=0)
+                vecs = (vecs - lo) / (vecs.max(axis=0) - lo) - 0.5  # graph.py:254-257
+            self.eig_vals, self._eig_vecs, self.eigs_stats = vals, vecs, stats
+            self._final_map, self._eig_pending = None, False  # (the block the solver left on the device is u, not phi)
+            if self.verbose:
+                print("All final eigenvalues are: \n{}".format(self.eig_vals))
+                print("-" * 72)
+                print("Final eigenvalues of interest are: \n{}".format(self.eig_vals))
+            return
         if PAIR_DRIVER == "c" and _spectra_c([self]):
             if self.verbose:
                 print("All final eigenvalues are: \n{}".format(self.eig_vals))
@@ -357,7 +409,8 @@ class Graph(object):
 
     # ------------------------------------------------------------------ graph filter (graph.py:320-354)
     def mean_filter_graph(self, values, iterations=300):
-        """out = ((D+I)^-1 (W+I))^iterations values, on the device."""
+        """out = ((D+I)^-1 (W+I))^iterations values, on the device.  W and D are whatever `adjacency_matrix` holds: the
+        inverse edge lengths by default, the cotangent weights (which may be negative) for `laplacian="cotangent"`."""
         return self.device.mean_filter(np.asarray(values, dtype=np.float64), iterations)
 
 
@@ -379,6 +432,10 @@ def compute_spectra(graphs):
     lockstep on its stream (`_paired_spectra`); graphs of different contexts run from one host
     thread each, every one on its own HIP stream (ctypes releases the GIL during library calls)."""
     graphs = list(graphs)
+    if any(getattr(g, "laplacian", "inverse_length") == "cotangent" for g in graphs):
+        for g in graphs:  # (cotangent graphs have no shared pair launch: one after the other)
+            g.get_graph_spectrum()
+        return
     build_devices(graphs)  # (two graphs that are still to be assembled: side by side)
     if len(graphs) == 2 and graphs[0].device.ctx is graphs[1].device.ctx and _pair_pays(graphs[0], graphs[1]):
         _paired_spectra(graphs[0], graphs[1])
@@ -412,7 +469,7 @@ def build_devices(graphs):
     `.device` of each."""
     graphs = list(graphs)
     todo = [g for g in graphs if g._device is None]
-    if len(todo) == 2 and os.environ.get("PF_PAIR_BUILD", "1") != "0" and (todo[0]._ctx is todo[1]._ctx):
+    if len(todo) == 2 and all(getattr(g, "laplacian", "inverse_length") == "inverse_length" for g in todo) and os.environ.get("PF_PAIR_BUILD", "1") != "0" and (todo[0]._ctx is todo[1]._ctx):
         ga, gb = todo
         meshes = []
         for g in todo:
@@ -602,6 +659,32 @@ def _device_eigs(dev, k, n_k_needed, k_buffer=1, minmax=False, verbose=False, wa
     return out
 
 
+def _inv_or_zero(m):
+    out = np.zeros_like(m)
+    np.divide(1.0, m, out=out, where=m > 0)
+    return out
+
+
+def _cotan_solver_kw(dev, n_k_needed):
+    """What the filtered solver has to know about the S of a cotangent device graph: the Gershgorin bound the assembler
+    reduced on the device, and the cut of `_device_from_matrix` scaled as `recursive_eig` scales it."""
+    hi = max(dev.hi, 1e-300)
+    return dict(hi=hi, cut=8.0 * (1 + 1) / max(dev.n, 1) * hi / 2.0 * (n_k_needed + 1) / 2.0, adapt_cut=True)
+
+
+def _cotan_vectors(mass, vecs, unit):
+    """Eigenvectors u of S = M^-1/2 (D - W) M^-1/2 (unit 2-norm columns) -> phi = M^-1/2 u of M^-1 (D - W): phi^T M phi = I
+    (`unit`: scaled to unit 2-norm instead, what `recursive_eig` returns); 0 on vertices in no face; `Graph`'s sign
+    convention - the largest-|entry| (lowest index on ties) positive - applied to phi."""
+    phi = np.asarray(vecs) * np.sqrt(_inv_or_zero(np.asarray(mass)))[:, None]
+    if phi.shape[1] == 0:
+        return phi
+    if unit:
+        phi = phi / np.linalg.norm(phi, axis=0)
+    lead = phi[np.argmax(np.abs(phi), axis=0), np.arange(phi.shape[1])]
+    return phi * np.where(lead < 0, -1.0, 1.0)
+
+
 def _device_from_matrix(matrix, ctx=None):
     """Upload a general sparse matrix (the argument of the reference's `recursive_eig`) and work out
     what the filtered solver needs to know about it: an upper bound of the spectrum (Gershgorin) and
@@ -629,9 +712,9 @@ def recursive_eig(matrix, k, n_k_needed, k_buffer=1, sigma=1e-10, which="LM"):
     with eigenvalue > 1e-10.
 
     A Laplacian produced by `Graph.get_laplacian_matrix()` carries its device graph and is solved in
-    place; any other scipy sparse matrix (the reference's signature) is uploaded with
-    `pf_graph_from_matrix`.  `sigma`/`which` select ARPACK's shift-invert mode in the reference and have no
-    counterpart here: the eigenvalues nearest zero of a positive semi-definite operator are always the
+    place (the M^-1 (D - W) of a cotangent `Graph` through its symmetric twin M^-1/2 (D - W) M^-1/2, the eigenvectors
+    mapped back); any other scipy sparse matrix (the reference's signature) is uploaded with `pf_graph_from_matrix`.
+    `sigma`/`which` select ARPACK's shift-invert mode in the reference and have no counterpart here: the eigenvalues nearest zero of a positive semi-definite operator are always the
     ones computed.  Returns raw (un-normalised, unit-2-norm) eigenvectors, sorted ascending.
 
     General matrices: null vectors are locked analytically when the rows sum to zero (one per connected component);
@@ -646,8 +729,12 @@ def recursive_eig(matrix, k, n_k_needed, k_buffer=1, sigma=1e-10, which="LM"):
         dev, solver_kw = _device_from_matrix(matrix)
         solver_kw["cut"] = solver_kw["cut"] * (n_k_needed + 1) / 2.0
         owned = True
+    elif getattr(dev, "cotangent", False):
+        solver_kw = _cotan_solver_kw(dev, n_k_needed)
     try:
         vals, vecs, _ = _device_eigs(dev, k, n_k_needed, k_buffer, minmax=False, verbose=True, **solver_kw)
+        if getattr(dev, "cotangent", False):  # the device graph of M^-1 (D - W) iterates its symmetric twin
+            vecs = _cotan_vectors(dev.mass, vecs, unit=True)
     finally:
         if owned:
             dev.close()
