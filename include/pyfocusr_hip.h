@@ -379,6 +379,42 @@ int pf_knn_upload(pf_ctx* ctx, const double* ref, int64_t n_ref, const double* q
 int pf_knn_run(pf_ctx* ctx);
 int pf_knn_download(pf_ctx* ctx, int64_t* idx_out, double* d2_out);
 
+/* ---- functional maps and ZoomOut (pf_fmap.hip; the reference has none: an extra) --------------------------------
+ * Exact 1-NN for 1 <= d <= 128 by a register- and LDS-tiled exhaustive scan: pf_knn1's arithmetic (left to right,
+ * separate multiply and add, lowest reference index on exact ties), so indices and distances are a brute force's bits.
+ * For d <= 16 pf_knn1 stays the production path (it prunes); this one takes small d so that the two can be compared.
+ * Non-finite coordinates: unspecified winner (no fault).  PF_E_ARG for d outside 1..128 or an empty set. */
+int pf_knn1_wide(pf_ctx* ctx, const double* ref, int64_t n_ref, const double* qry, int64_t n_qry, int32_t d,
+                 int64_t* idx_out, double* d2_out /* nullable */);
+/* Coordinate pairs ((q_c - r_c)^2 terms, 3 floating-point operations each, padding to chunks of 8 coordinates and 16
+ * references included) that the last COUNTED wide search evaluated - a wave drops 16 references once none of their
+ * partial sums is below its lanes' best; the call also sets the switch for the searches to come. */
+int pf_knn1_wide_count(pf_ctx* ctx, int32_t enable_counting, int64_t* coordinate_pairs);
+/* A point map T (T[i] in [0, n_t) for every SOURCE vertex i: Focusr's direction) and two M-orthonormal Laplace-Beltrami
+ * bases, ascending (laplace_beltrami_spectrum), resident for the whole iteration:
+ *   project  C[a][b] = sum_i mass_s[i] phi_s[i][a] phi_t[T[i]][b], k_s x k_t row-major: the coefficients of a function
+ *            on the target -> those of its pull-back on the source.  Rows in blocks of 512, each block summed in row
+ *            order, the blocks added in block order; no floating-point atomics: two calls give the same bits.
+ *   convert  Q = phi_s[:, :k_s] C (every entry summed over a ascending), then T[i] = the row of phi_t[:, :k_t] nearest
+ *            to Q[i]: the library's search for k_t <= 16, the wide scan above it; exact, lowest index on ties.
+ *   zoomout  k = k_start; loop { project (k, k); convert (k, k); stop at k == k_end; k = min(k + step, k_end) }, then
+ *            n_iter_at_end more rounds at k_end.  C_out (nullable): the last projection, k_end x k_end.
+ * pf_fmap_create      phi_t [n_t][K], phi_s [n_s][K], mass_s [n_s] (host), 1 <= K <= 128.
+ * pf_fmap_set_p2p     T [n_s]; validated on the device: an entry outside 0 .. n_t - 1 gives PF_E_ARG (no map is set).
+ * pf_fmap_get_p2p     T_out [n_s]; d2_out [n_s] (nullable) the squared distances of the last convert (PF_E_STATE if none).
+ * pf_fmap_project     1 <= k_s, k_t <= K; C_out nullable; C stays resident.  PF_E_STATE without a point map.
+ * pf_fmap_convert     C (host, k_s x k_t) or NULL for the resident one (PF_E_STATE if its shape differs).
+ * Everything runs on the ctx stream. */
+typedef struct pf_fmap pf_fmap;
+int pf_fmap_create(pf_ctx* ctx, const double* phi_t, int64_t n_t, const double* phi_s, int64_t n_s, const double* mass_s,
+                   int32_t K, pf_fmap** out);
+void pf_fmap_free(pf_fmap* h);
+int pf_fmap_set_p2p(pf_fmap* h, const int64_t* T);
+int pf_fmap_get_p2p(pf_fmap* h, int64_t* T_out, double* d2_out);
+int pf_fmap_project(pf_fmap* h, int32_t k_s, int32_t k_t, double* C_out);
+int pf_fmap_convert(pf_fmap* h, const double* C, int32_t k_s, int32_t k_t);
+int pf_fmap_zoomout(pf_fmap* h, int32_t k_start, int32_t k_end, int32_t step, int32_t n_iter_at_end, double* C_out);
+
 /* ---- the whole eigensolve in one call --------------------------------------------------------------------------
  * Replaces scipy.sparse.linalg.eigs(L, k, sigma=1e-10, which="LM", ncv=4k) at graph.py:372 (called from
  * recursive_eig, graph.py:357-389) for callers that bind the C-ABI without the Python driver: the n_wanted lowest

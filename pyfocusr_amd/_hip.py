@@ -181,6 +181,15 @@ SIGNATURES = {
     "pf_surface_raycast": (C.c_int, [C.c_void_p, _f64p, _f64p, C.c_int64, C.c_double, C.c_double, C.c_int32, _f64p, _i32p, _f64p,
                                      _i32p]),
     "pf_surface_vertex_normals": (C.c_int, [C.c_void_p, _f64p]),
+    "pf_knn1_wide": (C.c_int, [C.c_void_p, _f64p, C.c_int64, _f64p, C.c_int64, C.c_int32, _i64p, _f64p]),
+    "pf_knn1_wide_count": (C.c_int, [C.c_void_p, C.c_int32, _i64p]),
+    "pf_fmap_create": (C.c_int, [C.c_void_p, _f64p, C.c_int64, _f64p, C.c_int64, _f64p, C.c_int32, C.POINTER(C.c_void_p)]),
+    "pf_fmap_free": (None, [C.c_void_p]),
+    "pf_fmap_set_p2p": (C.c_int, [C.c_void_p, _i64p]),
+    "pf_fmap_get_p2p": (C.c_int, [C.c_void_p, _i64p, _f64p]),
+    "pf_fmap_project": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _f64p]),
+    "pf_fmap_convert": (C.c_int, [C.c_void_p, _f64p, C.c_int32, C.c_int32]),
+    "pf_fmap_zoomout": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _f64p]),
     "pf_surface_nd_create": (C.c_int, [C.c_void_p, _f64p, C.c_int64, C.c_int32, _i32p, C.c_int64, C.c_int32,
                                        C.POINTER(C.c_void_p)]),
     "pf_surface_nd_free": (None, [C.c_void_p]),
@@ -468,6 +477,23 @@ class Context(object):
         _check(self._lib.pf_knn1(self._h, _f64(ref), ref.shape[0], _f64(qry), qry.shape[0], ref.shape[1],
                                  idx.ctypes.data_as(_i64p), _f64(d2) if return_d2 else None))
         return (idx, d2) if return_d2 else idx
+
+    def knn1_wide(self, ref, qry, return_d2=False):
+        """`knn1` for 1 <= d <= 128 by the tiled exhaustive scan (`pf_knn1_wide`): the same arithmetic, the same bits."""
+        ref, qry = _c_f64(ref), _c_f64(qry)
+        if ref.ndim != 2 or qry.ndim != 2 or ref.shape[1] != qry.shape[1]:
+            raise ValueError("ref and qry must be (n, d) arrays with equal d")
+        idx = np.empty(qry.shape[0], dtype=np.int64)
+        d2 = np.empty(qry.shape[0], dtype=np.float64) if return_d2 else None
+        _check(self._lib.pf_knn1_wide(self._h, _f64(ref), ref.shape[0], _f64(qry), qry.shape[0], ref.shape[1],
+                                      idx.ctypes.data_as(_i64p), _f64(d2) if return_d2 else None))
+        return (idx, d2) if return_d2 else idx
+
+    def knn1_wide_count(self, enable_counting=False):
+        """Coordinate pairs the last counted `knn1_wide` evaluated (`pf_knn1_wide_count`); sets the switch for the next."""
+        pairs = C.c_int64()
+        _check(self._lib.pf_knn1_wide_count(self._h, int(bool(enable_counting)), C.byref(pairs)))
+        return int(pairs.value)
 
     def assign(self, rows, cols, return_duals=False):
         """Optimal one-to-one assignment on Euclidean costs (`pf_assign`): col_of_row (int64, n_rows) minimising
@@ -811,6 +837,77 @@ class DeviceSurfaceND(object):
     def close(self):
         if getattr(self, "_h", None):
             self._lib.pf_surface_nd_free(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+
+class DeviceFunctionalMap(object):
+    """Two Laplace-Beltrami bases, the source's vertex areas and a point map T (T[i] in [0, n_t) for every source vertex)
+    in HBM for functional-map iterations (`pf_fmap_*`): `project` (point map -> C), `convert` (C -> point map),
+    `zoomout`.  `close()` frees it; usable as a context manager."""
+
+    MAX_K = 128
+
+    def __init__(self, phi_t, phi_s, mass_s, ctx=None):
+        pt, ps, m = _c_f64(phi_t), _c_f64(phi_s), _c_f64(mass_s)
+        if pt.ndim != 2 or ps.ndim != 2 or pt.shape[1] != ps.shape[1] or pt.shape[0] == 0 or ps.shape[0] == 0:
+            raise ValueError("phi_t and phi_s must be non-empty (n, K) arrays with equal K")
+        if not 1 <= pt.shape[1] <= self.MAX_K:
+            raise ValueError("1 <= K <= %d basis functions, got %d" % (self.MAX_K, pt.shape[1]))
+        if m.shape != (ps.shape[0],):
+            raise ValueError("mass_s must have one entry per source vertex")
+        self.ctx = ctx if ctx is not None else default_context()
+        self._lib = self.ctx._lib
+        h = C.c_void_p()
+        _check(self._lib.pf_fmap_create(self.ctx._h, _f64(pt), pt.shape[0], _f64(ps), ps.shape[0], _f64(m), pt.shape[1], C.byref(h)))
+        self._h = h
+        self.n_t, self.n_s, self.K = pt.shape[0], ps.shape[0], pt.shape[1]
+        _live_graphs.add(self)
+        self.ctx._children.add(self)
+
+    def set_p2p(self, T):
+        T = np.ascontiguousarray(T, dtype=np.int64)
+        if T.shape != (self.n_s,):
+            raise ValueError("T must have one target index per source vertex")
+        _check(self._lib.pf_fmap_set_p2p(self._h, T.ctypes.data_as(_i64p)))
+
+    def get_p2p(self, return_d2=False):
+        T = np.empty(self.n_s, dtype=np.int64)
+        d2 = np.empty(self.n_s) if return_d2 else None
+        _check(self._lib.pf_fmap_get_p2p(self._h, T.ctypes.data_as(_i64p), _f64(d2) if return_d2 else None))
+        return (T, d2) if return_d2 else T
+
+    def project(self, k_s, k_t):
+        Cm = np.empty((int(k_s), int(k_t)))
+        _check(self._lib.pf_fmap_project(self._h, int(k_s), int(k_t), _f64(Cm)))
+        return Cm
+
+    def convert(self, k_s, k_t, Cm=None):
+        """The resident functional map (Cm None) or the given k_s x k_t one -> the point map, which stays on the device."""
+        if Cm is not None:
+            Cm = _c_f64(Cm, (int(k_s), int(k_t)))
+        _check(self._lib.pf_fmap_convert(self._h, _f64(Cm) if Cm is not None else None, int(k_s), int(k_t)))
+
+    def zoomout(self, k_start, k_end, step=1, n_iter_at_end=0):
+        Cm = np.empty((int(k_end), int(k_end)))
+        _check(self._lib.pf_fmap_zoomout(self._h, int(k_start), int(k_end), int(step), int(n_iter_at_end), _f64(Cm)))
+        return Cm
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.pf_fmap_free(self._h)
             self._h = None
 
     def __enter__(self):

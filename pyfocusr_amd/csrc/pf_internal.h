@@ -113,6 +113,8 @@ struct pf_ctx {
     unsigned long long* knn_visited = nullptr;
     size_t knn_visited_words = 0;
     int64_t knn_visited_waves = 0;
+    unsigned long long* wide_count = nullptr;  // pf_knn1_wide_count: chunks the last counted wide search went through (pf_fmap.hip)
+    bool wide_count_on = false;
     int32_t knn_mode = 0;  // 0: by depth (box hierarchy for k = 1, d >= PF_KNN_TREE_MIN_D = 7), 1: always the grid, 2: always the hierarchy
     // operator timing: event pairs recorded around filter applications, resolved lazily in pf_timing_get so
     // that timing never blocks the host (the solver queues the next application while this one runs)
@@ -408,6 +410,10 @@ int pf_morton_order(pf_graph* g, const double* d_pts, int32_t* d_overflow);
 
 // Rows per window of the resident Chebyshev kernel: one window per block, at most 256 blocks.
 static inline int32_t pf_window_rows(int64_t n_pad) { return n_pad <= 262144 ? 1024 : (n_pad <= 524288 ? 2048 : 4096); }
+
+// pf_knn.hip: pf_knn1_blocks with every column and scale 1 whose result stays on the device (ctx->knn_idx, ctx->knn_d2)
+int pf_knn1_device(pf_ctx* c, const double* ref_block, int64_t n_ref, int32_t ref_stride, const double* qry_block, int64_t n_qry,
+                   int32_t qry_stride, int32_t d);
 
 // pf_knn_tree.hip: the 1-NN search of pf_knn_run through a bounding-box hierarchy over all d coordinates
 // (spectral coordinates of 250k blob pairs, ms grid / hierarchy: d = 6: 1.15 / 1.90, 7: 1.98 / 1.91, 8: 29.5 / 8.8, 10: 6.3 / 2.1;

@@ -1102,15 +1102,10 @@ int pf_knn1(pf_ctx* c, const double* ref, int64_t n_ref, const double* qry, int6
     return pf_knn_download(c, idx_out, d2_out);
 }
 
-int pf_knn1_blocks(pf_ctx* c, const double* ref_block, int64_t n_ref, int32_t ref_stride, const double* qry_block, int64_t n_qry,
-                   int32_t qry_stride, int32_t d, const int32_t* col_ref, const double* scale_ref, const int32_t* col_qry,
-                   const double* scale_qry, int64_t* idx_out, double* d2_out) {
-    PF_CHECK(c && ref_block && qry_block && col_ref && scale_ref && col_qry && scale_qry && idx_out, PF_E_ARG,
-             "pf_knn1_blocks: NULL argument");
-    PF_CHECK(d >= 1 && d <= 16 && ref_stride >= 1 && qry_stride >= 1, PF_E_ARG, "pf_knn1_blocks: d = %d / strides out of range", d);
-    for (int32_t k = 0; k < d; ++k)
-        PF_CHECK(col_ref[k] >= 0 && col_ref[k] < ref_stride && col_qry[k] >= 0 && col_qry[k] < qry_stride, PF_E_ARG,
-                 "pf_knn1_blocks: column %d out of range", k);
+// the search of pf_knn1_blocks without the download (arguments checked by the caller)
+static int knn1_blocks_run(pf_ctx* c, const double* ref_block, int64_t n_ref, int32_t ref_stride, const double* qry_block, int64_t n_qry,
+                           int32_t qry_stride, int32_t d, const int32_t* col_ref, const double* scale_ref, const int32_t* col_qry,
+                           const double* scale_qry) {
     PF_TRY(knn_prepare(c, n_ref, n_qry, d));
     hipStream_t st = c->stream;
     CoordMap mr{}, mq{};
@@ -1122,7 +1117,19 @@ int pf_knn1_blocks(pf_ctx* c, const double* ref_block, int64_t n_ref, int32_t re
     k_coords_from_final<<<nblk(n_qry * d), PF_BLOCK, 0, st>>>(qry_block, n_qry, qry_stride, d, mq, c->knn_qry);
     PF_HIP(hipGetLastError());
     c->knn_ready = true;
-    PF_TRY(pf_knn_run(c));
+    return pf_knn_run(c);
+}
+
+int pf_knn1_blocks(pf_ctx* c, const double* ref_block, int64_t n_ref, int32_t ref_stride, const double* qry_block, int64_t n_qry,
+                   int32_t qry_stride, int32_t d, const int32_t* col_ref, const double* scale_ref, const int32_t* col_qry,
+                   const double* scale_qry, int64_t* idx_out, double* d2_out) {
+    PF_CHECK(c && ref_block && qry_block && col_ref && scale_ref && col_qry && scale_qry && idx_out, PF_E_ARG,
+             "pf_knn1_blocks: NULL argument");
+    PF_CHECK(d >= 1 && d <= 16 && ref_stride >= 1 && qry_stride >= 1, PF_E_ARG, "pf_knn1_blocks: d = %d / strides out of range", d);
+    for (int32_t k = 0; k < d; ++k)
+        PF_CHECK(col_ref[k] >= 0 && col_ref[k] < ref_stride && col_qry[k] >= 0 && col_qry[k] < qry_stride, PF_E_ARG,
+                 "pf_knn1_blocks: column %d out of range", k);
+    PF_TRY(knn1_blocks_run(c, ref_block, n_ref, ref_stride, qry_block, n_qry, qry_stride, d, col_ref, scale_ref, col_qry, scale_qry));
     return pf_knn_download(c, idx_out, d2_out);
 }
 
@@ -1145,3 +1152,12 @@ int pf_final_device(pf_graph* g, double** block, int64_t* n_rows, int32_t* n_col
 }
 
 }  // extern "C"
+
+int pf_knn1_device(pf_ctx* c, const double* ref_block, int64_t n_ref, int32_t ref_stride, const double* qry_block, int64_t n_qry,
+                   int32_t qry_stride, int32_t d) {
+    PF_CHECK(c && ref_block && qry_block && d >= 1 && d <= 16 && d <= ref_stride && d <= qry_stride, PF_E_ARG, "pf_knn1_device: bad argument");
+    int32_t col[16];
+    double one[16];
+    for (int32_t k = 0; k < 16; ++k) col[k] = k, one[k] = 1.0;  // x * 1.0 is x
+    return knn1_blocks_run(c, ref_block, n_ref, ref_stride, qry_block, n_qry, qry_stride, d, col, one, col, one);
+}
