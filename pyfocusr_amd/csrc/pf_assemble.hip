@@ -572,8 +572,6 @@ struct k_label_original {
 }
 };
 
-inline unsigned nblk(int64_t n) { return (unsigned)((n + PF_BLOCK - 1) / PF_BLOCK); }
-
 template <typename T>
 int dev_alloc(hipStream_t st, T** p, int64_t count) {
     PF_HIP(pf_malloc(st, (void**)p, sizeof(T) * (size_t)std::max<int64_t>(count, 1)));
@@ -702,24 +700,24 @@ struct FinishJob {
         tmp.push_back(d_roots);
         PF_HIP(pfl::memset_words(st, flags, 0, sizeof(int32_t) * (8 + PF_CC_ROUNDS)));
         stats = flags + 2;  // [0] isolated, [1] max degree, [2] asym, [3] changed, [4] n_roots
-        pfl::launch<k_row_stats>(dim3(nblk(n)), dim3(PF_BLOCK), 0, st, g->rowptr, n, stats);
+        pfl::launch<k_row_stats>(dim3(pf_blocks(n)), dim3(PF_BLOCK), 0, st, g->rowptr, n, stats);
         PF_HIP(hipGetLastError());
-        pfl::launch<k_symmetry_probe>(dim3(nblk(8 * n)), dim3(PF_BLOCK), 0, st, g->rowptr, g->col, numeric_symmetry ? g->w : nullptr, n, stats + 2, g->morder);
+        pfl::launch<k_symmetry_probe>(dim3(pf_blocks(8 * n)), dim3(PF_BLOCK), 0, st, g->rowptr, g->col, numeric_symmetry ? g->w : nullptr, n, stats + 2, g->morder);
         PF_HIP(hipGetLastError());
 
         // components
-        pfl::launch<k_label_init>(dim3(nblk(g->n_pad)), dim3(PF_BLOCK), 0, st, g->rowptr, g->col, n, g->n_pad, g->label, g->morder);
+        pfl::launch<k_label_init>(dim3(pf_blocks(g->n_pad)), dim3(PF_BLOCK), 0, st, g->rowptr, g->col, n, g->n_pad, g->label, g->morder);
         PF_HIP(hipGetLastError());
         // PF_CC_FIRST rounds are queued without asking: a round that follows a round without changes returns at once
         // (~2 us instead of ~15), and whether the last one still changed something is read back with everything else below
         for (round = 0; round < PF_CC_FIRST; ++round) {
             const int32_t* prev = round ? round_flags + round - 1 : nullptr;
-            pfl::launch<k_label_round>(dim3(nblk(n)), dim3(PF_BLOCK), 0, st, g->rowptr, g->col, n, g->label, round_flags + round, prev, g->morder);
+            pfl::launch<k_label_round>(dim3(pf_blocks(n)), dim3(PF_BLOCK), 0, st, g->rowptr, g->col, n, g->label, round_flags + round, prev, g->morder);
             PF_HIP(hipGetLastError());
         }
-        pfl::launch<k_label_compress>(dim3(nblk(n)), dim3(PF_BLOCK), 0, st, g->label, n, nullptr);
+        pfl::launch<k_label_compress>(dim3(pf_blocks(n)), dim3(PF_BLOCK), 0, st, g->label, n, nullptr);
         PF_HIP(hipGetLastError());
-        pfl::launch<k_collect_roots>(dim3(nblk(n)), dim3(PF_BLOCK), 0, st, g->label, g->rowptr, n, d_roots, stats + 4);
+        pfl::launch<k_collect_roots>(dim3(pf_blocks(n)), dim3(PF_BLOCK), 0, st, g->label, g->rowptr, n, d_roots, stats + 4);
         PF_HIP(hipGetLastError());
         return PF_OK;
     }
@@ -737,7 +735,7 @@ struct FinishJob {
         PF_TRY(pf_compute_order(g, d_pts, robust ? nullptr : flags));  // (flags[0]: free for this; the statistics start at flags + 2)
         if (robust) PF_HIP(pfl::memset_words(st, flags, 0, sizeof(int32_t)));
         if (!g->perm_m) g->perm_m = g->perm, g->iperm_m = g->iperm;  // (no m-space: a graph handed in as a matrix)
-        pfl::launch<k_slice_widths>(dim3(nblk(g->n_pad)), dim3(PF_BLOCK), 0, ls, g->rowptr, g->perm_m, n, g->n_slices, width64);
+        pfl::launch<k_slice_widths>(dim3(pf_blocks(g->n_pad)), dim3(PF_BLOCK), 0, ls, g->rowptr, g->perm_m, n, g->n_slices, width64);
         PF_HIP(hipGetLastError());
         PF_TRY(pf_exclusive_scan_i64(ls, width64, g->slice_ptr, g->n_slices + 1));
         if (g->side_stream) {  // join: the build stream waits for the side chain
@@ -798,17 +796,17 @@ struct FinishJob {
             for (;;) {
                 PF_CHECK(round + 3 <= PF_CC_ROUNDS, PF_E_HIP, "pf_graph_build: component labelling did not converge");
                 for (int b = 0; b < 3; ++b, ++round) {
-                    pfl::launch<k_label_round>(dim3(nblk(n)), dim3(PF_BLOCK), 0, st, g->rowptr, g->col, n, g->label, round_flags + round, nullptr, g->morder);
+                    pfl::launch<k_label_round>(dim3(pf_blocks(n)), dim3(PF_BLOCK), 0, st, g->rowptr, g->col, n, g->label, round_flags + round, nullptr, g->morder);
                     PF_HIP(hipGetLastError());
                 }
-                pfl::launch<k_label_compress>(dim3(nblk(n)), dim3(PF_BLOCK), 0, st, g->label, n, nullptr);
+                pfl::launch<k_label_compress>(dim3(pf_blocks(n)), dim3(PF_BLOCK), 0, st, g->label, n, nullptr);
                 PF_HIP(hipGetLastError());
                 PF_HIP(pfl::memcpy_async(st, &differing, round_flags + round - 1, sizeof(int32_t), hipMemcpyDeviceToHost));
                 PF_HIP(pfl::sync(st));
                 if (!differing) break;
             }
             PF_HIP(pfl::memset_words(st, stats + 4, 0, sizeof(int32_t)));
-            pfl::launch<k_collect_roots>(dim3(nblk(n)), dim3(PF_BLOCK), 0, st, g->label, g->rowptr, n, d_roots, stats + 4);
+            pfl::launch<k_collect_roots>(dim3(pf_blocks(n)), dim3(PF_BLOCK), 0, st, g->label, g->rowptr, n, d_roots, stats + 4);
             PF_HIP(hipGetLastError());
             PF_HIP(pfl::memcpy_async(st, &n_roots, stats + 4, sizeof(int32_t), hipMemcpyDeviceToHost));
             PF_HIP(pfl::memcpy_async(st, h_roots, d_roots, sizeof(h_roots), hipMemcpyDeviceToHost));
@@ -967,17 +965,17 @@ struct MeshBuild {
             PF_TRY(scratch(&faces_m, n_edges));
             d_pts = pts_m, d_faces = faces_m;
             if (n) {
-                pfl::launch<k_renumber_points>(dim3(nblk(3 * n)), dim3(PF_BLOCK), 0, st, mesh->pts, g->morder, n, pts_m);
+                pfl::launch<k_renumber_points>(dim3(pf_blocks(3 * n)), dim3(PF_BLOCK), 0, st, mesh->pts, g->morder, n, pts_m);
                 PF_HIP(hipGetLastError());
             }
             if (n_edges) {
-                pfl::launch<k_renumber_faces>(dim3(nblk(n_edges)), dim3(PF_BLOCK), 0, st, mesh->faces, g->mrank, n_edges, n, faces_m);
+                pfl::launch<k_renumber_faces>(dim3(pf_blocks(n_edges)), dim3(PF_BLOCK), 0, st, mesh->faces, g->mrank, n_edges, n, faces_m);
                 PF_HIP(hipGetLastError());
             }
 
             if (face_bound) PF_TRY(scratch(&pmin, 1));
             if (n_edges) {
-                pfl::launch<k_count_edges>(dim3(nblk(n_edges)), dim3(PF_BLOCK), 0, st, d_faces, n_edges, vpf, n, b_cnt, b_rank, b_flags, reinterpret_cast<double*>(pmin));
+                pfl::launch<k_count_edges>(dim3(pf_blocks(n_edges)), dim3(PF_BLOCK), 0, st, d_faces, n_edges, vpf, n, b_cnt, b_rank, b_flags, reinterpret_cast<double*>(pmin));
                 PF_HIP(hipGetLastError());
             }
             // No read-back on the way: faces the counting kernel flags (index out of range, repeated vertex) are skipped by
@@ -986,18 +984,18 @@ struct MeshBuild {
             // (each one costs ~30 us of idle device: 8 per mesh at first, 2 now).
             PF_TRY(pf_exclusive_scan_i32(st, b_cnt, b_start, n + 1));
             if (n_edges) {
-                pfl::launch<k_scatter_edges>(dim3(nblk(n_edges)), dim3(PF_BLOCK), 0, st, d_faces, d_pts, n_edges, vpf, n, b_start, b_rank, b_rcol, b_rw, b_flags);
+                pfl::launch<k_scatter_edges>(dim3(pf_blocks(n_edges)), dim3(PF_BLOCK), 0, st, d_faces, d_pts, n_edges, vpf, n, b_start, b_rank, b_rcol, b_rw, b_flags);
                 PF_HIP(hipGetLastError());
             }
             return PF_OK;
         }
         if (k == 1) {  // CSR(W), degrees, the face bound
-            pfl::launch<k_sort_unique_rows>(dim3(nblk(n)), dim3(PF_BLOCK), 0, st, b_start, n, b_rcol, b_rw, b_ucnt, g->morder);
+            pfl::launch<k_sort_unique_rows>(dim3(pf_blocks(n)), dim3(PF_BLOCK), 0, st, b_start, n, b_rcol, b_rw, b_ucnt, g->morder);
             PF_HIP(hipGetLastError());
             PF_TRY(pf_exclusive_scan_i32(st, b_ucnt, g->rowptr, n + 1));
             PF_TRY(dev_alloc(st, &g->col, n_edges));
             PF_TRY(dev_alloc(st, &g->w, n_edges));
-            pfl::launch<k_compact_rows>(dim3(nblk(n)), dim3(PF_BLOCK), 0, st, b_start, g->rowptr, n, b_rcol, b_rw, g->col, g->w, g->deg, g->g, g->sg);
+            pfl::launch<k_compact_rows>(dim3(pf_blocks(n)), dim3(PF_BLOCK), 0, st, b_start, g->rowptr, n, b_rcol, b_rw, g->col, g->w, g->deg, g->g, g->sg);
             PF_HIP(hipGetLastError());
             // the face-by-face bound of the spectrum (k_face_bound); it holds if every undirected edge lies in exactly two
             // triangles: W symmetric and no directed edge listed twice - both known after the read-back
@@ -1014,7 +1012,7 @@ struct MeshBuild {
                 g->side_stream = side;
             }
             if (face_bound) {
-                pfl::launch<k_face_bound>(dim3(nblk(n_faces)), dim3(PF_BLOCK), 0, g->side_stream ? g->side_stream : st, d_faces, d_pts, n_faces, n, pmin);
+                pfl::launch<k_face_bound>(dim3(pf_blocks(n_faces)), dim3(PF_BLOCK), 0, g->side_stream ? g->side_stream : st, d_faces, d_pts, n_faces, n, pmin);
                 PF_HIP(hipGetLastError());
             }
             fin.g = g, fin.d_pts = d_pts, fin.numeric_symmetry = false, fin.d_extra = b_flags, fin.h_extra = h_flags;
@@ -1360,7 +1358,7 @@ int pf_graph_from_matrix(pf_ctx* ctx, int64_t n, const int32_t* rowptr, const in
     PF_HIP(pfl::memset_words(st, g->g, 0, sizeof(double) * g->n_pad));
     PF_HIP(pfl::memset_words(st, g->sg, 0, sizeof(double) * g->n_pad));
     PF_HIP(pfl::event_record(st, ctx->ev0));
-    pfl::launch<k_csr_count_offdiag>(dim3(nblk(n)), dim3(PF_BLOCK), 0, st, rp, ci, n, cnt, flags);
+    pfl::launch<k_csr_count_offdiag>(dim3(pf_blocks(n)), dim3(PF_BLOCK), 0, st, rp, ci, n, cnt, flags);
     PF_HIP(hipGetLastError());
     PF_TRY(pf_exclusive_scan_i32(st, cnt, g->rowptr, n + 1));
     int32_t h_flag = 0, nnz32 = 0;
@@ -1371,7 +1369,7 @@ int pf_graph_from_matrix(pf_ctx* ctx, int64_t n, const int32_t* rowptr, const in
     g->nnz_w = nnz32;
     PF_TRY(dev_alloc(st, &g->col, g->nnz_w));
     PF_TRY(dev_alloc(st, &g->w, g->nnz_w));
-    pfl::launch<k_csr_split>(dim3(nblk(n)), dim3(PF_BLOCK), 0, st, rp, ci, va, g->rowptr, n, g->col, g->w, g->deg, g->g, g->sg);
+    pfl::launch<k_csr_split>(dim3(pf_blocks(n)), dim3(PF_BLOCK), 0, st, rp, ci, va, g->rowptr, n, g->col, g->w, g->deg, g->g, g->sg);
     PF_HIP(hipGetLastError());
     PF_TRY(pf_graph_finish_general(g, nullptr));
     guard.ok = true;
@@ -1415,7 +1413,7 @@ int pf_graph_download(pf_graph* g, int32_t* rowptr, int32_t* colidx, double* w, 
         };
         do {
             if (bad(pf_malloc(st, (void**)&len, sizeof(int32_t) * (size_t)(n + 1))) || bad(pf_malloc(st, (void**)&rp, sizeof(int32_t) * (size_t)(n + 1)))) break;
-            pfl::launch<k_len_original>(dim3(nblk(n + 1)), dim3(PF_BLOCK), 0, st, g->rowptr, g->mrank, n, len);
+            pfl::launch<k_len_original>(dim3(pf_blocks(n + 1)), dim3(PF_BLOCK), 0, st, g->rowptr, g->mrank, n, len);
             if (bad(hipGetLastError())) break;
             if (pf_exclusive_scan_i32(st, len, rp, n + 1) != PF_OK) {
                 rc = PF_E_HIP;
@@ -1427,13 +1425,13 @@ int pf_graph_download(pf_graph* g, int32_t* rowptr, int32_t* colidx, double* w, 
             if (l_offdiag && bad(pf_malloc(st, (void**)&lo, sizeof(double) * ne))) break;
             if (deg && bad(pf_malloc(st, (void**)&dg, sizeof(double) * (size_t)n))) break;
             if (l_diag && bad(pf_malloc(st, (void**)&ld, sizeof(double) * (size_t)n))) break;
-            pfl::launch<k_rows_original>(dim3(nblk(n)), dim3(PF_BLOCK), 0, st, g->rowptr, g->col, g->w, g->g, g->deg, g->mrank, g->morder, rp, n, co, wo, lo, dg, ld);
+            pfl::launch<k_rows_original>(dim3(pf_blocks(n)), dim3(PF_BLOCK), 0, st, g->rowptr, g->col, g->w, g->g, g->deg, g->mrank, g->morder, rp, n, co, wo, lo, dg, ld);
             if (bad(hipGetLastError())) break;
             if (component_label) {
                 if (bad(pf_malloc(st, (void**)&lab, sizeof(int32_t) * (size_t)n)) || bad(pf_malloc(st, (void**)&small, sizeof(int32_t) * (size_t)n))) break;
                 if (bad(pfl::memset_words(st, small, 0x7f, sizeof(int32_t) * (size_t)n))) break;
-                pfl::launch<k_label_min_original>(dim3(nblk(n)), dim3(PF_BLOCK), 0, st, g->label, g->morder, n, small);
-                pfl::launch<k_label_original>(dim3(nblk(n)), dim3(PF_BLOCK), 0, st, g->label, g->mrank, small, n, lab);
+                pfl::launch<k_label_min_original>(dim3(pf_blocks(n)), dim3(PF_BLOCK), 0, st, g->label, g->morder, n, small);
+                pfl::launch<k_label_original>(dim3(pf_blocks(n)), dim3(PF_BLOCK), 0, st, g->label, g->mrank, small, n, lab);
                 if (bad(hipGetLastError())) break;
                 if (bad(pfl::memcpy_async(st, component_label, lab, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost))) break;
             }
@@ -1456,7 +1454,7 @@ int pf_graph_download(pf_graph* g, int32_t* rowptr, int32_t* colidx, double* w, 
     double* tmp_diag = nullptr;
     if (l_diag) {  // g->diag is stored in solver order: rebuild g_i deg_i in mesh order
         PF_HIP(pf_malloc(st, (void**)&tmp_diag, sizeof(double) * g->n));
-        pfl::launch<k_l_diag>(dim3(nblk(g->n)), dim3(PF_BLOCK), 0, st, g->deg, g->g, g->n, tmp_diag);
+        pfl::launch<k_l_diag>(dim3(pf_blocks(g->n)), dim3(PF_BLOCK), 0, st, g->deg, g->g, g->n, tmp_diag);
         hipError_t ed = hipGetLastError();
         if (ed == hipSuccess) ed = pfl::memcpy_async(st, l_diag, tmp_diag, sizeof(double) * g->n, hipMemcpyDeviceToHost);
         if (ed != hipSuccess) {
@@ -1469,7 +1467,7 @@ int pf_graph_download(pf_graph* g, int32_t* rowptr, int32_t* colidx, double* w, 
     if (component_label) PF_HIP(pfl::memcpy_async(st, component_label, g->label, sizeof(int32_t) * g->n, hipMemcpyDeviceToHost));
     if (l_offdiag && g->nnz_w) {
         PF_HIP(pf_malloc(st, (void**)&tmp, sizeof(double) * g->nnz_w));
-        pfl::launch<k_l_offdiag>(dim3(nblk(g->n)), dim3(PF_BLOCK), 0, st, g->rowptr, g->w, g->g, g->n, tmp);
+        pfl::launch<k_l_offdiag>(dim3(pf_blocks(g->n)), dim3(PF_BLOCK), 0, st, g->rowptr, g->w, g->g, g->n, tmp);
         hipError_t e = hipGetLastError();
         if (e == hipSuccess) e = pfl::memcpy_async(st, l_offdiag, tmp, sizeof(double) * g->nnz_w, hipMemcpyDeviceToHost);
         if (e != hipSuccess) {

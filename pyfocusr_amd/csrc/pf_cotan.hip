@@ -26,8 +26,6 @@
 
 namespace {
 
-inline unsigned nblk(int64_t n) { return (unsigned)((n + PF_BLOCK - 1) / PF_BLOCK); }
-
 constexpr int PF_COTAN_MAX_COLS = 8;
 
 __device__ __forceinline__ bool face_usable(const int32_t* __restrict__ faces, int64_t f, int64_t n, int32_t* i) {
@@ -306,7 +304,7 @@ int pf_graph_build_cotan(pf_mesh* mesh, int32_t mass_kind, pf_graph** out) {
     int32_t *cnt = nullptr, *start = nullptr, *rank = nullptr, *rcol = nullptr, *ucnt = nullptr, *flags = nullptr;
     long long* key = nullptr;
     unsigned long long* hi_bits = nullptr;
-    const unsigned face_blocks = nblk(n_faces);
+    const unsigned face_blocks = pf_blocks(n_faces);
     PF_TRY(job.scratch(&half_cot, 3 * n_faces));
     PF_TRY(job.scratch(&area, n_faces));
     PF_TRY(job.scratch(&partial, face_blocks));
@@ -353,7 +351,7 @@ int pf_graph_build_cotan(pf_mesh* mesh, int32_t mass_kind, pf_graph** out) {
         k_cotan_scatter<<<face_blocks, PF_BLOCK, 0, st>>>(mesh->faces, n_faces, n, half_cot, start, rank, key, val);
         PF_HIP(hipGetLastError());
     }
-    k_cotan_rows<<<nblk(n + 1), PF_BLOCK, 0, st>>>(start, n, key, val, area, rcol, rw, ucnt, g->cot_diag, g->cot_mass, g->cot_sqrtm);
+    k_cotan_rows<<<pf_blocks(n + 1), PF_BLOCK, 0, st>>>(start, n, key, val, area, rcol, rw, ucnt, g->cot_diag, g->cot_mass, g->cot_sqrtm);
     PF_HIP(hipGetLastError());
     PF_TRY(pf_exclusive_scan_i32(st, ucnt, g->rowptr, n + 1));
     // the one read-back before the storage is sized: the flags, the entry count, the area's partial sums
@@ -373,7 +371,7 @@ int pf_graph_build_cotan(pf_mesh* mesh, int32_t mass_kind, pf_graph** out) {
     PF_TRY(job.keep(&g->col, g->nnz_w));
     PF_TRY(job.keep(&g->w, g->nnz_w));
     PF_TRY(job.keep(&g->cot_w, g->nnz_w));
-    k_cotan_compact<<<nblk(n), PF_BLOCK, 0, st>>>(start, g->rowptr, n, rcol, rw, g->cot_diag, g->cot_mass, g->cot_sqrtm, g->col, g->cot_w,
+    k_cotan_compact<<<pf_blocks(n), PF_BLOCK, 0, st>>>(start, g->rowptr, n, rcol, rw, g->cot_diag, g->cot_mass, g->cot_sqrtm, g->col, g->cot_w,
                                                  g->w, g->deg, g->g, g->sg, hi_bits);
     PF_HIP(hipGetLastError());
     PF_TRY(pf_graph_finish_general(g, g->pts));
@@ -415,7 +413,7 @@ int pf_cotan_apply(pf_graph* g, const double* x, int32_t ncols, double* out) {
     double* d_out = s.get<double>(count);
     s.upload(d_x, x, count);
     if (s.ok()) {
-        k_cotan_apply<<<nblk(g->n), PF_BLOCK, 0, s.st>>>(g->rowptr, g->col, g->cot_w, g->cot_mass, g->n, ncols, d_x, d_out);
+        k_cotan_apply<<<pf_blocks(g->n), PF_BLOCK, 0, s.st>>>(g->rowptr, g->col, g->cot_w, g->cot_mass, g->n, ncols, d_x, d_out);
         s.launched();
     }
     s.download(out, d_out, count);

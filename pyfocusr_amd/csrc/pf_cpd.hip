@@ -51,8 +51,6 @@ constexpr int CPD_CHUNK = 128;  // points of the walked set per block (blockIdx.
                                 // waves; with 1024-point chunks the 400 waves left most SIMDs idle behind exp()'s latency
 constexpr int GRAM_COLS = 8;     // columns of V per thread
 
-inline unsigned nblk(int64_t n) { return (unsigned)((n + PF_BLOCK - 1) / PF_BLOCK); }
-
 template <int D>
 __device__ __forceinline__ double sqdist(const double (&a)[D], const double* __restrict__ b) {
     double s = 0.0;
@@ -359,10 +357,10 @@ template <int D>
 int run_estep(pf_cpd* h, double inv2s, double c) {
     hipStream_t st = h->ctx->stream;
     double *Pt1 = h->out, *P1 = h->out + h->N, *PX = h->out + h->N + h->M;
-    k_cpd_colsum<D><<<dim3(nblk(h->N), h->chunks_m), PF_BLOCK, 0, st>>>(h->X, h->N, h->TY, h->M, inv2s, h->part);
-    k_cpd_colfinish<<<nblk(h->N), PF_BLOCK, 0, st>>>(h->part, h->chunks_m, h->N, c, h->den, Pt1);
-    k_cpd_rowsum<D><<<dim3(nblk(h->M), h->chunks_n), PF_BLOCK, 0, st>>>(h->X, h->N, h->TY, h->M, inv2s, h->den, h->part);
-    k_cpd_rowfinish<<<nblk(h->M * (D + 1)), PF_BLOCK, 0, st>>>(h->part, h->chunks_n, h->M, D, P1, PX);
+    k_cpd_colsum<D><<<dim3(pf_blocks(h->N), h->chunks_m), PF_BLOCK, 0, st>>>(h->X, h->N, h->TY, h->M, inv2s, h->part);
+    k_cpd_colfinish<<<pf_blocks(h->N), PF_BLOCK, 0, st>>>(h->part, h->chunks_m, h->N, c, h->den, Pt1);
+    k_cpd_rowsum<D><<<dim3(pf_blocks(h->M), h->chunks_n), PF_BLOCK, 0, st>>>(h->X, h->N, h->TY, h->M, inv2s, h->den, h->part);
+    k_cpd_rowfinish<<<pf_blocks(h->M * (D + 1)), PF_BLOCK, 0, st>>>(h->part, h->chunks_n, h->M, D, P1, PX);
     PF_HIP(hipGetLastError());
     return PF_OK;
 }
@@ -370,7 +368,7 @@ int run_estep(pf_cpd* h, double inv2s, double c) {
 template <int D>
 int run_gram(hipStream_t st, const double* A, int64_t n_a, const double* B, int64_t n_b, double inv2b, const double* V, int32_t C,
              double* out) {
-    k_gram<D><<<dim3(nblk(n_a), (unsigned)((C + GRAM_COLS - 1) / GRAM_COLS)), PF_BLOCK, 0, st>>>(A, n_a, B, n_b, inv2b, V, C, out);
+    k_gram<D><<<dim3(pf_blocks(n_a), (unsigned)((C + GRAM_COLS - 1) / GRAM_COLS)), PF_BLOCK, 0, st>>>(A, n_a, B, n_b, inv2b, V, C, out);
     PF_HIP(hipGetLastError());
     return PF_OK;
 }
@@ -522,7 +520,7 @@ int pf_cpd_weighted_gram(pf_cpd* h, double* H) {
     hipStream_t st = h->ctx->stream;
     const unsigned tiles = (unsigned)((h->K + GRAM_TILE - 1) / GRAM_TILE);
     k_weighted_gram<<<dim3(tiles, tiles, (unsigned)h->chunks_h), GRAM_TILE * GRAM_TILE, 0, st>>>(h->Q, h->out + h->N, h->M, h->K, h->hpart);
-    k_sum_chunks<<<nblk((int64_t)h->K * h->K), PF_BLOCK, 0, st>>>(h->hpart, h->chunks_h, (int64_t)h->K * h->K, h->H);
+    k_sum_chunks<<<pf_blocks((int64_t)h->K * h->K), PF_BLOCK, 0, st>>>(h->hpart, h->chunks_h, (int64_t)h->K * h->K, h->H);
     PF_HIP(hipGetLastError());
     PF_HIP(hipMemcpyAsync(H, h->H, sizeof(double) * (size_t)h->K * h->K, hipMemcpyDeviceToHost, st));
     PF_HIP(hipStreamSynchronize(st));
@@ -554,10 +552,10 @@ int pf_cpd_affine_sums(pf_cpd* h, double* shifts, double* sums) {
     const unsigned bm = (unsigned)((h->M + MOM_ROWS - 1) / MOM_ROWS), bn = (unsigned)((h->N + MOM_ROWS - 1) / MOM_ROWS);
     double *Pt1 = h->out, *P1 = h->out + h->N, *PX = h->out + h->N + h->M;
     k_affine_moments_m<<<bm, PF_BLOCK, 0, st>>>(P1, PX, h->Y, h->shift, h->shift + 16, h->M, D, h->mpart);
-    k_sum_chunks<<<nblk(Lm), PF_BLOCK, 0, st>>>(h->mpart, (int)bm, Lm, h->msum);
+    k_sum_chunks<<<pf_blocks(Lm), PF_BLOCK, 0, st>>>(h->mpart, (int)bm, Lm, h->msum);
     PF_HIP(hipMemcpyAsync(sums, h->msum, sizeof(double) * Lm, hipMemcpyDeviceToHost, st));
     k_moments_n<<<bn, PF_BLOCK, 0, st>>>(Pt1, h->X, h->shift, h->N, D, h->mpart);
-    k_sum_chunks<<<nblk(Ln), PF_BLOCK, 0, st>>>(h->mpart, (int)bn, Ln, h->msum);
+    k_sum_chunks<<<pf_blocks(Ln), PF_BLOCK, 0, st>>>(h->mpart, (int)bn, Ln, h->msum);
     PF_HIP(hipGetLastError());
     PF_HIP(hipMemcpyAsync(sums + Lm, h->msum, sizeof(double) * Ln, hipMemcpyDeviceToHost, st));
     PF_HIP(hipMemcpyAsync(shifts, h->shift, sizeof(double) * 32, hipMemcpyDeviceToHost, st));
@@ -572,7 +570,7 @@ int pf_cpd_apply_affine(pf_cpd* h, const double* B, const double* t) {
     const int D = h->D;
     PF_HIP(hipMemcpyAsync(h->msum, B, sizeof(double) * D * D, hipMemcpyHostToDevice, st));
     PF_HIP(hipMemcpyAsync(h->msum + D * D, t, sizeof(double) * D, hipMemcpyHostToDevice, st));
-    k_apply_affine<<<nblk(h->M * D), PF_BLOCK, 0, st>>>(h->Y, h->msum, h->M, D, h->TY);
+    k_apply_affine<<<pf_blocks(h->M * D), PF_BLOCK, 0, st>>>(h->Y, h->msum, h->M, D, h->TY);
     PF_HIP(hipGetLastError());
     PF_HIP(hipStreamSynchronize(st));  // B and t are the caller's again
     return PF_OK;
@@ -587,7 +585,7 @@ int pf_cpd_deform_sums(pf_cpd* h, double* H, double* R) {
     double *P1 = h->out + h->N, *PX = h->out + h->N + h->M;
     const unsigned tiles = (unsigned)((K + GRAM_TILE - 1) / GRAM_TILE);
     k_weighted_gram<<<dim3(tiles, tiles, (unsigned)h->chunks_h), GRAM_TILE * GRAM_TILE, 0, st>>>(h->Q, P1, h->M, K, h->hpart);
-    k_sum_chunks<<<nblk((int64_t)K * K), PF_BLOCK, 0, st>>>(h->hpart, h->chunks_h, (int64_t)K * K, h->H);
+    k_sum_chunks<<<pf_blocks((int64_t)K * K), PF_BLOCK, 0, st>>>(h->hpart, h->chunks_h, (int64_t)K * K, h->H);
     PF_HIP(hipMemcpyAsync(H, h->H, sizeof(double) * (size_t)K * K, hipMemcpyDeviceToHost, st));
     const unsigned bm = (unsigned)((h->M + MOM_ROWS - 1) / MOM_ROWS);
     const int64_t need = (int64_t)bm * K * D;
@@ -604,7 +602,7 @@ int pf_cpd_deform_sums(pf_cpd* h, double* H, double* R) {
         h->msum_cap = (int64_t)K * D;
     }
     k_deform_rhs<<<bm, PF_BLOCK, 0, st>>>(h->Q, P1, PX, h->Y, h->M, K, D, h->mpart);
-    k_sum_chunks<<<nblk((int64_t)K * D), PF_BLOCK, 0, st>>>(h->mpart, (int)bm, (int64_t)K * D, h->msum);
+    k_sum_chunks<<<pf_blocks((int64_t)K * D), PF_BLOCK, 0, st>>>(h->mpart, (int)bm, (int64_t)K * D, h->msum);
     PF_HIP(hipGetLastError());
     PF_HIP(hipMemcpyAsync(R, h->msum, sizeof(double) * K * D, hipMemcpyDeviceToHost, st));
     PF_HIP(hipStreamSynchronize(st));
@@ -620,9 +618,9 @@ int pf_cpd_apply_deform(pf_cpd* h, const double* C, double* sums) {
     const int D = h->D, K = h->K;
     double *Pt1 = h->out, *P1 = h->out + h->N, *PX = h->out + h->N + h->M;
     PF_HIP(hipMemcpyAsync(h->msum, C, sizeof(double) * K * D, hipMemcpyHostToDevice, st));
-    k_apply_deform<<<nblk(h->M * D), PF_BLOCK, 0, st>>>(h->Y, h->Q, h->msum, h->M, K, D, h->TY);
+    k_apply_deform<<<pf_blocks(h->M * D), PF_BLOCK, 0, st>>>(h->Y, h->Q, h->msum, h->M, K, D, h->TY);
     // variance sums with the new TY and the posterior of this iteration: [Np, yPy, trPXY | sum Pt1, xPx]
-    const unsigned bm = nblk(h->M), bn = (unsigned)((h->N + MOM_ROWS - 1) / MOM_ROWS);
+    const unsigned bm = pf_blocks(h->M), bn = (unsigned)((h->N + MOM_ROWS - 1) / MOM_ROWS);
     k_variance_m<<<bm, PF_BLOCK, 0, st>>>(P1, PX, h->TY, h->M, D, h->mpart);
     k_sum_chunks<<<1, PF_BLOCK, 0, st>>>(h->mpart, (int)bm, 3, h->msum);  // C has been consumed (stream order)
     PF_HIP(hipMemcpyAsync(sums, h->msum, sizeof(double) * 3, hipMemcpyDeviceToHost, st));

@@ -35,8 +35,6 @@ constexpr int ES_SORT_THREADS = 1024;
 constexpr int ES_MAX_SAMPLES = 16384;  // one column is sorted by one block in LDS (128 KB at the limit)
 constexpr int ES_RED_THREADS = 256;
 
-inline unsigned es_blocks(int64_t n) { return (unsigned)((n + PF_BLOCK - 1) / PF_BLOCK); }
-
 // vals[c][r] = fin[rows[r]][col[c]] * sign[c]  (coordinate-major);  raw[r][0..3) = pts[rows[r]]
 __global__ __launch_bounds__(PF_BLOCK) void k_es_gather(const double* __restrict__ fin, int32_t fc, const double* __restrict__ pts,
                                                         const int64_t* __restrict__ rows, int64_t m, int32_t k,
@@ -260,14 +258,14 @@ extern "C" int pf_eigsort_costs(pf_graph* gt, pf_graph* gs, const int64_t* rows_
         double* ls = lt + kt;
         double* lsf = ls + ks;
         double* d_out = lsf + ks;
-        k_es_gather<<<es_blocks(mt * (k + 3)), PF_BLOCK, 0, st>>>(gt->final_vecs, gt->final_count, gt->pts, d_rows_t, mt, k, d_col, d_sign,
+        k_es_gather<<<pf_blocks(mt * (k + 3)), PF_BLOCK, 0, st>>>(gt->final_vecs, gt->final_count, gt->pts, d_rows_t, mt, k, d_col, d_sign,
                                                                   vals_t, raw_t);
-        k_es_gather<<<es_blocks(ms * (k + 3)), PF_BLOCK, 0, st>>>(gs->final_vecs, gs->final_count, gs->pts, d_rows_s, ms, k, d_col + k,
+        k_es_gather<<<pf_blocks(ms * (k + 3)), PF_BLOCK, 0, st>>>(gs->final_vecs, gs->final_count, gs->pts, d_rows_s, ms, k, d_col + k,
                                                                   d_sign + k, vals_s, raw_s);
         k_es_minmax<<<3, ES_RED_THREADS, 0, st>>>(raw_t, mt, lohi);
         k_es_minmax<<<3, ES_RED_THREADS, 0, st>>>(raw_s, ms, lohi + 6);
-        k_es_normalize<<<es_blocks(3 * mt), PF_BLOCK, 0, st>>>(raw_t, lohi, mt, norm_t);
-        k_es_normalize<<<es_blocks(3 * ms), PF_BLOCK, 0, st>>>(raw_s, lohi + 6, ms, norm_s);
+        k_es_normalize<<<pf_blocks(3 * mt), PF_BLOCK, 0, st>>>(raw_t, lohi, mt, norm_t);
+        k_es_normalize<<<pf_blocks(3 * ms), PF_BLOCK, 0, st>>>(raw_s, lohi + 6, ms, norm_s);
         k_es_sort_log<<<(unsigned)(2 * k), ES_SORT_THREADS, sort_lds, st>>>(vals_t, vals_s, mt, ms, k, lt, ls, lsf);
         k_es_w1<<<(unsigned)(k * k), ES_RED_THREADS, 0, st>>>(lt, ls, lsf, mt, ms, k, d_out);
         if (fail(hipGetLastError())) break;

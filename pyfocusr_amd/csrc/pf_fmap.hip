@@ -53,7 +53,6 @@ constexpr int TILE_Z = 32;       // contraction steps per LDS tile
 constexpr int TILE_LD = TILE + 1;
 constexpr int PROJ_ROWS = 512;   // rows per partial sum of the projection
 
-inline unsigned nblk(int64_t n) { return (unsigned)((n + PF_BLOCK - 1) / PF_BLOCK); }
 inline int pad_d(int d) { return (d + WIDE_DC - 1) / WIDE_DC * WIDE_DC; }
 __host__ __device__ inline int64_t imin(int64_t a, int64_t b) { return a < b ? a : b; }
 
@@ -197,7 +196,7 @@ int wide_search(pf_ctx* c, Scratch& s, const double* ref, int64_t n_ref, int32_t
         k_knn_wide<true><<<grid, PF_BLOCK, 0, s.st>>>(ref, n_ref, ref_stride, qt, n_qry, ld, d, d_pad, tile_refs, per, pb, pi, c->wide_count);
     else
         k_knn_wide<false><<<grid, PF_BLOCK, 0, s.st>>>(ref, n_ref, ref_stride, qt, n_qry, ld, d, d_pad, tile_refs, per, pb, pi, nullptr);
-    if (splits > 1) k_wide_merge<<<nblk(n_qry), PF_BLOCK, 0, s.st>>>(pb, pi, n_qry, (int32_t)splits, d2_out, idx_out);
+    if (splits > 1) k_wide_merge<<<pf_blocks(n_qry), PF_BLOCK, 0, s.st>>>(pb, pi, n_qry, (int32_t)splits, d2_out, idx_out);
     s.launched();
     return PF_OK;
 }
@@ -325,7 +324,7 @@ static int fmap_project(pf_fmap* h, int32_t k_s, int32_t k_t) {
         const ProjLoad ld{h->phi_s, h->phi_t, h->mass, h->T, h->K};
         const dim3 grid((unsigned)((k_s + TILE - 1) / TILE), (unsigned)((k_t + TILE - 1) / TILE), (unsigned)blocks);
         k_fmap_tile<ProjLoad, false><<<grid, PF_BLOCK, 0, s.st>>>(ld, k_s, k_t, h->n_s, PROJ_ROWS, part, count, k_t, 1);
-        if (blocks > 1) k_fmap_combine<<<nblk(count), PF_BLOCK, 0, s.st>>>(part, count, blocks, h->C);
+        if (blocks > 1) k_fmap_combine<<<pf_blocks(count), PF_BLOCK, 0, s.st>>>(part, count, blocks, h->C);
         s.launched();
     }
     PF_CHECK(s.ok(), PF_E_HIP, "pf_fmap_project: %s", hipGetErrorString(s.err));
@@ -355,7 +354,7 @@ static int fmap_convert(pf_fmap* h, int32_t k_s, int32_t k_t) {
     }
     if (!wide) {
         PF_TRY(pf_knn1_device(c, h->phi_t, h->n_t, h->K, h->Q, h->n_s, k_t, k_t));
-        k_fmap_take_knn<<<nblk(h->n_s), PF_BLOCK, 0, c->stream>>>(c->knn_idx, c->knn_d2, h->n_s, h->T, h->d2);
+        k_fmap_take_knn<<<pf_blocks(h->n_s), PF_BLOCK, 0, c->stream>>>(c->knn_idx, c->knn_d2, h->n_s, h->T, h->d2);
         PF_HIP(hipGetLastError());
     }
     h->has_T = h->has_d2 = true;
@@ -382,12 +381,12 @@ int pf_knn1_wide(pf_ctx* c, const double* ref, int64_t n_ref, const double* qry,
     s.upload(d_ref, ref, (size_t)(n_ref * d));
     s.upload(d_qry, qry, (size_t)(n_qry * d));
     if (s.ok()) {
-        k_wide_transpose<<<nblk(ld * d_pad), PF_BLOCK, 0, s.st>>>(d_qry, n_qry, d, d, d_pad, ld, d_qt);
+        k_wide_transpose<<<pf_blocks(ld * d_pad), PF_BLOCK, 0, s.st>>>(d_qry, n_qry, d, d, d_pad, ld, d_qt);
         s.launched();
     }
     PF_TRY(wide_search(c, s, d_ref, n_ref, d, d_qt, n_qry, ld, d, d_d2, d_idx));
     if (s.ok()) {
-        k_fmap_widen<<<nblk(n_qry), PF_BLOCK, 0, s.st>>>(d_idx, n_qry, d_idx64);
+        k_fmap_widen<<<pf_blocks(n_qry), PF_BLOCK, 0, s.st>>>(d_idx, n_qry, d_idx64);
         s.launched();
     }
     s.download(idx_out, d_idx64, (size_t)n_qry);
@@ -464,7 +463,7 @@ int pf_fmap_set_p2p(pf_fmap* h, const int64_t* T) {
         s.upload(d_in, T, (size_t)h->n_s);
         s.zero(d_bad, sizeof(int32_t));
         if (s.ok()) {
-            k_fmap_set_map<<<nblk(h->n_s), PF_BLOCK, 0, s.st>>>(d_in, h->n_s, h->n_t, h->T, d_bad);
+            k_fmap_set_map<<<pf_blocks(h->n_s), PF_BLOCK, 0, s.st>>>(d_in, h->n_s, h->n_t, h->T, d_bad);
             s.launched();
         }
         s.download(&bad, d_bad, 1);
@@ -485,7 +484,7 @@ int pf_fmap_get_p2p(pf_fmap* h, int64_t* T_out, double* d2_out) {
     Scratch s(c->stream);
     int64_t* d_out = s.get<int64_t>((size_t)h->n_s);
     if (s.ok()) {
-        k_fmap_widen<<<nblk(h->n_s), PF_BLOCK, 0, s.st>>>(h->T, h->n_s, d_out);
+        k_fmap_widen<<<pf_blocks(h->n_s), PF_BLOCK, 0, s.st>>>(h->T, h->n_s, d_out);
         s.launched();
     }
     s.download(T_out, d_out, (size_t)h->n_s);

@@ -49,6 +49,9 @@ constexpr int PF_STAGE_SLOTS = 8;   // pinned staging slots per ctx ...
 constexpr size_t PF_STAGE_BYTES = 32768;  // ... of this size each
 constexpr int PF_WS_TMPS = 4;      // temporaries behind the workspace slots (Chebyshev rotation)
 
+// blocks of PF_BLOCK threads that cover n items
+inline unsigned pf_blocks(int64_t n) { return (unsigned)((n + PF_BLOCK - 1) / PF_BLOCK); }
+
 // device buffers of the box hierarchy of pf_knn_tree.hip (1-NN for deep coordinates); they grow and stay with the ctx
 struct pf_knn_tree {
     double* pts = nullptr;       // [n_leaf][d][64] leaves, coordinate-major
@@ -374,6 +377,37 @@ struct Scratch {
         if (ok()) err = hipStreamSynchronize(st);
     }
 };
+
+// pf_tri_hierarchy.hip: the chunk / super-chunk structure over the fan triangles of a surface in d coordinates that
+// pf_surface.hip (d = 3) and pf_surface_nd.hip search; pf_tri_hierarchy.h describes it and holds the device helpers
+constexpr int PF_ND_MAX = 16;  // coordinates (the limit of pf_knn_upload and pf_assign)
+struct TriHierarchy {
+    double* tri = nullptr;        // SoA [3 corners][d][n_tri], Morton order
+    int32_t* tri_orig = nullptr;  // [n_tri] sorted position -> fan-triangle index (face * (vpf-2) + fan position)
+    double* box = nullptr;        // [n_chunks][2][d] lo, hi
+    double* sbox = nullptr;       // [n_super][2][d] boxes of 64 consecutive chunks
+    int64_t n_tri = 0, n_chunks = 0, n_super = 0;
+    int32_t d = 0;
+};
+// the box the Morton keys are taken in: the leading nk = min(d, 3) coordinates
+struct KeyBox {
+    double lo[3], ext[3];
+    int32_t nk;
+};
+// The key box of n host points of depth d.  finite_only leaves every non-finite coordinate out (queries); without it
+// only NaN is left out and an infinite coordinate flattens its axis (the vertices of a surface, as ever: the order of the
+// triangles decides the order of the winding sums).
+KeyBox pf_key_box(const double* pts, int64_t n, int32_t d, bool finite_only);
+// The order of n items along the Morton curve in box bb, as a device permutation (sorted position -> item; stable): the
+// centroids of the fan triangles of (d_pts [..][d], d_faces, vpf), or with d_faces == NULL the points d_pts themselves.
+// Keys, values and the sort's temporary are scratch of sc; NULL after a failure.
+const int32_t* pf_surface_morton_order(Scratch& sc, const double* d_pts, int32_t d, const int32_t* d_faces, int32_t vpf, int64_t n,
+                                       const KeyBox& bb);
+// keys -> stable sort -> gather -> chunk boxes -> super boxes, queued on sc's stream; h owns its four buffers from here on,
+// also after a failure (sc.err)
+void pf_tri_hierarchy_build(Scratch& sc, TriHierarchy& h, const double* d_pts, int32_t d, const int32_t* d_faces, int64_t n_faces,
+                            int32_t vpf, const KeyBox& bb);
+void pf_tri_hierarchy_free(hipStream_t st, TriHierarchy& h);
 
 // SELL-64 entry layout inside a slice of `width` entries per row: entries come in PAIRS per lane, so that one
 // lane reads two values with one 16-byte load and two column indices with one 8-byte load (the widest

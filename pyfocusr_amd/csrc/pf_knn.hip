@@ -36,8 +36,6 @@ namespace {
 
 constexpr int KNN_LDS_DOUBLES = 4096;  // LDS tile budget: 32 KiB of coordinates -> 512 points at d = 8, 256 at d = 16
 
-inline unsigned nblk(int64_t n) { return (unsigned)((n + PF_BLOCK - 1) / PF_BLOCK); }
-
 struct KnnGrid {
     int a0, a1;      // grid axes (a1 == a0 when d == 1)
     int r0, r1;      // cells per axis
@@ -826,25 +824,25 @@ int sort_points(pf_ctx* c, const double* pts, int64_t n, int d, int morton, int 
         if (e == hipSuccess) {
             int32_t* start = hist + n_buckets + 1;
             int32_t* cursor = start + n_buckets + 1;
-            k_cell_keys<<<nblk(n), PF_BLOCK, 0, st>>>(pts, n, d, (const KnnGrid*)c->knn_grid, morton, k0, nullptr, hist);
+            k_cell_keys<<<pf_blocks(n), PF_BLOCK, 0, st>>>(pts, n, d, (const KnnGrid*)c->knn_grid, morton, k0, nullptr, hist);
             e = hipGetLastError();
             if (e == hipSuccess && pf_exclusive_scan_i32(st, hist, start, n_buckets + 1) != PF_OK) e = hipErrorUnknown;
             if (e == hipSuccess) {
-                k_bucket_scatter<<<nblk(n), PF_BLOCK, 0, st>>>(k0, n, start, cursor, key_out, orig_out, pts, d, rows_out);
+                k_bucket_scatter<<<pf_blocks(n), PF_BLOCK, 0, st>>>(k0, n, start, cursor, key_out, orig_out, pts, d, rows_out);
                 e = hipGetLastError();
             }
         }
     } else {
         if (e == hipSuccess) e = pf_malloc(st, (void**)&v0, sizeof(int32_t) * n);
         if (e == hipSuccess) {
-            k_cell_keys<<<nblk(n), PF_BLOCK, 0, st>>>(pts, n, d, (const KnnGrid*)c->knn_grid, morton, k0, v0, nullptr);
+            k_cell_keys<<<pf_blocks(n), PF_BLOCK, 0, st>>>(pts, n, d, (const KnnGrid*)c->knn_grid, morton, k0, v0, nullptr);
             e = hipGetLastError();
         }
         if (e == hipSuccess) e = hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, k0, key_out, v0, orig_out, (int)n, 0, key_bits, st);
         if (e == hipSuccess) e = pf_malloc(st, &tmp, bytes);
         if (e == hipSuccess) e = hipcub::DeviceRadixSort::SortPairs(tmp, bytes, k0, key_out, v0, orig_out, (int)n, 0, key_bits, st);
         if (e == hipSuccess) {
-            k_gather_rows<<<nblk(n), PF_BLOCK, 0, st>>>(pts, orig_out, n, d, rows_out);
+            k_gather_rows<<<pf_blocks(n), PF_BLOCK, 0, st>>>(pts, orig_out, n, d, rows_out);
             e = hipGetLastError();
         }
     }
@@ -978,10 +976,10 @@ int pf_knn_run(pf_ctx* c) {
     k_make_grid<<<1, 1, 0, st>>>(c->knn_ext, d, res, (KnnGrid*)c->knn_grid);
     PF_HIP(hipGetLastError());
     PF_TRY(sort_points(c, c->knn_ref, c->knn_nref, d, 0, cell_bits, c->knn_ref_key, c->knn_ref_orig, c->knn_ref_s));
-    k_cell_start<<<nblk(n_cells + 1), PF_BLOCK, 0, st>>>(c->knn_ref_key, c->knn_nref, n_cells, c->knn_cell_start);
+    k_cell_start<<<pf_blocks(n_cells + 1), PF_BLOCK, 0, st>>>(c->knn_ref_key, c->knn_nref, n_cells, c->knn_cell_start);
     PF_HIP(hipGetLastError());
     if (c->knn_k == 1) {
-        k_gather_rows_soa<<<nblk(c->knn_nref), PF_BLOCK, 0, st>>>(c->knn_ref, c->knn_ref_orig, c->knn_nref, d, c->knn_ref_ld, c->knn_ref_soa);
+        k_gather_rows_soa<<<pf_blocks(c->knn_nref), PF_BLOCK, 0, st>>>(c->knn_ref, c->knn_ref_orig, c->knn_nref, d, c->knn_ref_ld, c->knn_ref_soa);
         PF_HIP(hipGetLastError());
     }
     PF_TRY(sort_points(c, c->knn_qry, c->knn_nqry, d, 1, 32, c->knn_qry_key, c->knn_qry_orig, c->knn_qry_s));
@@ -1113,8 +1111,8 @@ static int knn1_blocks_run(pf_ctx* c, const double* ref_block, int64_t n_ref, in
         mr.col[k] = col_ref[k], mr.scale[k] = scale_ref[k];
         mq.col[k] = col_qry[k], mq.scale[k] = scale_qry[k];
     }
-    k_coords_from_final<<<nblk(n_ref * d), PF_BLOCK, 0, st>>>(ref_block, n_ref, ref_stride, d, mr, c->knn_ref);
-    k_coords_from_final<<<nblk(n_qry * d), PF_BLOCK, 0, st>>>(qry_block, n_qry, qry_stride, d, mq, c->knn_qry);
+    k_coords_from_final<<<pf_blocks(n_ref * d), PF_BLOCK, 0, st>>>(ref_block, n_ref, ref_stride, d, mr, c->knn_ref);
+    k_coords_from_final<<<pf_blocks(n_qry * d), PF_BLOCK, 0, st>>>(qry_block, n_qry, qry_stride, d, mq, c->knn_qry);
     PF_HIP(hipGetLastError());
     c->knn_ready = true;
     return pf_knn_run(c);

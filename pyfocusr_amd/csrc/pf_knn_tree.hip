@@ -33,8 +33,6 @@
 
 namespace {
 
-inline unsigned nblk(int64_t n) { return (unsigned)((n + PF_BLOCK - 1) / PF_BLOCK); }
-
 constexpr int TREE_AXES = 5;
 
 struct TreeGrid {
@@ -384,12 +382,12 @@ int pf_knn_tree_run(pf_ctx* c) {
             break;
         }
         k_tree_grid<<<1, 1, 0, st>>>(c->knn_ext, d, (TreeGrid*)T.grid);
-        k_tree_keys<<<nblk(n), PF_BLOCK, 0, st>>>(c->knn_ref, n, d, (const TreeGrid*)T.grid, k0, v0);
+        k_tree_keys<<<pf_blocks(n), PF_BLOCK, 0, st>>>(c->knn_ref, n, d, (const TreeGrid*)T.grid, k0, v0);
         if ((rc = sort_by_key(st, k0, v0, k1, v1, n)) != PF_OK) break;
-        k_tree_leaves<<<nblk(n_leaf * PF_WAVE), PF_BLOCK, 0, st>>>(c->knn_ref, v1, n, d, n_leaf * PF_WAVE, T.pts, T.orig);
-        k_tree_leaf_boxes<<<nblk(n_sup * PF_WAVE * d), PF_BLOCK, 0, st>>>(T.pts, (int32_t)n_leaf, (int32_t)n_sup, d, T.leaf_lo, leaf_hi);
-        k_tree_super_boxes<<<nblk(ns_pad * d), PF_BLOCK, 0, st>>>(T.leaf_lo, leaf_hi, (int32_t)n_sup, (int32_t)ns_pad, d, T.sup_lo, sup_hi);
-        k_tree_keys<<<nblk(nq), PF_BLOCK, 0, st>>>(c->knn_qry, nq, d, (const TreeGrid*)T.grid, k0, v0);
+        k_tree_leaves<<<pf_blocks(n_leaf * PF_WAVE), PF_BLOCK, 0, st>>>(c->knn_ref, v1, n, d, n_leaf * PF_WAVE, T.pts, T.orig);
+        k_tree_leaf_boxes<<<pf_blocks(n_sup * PF_WAVE * d), PF_BLOCK, 0, st>>>(T.pts, (int32_t)n_leaf, (int32_t)n_sup, d, T.leaf_lo, leaf_hi);
+        k_tree_super_boxes<<<pf_blocks(ns_pad * d), PF_BLOCK, 0, st>>>(T.leaf_lo, leaf_hi, (int32_t)n_sup, (int32_t)ns_pad, d, T.sup_lo, sup_hi);
+        k_tree_keys<<<pf_blocks(nq), PF_BLOCK, 0, st>>>(c->knn_qry, nq, d, (const TreeGrid*)T.grid, k0, v0);
         if ((rc = sort_by_key(st, k0, v0, k1, T.qry_order, nq)) != PF_OK) break;
         TreeArgs a{T.pts, T.orig, T.leaf_lo, leaf_hi, T.sup_lo, sup_hi, c->knn_qry, T.qry_order, nq, (int32_t)n_leaf, (int32_t)n_sup,
                    (int32_t)ns_pad, c->knn_idx, c->knn_d2, T.count_visits ? T.counters : nullptr};

@@ -22,8 +22,6 @@
 
 namespace {
 
-inline unsigned nblk(int64_t n) { return (unsigned)((n + PF_BLOCK - 1) / PF_BLOCK); }
-
 // tuning knobs of the operator kernel (tools/tune_spmv.sh builds variants with -D...)
 #ifndef PF_OP_BLOCK
 #define PF_OP_BLOCK 256
@@ -1236,7 +1234,7 @@ int pf_ws_upload(pf_graph* g, int32_t slot, const double* x) {
     hipStream_t st = g->ctx->stream;
     PF_TRY(stage_ensure(g, g->n));
     PF_HIP(hipMemcpyAsync(g->stage, x, sizeof(double) * g->n, hipMemcpyHostToDevice, st));
-    k_permute_in<<<nblk(g->n_pad), PF_BLOCK, 0, st>>>(g->stage, g->perm, g->n_pad, pf_slot(g, slot));
+    k_permute_in<<<pf_blocks(g->n_pad), PF_BLOCK, 0, st>>>(g->stage, g->perm, g->n_pad, pf_slot(g, slot));
     PF_HIP(hipGetLastError());
     PF_HIP(hipStreamSynchronize(st));  // x may be a temporary on the host side
     return PF_OK;
@@ -1248,7 +1246,7 @@ int pf_ws_download(pf_graph* g, int32_t first, int32_t count, double* out) {
     if (count == 0) return PF_OK;
     hipStream_t st = g->ctx->stream;
     PF_TRY(stage_ensure(g, (int64_t)count * g->n));
-    k_permute_out<<<nblk(g->n), PF_BLOCK, 0, st>>>(g->ws, g->n_pad, first, count, g->iperm, g->n, g->stage);
+    k_permute_out<<<pf_blocks(g->n), PF_BLOCK, 0, st>>>(g->ws, g->n_pad, first, count, g->iperm, g->n, g->stage);
     PF_HIP(hipGetLastError());
     PF_HIP(hipMemcpyAsync(out, g->stage, sizeof(double) * (size_t)count * g->n, hipMemcpyDeviceToHost, st));
     PF_HIP(hipStreamSynchronize(st));
@@ -1268,14 +1266,14 @@ int pf_ws_copy(pf_graph* g, int32_t src, int32_t dst, int32_t count) {
 int pf_mask_isolated(pf_graph* g, int32_t slot) {
     PF_TRY(check_slots(g, slot, 1, "pf_mask_isolated"));
     if (g->n_isolated == 0) return PF_OK;
-    k_mask_isolated<<<nblk(g->n), PF_BLOCK, 0, g->ctx->stream>>>(pf_slot(g, slot), g->rowptr, g->perm_m, g->n);
+    k_mask_isolated<<<pf_blocks(g->n), PF_BLOCK, 0, g->ctx->stream>>>(pf_slot(g, slot), g->rowptr, g->perm_m, g->n);
     PF_HIP(hipGetLastError());
     return PF_OK;
 }
 
 int pf_start_vector(pf_graph* g, int32_t slot, uint64_t seed) {
     PF_TRY(check_slots(g, slot, 1, "pf_start_vector"));
-    k_start_vector<<<nblk(g->n_pad), PF_BLOCK, 0, g->ctx->stream>>>(pf_slot(g, slot), g->smooth, g->perm, g->perm_m, g->rowptr, g->n_pad,
+    k_start_vector<<<pf_blocks(g->n_pad), PF_BLOCK, 0, g->ctx->stream>>>(pf_slot(g, slot), g->smooth, g->perm, g->perm_m, g->rowptr, g->n_pad,
                                                                     (unsigned long long)seed, 0.5);
     PF_HIP(hipGetLastError());
     return PF_OK;
@@ -1291,13 +1289,13 @@ int pf_lock_null_vectors(pf_graph* g, int32_t op, int32_t* n_locked) {
     hipStream_t st = g->ctx->stream;
     PF_TRY(pf_reduce_ensure(g, 1));
     for (int32_t c = 0; c < nc; ++c) {
-        k_null_vector<<<nblk(g->n_pad), PF_BLOCK, 0, st>>>(pf_slot(g, c), g->label, g->rowptr, g->deg, g->perm_m, g->n_pad,
+        k_null_vector<<<pf_blocks(g->n_pad), PF_BLOCK, 0, st>>>(pf_slot(g, c), g->label, g->rowptr, g->deg, g->perm_m, g->n_pad,
                                                           g->roots[c], op == PF_OP_SYM && !g->unit_g, g->is_cotan ? g->cot_sqrtm : nullptr);
         PF_HIP(hipGetLastError());
         // normalised with the norm still on the device (the same 1 / sqrt as on the host: the same bits; a component has at
         // least two vertices, so the norm is positive) - no wait at the head of a solve
         PF_TRY(dots_device(g, c, c, 1, g->coef, nullptr, 0));
-        k_scale_rsqrt<<<nblk(g->n_pad), PF_BLOCK, 0, st>>>(pf_slot(g, c), g->n_pad, g->coef);
+        k_scale_rsqrt<<<pf_blocks(g->n_pad), PF_BLOCK, 0, st>>>(pf_slot(g, c), g->n_pad, g->coef);
         PF_HIP(hipGetLastError());
     }
     *n_locked = nc;
@@ -1517,7 +1515,7 @@ static int orth_launch_pass(OrthArgs2& a2, int ng, int64_t n_chunks, int64_t n_p
     } else {
         k_orth_dots<1><<<dim3((unsigned)n_chunks, (unsigned)(count + 1), (unsigned)ng), PF_BLOCK, 0, st>>>(a2);
         PF_HIP(hipGetLastError());
-        k_orth_project<1><<<dim3(nblk(n_pad / 2), 1u, (unsigned)ng), PF_BLOCK, 0, st>>>(a2);
+        k_orth_project<1><<<dim3(pf_blocks(n_pad / 2), 1u, (unsigned)ng), PF_BLOCK, 0, st>>>(a2);
     }
     PF_HIP(hipGetLastError());
     return PF_OK;
@@ -1625,18 +1623,18 @@ int pf_orth_begin(pf_graph* g, int32_t w, int32_t first, int32_t count, int32_t 
     } else if (count == 0) {
         k_dot_partial<<<dim3((unsigned)g->n_chunks, 1u), PF_BLOCK, 0, st>>>(g->ws, g->n_pad, w, w, g->n_chunks, g->partials);
         PF_HIP(hipGetLastError());
-        k_scale_finishing<<<nblk(g->n_pad), PF_BLOCK, 0, st>>>(pf_slot(g, w), g->n_pad, g->partials, g->n_chunks, normalize ? 1 : 0,
+        k_scale_finishing<<<pf_blocks(g->n_pad), PF_BLOCK, 0, st>>>(pf_slot(g, w), g->n_pad, g->partials, g->n_chunks, normalize ? 1 : 0,
                                                               hsum, count, nrm2, g->orth_host);
         PF_HIP(hipGetLastError());
     } else {
         for (int pass = 0; pass < 2; ++pass) {
             PF_TRY(dots_device(g, w, first, count, hpass, hsum, pass));
-            k_multi_axpy<<<nblk(g->n_pad / 2), PF_BLOCK, 0, st>>>(g->ws, g->n_pad, first, count, w, hpass);
+            k_multi_axpy<<<pf_blocks(g->n_pad / 2), PF_BLOCK, 0, st>>>(g->ws, g->n_pad, first, count, w, hpass);
             PF_HIP(hipGetLastError());
         }
         PF_TRY(dots_device(g, w, w, 1, nrm2, nullptr, 0));
         if (normalize) {
-            k_scale_rsqrt<<<nblk(g->n_pad), PF_BLOCK, 0, st>>>(pf_slot(g, w), g->n_pad, nrm2);
+            k_scale_rsqrt<<<pf_blocks(g->n_pad), PF_BLOCK, 0, st>>>(pf_slot(g, w), g->n_pad, nrm2);
             PF_HIP(hipGetLastError());
         }
         PF_HIP(hipMemcpyAsync(g->orth_host, hsum, sizeof(double) * count, hipMemcpyDeviceToHost, st));
@@ -1740,17 +1738,17 @@ int pf_orth_end(pf_graph* g, double* h, double* nrm) {
             PF_HIP(hipGetLastError());
         }
         if (split > 0) {
-            k_axpy_finishing<<<nblk(g->n_pad / 2), PF_BLOCK, 0, st>>>(g->ws, g->n_pad, first, split, w, g->partials, g->n_chunks, hsum, 1);
+            k_axpy_finishing<<<pf_blocks(g->n_pad / 2), PF_BLOCK, 0, st>>>(g->ws, g->n_pad, first, split, w, g->partials, g->n_chunks, hsum, 1);
             PF_HIP(hipGetLastError());
         }
         if (count > split) {
-            k_axpy_finishing<<<nblk(g->n_pad / 2), PF_BLOCK, 0, st>>>(g->ws, g->n_pad, g->orth_first2_now, count - split, w,
+            k_axpy_finishing<<<pf_blocks(g->n_pad / 2), PF_BLOCK, 0, st>>>(g->ws, g->n_pad, g->orth_first2_now, count - split, w,
                                                                       g->partials + (size_t)split * g->n_chunks, g->n_chunks, hsum + split, 1);
             PF_HIP(hipGetLastError());
         }
         k_dot_partial<<<dim3((unsigned)g->n_chunks, 1u), PF_BLOCK, 0, st>>>(g->ws, g->n_pad, w, w, g->n_chunks, g->partials);
         PF_HIP(hipGetLastError());
-        k_scale_finishing<<<nblk(g->n_pad), PF_BLOCK, 0, st>>>(pf_slot(g, w), g->n_pad, g->partials, g->n_chunks, g->orth_normalize,
+        k_scale_finishing<<<pf_blocks(g->n_pad), PF_BLOCK, 0, st>>>(pf_slot(g, w), g->n_pad, g->partials, g->n_chunks, g->orth_normalize,
                                                               hsum, count, nrm2, g->orth_host);
         PF_HIP(hipGetLastError());
         PF_HIP(hipStreamSynchronize(st));
@@ -1807,7 +1805,7 @@ int pf_orth(pf_graph* g, int32_t w, int32_t first, int32_t count, double* h, dou
 
 int pf_scale(pf_graph* g, int32_t slot, double alpha) {
     PF_TRY(check_slots(g, slot, 1, "pf_scale"));
-    k_scale<<<nblk(g->n_pad), PF_BLOCK, 0, g->ctx->stream>>>(pf_slot(g, slot), g->n_pad, alpha);
+    k_scale<<<pf_blocks(g->n_pad), PF_BLOCK, 0, g->ctx->stream>>>(pf_slot(g, slot), g->n_pad, alpha);
     PF_HIP(hipGetLastError());
     return PF_OK;
 }
@@ -1877,7 +1875,7 @@ int pf_combine2(pf_graph* g, int32_t src_first, int32_t m, const double* Y, int3
     hipError_t e = staged ? hipSuccess : hipMemcpyAsync(dY, Y, bytes, hipMemcpyHostToDevice, st);
     for (int32_t c0 = 0; c0 < k && e == hipSuccess; c0 += COMBINE_COLS) {
         const int32_t nc = std::min(COMBINE_COLS, k - c0);
-        k_combine<<<dim3(nblk(g->n_pad), two ? 2u : 1u), PF_BLOCK, 0, st>>>(g->ws, g->n_pad, src_first, m, dY, k, c0, nc, dst_first, src_first2,
+        k_combine<<<dim3(pf_blocks(g->n_pad), two ? 2u : 1u), PF_BLOCK, 0, st>>>(g->ws, g->n_pad, src_first, m, dY, k, c0, nc, dst_first, src_first2,
                                                                           dst_first2);
         e = hipGetLastError();
     }
@@ -2162,7 +2160,7 @@ int pf_finalize_vectors_begin(pf_graph* g, int32_t first, int32_t count, int32_t
     hipError_t e = pf_malloc(st, (void**)&d_out, sizeof(double) * (size_t)g->n * count);
     if (e == hipSuccess) {
         k_vec_params<<<1, PF_WAVE, 0, st>>>(fin, count, minmax, d_params);
-        k_vec_apply<<<nblk(g->n), PF_BLOCK, 0, st>>>(g->ws, g->n_pad, g->n, first, count, g->sg, g->iperm, g->mrank, from_sym, d_params, d_out);
+        k_vec_apply<<<pf_blocks(g->n), PF_BLOCK, 0, st>>>(g->ws, g->n_pad, g->n, first, count, g->sg, g->iperm, g->mrank, from_sym, d_params, d_out);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpyAsync(d_stats, fin, sizeof(VecStats) * count, hipMemcpyDeviceToDevice, st);
@@ -2269,7 +2267,7 @@ int pf_final_remap_begin(pf_graph* g, const int32_t* col, const double* sign, in
     PF_CHECK(ctx->copy_stream && g->final_ready && g->final_done, PF_E_STATE, "pf_final_remap_begin: no download machinery (call after pf_finalize_vectors_begin)");
     double* d_tmp = nullptr;
     PF_HIP(pf_malloc(st, (void**)&d_tmp, sizeof(double) * (size_t)g->n * count));
-    k_final_remap<<<nblk(g->n * count), PF_BLOCK, 0, st>>>(g->final_vecs, g->n, g->final_count, count, m, d_tmp);
+    k_final_remap<<<pf_blocks(g->n * count), PF_BLOCK, 0, st>>>(g->final_vecs, g->n, g->final_count, count, m, d_tmp);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         pf_free(st, d_tmp);
@@ -2304,7 +2302,7 @@ static int rows_to_host(pf_graph* g, const double* src, int32_t width, const int
     hipError_t e = pf_malloc(st, (void**)&d_out, sizeof(double) * (size_t)n_rows * width);
     if (e == hipSuccess) e = hipMemcpyAsync(d_rows, rows, sizeof(int64_t) * n_rows, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) {
-        k_final_rows<<<nblk(n_rows * width), PF_BLOCK, 0, st>>>(src, d_rows, n_rows, width, d_out);
+        k_final_rows<<<pf_blocks(n_rows * width), PF_BLOCK, 0, st>>>(src, d_rows, n_rows, width, d_out);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, sizeof(double) * (size_t)n_rows * width, hipMemcpyDeviceToHost, st);
@@ -2348,7 +2346,7 @@ int pf_mean_filter(pf_graph* g, const double* values, int32_t ncols, int32_t ite
         PF_HIP(pf_malloc(st, (void**)&g->mf_col, sizeof(int32_t) * entries));
         PF_HIP(pf_malloc(st, (void**)&g->mf_val, sizeof(double) * entries));
         // (a cotangent graph filters with its cotangent weights: g->w / g->deg hold the entries of S there)
-        k_fill_mean_filter<<<nblk(g->n_pad), PF_BLOCK, 0, st>>>(g->rowptr, g->col, g->is_cotan ? g->cot_w : g->w, g->is_cotan ? g->cot_diag : g->deg, g->perm_m, g->iperm_m, g->morder, g->n_pad,
+        k_fill_mean_filter<<<pf_blocks(g->n_pad), PF_BLOCK, 0, st>>>(g->rowptr, g->col, g->is_cotan ? g->cot_w : g->w, g->is_cotan ? g->cot_diag : g->deg, g->perm_m, g->iperm_m, g->morder, g->n_pad,
                                                                 g->slice_ptr, g->mf_col, g->mf_val);
         PF_HIP(hipGetLastError());
     }
@@ -2359,14 +2357,14 @@ int pf_mean_filter(pf_graph* g, const double* values, int32_t ncols, int32_t ite
     if (e == hipSuccess) e = pf_malloc(st, (void**)&b, bytes_pad);
     if (e == hipSuccess) e = hipMemcpyAsync(m, values, bytes_mesh, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) {
-        k_rows_in<<<nblk(g->n_pad * ncols), PF_BLOCK, 0, st>>>(m, g->perm, g->n_pad, ncols, a);
+        k_rows_in<<<pf_blocks(g->n_pad * ncols), PF_BLOCK, 0, st>>>(m, g->perm, g->n_pad, ncols, a);
         for (int32_t it = 0; it < iterations; ++it) {
-            if (ncols == 3) k_mean_filter<3><<<nblk(g->n_pad), PF_BLOCK, 0, st>>>(g->slice_ptr, g->mf_col, g->mf_val, g->perm, g->n_pad, ncols, a, b);
-            else if (ncols == 1) k_mean_filter<1><<<nblk(g->n_pad), PF_BLOCK, 0, st>>>(g->slice_ptr, g->mf_col, g->mf_val, g->perm, g->n_pad, ncols, a, b);
-            else k_mean_filter<0><<<nblk(g->n_pad), PF_BLOCK, 0, st>>>(g->slice_ptr, g->mf_col, g->mf_val, g->perm, g->n_pad, ncols, a, b);
+            if (ncols == 3) k_mean_filter<3><<<pf_blocks(g->n_pad), PF_BLOCK, 0, st>>>(g->slice_ptr, g->mf_col, g->mf_val, g->perm, g->n_pad, ncols, a, b);
+            else if (ncols == 1) k_mean_filter<1><<<pf_blocks(g->n_pad), PF_BLOCK, 0, st>>>(g->slice_ptr, g->mf_col, g->mf_val, g->perm, g->n_pad, ncols, a, b);
+            else k_mean_filter<0><<<pf_blocks(g->n_pad), PF_BLOCK, 0, st>>>(g->slice_ptr, g->mf_col, g->mf_val, g->perm, g->n_pad, ncols, a, b);
             std::swap(a, b);
         }
-        k_rows_out<<<nblk(g->n * ncols), PF_BLOCK, 0, st>>>(a, g->iperm, g->n, ncols, m);
+        k_rows_out<<<pf_blocks(g->n * ncols), PF_BLOCK, 0, st>>>(a, g->iperm, g->n, ncols, m);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpyAsync(out, m, bytes_mesh, hipMemcpyDeviceToHost, st);
@@ -2422,7 +2420,7 @@ int pf_axpy(pf_graph* g, int32_t w, int32_t first, int32_t count, const double* 
     std::vector<double> neg(coef, coef + count);
     for (double& v : neg) v = -v;  // k_multi_axpy subtracts
     PF_HIP(hipMemcpyAsync(g->coef, neg.data(), sizeof(double) * count, hipMemcpyHostToDevice, st));
-    k_multi_axpy<<<nblk(g->n_pad / 2), PF_BLOCK, 0, st>>>(g->ws, g->n_pad, first, count, w, g->coef);
+    k_multi_axpy<<<pf_blocks(g->n_pad / 2), PF_BLOCK, 0, st>>>(g->ws, g->n_pad, first, count, w, g->coef);
     PF_HIP(hipGetLastError());
     PF_HIP(hipStreamSynchronize(st));  // neg goes out of scope
     return PF_OK;
@@ -2464,7 +2462,7 @@ int pf_rows_create(pf_graph* g, const int64_t* rows, int64_t n, pf_rows** out) {
         if (e == hipSuccess) e = pf_malloc(st, (void**)&tmp, sizeof(int64_t) * n);
         if (e == hipSuccess) e = hipMemcpyAsync(tmp, rows, sizeof(int64_t) * n, hipMemcpyHostToDevice, st);
         if (e == hipSuccess) {
-            k_rows_to_new<<<nblk(n), PF_BLOCK, 0, st>>>(tmp, g->iperm, n, r->idx);
+            k_rows_to_new<<<pf_blocks(n), PF_BLOCK, 0, st>>>(tmp, g->iperm, n, r->idx);
             e = hipGetLastError();
         }
         if (e == hipSuccess) e = hipStreamSynchronize(st);
@@ -2484,7 +2482,7 @@ int pf_rows_gather(pf_rows* r, int32_t slot, double* out) {
     PF_TRY(check_slots(r->g, slot, 1, "pf_rows_gather"));
     if (r->n == 0) return PF_OK;
     hipStream_t st = r->g->ctx->stream;
-    k_rows_gather<<<nblk(r->n), PF_BLOCK, 0, st>>>(pf_slot(r->g, slot), r->idx, r->n, r->buf);
+    k_rows_gather<<<pf_blocks(r->n), PF_BLOCK, 0, st>>>(pf_slot(r->g, slot), r->idx, r->n, r->buf);
     PF_HIP(hipGetLastError());
     PF_HIP(hipMemcpyAsync(out, r->buf, sizeof(double) * r->n, hipMemcpyDeviceToHost, st));
     PF_HIP(hipStreamSynchronize(st));
@@ -2497,7 +2495,7 @@ int pf_rows_scatter(pf_rows* r, int32_t slot, const double* in) {
     if (r->n == 0) return PF_OK;
     hipStream_t st = r->g->ctx->stream;
     PF_HIP(hipMemcpyAsync(r->buf, in, sizeof(double) * r->n, hipMemcpyHostToDevice, st));
-    k_rows_scatter<<<nblk(r->n), PF_BLOCK, 0, st>>>(pf_slot(r->g, slot), r->idx, r->n, r->buf);
+    k_rows_scatter<<<pf_blocks(r->n), PF_BLOCK, 0, st>>>(pf_slot(r->g, slot), r->idx, r->n, r->buf);
     PF_HIP(hipGetLastError());
     PF_HIP(hipStreamSynchronize(st));  // `in` is the caller's again
     return PF_OK;
@@ -2510,7 +2508,7 @@ int pf_rows_gather_dev(pf_rows* r, int32_t slot, double* dst) {
     PF_CHECK(r && (dst || r->n == 0), PF_E_ARG, "pf_rows_gather_dev: NULL argument");
     PF_TRY(check_slots(r->g, slot, 1, "pf_rows_gather_dev"));
     if (r->n == 0) return PF_OK;
-    k_rows_gather<<<nblk(r->n), PF_BLOCK, 0, r->g->ctx->stream>>>(pf_slot(r->g, slot), r->idx, r->n, dst);
+    k_rows_gather<<<pf_blocks(r->n), PF_BLOCK, 0, r->g->ctx->stream>>>(pf_slot(r->g, slot), r->idx, r->n, dst);
     PF_HIP(hipGetLastError());
     return PF_OK;
 }
@@ -2519,7 +2517,7 @@ int pf_rows_scatter_dev(pf_rows* r, int32_t slot, const double* src) {
     PF_CHECK(r && (src || r->n == 0), PF_E_ARG, "pf_rows_scatter_dev: NULL argument");
     PF_TRY(check_slots(r->g, slot, 1, "pf_rows_scatter_dev"));
     if (r->n == 0) return PF_OK;
-    k_rows_scatter<<<nblk(r->n), PF_BLOCK, 0, r->g->ctx->stream>>>(pf_slot(r->g, slot), r->idx, r->n, src);
+    k_rows_scatter<<<pf_blocks(r->n), PF_BLOCK, 0, r->g->ctx->stream>>>(pf_slot(r->g, slot), r->idx, r->n, src);
     PF_HIP(hipGetLastError());
     return PF_OK;
 }
@@ -2540,7 +2538,7 @@ int pf_rows_gather2_dev(pf_rows* r, int32_t slot_a, int32_t slot_b, double* dst,
     PF_TRY(check_slots(r->g, slot_a, 1, "pf_rows_gather2_dev"));
     if (slot_b >= 0) PF_TRY(check_slots(r->g, slot_b, 1, "pf_rows_gather2_dev"));
     if (r->n == 0) return PF_OK;
-    k_rows_gather2<<<nblk(r->n), PF_BLOCK, 0, r->g->ctx->stream>>>(pf_slot(r->g, slot_a), slot_b >= 0 ? pf_slot(r->g, slot_b) : nullptr,
+    k_rows_gather2<<<pf_blocks(r->n), PF_BLOCK, 0, r->g->ctx->stream>>>(pf_slot(r->g, slot_a), slot_b >= 0 ? pf_slot(r->g, slot_b) : nullptr,
                                                                   r->idx, r->n, stride, dst);
     PF_HIP(hipGetLastError());
     return PF_OK;
@@ -2552,7 +2550,7 @@ int pf_rows_scatter2_dev(pf_rows* r, int32_t slot_a, int32_t slot_b, const doubl
     PF_TRY(check_slots(r->g, slot_a, 1, "pf_rows_scatter2_dev"));
     if (slot_b >= 0) PF_TRY(check_slots(r->g, slot_b, 1, "pf_rows_scatter2_dev"));
     if (r->n == 0) return PF_OK;
-    k_rows_scatter2<<<nblk(r->n), PF_BLOCK, 0, r->g->ctx->stream>>>(pf_slot(r->g, slot_a), slot_b >= 0 ? pf_slot(r->g, slot_b) : nullptr,
+    k_rows_scatter2<<<pf_blocks(r->n), PF_BLOCK, 0, r->g->ctx->stream>>>(pf_slot(r->g, slot_a), slot_b >= 0 ? pf_slot(r->g, slot_b) : nullptr,
                                                                    r->idx, r->off, r->n, stride, src);
     PF_HIP(hipGetLastError());
     return PF_OK;
@@ -2562,7 +2560,7 @@ int pf_rows_fill(pf_rows* r, int32_t slot, double value) {
     PF_CHECK(r != nullptr, PF_E_ARG, "pf_rows_fill: NULL argument");
     PF_TRY(check_slots(r->g, slot, 1, "pf_rows_fill"));
     if (r->n == 0) return PF_OK;
-    k_rows_fill<<<nblk(r->n), PF_BLOCK, 0, r->g->ctx->stream>>>(pf_slot(r->g, slot), r->idx, r->n, value);
+    k_rows_fill<<<pf_blocks(r->n), PF_BLOCK, 0, r->g->ctx->stream>>>(pf_slot(r->g, slot), r->idx, r->n, value);
     PF_HIP(hipGetLastError());
     return PF_OK;
 }

@@ -22,8 +22,6 @@
 
 namespace {
 
-inline unsigned nblk(int64_t n) { return (unsigned)((n + PF_BLOCK - 1) / PF_BLOCK); }
-
 __device__ __forceinline__ unsigned long long enc_f64(double d) {
     const unsigned long long u = (unsigned long long)__double_as_longlong(d);
     return (u >> 63) ? ~u : (u | (1ull << 63));
@@ -367,7 +365,7 @@ int pf_morton_order(pf_graph* g, const double* d_pts, int32_t* d_overflow) {
         if (fail(pfl::memset_words(st, g->order_bbox, 0, 6 * sizeof(unsigned long long)))) break;
         if (n == 0) break;
         pfl::launch<k_bbox>(dim3(256), dim3(PF_BLOCK), 0, st, d_pts, n, g->order_bbox);
-        pfl::launch<k_morton_keys>(dim3(nblk(n)), dim3(PF_BLOCK), 0, st, d_pts, n, g->order_bbox, k0, v0);
+        pfl::launch<k_morton_keys>(dim3(pf_blocks(n)), dim3(PF_BLOCK), 0, st, d_pts, n, g->order_bbox, k0, v0);
         if (fail(hipGetLastError())) break;
         const bool counting = d_overflow != nullptr && n >= 4096;  // (else: the general sort)
         if (counting) {
@@ -378,15 +376,15 @@ int pf_morton_order(pf_graph* g, const double* d_pts, int32_t* d_overflow) {
             if (fail(pf_malloc(st, (void**)&hist, sizeof(int32_t) * (size_t)(2 * nb + 2)))) break;  // [nb + 1] counts, then [nb] cursors
             if (fail(pf_malloc(st, (void**)&bstart, sizeof(int32_t) * (size_t)(nb + 1)))) break;
             if (fail(pfl::memset_words(st, hist, 0, sizeof(int32_t) * (size_t)(2 * nb + 2)))) break;
-            pfl::launch<k_order_hist>(dim3(nblk(n)), dim3(PF_BLOCK), 0, st, k0, n, shift, hist);
+            pfl::launch<k_order_hist>(dim3(pf_blocks(n)), dim3(PF_BLOCK), 0, st, k0, n, shift, hist);
             if (fail(hipGetLastError())) break;
             if (pf_exclusive_scan_i32(st, hist, bstart, nb + 1) != PF_OK) {
                 rc = PF_E_HIP;
                 break;
             }
             // k1 / v0: the bucketed keys and vertices (v0's identity is not needed any more: the index is the thread's own)
-            pfl::launch<k_order_scatter>(dim3(nblk(n)), dim3(PF_BLOCK), 0, st, k0, n, shift, bstart, hist + nb + 1, k1, v0);
-            pfl::launch<k_order_rank>(dim3(nblk(n)), dim3(PF_BLOCK), 0, st, k1, v0, n, shift, bstart, g->morder, d_overflow);
+            pfl::launch<k_order_scatter>(dim3(pf_blocks(n)), dim3(PF_BLOCK), 0, st, k0, n, shift, bstart, hist + nb + 1, k1, v0);
+            pfl::launch<k_order_rank>(dim3(pf_blocks(n)), dim3(PF_BLOCK), 0, st, k1, v0, n, shift, bstart, g->morder, d_overflow);
             if (fail(hipGetLastError())) break;
         } else {
             size_t need = 0;
@@ -395,7 +393,7 @@ int pf_morton_order(pf_graph* g, const double* d_pts, int32_t* d_overflow) {
             if (fail(pf_malloc(st, &tmp, need))) break;
             if (fail(hipcub::DeviceRadixSort::SortPairs(tmp, need, k0, k1, v0, g->morder, in, 0, 30, st))) break;
         }
-        pfl::launch<k_scatter_pos>(dim3(nblk(n)), dim3(PF_BLOCK), 0, st, g->morder, n, g->mrank);
+        pfl::launch<k_scatter_pos>(dim3(pf_blocks(n)), dim3(PF_BLOCK), 0, st, g->morder, n, g->mrank);
         if (fail(hipGetLastError())) break;
     } while (0);
     pf_free(st, k0);
@@ -430,9 +428,9 @@ static int order_in_windows(pf_graph* g, const double* d_pts) {
         if (fail(pf_malloc(st, (void**)&bflag, sizeof(unsigned) * std::max<int64_t>(n, 1)))) break;
         if (fail(pf_malloc(st, (void**)&k0, sizeof(unsigned) * std::max<int64_t>(n, 1)))) break;
         if (fail(pfl::memset_words(ls, bflag, 0, sizeof(unsigned) * std::max<int64_t>(n, 1)))) break;
-        pfl::launch<k_boundary_flags>(dim3(nblk(n)), dim3(PF_BLOCK), 0, ls, nullptr, g->rowptr, g->col, nullptr, n, win_rows, bflag);
-        pfl::launch<k_second_ring_flags>(dim3(nblk(n)), dim3(PF_BLOCK), 0, ls, nullptr, g->rowptr, g->col, nullptr, n, bflag);
-        pfl::launch<k_degree_keys>(dim3(nblk(n)), dim3(PF_BLOCK), 0, ls, nullptr, g->rowptr, bflag, n, win_rows, k0);
+        pfl::launch<k_boundary_flags>(dim3(pf_blocks(n)), dim3(PF_BLOCK), 0, ls, nullptr, g->rowptr, g->col, nullptr, n, win_rows, bflag);
+        pfl::launch<k_second_ring_flags>(dim3(pf_blocks(n)), dim3(PF_BLOCK), 0, ls, nullptr, g->rowptr, g->col, nullptr, n, bflag);
+        pfl::launch<k_degree_keys>(dim3(pf_blocks(n)), dim3(PF_BLOCK), 0, ls, nullptr, g->rowptr, bflag, n, win_rows, k0);
         if (fail(hipGetLastError())) break;
         if (win_rows <= 4096) {
             int32_t n_pow2 = 2;
@@ -443,16 +441,16 @@ static int order_in_windows(pf_graph* g, const double* d_pts) {
             int bits2 = 12;
             for (int64_t w = (n + win_rows - 1) / win_rows; w > 0; w >>= 1) ++bits2;
             if (fail(pf_malloc(st, (void**)&k1, sizeof(unsigned) * n)) || fail(pf_malloc(st, (void**)&v1, sizeof(int32_t) * n))) break;
-            pfl::launch<k_iota>(dim3(nblk(n)), dim3(PF_BLOCK), 0, ls, v1, n);
+            pfl::launch<k_iota>(dim3(pf_blocks(n)), dim3(PF_BLOCK), 0, ls, v1, n);
             size_t need = 0;
             pfl::flush_self();  // (a library sort launches at once: whatever this thread has recorded goes first)
             if (fail(hipcub::DeviceRadixSort::SortPairs(nullptr, need, k0, k1, v1, g->perm_m, (int)n, 0, bits2, ls))) break;
             if (fail(pf_malloc(st, &tmp, need))) break;
             if (fail(hipcub::DeviceRadixSort::SortPairs(tmp, need, k0, k1, v1, g->perm_m, (int)n, 0, bits2, ls))) break;
         }
-        pfl::launch<k_finish_perm>(dim3(nblk(g->n_pad)), dim3(PF_BLOCK), 0, ls, g->perm_m, g->iperm_m, n, g->n_pad);
-        pfl::launch<k_compose_perm>(dim3(nblk(g->n_pad)), dim3(PF_BLOCK), 0, ls, g->perm_m, g->morder, g->n_pad, g->perm, g->iperm);
-        pfl::launch<k_smooth_start>(dim3(nblk(g->n_pad)), dim3(PF_BLOCK), 0, ls, d_pts, g->perm_m, g->order_bbox, g->n_pad, g->smooth);
+        pfl::launch<k_finish_perm>(dim3(pf_blocks(g->n_pad)), dim3(PF_BLOCK), 0, ls, g->perm_m, g->iperm_m, n, g->n_pad);
+        pfl::launch<k_compose_perm>(dim3(pf_blocks(g->n_pad)), dim3(PF_BLOCK), 0, ls, g->perm_m, g->morder, g->n_pad, g->perm, g->iperm);
+        pfl::launch<k_smooth_start>(dim3(pf_blocks(g->n_pad)), dim3(PF_BLOCK), 0, ls, d_pts, g->perm_m, g->order_bbox, g->n_pad, g->smooth);
         if (fail(hipGetLastError())) break;
     } while (0);
     pf_free(st, bflag);
@@ -492,10 +490,10 @@ int pf_compute_order(pf_graph* g, const double* d_pts, int32_t* d_overflow) {
         if (fail(pfl::memset_words(st, bbox, 0, 6 * sizeof(unsigned long long) + sizeof(unsigned) * (size_t)n))) break;
         if (d_pts) {
             pfl::launch<k_bbox>(dim3(256), dim3(PF_BLOCK), 0, st, d_pts, n, bbox);
-            pfl::launch<k_morton_keys>(dim3(nblk(n)), dim3(PF_BLOCK), 0, st, d_pts, n, bbox, k0, v0);
+            pfl::launch<k_morton_keys>(dim3(pf_blocks(n)), dim3(PF_BLOCK), 0, st, d_pts, n, bbox, k0, v0);
         } else {  // no geometry (graph handed in as a matrix): keep the caller's order, only sort degrees in windows
             if (fail(pfl::memset_words(st, k0, 0, sizeof(unsigned) * n))) break;
-            pfl::launch<k_iota>(dim3(nblk(n)), dim3(PF_BLOCK), 0, st, v0, n);
+            pfl::launch<k_iota>(dim3(pf_blocks(n)), dim3(PF_BLOCK), 0, st, v0, n);
         }
         if (fail(hipGetLastError())) break;
         const bool counting = d_pts != nullptr && d_overflow != nullptr && n >= 4096;  // (else: the general sort)
@@ -524,13 +522,13 @@ int pf_compute_order(pf_graph* g, const double* d_pts, int32_t* d_overflow) {
             }
             bool bad = fail(pfl::memset_words(st, hist, 0, sizeof(int32_t) * (size_t)(2 * nb + 2)));
             if (!bad) {
-                pfl::launch<k_order_hist>(dim3(nblk(n)), dim3(PF_BLOCK), 0, st, k0, n, shift, hist);
+                pfl::launch<k_order_hist>(dim3(pf_blocks(n)), dim3(PF_BLOCK), 0, st, k0, n, shift, hist);
                 bad = fail(hipGetLastError()) || pf_exclusive_scan_i32(st, hist, bstart, nb + 1) != PF_OK;
             }
             if (!bad) {
                 // k1 / v0: the bucketed keys and vertices (v0's identity is not needed any more: the index is the thread's own)
-                pfl::launch<k_order_scatter>(dim3(nblk(n)), dim3(PF_BLOCK), 0, st, k0, n, shift, bstart, hist + nb + 1, k1, v0);
-                pfl::launch<k_order_rank>(dim3(nblk(n)), dim3(PF_BLOCK), 0, st, k1, v0, n, shift, bstart, v1, d_overflow);
+                pfl::launch<k_order_scatter>(dim3(pf_blocks(n)), dim3(PF_BLOCK), 0, st, k0, n, shift, bstart, hist + nb + 1, k1, v0);
+                pfl::launch<k_order_rank>(dim3(pf_blocks(n)), dim3(PF_BLOCK), 0, st, k1, v0, n, shift, bstart, v1, d_overflow);
                 bad = fail(hipGetLastError());
             }
             pf_free(st, hist);
@@ -543,10 +541,10 @@ int pf_compute_order(pf_graph* g, const double* d_pts, int32_t* d_overflow) {
             break;
         }
         // v0 <- Morton position of every vertex (scratch until the second sort); the boundary flags in their zeroed block
-        pfl::launch<k_scatter_pos>(dim3(nblk(n)), dim3(PF_BLOCK), 0, st, v1, n, v0);
-        pfl::launch<k_boundary_flags>(dim3(nblk(n)), dim3(PF_BLOCK), 0, st, v1, g->rowptr, g->col, v0, n, win_rows, bflag);
-        pfl::launch<k_second_ring_flags>(dim3(nblk(n)), dim3(PF_BLOCK), 0, st, v1, g->rowptr, g->col, v0, n, bflag);
-        pfl::launch<k_degree_keys>(dim3(nblk(n)), dim3(PF_BLOCK), 0, st, v1, g->rowptr, bflag, n, win_rows, k0);
+        pfl::launch<k_scatter_pos>(dim3(pf_blocks(n)), dim3(PF_BLOCK), 0, st, v1, n, v0);
+        pfl::launch<k_boundary_flags>(dim3(pf_blocks(n)), dim3(PF_BLOCK), 0, st, v1, g->rowptr, g->col, v0, n, win_rows, bflag);
+        pfl::launch<k_second_ring_flags>(dim3(pf_blocks(n)), dim3(PF_BLOCK), 0, st, v1, g->rowptr, g->col, v0, n, bflag);
+        pfl::launch<k_degree_keys>(dim3(pf_blocks(n)), dim3(PF_BLOCK), 0, st, v1, g->rowptr, bflag, n, win_rows, k0);
         if (fail(hipGetLastError())) break;
         if (win_rows <= 4096) {
             int32_t n_pow2 = 2;
@@ -557,8 +555,8 @@ int pf_compute_order(pf_graph* g, const double* d_pts, int32_t* d_overflow) {
             need = tmp_bytes;
             if (fail(hipcub::DeviceRadixSort::SortPairs(tmp, need, k0, k1, v1, g->perm, in, 0, bits2, st))) break;
         }
-        pfl::launch<k_finish_perm>(dim3(nblk(g->n_pad)), dim3(PF_BLOCK), 0, st, g->perm, g->iperm, n, g->n_pad);
-        if (d_pts) pfl::launch<k_smooth_start>(dim3(nblk(g->n_pad)), dim3(PF_BLOCK), 0, st, d_pts, g->perm, bbox, g->n_pad, g->smooth);
+        pfl::launch<k_finish_perm>(dim3(pf_blocks(g->n_pad)), dim3(PF_BLOCK), 0, st, g->perm, g->iperm, n, g->n_pad);
+        if (d_pts) pfl::launch<k_smooth_start>(dim3(pf_blocks(g->n_pad)), dim3(PF_BLOCK), 0, st, d_pts, g->perm, bbox, g->n_pad, g->smooth);
         else if (fail(pfl::memset_words(st, g->smooth, 0, sizeof(double) * g->n_pad))) break;  // start vector = noise only
         if (fail(hipGetLastError())) break;
     } while (0);

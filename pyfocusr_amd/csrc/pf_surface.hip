@@ -1,9 +1,8 @@
 // Queries against a triangulated surface: closest points, many-query distances, signed distances, winding numbers,
-// ray casting.  All five work on one structure, built once per surface (pf_surface_create): the triangles (polygons
-// fan-triangulated) are sorted along a Morton curve of their centroids (hipCUB radix sort) and cut into chunks of 64
-// consecutive ones, each with its bounding box; coordinates are stored SoA so that a wave reads 64 consecutive triangles
-// coalesced.  64 consecutive chunks form a super-chunk with its own box (two levels are enough: 500k triangles = 7813
-// chunks = 123 super-chunks, two per lane).  In the order of the file:
+// ray casting.  All five work on one structure, built once per surface (pf_surface_create): the triangle hierarchy of
+// pf_tri_hierarchy.h at d = 3 - fan triangles along a Morton curve, chunks of 64 with their boxes, super-chunks of 64
+// chunks - which that header describes together with the argument why pruning by its boxes changes no result.  In the
+// order of the file:
 //
 // Closest point (pf_surface_closest, k_closest) - the search inside the ICP pre-alignment (reference:
 // vtk_functions.py:12-29 -> vtkIterativeClosestPointTransform, whose inner loop asks a vtkCellLocator for the closest
@@ -35,23 +34,19 @@
 // of the signed structure as ray directions.
 //
 // Each section's own comment has the details.  The entry points (extern "C", at the end) keep their device scratch in a
-// Scratch, and sort along the Morton curve through morton_order.
+// Scratch, and sort along the Morton curve through pf_surface_morton_order.
 #include <hipcub/hipcub.hpp>
 
 #include <cmath>
 #include <limits>
 
-#include "pf_internal.h"
+#include "pf_tri_hierarchy.h"
 
 struct pf_surface {
     pf_ctx* ctx = nullptr;
-    int64_t n_points = 0, n_faces = 0, n_tri = 0, n_chunks = 0;
+    int64_t n_points = 0, n_faces = 0;
     int32_t vpf = 0;
-    double* tri = nullptr;       // SoA [9][n_tri]: ax ay az bx by bz cx cy cz, Morton order
-    int32_t* tri_orig = nullptr; // [n_tri] sorted position -> triangle index (face * (vpf-2) + fan position)
-    double* box = nullptr;       // [n_chunks][6] lo xyz, hi xyz
-    double* sbox = nullptr;      // [n_super][6] boxes of 64 consecutive chunks
-    int64_t n_super = 0;
+    TriHierarchy h;              // d = 3: tri SoA [9][n_tri] ax ay az bx by bz cx cy cz, boxes [6] lo xyz, hi xyz
     // signed distances (pf_surface_prepare_signed; NULL until then)
     double* pts = nullptr;       // [n_points][3]
     int32_t* faces = nullptr;    // [n_faces][vpf]
@@ -64,151 +59,6 @@ struct pf_surface {
 };
 
 namespace {
-
-constexpr int PF_TRI_CHUNK = 64;  // one triangle per lane and scan
-
-inline unsigned nblk(int64_t n) { return (unsigned)((n + PF_BLOCK - 1) / PF_BLOCK); }
-
-struct Box3 {
-    double lo[3], ext[3];
-};
-
-__device__ __forceinline__ unsigned spread10(unsigned v) {
-    v &= 0x3ffu;
-    v = (v | (v << 16)) & 0x030000ffu;
-    v = (v | (v << 8)) & 0x0300f00fu;
-    v = (v | (v << 4)) & 0x030c30c3u;
-    v = (v | (v << 2)) & 0x09249249u;
-    return v;
-}
-
-// 30-bit Morton key of a point in box bb: 10 bits per axis, x lowest; outside the box clamps, NaN and a flat axis give 0.
-// The point comes as coord(axis), so that an axis is loaded where it is used (registers: as few as the loops this replaces).
-template <class Coord>
-__device__ __forceinline__ unsigned morton_key(Coord coord, const Box3& bb) {
-    unsigned code = 0;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        double u = bb.ext[a] > 0.0 ? (coord(a) - bb.lo[a]) / bb.ext[a] : 0.0;
-        u = u < 0.0 ? 0.0 : (u > 1.0 ? 1.0 : u);
-        if (!(u == u)) u = 0.0;  // the clamp lets NaN through
-        code |= spread10((unsigned)(u * 1023.0)) << a;
-    }
-    return code;
-}
-
-__device__ __forceinline__ double wave_min(double v) {
-    for (int off = PF_WAVE / 2; off > 0; off >>= 1) v = fmin(v, __shfl_xor(v, off, PF_WAVE));
-    return v;
-}
-
-__device__ __forceinline__ double wave_max(double v) {
-    for (int off = PF_WAVE / 2; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off, PF_WAVE));
-    return v;
-}
-
-__device__ __forceinline__ double wave_sum(double v) {  // fixed butterfly: the same order on every run
-    for (int off = PF_WAVE / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, PF_WAVE);
-    return v;
-}
-
-// the least d of the wave and its index, in every lane; lowest index on ties
-__device__ __forceinline__ void wave_argmin(double& d, int64_t& i) {
-    for (int off = PF_WAVE / 2; off > 0; off >>= 1) {
-        const double od = __shfl_xor(d, off, PF_WAVE);
-        const int64_t oi = __shfl_xor(i, off, PF_WAVE);
-        if (od < d || (od == d && oi < i)) d = od, i = oi;
-    }
-}
-
-__device__ __forceinline__ void tri_vertices(const int32_t* __restrict__ faces, int32_t vpf, int64_t t, int32_t v[3]) {
-    const int32_t per = vpf - 2;
-    const int64_t f = t / per;
-    const int32_t j = (int32_t)(t - f * per);
-    v[0] = faces[f * vpf];
-    v[1] = faces[f * vpf + j + 1];
-    v[2] = faces[f * vpf + j + 2];
-}
-
-__global__ __launch_bounds__(PF_BLOCK) void k_tri_keys(const double* __restrict__ pts, const int32_t* __restrict__ faces,
-                                                       int32_t vpf, int64_t n_tri, Box3 bb, unsigned* __restrict__ keys,
-                                                       int32_t* __restrict__ vals) {
-    const int64_t t = (int64_t)blockIdx.x * PF_BLOCK + threadIdx.x;
-    if (t >= n_tri) return;
-    int32_t v[3];
-    tri_vertices(faces, vpf, t, v);
-    const auto centroid = [&](int a) { return (pts[3 * (int64_t)v[0] + a] + pts[3 * (int64_t)v[1] + a] + pts[3 * (int64_t)v[2] + a]) / 3.0; };
-    keys[t] = morton_key(centroid, bb);
-    vals[t] = (int32_t)t;
-}
-
-__global__ __launch_bounds__(PF_BLOCK) void k_qry_keys(const double* __restrict__ qry, int64_t n, Box3 bb,
-                                                       unsigned* __restrict__ keys, int32_t* __restrict__ vals) {
-    const int64_t i = (int64_t)blockIdx.x * PF_BLOCK + threadIdx.x;
-    if (i >= n) return;
-    keys[i] = morton_key([&](int a) { return qry[3 * i + a]; }, bb);
-    vals[i] = (int32_t)i;
-}
-
-__global__ __launch_bounds__(PF_BLOCK) void k_tri_gather(const double* __restrict__ pts, const int32_t* __restrict__ faces,
-                                                         int32_t vpf, int64_t n_tri, const int32_t* __restrict__ order,
-                                                         double* __restrict__ tri, int32_t* __restrict__ tri_orig) {
-    const int64_t s = (int64_t)blockIdx.x * PF_BLOCK + threadIdx.x;
-    if (s >= n_tri) return;
-    const int32_t t = order[s];
-    int32_t v[3];
-    tri_vertices(faces, vpf, t, v);
-#pragma unroll
-    for (int c = 0; c < 3; ++c)
-#pragma unroll
-        for (int a = 0; a < 3; ++a) tri[(int64_t)(3 * c + a) * n_tri + s] = pts[3 * (int64_t)v[c] + a];
-    tri_orig[s] = t;
-}
-
-// one wave per chunk
-__global__ __launch_bounds__(PF_WAVE) void k_chunk_boxes(const double* __restrict__ tri, int64_t n_tri, double* __restrict__ box) {
-    const int64_t c = blockIdx.x;
-    const int lane = threadIdx.x;
-    const double inf = std::numeric_limits<double>::infinity();
-    double lo[3] = {inf, inf, inf}, hi[3] = {-inf, -inf, -inf};
-    for (int64_t s = c * PF_TRI_CHUNK + lane; s < (c + 1) * PF_TRI_CHUNK && s < n_tri; s += PF_WAVE) {
-#pragma unroll
-        for (int k = 0; k < 9; ++k) {
-            const double x = tri[(int64_t)k * n_tri + s];
-            lo[k % 3] = fmin(lo[k % 3], x);  // fmin/fmax ignore NaN: a NaN vertex never widens a box
-            hi[k % 3] = fmax(hi[k % 3], x);
-        }
-    }
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        for (int off = PF_WAVE / 2; off > 0; off >>= 1) {
-            lo[a] = fmin(lo[a], __shfl_xor(lo[a], off, PF_WAVE));
-            hi[a] = fmax(hi[a], __shfl_xor(hi[a], off, PF_WAVE));
-        }
-        if (lane == 0) {
-            box[6 * c + a] = lo[a];
-            box[6 * c + 3 + a] = hi[a];
-        }
-    }
-}
-
-// one wave per super-chunk: union of its 64 chunk boxes
-__global__ __launch_bounds__(PF_WAVE) void k_super_boxes(const double* __restrict__ box, int64_t n_chunks, double* __restrict__ sbox) {
-    const int64_t c = (int64_t)blockIdx.x * PF_WAVE + threadIdx.x;
-    const double inf = std::numeric_limits<double>::infinity();
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        double lo = c < n_chunks ? box[6 * c + a] : inf, hi = c < n_chunks ? box[6 * c + 3 + a] : -inf;
-        for (int off = PF_WAVE / 2; off > 0; off >>= 1) {
-            lo = fmin(lo, __shfl_xor(lo, off, PF_WAVE));
-            hi = fmax(hi, __shfl_xor(hi, off, PF_WAVE));
-        }
-        if (threadIdx.x == 0) {
-            sbox[6 * (int64_t)blockIdx.x + a] = lo;
-            sbox[6 * (int64_t)blockIdx.x + 3 + a] = hi;
-        }
-    }
-}
 
 __device__ __forceinline__ double dot3(const double a[3], const double b[3]) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
 
@@ -270,49 +120,11 @@ __device__ __forceinline__ int closest_on_triangle(const double p[3], const doub
     return PF_REGION_FACE;
 }
 
-__device__ __forceinline__ double box_dist2(const double p[3], const double* __restrict__ bx) {
-    double s = 0.0;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const double below = bx[a] - p[a], above = p[a] - bx[3 + a];
-        const double d = fmax(fmax(below, above), 0.0);
-        s += d * d;
-    }
-    return s;
-}
-
-// The chunk nearest to p, for a whole wave: the nearest super-chunk, then the nearest chunk inside it, by box distance
-// (one box per lane), lowest index on ties; n_chunks when there is none (a NaN point, no finite box).  Every lane
-// returns the same.
-__device__ __forceinline__ int64_t nearest_chunk(const double p[3], const double* __restrict__ box, const double* __restrict__ sbox,
-                                                 int64_t n_chunks, int64_t n_super, int lane) {
-    const double inf = std::numeric_limits<double>::infinity();
-    double nd = inf;
-    int64_t ns = n_super;  // sentinel: none
-    for (int64_t s = lane; s < n_super; s += PF_WAVE) {
-        const double d = box_dist2(p, sbox + 6 * s);
-        if (d < nd) nd = d, ns = s;
-    }
-    wave_argmin(nd, ns);
-    int64_t c0 = n_chunks;
-    if (ns < n_super) {
-        c0 = ns * PF_WAVE + lane;
-        nd = c0 < n_chunks ? box_dist2(p, box + 6 * c0) : inf;
-        if (!(nd < inf)) c0 = n_chunks;
-        wave_argmin(nd, c0);
-    }
-    return c0;
-}
-
 struct Best {
     double d2;
     int32_t orig;  // triangle index (tie-break: lowest)
     double pt[3];
 };
-
-__device__ __forceinline__ bool better(double d2, int32_t orig, double bd2, int32_t borig) {
-    return d2 < bd2 || (d2 == bd2 && orig < borig);
-}
 
 // One triangle per lane from each of NB chunks: all loads are issued before the arithmetic, so the NB memory
 // latencies overlap (the kernel is latency-bound: few waves, dependent loads).  Slots past the end of the mesh or
@@ -345,8 +157,6 @@ __device__ __forceinline__ void scan_chunks(const double* __restrict__ tri, cons
     }
 }
 
-constexpr double PF_BOX_SLACK = 1.0 + 1e-9;  // the box test must never reject on a rounding error
-
 // one block of PF_CLOSEST_WAVES waves per query point (8 waves measured slower: 0.29 vs 0.25 ms per 1000 landmarks)
 constexpr int PF_CLOSEST_WAVES = 4;
 
@@ -366,7 +176,7 @@ __global__ __launch_bounds__(PF_CLOSEST_WAVES* PF_WAVE) void k_closest(const dou
     const double inf = std::numeric_limits<double>::infinity();
 
     // (1) the chunk nearest to the query - every wave, same result
-    const int64_t c0 = nearest_chunk(p, box, sbox, n_chunks, n_super, lane);
+    const int64_t c0 = nearest_chunk<3>([&](const double* __restrict__ bx) { return box_dist2<3>(p, bx); }, box, sbox, n_chunks, n_super, lane);
     Best best;
     best.d2 = inf, best.orig = 0x7fffffff, best.pt[0] = best.pt[1] = best.pt[2] = 0.0;
     if (c0 < n_chunks) {
@@ -381,13 +191,13 @@ __global__ __launch_bounds__(PF_CLOSEST_WAVES* PF_WAVE) void k_closest(const dou
     const unsigned long long mine = 0x1111111111111111ull << wave;
     for (int64_t sb = 0; sb < n_super; sb += PF_WAVE) {
         const int64_t s = sb + lane;
-        unsigned long long smask = __ballot(s < n_super && box_dist2(p, sbox + 6 * s) <= bound * PF_BOX_SLACK);
+        unsigned long long smask = __ballot(s < n_super && box_dist2<3>(p, sbox + 6 * s) <= bound * PF_BOX_SLACK);
         while (smask) {
             const int64_t ss = sb + __ffsll((long long)smask) - 1;
             smask &= smask - 1;
-            if (box_dist2(p, sbox + 6 * ss) > bound * PF_BOX_SLACK) continue;  // the bound has shrunk since the ballot
+            if (box_dist2<3>(p, sbox + 6 * ss) > bound * PF_BOX_SLACK) continue;  // the bound has shrunk since the ballot
             const int64_t c = ss * PF_WAVE + lane;
-            unsigned long long mask = __ballot(c < n_chunks && c != c0 && box_dist2(p, box + 6 * c) <= bound * PF_BOX_SLACK) & mine;
+            unsigned long long mask = __ballot(c < n_chunks && c != c0 && box_dist2<3>(p, box + 6 * c) <= bound * PF_BOX_SLACK) & mine;
             while (mask) {
                 int64_t batch[NB];
 #pragma unroll
@@ -402,7 +212,7 @@ __global__ __launch_bounds__(PF_CLOSEST_WAVES* PF_WAVE) void k_closest(const dou
                 scan_chunks<NB>(tri, tri_orig, n_tri, batch, lane, p, best);
                 bound = wave_min(best.d2);
                 // drop the remaining chunks the tighter bound excludes (one box per lane, as in the ballot above)
-                mask &= __ballot(c < n_chunks && box_dist2(p, box + 6 * c) <= bound * PF_BOX_SLACK);
+                mask &= __ballot(c < n_chunks && box_dist2<3>(p, box + 6 * c) <= bound * PF_BOX_SLACK);
             }
         }
     }
@@ -441,21 +251,8 @@ __global__ __launch_bounds__(PF_CLOSEST_WAVES* PF_WAVE) void k_closest(const dou
 // fewer than 16 x 4096 queries), one packet per wave.  The wave walks the same super-chunk / chunk hierarchy as
 // k_closest, but a chunk is loaded ONCE per packet: its 64 triangles are staged in LDS (one coalesced load per lane)
 // and the lanes of each query share them out, reading from LDS by broadcast.  A triangle whose own box is farther than
-// the query's bound is skipped before the exact test.  Exactness: every exact test is the one of k_closest (same
-// closest_on_triangle / better, same PF_BOX_SLACK); the packet's box test (box of the queries against a chunk box) is
-// never larger than the point-box test of any query inside it, and a triangle's box never farther than the triangle,
-// so nothing the per-query search would test is skipped, and the lanes of a query merge with the same tie rule.
-
-// squared distance between two boxes (0 if they overlap); never larger than box_dist2 of any point of the first box
-__device__ __forceinline__ double boxbox_dist2(const double lo[3], const double hi[3], const double* __restrict__ bx) {
-    double s = 0.0;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const double d = fmax(fmax(bx[a] - hi[a], lo[a] - bx[3 + a]), 0.0);
-        s += d * d;
-    }
-    return s;
-}
+// the query's bound is skipped before the exact test.  Every exact test is the one of k_closest (same
+// closest_on_triangle / better, same PF_BOX_SLACK); pf_tri_hierarchy.h has the argument for the packet's tests.
 
 // the larger distance wins; lowest query index on ties; idx < 0 = none
 __device__ __forceinline__ bool later_max(double d2, int64_t idx, double bd2, int64_t bidx) {
@@ -539,28 +336,29 @@ __global__ __launch_bounds__(PF_WAVE) void k_distance(const double* __restrict__
             qbest = query_min(best.d2);
         };
         // does any query's own point-box test (k_closest's) keep chunk c?
-        auto wanted = [&](int64_t c) { return __ballot(ok && box_dist2(p, box + 6 * c) <= qbest * PF_BOX_SLACK) != 0; };
+        auto wanted = [&](int64_t c) { return __ballot(ok && box_dist2<3>(p, box + 6 * c) <= qbest * PF_BOX_SLACK) != 0; };
 
         // (1) seed: the chunk nearest to the packet's centre
         const double ctr[3] = {0.5 * (lo[0] + hi[0]), 0.5 * (lo[1] + hi[1]), 0.5 * (lo[2] + hi[2])};
-        const int64_t c0 = nearest_chunk(ctr, box, sbox, n_chunks, n_super, lane);
+        const int64_t c0 = nearest_chunk<3>([&](const double* __restrict__ bx) { return box_dist2<3>(ctr, bx); }, box, sbox, n_chunks,
+                                            n_super, lane);
         if (c0 < n_chunks) scan(c0);
         double bound = wave_max(ok ? qbest : -inf);  // the packet's bound: its worst query
 
         // (2) every chunk whose box is within the bound of the packet's box and of some query
         for (int64_t sb = 0; sb < n_super; sb += PF_WAVE) {
             const int64_t s = sb + lane;
-            unsigned long long smask = __ballot(s < n_super && boxbox_dist2(lo, hi, sbox + 6 * s) <= bound * PF_BOX_SLACK);
+            unsigned long long smask = __ballot(s < n_super && boxbox_dist2<3>(lo, hi, sbox + 6 * s) <= bound * PF_BOX_SLACK);
             while (smask) {
                 const int64_t ss = sb + __ffsll((long long)smask) - 1;
                 smask &= smask - 1;
-                if (boxbox_dist2(lo, hi, sbox + 6 * ss) > bound * PF_BOX_SLACK) continue;  // the bound has shrunk
+                if (boxbox_dist2<3>(lo, hi, sbox + 6 * ss) > bound * PF_BOX_SLACK) continue;  // the bound has shrunk
                 const int64_t c = ss * PF_WAVE + lane;
-                unsigned long long mask = __ballot(c < n_chunks && c != c0 && boxbox_dist2(lo, hi, box + 6 * c) <= bound * PF_BOX_SLACK);
+                unsigned long long mask = __ballot(c < n_chunks && c != c0 && boxbox_dist2<3>(lo, hi, box + 6 * c) <= bound * PF_BOX_SLACK);
                 while (mask) {
                     const int64_t cc = ss * PF_WAVE + __ffsll((long long)mask) - 1;
                     mask &= mask - 1;
-                    if (boxbox_dist2(lo, hi, box + 6 * cc) > bound * PF_BOX_SLACK || !wanted(cc)) continue;
+                    if (boxbox_dist2<3>(lo, hi, box + 6 * cc) > bound * PF_BOX_SLACK || !wanted(cc)) continue;
                     scan(cc);
                     bound = wave_max(ok ? qbest : -inf);
                 }
@@ -651,7 +449,7 @@ __global__ __launch_bounds__(PF_BLOCK) void k_tri_normals(const double* __restri
     const int64_t t = (int64_t)blockIdx.x * PF_BLOCK + threadIdx.x;
     if (t >= n_tri) return;
     int32_t v[3];
-    tri_vertices(faces, vpf, t, v);
+    tri_corners(faces, vpf, t, v);
     double x[3][3];
 #pragma unroll
     for (int c = 0; c < 3; ++c)
@@ -707,7 +505,7 @@ __global__ __launch_bounds__(PF_BLOCK) void k_edge_normals(const unsigned long l
         for (int k = 0; k < 2; ++k) {
             const int32_t h = hedge[i + k];
             int32_t v[3];
-            tri_vertices(faces, vpf, h / 3, v);
+            tri_corners(faces, vpf, h / 3, v);
             const int j = h % 3;
             fwd[k] = v[j] < v[j == 2 ? 0 : j + 1];
         }
@@ -764,7 +562,7 @@ __global__ __launch_bounds__(PF_BLOCK) void k_signed(const double* __restrict__ 
     for (int32_t j = 0; j < per; ++j) {
         const int32_t t = f * per + j;
         int32_t v[3];
-        tri_vertices(faces, vpf, t, v);
+        tri_corners(faces, vpf, t, v);
         const double a[3] = {pts[3 * (int64_t)v[0]], pts[3 * (int64_t)v[0] + 1], pts[3 * (int64_t)v[0] + 2]};
         const double b[3] = {pts[3 * (int64_t)v[1]], pts[3 * (int64_t)v[1] + 1], pts[3 * (int64_t)v[1] + 2]};
         const double c[3] = {pts[3 * (int64_t)v[2]], pts[3 * (int64_t)v[2] + 1], pts[3 * (int64_t)v[2] + 2]};
@@ -1255,64 +1053,25 @@ __global__ __launch_bounds__(PF_WAVE) void k_raycast(const double* __restrict__ 
 
 // ---- host side ---------------------------------------------------------------------------------------------------------
 
-// The box the Morton keys of n points are taken in.  finite_only leaves every non-finite coordinate out (queries);
-// without it only NaN is left out and an infinite coordinate flattens its axis (the vertices of a surface, as ever: the
-// order of the triangles decides the order of the winding sums).
-Box3 point_box(const double* pts, int64_t n, bool finite_only) {
-    Box3 bb;
-    for (int a = 0; a < 3; ++a) {
-        double lo = std::numeric_limits<double>::infinity(), hi = -lo;
-        for (int64_t i = 0; i < n; ++i) {
-            const double x = pts[3 * i + a];
-            if (finite_only && !std::isfinite(x)) continue;
-            if (x < lo) lo = x;
-            if (x > hi) hi = x;
-        }
-        bb.lo[a] = lo;
-        bb.ext[a] = hi - lo;
-        if (!(bb.ext[a] > 0.0) || !std::isfinite(bb.ext[a])) bb.ext[a] = 0.0;
-    }
-    return bb;
-}
-
-// The order of n items along the Morton curve in box bb, as a device permutation (sorted position -> item; stable): the
-// centroids of the fan triangles of (d_pts, d_faces, vpf), or with d_faces == NULL the points d_pts themselves.  Keys,
-// values and the sort's temporary are scratch of sc; NULL after a failure.
-const int32_t* morton_order(Scratch& sc, const double* d_pts, const int32_t* d_faces, int32_t vpf, int64_t n, const Box3& bb) {
-    unsigned *k0 = sc.get<unsigned>(n), *k1 = sc.get<unsigned>(n);
-    int32_t *v0 = sc.get<int32_t>(n), *v1 = sc.get<int32_t>(n);
-    size_t need = 0;
-    if (sc.ok()) {
-        if (d_faces)
-            k_tri_keys<<<nblk(n), PF_BLOCK, 0, sc.st>>>(d_pts, d_faces, vpf, n, bb, k0, v0);
-        else
-            k_qry_keys<<<nblk(n), PF_BLOCK, 0, sc.st>>>(d_pts, n, bb, k0, v0);
-        sc.launched();
-    }
-    if (sc.ok()) sc.note(hipcub::DeviceRadixSort::SortPairs(nullptr, need, k0, k1, v0, v1, (int)n, 0, 30, sc.st));
-    void* tmp = sc.get<char>(need);
-    if (sc.ok()) sc.note(hipcub::DeviceRadixSort::SortPairs(tmp, need, k0, k1, v0, v1, (int)n, 0, 30, sc.st));
-    return sc.ok() ? v1 : nullptr;
-}
-
 // the search of pf_surface_distance on queries already in HBM (d_q): Morton sort, k_distance, the fixed-order
 // statistics.  d_d2 / d_face may be NULL; d_stats [PF_DIST_STATS] may not.
-hipError_t distance_search(pf_surface* s, hipStream_t st, const double* d_q, int64_t n_qry, const Box3& bb, double* d_d2,
+hipError_t distance_search(pf_surface* s, hipStream_t st, const double* d_q, int64_t n_qry, const KeyBox& bb, double* d_d2,
                            int32_t* d_face, double* d_stats) {
     // 16 queries per wave once that gives >= 4096 waves (4 per SIMD), else 4 (measured: profiles/surface_distance.md)
     const bool big = n_qry >= (int64_t)16 * 4096;
     const int64_t n_pack = big ? (n_qry + 15) / 16 : (n_qry + 3) / 4;
+    const TriHierarchy& h = s->h;
     // no synchronise here: the scratch goes back at enqueue time, and the cache hands these blocks out again only to work
     // queued behind the kernels below
     Scratch sc(st);
-    const int32_t* perm = morton_order(sc, d_q, nullptr, 0, n_qry, bb);
+    const int32_t* perm = pf_surface_morton_order(sc, d_q, 3, nullptr, 0, n_qry, bb);
     double* d_part = sc.get<double>(PF_DIST_STATS * n_pack);
     if (sc.ok()) {
         if (big)
-            k_distance<16><<<(unsigned)n_pack, PF_WAVE, 0, st>>>(s->tri, s->tri_orig, s->box, s->sbox, s->n_tri, s->n_chunks, s->n_super,
+            k_distance<16><<<(unsigned)n_pack, PF_WAVE, 0, st>>>(h.tri, h.tri_orig, h.box, h.sbox, h.n_tri, h.n_chunks, h.n_super,
                                                                  d_q, perm, n_qry, s->vpf - 2, d_d2, d_face, d_part);
         else
-            k_distance<4><<<(unsigned)n_pack, PF_WAVE, 0, st>>>(s->tri, s->tri_orig, s->box, s->sbox, s->n_tri, s->n_chunks, s->n_super,
+            k_distance<4><<<(unsigned)n_pack, PF_WAVE, 0, st>>>(h.tri, h.tri_orig, h.box, h.sbox, h.n_tri, h.n_chunks, h.n_super,
                                                                 d_q, perm, n_qry, s->vpf - 2, d_d2, d_face, d_part);
         k_distance_stats<<<1, PF_BLOCK, 0, st>>>(d_part, n_pack, d_stats);
         sc.launched();
@@ -1336,10 +1095,7 @@ void pf_surface_free(pf_surface* s) {
     hipSetDevice(s->ctx->device);
     hipStreamSynchronize(s->ctx->stream);
     hipStream_t st = s->ctx->stream;
-    pf_free(st, s->tri);
-    pf_free(st, s->tri_orig);
-    pf_free(st, s->box);
-    pf_free(st, s->sbox);
+    pf_tri_hierarchy_free(st, s->h);
     pf_free(st, s->pts);
     pf_free(st, s->faces);
     pf_free(st, s->tnrm);
@@ -1359,34 +1115,20 @@ int pf_surface_create(pf_ctx* ctx, const double* pts, int64_t n, const int32_t* 
     for (int64_t i = 0; i < n_faces * vpf; ++i)
         PF_CHECK(faces[i] >= 0 && faces[i] < n, PF_E_ARG, "pf_surface_create: face %lld references vertex %d of %lld",
                  (long long)(i / vpf), faces[i], (long long)n);
-    const Box3 bb = point_box(pts, n, false);
+    const KeyBox bb = pf_key_box(pts, n, 3, false);
     PF_HIP(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     pf_surface* s = new pf_surface();
     s->ctx = ctx;
     s->n_points = n, s->n_faces = n_faces, s->vpf = vpf;
-    s->n_tri = n_faces * (vpf - 2);
-    s->n_chunks = (s->n_tri + PF_TRI_CHUNK - 1) / PF_TRI_CHUNK;
-    s->n_super = (s->n_chunks + PF_WAVE - 1) / PF_WAVE;
-    const int64_t T = s->n_tri;
     hipError_t e;
     {
         Scratch sc(st);
         double* d_pts = sc.get<double>(3 * n);
         int32_t* d_faces = sc.get<int32_t>(n_faces * vpf);
-        s->tri = sc.keep<double>(9 * T);
-        s->tri_orig = sc.keep<int32_t>(T);
-        s->box = sc.keep<double>(6 * s->n_chunks);
-        s->sbox = sc.keep<double>(6 * s->n_super);
         sc.upload(d_pts, pts, 3 * n);
         sc.upload(d_faces, faces, n_faces * vpf);
-        const int32_t* order = morton_order(sc, d_pts, d_faces, vpf, T, bb);
-        if (sc.ok()) {
-            k_tri_gather<<<nblk(T), PF_BLOCK, 0, st>>>(d_pts, d_faces, vpf, T, order, s->tri, s->tri_orig);
-            k_chunk_boxes<<<(unsigned)s->n_chunks, PF_WAVE, 0, st>>>(s->tri, T, s->box);
-            k_super_boxes<<<(unsigned)s->n_super, PF_WAVE, 0, st>>>(s->box, s->n_chunks, s->sbox);
-            sc.launched();
-        }
+        pf_tri_hierarchy_build(sc, s->h, d_pts, 3, d_faces, n_faces, vpf, bb);
         sc.sync();  // the host arrays may go away after the call
         e = sc.err;
     }
@@ -1405,13 +1147,14 @@ int pf_surface_closest(pf_surface* s, const double* qry, int64_t n_qry, double* 
     if (n_qry == 0) return PF_OK;
     PF_HIP(hipSetDevice(s->ctx->device));
     hipStream_t st = s->ctx->stream;
+    const TriHierarchy& h = s->h;
     Scratch sc(st);
     double *d_q = sc.get<double>(3 * n_qry), *d_pt = sc.get<double>(3 * n_qry), *d_d2 = sc.get<double>(n_qry);
     int32_t* d_face = sc.get<int32_t>(n_qry);
     sc.upload(d_q, qry, 3 * n_qry);
     if (sc.ok()) {
-        k_closest<<<(unsigned)n_qry, PF_CLOSEST_WAVES * PF_WAVE, 0, st>>>(s->tri, s->tri_orig, s->box, s->sbox, s->n_tri, s->n_chunks,
-                                                                          s->n_super, d_q, n_qry, s->vpf - 2, d_pt, d_face, d_d2);
+        k_closest<<<(unsigned)n_qry, PF_CLOSEST_WAVES * PF_WAVE, 0, st>>>(h.tri, h.tri_orig, h.box, h.sbox, h.n_tri, h.n_chunks,
+                                                                          h.n_super, d_q, n_qry, s->vpf - 2, d_pt, d_face, d_d2);
         sc.launched();
     }
     sc.download(out_pts, d_pt, 3 * n_qry);
@@ -1428,7 +1171,7 @@ int pf_surface_closest(pf_surface* s, const double* qry, int64_t n_qry, double* 
 int pf_surface_distance(pf_surface* s, const double* qry, int64_t n_qry, double* out_d2, int32_t* out_face, double* stats) {
     PF_CHECK(s && qry, PF_E_ARG, "pf_surface_distance: NULL argument");
     PF_CHECK(n_qry >= 1 && n_qry < ((int64_t)1 << 31), PF_E_ARG, "pf_surface_distance: n_qry = %lld out of range", (long long)n_qry);
-    const Box3 bb = point_box(qry, n_qry, true);
+    const KeyBox bb = pf_key_box(qry, n_qry, 3, true);
     PF_HIP(hipSetDevice(s->ctx->device));
     hipStream_t st = s->ctx->stream;
     Scratch sc(st);
@@ -1451,7 +1194,7 @@ int pf_surface_distance(pf_surface* s, const double* qry, int64_t n_qry, double*
 
 int pf_surface_prepare_signed(pf_surface* s, const double* points, const int32_t* faces, int64_t* topology) {
     PF_CHECK(s && points && faces, PF_E_ARG, "pf_surface_prepare_signed: NULL argument");
-    const int64_t n = s->n_points, T = s->n_tri, H = 3 * T, nf = s->n_faces * s->vpf;
+    const int64_t n = s->n_points, T = s->h.n_tri, H = 3 * T, nf = s->n_faces * s->vpf;
     PF_CHECK(H < ((int64_t)1 << 31), PF_E_ARG, "pf_surface_prepare_signed: %lld half-edges out of range", (long long)H);
     for (int64_t i = 0; i < nf; ++i)  // the same arrays as at pf_surface_create, or at least indices within them
         PF_CHECK(faces[i] >= 0 && faces[i] < n, PF_E_ARG, "pf_surface_prepare_signed: face %lld references vertex %d of %lld",
@@ -1479,7 +1222,7 @@ int pf_surface_prepare_signed(pf_surface* s, const double* points, const int32_t
         sc.upload(s->faces, faces, nf);
         sc.zero(cnt, sizeof(unsigned long long) * 4);
         if (sc.ok()) {
-            k_tri_normals<<<nblk(T), PF_BLOCK, 0, st>>>(s->pts, s->faces, s->vpf, T, nb, s->tnrm, tang, ek0, vk0, h0);
+            k_tri_normals<<<pf_blocks(T), PF_BLOCK, 0, st>>>(s->pts, s->faces, s->vpf, T, nb, s->tnrm, tang, ek0, vk0, h0);
             sc.launched();
         }
         // both sorts are stable and start from half-edge order: equal keys stay in triangle order.  They share the value
@@ -1490,12 +1233,12 @@ int pf_surface_prepare_signed(pf_surface* s, const double* points, const int32_t
         void* tmp = sc.get<char>(need_e > need_v ? need_e : need_v);
         if (sc.ok()) sc.note(hipcub::DeviceRadixSort::SortPairs(tmp, need_e, ek0, ek1, h0, h1, (int)H, 0, 2 * nb, st));
         if (sc.ok()) {
-            k_edge_normals<<<nblk(H), PF_BLOCK, 0, st>>>(ek1, h1, H, s->faces, s->vpf, s->tnrm, s->enrm, cnt);
+            k_edge_normals<<<pf_blocks(H), PF_BLOCK, 0, st>>>(ek1, h1, H, s->faces, s->vpf, s->tnrm, s->enrm, cnt);
             sc.launched();
         }
         if (sc.ok()) sc.note(hipcub::DeviceRadixSort::SortPairs(tmp, need_v, vk0, vk1, h0, h1, (int)H, 0, nb, st));
         if (sc.ok()) {
-            k_vertex_normals<<<nblk(n), PF_BLOCK, 0, st>>>(vk1, h1, H, n, s->tnrm, tang, s->vnrm);
+            k_vertex_normals<<<pf_blocks(n), PF_BLOCK, 0, st>>>(vk1, h1, H, n, s->tnrm, tang, s->vnrm);
             sc.launched();
         }
         sc.download(counts, cnt, 4);
@@ -1518,7 +1261,7 @@ int pf_surface_signed_distance(pf_surface* s, const double* qry, int64_t n_qry, 
     PF_CHECK(n_qry >= 1 && n_qry < ((int64_t)1 << 31), PF_E_ARG, "pf_surface_signed_distance: n_qry = %lld out of range",
              (long long)n_qry);
     PF_CHECK(s->vnrm, PF_E_ARG, "pf_surface_signed_distance: pf_surface_prepare_signed has not been called");
-    const Box3 bb = point_box(qry, n_qry, true);
+    const KeyBox bb = pf_key_box(qry, n_qry, 3, true);
     PF_HIP(hipSetDevice(s->ctx->device));
     hipStream_t st = s->ctx->stream;
     Scratch sc(st);
@@ -1532,7 +1275,7 @@ int pf_surface_signed_distance(pf_surface* s, const double* qry, int64_t n_qry, 
     sc.zero(d_amb, sizeof(unsigned long long));
     if (sc.ok()) sc.note(distance_search(s, st, d_q, n_qry, bb, d_d2, d_face, d_stats));
     if (sc.ok()) {
-        k_signed<<<nblk(n_qry), PF_BLOCK, 0, st>>>(s->pts, s->faces, s->vpf, s->tnrm, s->enrm, s->vnrm, d_q, n_qry, d_d2, d_face,
+        k_signed<<<pf_blocks(n_qry), PF_BLOCK, 0, st>>>(s->pts, s->faces, s->vpf, s->tnrm, s->enrm, s->vnrm, d_q, n_qry, d_d2, d_face,
                                                    d_sd, d_feat, d_amb);
         sc.launched();
     }
@@ -1554,11 +1297,12 @@ int pf_surface_prepare_winding(pf_surface* s) {
     if (s->dip) return PF_OK;  // built once: the triangles never change
     PF_HIP(hipSetDevice(s->ctx->device));
     hipStream_t st = s->ctx->stream;
+    const TriHierarchy& h = s->h;
     Scratch sc(st);  // no scratch, two blocks to keep: published only when everything worked
-    double *dip = sc.keep<double>(PF_DIPOLE * s->n_chunks), *sdip = sc.keep<double>(PF_DIPOLE * s->n_super);
+    double *dip = sc.keep<double>(PF_DIPOLE * h.n_chunks), *sdip = sc.keep<double>(PF_DIPOLE * h.n_super);
     if (sc.ok()) {
-        k_chunk_dipoles<<<(unsigned)s->n_chunks, PF_WAVE, 0, st>>>(s->tri, s->n_tri, s->box, dip);
-        k_super_dipoles<<<(unsigned)s->n_super, PF_WAVE, 0, st>>>(s->tri, s->n_tri, dip, s->n_chunks, s->sbox, sdip);
+        k_chunk_dipoles<<<(unsigned)h.n_chunks, PF_WAVE, 0, st>>>(h.tri, h.n_tri, h.box, dip);
+        k_super_dipoles<<<(unsigned)h.n_super, PF_WAVE, 0, st>>>(h.tri, h.n_tri, dip, h.n_chunks, h.sbox, sdip);
         sc.launched();
     }
     sc.sync();
@@ -1579,22 +1323,23 @@ int pf_surface_winding(pf_surface* s, const double* qry, int64_t n_qry, double b
     // beta <= 0: exact.  A query may lie inside a cluster's ball for beta <= 1, where the dropped part has no bound.
     PF_CHECK(beta <= 0.0 || (beta > 1.0 && std::isfinite(beta)), PF_E_ARG,
              "pf_surface_winding: beta = %g: use beta <= 0 (exact) or a finite beta > 1", beta);
-    const Box3 bb = point_box(qry, n_qry, true);
+    const KeyBox bb = pf_key_box(qry, n_qry, 3, true);
     PF_HIP(hipSetDevice(s->ctx->device));
     hipStream_t st = s->ctx->stream;
+    const TriHierarchy& h = s->h;
     const int64_t n_pack = (n_qry + PF_WIND_PACKET - 1) / PF_WIND_PACKET;
     Scratch sc(st);
     double* d_q = sc.get<double>(3 * n_qry);
     double* d_w = out_w ? sc.get<double>(n_qry) : nullptr;
     double* d_b = out_bound ? sc.get<double>(n_qry) : nullptr;
     sc.upload(d_q, qry, 3 * n_qry);
-    const int32_t* perm = morton_order(sc, d_q, nullptr, 0, n_qry, bb);
+    const int32_t* perm = pf_surface_morton_order(sc, d_q, 3, nullptr, 0, n_qry, bb);
     if (sc.ok()) {
         if (beta > 0.0)
-            k_winding<true><<<(unsigned)n_pack, PF_WAVE, 0, st>>>(s->tri, s->n_tri, s->n_chunks, s->n_super, s->dip, s->sdip, d_q, perm,
+            k_winding<true><<<(unsigned)n_pack, PF_WAVE, 0, st>>>(h.tri, h.n_tri, h.n_chunks, h.n_super, s->dip, s->sdip, d_q, perm,
                                                                   n_qry, beta, d_w, d_b);
         else
-            k_winding<false><<<(unsigned)n_pack, PF_WAVE, 0, st>>>(s->tri, s->n_tri, s->n_chunks, s->n_super, s->dip, s->sdip, d_q, perm,
+            k_winding<false><<<(unsigned)n_pack, PF_WAVE, 0, st>>>(h.tri, h.n_tri, h.n_chunks, h.n_super, s->dip, s->sdip, d_q, perm,
                                                                    n_qry, 0.0, d_w, d_b);
         sc.launched();
     }
@@ -1614,9 +1359,10 @@ int pf_surface_raycast(pf_surface* s, const double* origins, const double* dirs,
     PF_CHECK(n_rays >= 1 && n_rays < ((int64_t)1 << 31), PF_E_ARG, "pf_surface_raycast: n_rays = %lld out of range", (long long)n_rays);
     PF_CHECK(t_min <= t_max, PF_E_ARG, "pf_surface_raycast: the interval [%g, %g] is empty or NaN", t_min, t_max);
     PF_CHECK(facing >= -1 && facing <= 1, PF_E_ARG, "pf_surface_raycast: facing = %d: use -1 (back), 0 (any) or 1 (front)", facing);
-    const Box3 bb = point_box(origins, n_rays, true);
+    const KeyBox bb = pf_key_box(origins, n_rays, 3, true);
     PF_HIP(hipSetDevice(s->ctx->device));
     hipStream_t st = s->ctx->stream;
+    const TriHierarchy& h = s->h;
     // the packet rule of distance_search: 16 rays per wave once that gives >= 4096 waves, else 4
     const bool big = n_rays >= (int64_t)16 * 4096;
     const unsigned n_pack = (unsigned)(big ? (n_rays + 15) / 16 : (n_rays + 3) / 4);
@@ -1628,10 +1374,10 @@ int pf_surface_raycast(pf_surface* s, const double* origins, const double* dirs,
     int32_t* d_cnt = out_count ? sc.get<int32_t>(n_rays) : nullptr;
     sc.upload(d_o, origins, 3 * n_rays);
     sc.upload(d_d, dirs, 3 * n_rays);
-    const int32_t* perm = morton_order(sc, d_o, nullptr, 0, n_rays, bb);
+    const int32_t* perm = pf_surface_morton_order(sc, d_o, 3, nullptr, 0, n_rays, bb);
     if (sc.ok()) {
         const auto launch = [&](auto kernel) {
-            kernel<<<n_pack, PF_WAVE, 0, st>>>(s->tri, s->tri_orig, s->box, s->sbox, s->n_tri, s->n_chunks, s->n_super, d_o, d_d, perm,
+            kernel<<<n_pack, PF_WAVE, 0, st>>>(h.tri, h.tri_orig, h.box, h.sbox, h.n_tri, h.n_chunks, h.n_super, d_o, d_d, perm,
                                                n_rays, t_min, t_max, facing, s->vpf - 2, d_t, d_face, d_uv, d_cnt);
         };
         if (big)

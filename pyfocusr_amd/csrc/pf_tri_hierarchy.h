@@ -1,0 +1,135 @@
+// The triangle hierarchy under every surface query (pf_surface.hip: d = 3; pf_surface_nd.hip: 1 <= d <= 16), and the
+// device helpers its searches share.  Built in pf_tri_hierarchy.hip (pf_tri_hierarchy_build, declared in pf_internal.h).
+//
+// Structure.  The fan triangles (0, j+1, j+2) of the faces are sorted along a Morton curve of their centroids (hipCUB
+// radix sort, stable) and cut into chunks of PF_TRI_CHUNK = 64 consecutive ones, each with its d-dimensional bounding
+// box lo[d] | hi[d]; 64 consecutive chunks form a super-chunk with its own box (two levels are enough: 500k triangles =
+// 7813 chunks = 123 super-chunks, two per lane).  Coordinates are stored SoA, [corner][coordinate][triangle], so a wave
+// reads 64 consecutive triangles coalesced.  The Morton key takes 10 bits from each of the LEADING min(d, 3) coordinates
+// only.  Spectral coordinates come ordered by eigenvalue: the first ones are the smoothest eigenfunctions and carry the
+// coarse geometry of the surface, the later ones oscillate and would scatter neighbours along the curve; three
+// coordinates at 10 bits fill the 30-bit key, and a 2-manifold needs no more to be cut into compact pieces.  The key only
+// decides which triangles share a chunk, that is how tight the boxes are; the boxes span all d coordinates and no
+// closest-point result depends on the order (the winding sums do: their order is the triangles').
+//
+// Exactness of the closest-point searches (k_closest, k_distance, k_closest_nd).  The result of a query is the minimum
+// over ALL fan triangles of the exact point-triangle squared distance, lowest fan-triangle index on exact ties (better),
+// NaN distances never winning - what a brute-force scan computes.  A search skips (a) a super-chunk or chunk whose box is
+// farther from the query, or from the box of a packet of queries, than the bound (the query's best distance so far; for
+// a packet the largest of its queries') times PF_BOX_SLACK, (b) in a packet, a chunk farther than that from every single
+// query, (c) a triangle whose own box is farther than the query's best x slack.  A box contains its triangles, a
+// packet's box its queries, so in exact arithmetic each of these distances is a lower bound of the point-triangle
+// distance, and what is skipped is strictly farther than a triangle already found: it can neither win nor tie.  In
+// floating point a box distance (d subtractions, squares and additions) carries a relative error of about
+// (d + 2) eps <= 4e-15 at d = 16, and so does the exact test's d2; the slack of 1e-9 covers both a million times over,
+// and a triangle within the slack is tested, not skipped.  Bounds only shrink, so a test made against an older, larger
+// bound errs on the side of testing.  Lanes and waves of a query merge with the same (d2, index) rule.
+//
+// Depth.  Every helper that loops over coordinates is templated on D: the depth it is compiled for (loops unrolled, d
+// ignored), or D = 0 for any d <= PF_ND_MAX, unrolled to 16 behind the uniform guard k < d so that no array is indexed at
+// run time.
+#pragma once
+#include <limits>
+
+#include "pf_internal.h"
+
+constexpr int PF_TRI_CHUNK = 64;             // triangles per chunk: one per lane and scan
+constexpr double PF_BOX_SLACK = 1.0 + 1e-9;  // a box test must never reject on a rounding error (see above)
+
+#define PF_FOR_DEPTH(k) _Pragma("unroll") for (int k = 0; k < (D ? D : PF_ND_MAX); ++k) if (D != 0 || k < d)
+
+__device__ __forceinline__ double wave_min(double v) {
+    for (int off = PF_WAVE / 2; off > 0; off >>= 1) v = fmin(v, __shfl_xor(v, off, PF_WAVE));
+    return v;
+}
+
+__device__ __forceinline__ double wave_max(double v) {
+    for (int off = PF_WAVE / 2; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off, PF_WAVE));
+    return v;
+}
+
+__device__ __forceinline__ double wave_sum(double v) {  // fixed butterfly: the same order on every run
+    for (int off = PF_WAVE / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, PF_WAVE);
+    return v;
+}
+
+// the least d of the wave and its index, in every lane; lowest index on ties
+__device__ __forceinline__ void wave_argmin(double& d, int64_t& i) {
+    for (int off = PF_WAVE / 2; off > 0; off >>= 1) {
+        const double od = __shfl_xor(d, off, PF_WAVE);
+        const int64_t oi = __shfl_xor(i, off, PF_WAVE);
+        if (od < d || (od == d && oi < i)) d = od, i = oi;
+    }
+}
+
+// the tie rule of every search; a NaN d2 compares false: never wins
+__device__ __forceinline__ bool better(double d2, int32_t orig, double bd2, int32_t borig) {
+    return d2 < bd2 || (d2 == bd2 && orig < borig);
+}
+
+// corners of fan triangle t = face * (vpf - 2) + fan position
+__device__ __forceinline__ void tri_corners(const int32_t* __restrict__ faces, int32_t vpf, int64_t t, int32_t v[3]) {
+    const int32_t per = vpf - 2;
+    const int64_t f = t / per;
+    const int32_t j = (int32_t)(t - f * per);
+    v[0] = faces[f * vpf];
+    v[1] = faces[f * vpf + j + 1];
+    v[2] = faces[f * vpf + j + 2];
+}
+
+// Squared distances to a box bx = lo[d] | hi[d], 0 inside: of a point; of a box lo | hi (never larger than the former
+// for any point of that box); of that box's centre
+template <int D>
+__device__ __forceinline__ double box_dist2(const double* p, const double* __restrict__ bx, int d = D) {
+    double s = 0.0;
+    PF_FOR_DEPTH(k) {
+        const double e = fmax(fmax(bx[k] - p[k], p[k] - bx[d + k]), 0.0);
+        s += e * e;
+    }
+    return s;
+}
+
+template <int D>
+__device__ __forceinline__ double boxbox_dist2(const double* lo, const double* hi, const double* __restrict__ bx, int d = D) {
+    double s = 0.0;
+    PF_FOR_DEPTH(k) {
+        const double e = fmax(fmax(bx[k] - hi[k], lo[k] - bx[d + k]), 0.0);
+        s += e * e;
+    }
+    return s;
+}
+
+template <int D>
+__device__ __forceinline__ double centre_dist2(const double* lo, const double* hi, const double* __restrict__ bx, int d = D) {
+    double s = 0.0;
+    PF_FOR_DEPTH(k) {
+        const double ctr = 0.5 * (lo[k] + hi[k]);
+        const double e = fmax(fmax(bx[k] - ctr, ctr - bx[d + k]), 0.0);
+        s += e * e;
+    }
+    return s;
+}
+
+// The seed of a search, for a whole wave: the nearest super-chunk, then the nearest chunk inside it, by dist(box) (one
+// box per lane), lowest index on ties; n_chunks when there is none (a NaN point, no finite box).  Only a heuristic for a
+// good first bound.  Every lane returns the same.
+template <int D, class Dist>
+__device__ __forceinline__ int64_t nearest_chunk(Dist dist, const double* __restrict__ box, const double* __restrict__ sbox,
+                                                 int64_t n_chunks, int64_t n_super, int lane, int d = D) {
+    const double inf = std::numeric_limits<double>::infinity();
+    double nd = inf;
+    int64_t ns = n_super;  // sentinel: none
+    for (int64_t s = lane; s < n_super; s += PF_WAVE) {
+        const double e = dist(sbox + 2 * d * s);
+        if (e < nd) nd = e, ns = s;
+    }
+    wave_argmin(nd, ns);
+    int64_t c0 = n_chunks;
+    if (ns < n_super) {
+        c0 = ns * PF_WAVE + lane;
+        nd = c0 < n_chunks ? dist(box + 2 * d * c0) : inf;
+        if (!(nd < inf)) c0 = n_chunks;
+        wave_argmin(nd, c0);
+    }
+    return c0;
+}

@@ -344,6 +344,41 @@ def test_three_dimensions_equal_the_icp_search(ctx, sphere):
 
 
 @pytest.mark.gpu
+def test_quad_mesh_at_three_dimensions_agrees_across_every_search(ctx):
+    """One hierarchy build serves `DeviceSurfaceND` and `DeviceSurface`.  2 116 quads = 4 232 fan triangles: fan position 1
+    in every face, 67 chunks (the last one of 8 triangles), two super-chunks; 299 queries fill no packet of 4, 8 or 16.
+    A build that strides the boxes wrongly, miscounts the last chunk or drops the fan position cannot give the brute-force
+    answer here, whichever search reads it."""
+    from pyfocusr_amd import _hip
+
+    n = 47
+    ij, _, quads = _grid(n)
+    n_tri = 2 * len(quads)
+    assert n_tri > 4096 and n_tri % 64 != 0
+    rng = np.random.default_rng(47)
+    x = np.ascontiguousarray(np.concatenate([ij + 0.2 * rng.uniform(-1.0, 1.0, size=ij.shape),
+                                             1.5 * rng.normal(size=(len(ij), 1))], axis=1))
+    w = rng.dirichlet([1.0, 1.0, 1.0, 1.0], size=150)
+    near = np.einsum("qc,qck->qk", w, x[quads[rng.integers(0, len(quads), 150)]]) + 0.05 * rng.normal(size=(150, 3))
+    far = rng.uniform(x.min(0) - 3.0, x.max(0) + 3.0, size=(149, 3))
+    q = np.concatenate([near, far])
+    assert len(q) == 299
+    want = ref.closest_points_on_surface_nd(x, quads, q)
+    second = want["vertices"][:, 1] != quads[want["face"], 1]  # the winner is fan triangle (0, 2, 3) of its quad
+    assert np.all(want["face"] >= 0) and second.any() and not second.all()
+
+    _same(_search(ctx, x, quads, q), want)
+    surf = _hip.DeviceSurface(x, quads, ctx=ctx)
+    try:
+        dist_d2, dist_face, _ = surf.distance(q)
+        _, near_face, near_d2 = surf.closest(q)
+    finally:
+        surf.close()
+    assert dist_d2.tobytes() == want["d2"].tobytes() and np.array_equal(dist_face, want["face"])
+    assert near_d2.tobytes() == want["d2"].tobytes() and np.array_equal(near_face, want["face"])
+
+
+@pytest.mark.gpu
 def test_known_answers_on_an_integer_grid(ctx):
     from pyfocusr_amd import interpolate_on_surface
 
