@@ -415,6 +415,22 @@ int pf_fmap_project(pf_fmap* h, int32_t k_s, int32_t k_t, double* C_out);
 int pf_fmap_convert(pf_fmap* h, const double* C, int32_t k_s, int32_t k_t);
 int pf_fmap_zoomout(pf_fmap* h, int32_t k_start, int32_t k_end, int32_t step, int32_t n_iter_at_end, double* C_out);
 
+/* ---- spectral descriptors (pf_descriptors.hip; the reference has none: an extra) ---------------------------------
+ * Every descriptor sum_a phi[i][a]^2 g_t(lambda_a) - heat kernel signature, wave kernel signature, ... - through one
+ * host-made table G [K][T] row-major (K basis functions, T samples).  All arrays are host arrays, FP64, row-major; no
+ * handle, no state; everything runs on the ctx stream and the call returns when the result has arrived.
+ *   pf_spectral_descriptors     out[i][t] = sum_a (phi[i][a] * phi[i][a]) * G[a][t], n x T: a ascending, a separate
+ *            multiply and a separate add per term (no contraction): the bits of the plain loop.
+ *   pf_descriptor_coefficients  A_out[a][t] = sum_i phi[i][a] * (mass[i] * F[i][t]), k_out x T, a < k_out <= K, with F
+ *            the array above (all K columns of phi enter it), formed on chip and never written to memory.  Rows in
+ *            blocks of 512, each block summed in row order, the blocks added in block order; no floating-point
+ *            atomics: two calls give the same bits.  A row with mass 0 or with phi all zero adds exactly 0.
+ * Limits: n >= 1, 1 <= K <= 128, 1 <= T <= 512, 1 <= k_out <= K; outside them, or with a NULL pointer, PF_E_ARG and
+ * nothing is launched.  PF_E_HIP for a failed allocation, copy or launch. */
+int pf_spectral_descriptors(pf_ctx* ctx, const double* phi, int64_t n, int32_t K, const double* G, int32_t T, double* out);
+int pf_descriptor_coefficients(pf_ctx* ctx, const double* phi, const double* mass, int64_t n, int32_t K, const double* G,
+                               int32_t T, int32_t k_out, double* A_out);
+
 /* ---- the whole eigensolve in one call --------------------------------------------------------------------------
  * Replaces scipy.sparse.linalg.eigs(L, k, sigma=1e-10, which="LM", ncv=4k) at graph.py:372 (called from
  * recursive_eig, graph.py:357-389) for callers that bind the C-ABI without the Python driver: the n_wanted lowest

@@ -17,6 +17,8 @@ from .functional_maps import (functional_map_from_p2p, p2p_from_functional_map, 
 from .laplace_beltrami import cotangent_laplacian, laplace_beltrami_spectrum, mean_curvature, mean_curvature_normals
 from .ray_casting import (hit_points, ray_crossings, ray_mesh_intersections, thickness_along_normals,
                           vertex_normals)
+from .spectral_descriptors import (descriptor_coefficients, descriptor_correspondences, functional_map_from_descriptors,
+                                   heat_kernel_signature, signature_on_mesh, spectral_descriptors, wave_kernel_signature)
 from .surface_distance import (point_to_surface_distances, points_inside, signed_distances_on_mesh,
                                signed_point_to_surface_distances, summarize_distances, summarize_signed_distances,
                                surface_distance_metrics, winding_numbers)

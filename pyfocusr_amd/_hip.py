@@ -190,6 +190,8 @@ SIGNATURES = {
     "pf_fmap_project": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _f64p]),
     "pf_fmap_convert": (C.c_int, [C.c_void_p, _f64p, C.c_int32, C.c_int32]),
     "pf_fmap_zoomout": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _f64p]),
+    "pf_spectral_descriptors": (C.c_int, [C.c_void_p, _f64p, C.c_int64, C.c_int32, _f64p, C.c_int32, _f64p]),
+    "pf_descriptor_coefficients": (C.c_int, [C.c_void_p, _f64p, _f64p, C.c_int64, C.c_int32, _f64p, C.c_int32, C.c_int32, _f64p]),
     "pf_surface_nd_create": (C.c_int, [C.c_void_p, _f64p, C.c_int64, C.c_int32, _i32p, C.c_int64, C.c_int32,
                                        C.POINTER(C.c_void_p)]),
     "pf_surface_nd_free": (None, [C.c_void_p]),
@@ -494,6 +496,29 @@ class Context(object):
         pairs = C.c_int64()
         _check(self._lib.pf_knn1_wide_count(self._h, int(bool(enable_counting)), C.byref(pairs)))
         return int(pairs.value)
+
+    # ---- spectral descriptors ----------------------------------------------------------
+    def spectral_descriptors(self, phi, G):
+        """F (n, T): F[i, t] = sum_a phi[i, a]^2 G[a, t] (`pf_spectral_descriptors`).  Only the shapes are checked
+        here; the library refuses K > 128, T > 512 and n = 0 with `PfError` (PF_E_ARG)."""
+        phi, G = _c_f64(phi), _c_f64(G)
+        if phi.ndim != 2 or G.ndim != 2 or G.shape[0] != phi.shape[1]:
+            raise ValueError("phi must be (n, K) and G (K, T)")
+        out = np.empty((phi.shape[0], G.shape[1]), dtype=np.float64)
+        _check(self._lib.pf_spectral_descriptors(self._h, _f64(phi), phi.shape[0], phi.shape[1], _f64(G), G.shape[1], _f64(out)))
+        return out
+
+    def descriptor_coefficients(self, phi, mass, G, k_out):
+        """A (k_out, T): A[a, t] = sum_i mass[i] phi[i, a] F[i, t] with F as in `spectral_descriptors`, never stored
+        (`pf_descriptor_coefficients`).  Shapes are checked here, the limits by the library (PF_E_ARG)."""
+        phi, G = _c_f64(phi), _c_f64(G)
+        if phi.ndim != 2 or G.ndim != 2 or G.shape[0] != phi.shape[1]:
+            raise ValueError("phi must be (n, K) and G (K, T)")
+        mass = _c_f64(mass, (phi.shape[0],))
+        out = np.empty((max(int(k_out), 0), G.shape[1]), dtype=np.float64)
+        _check(self._lib.pf_descriptor_coefficients(self._h, _f64(phi), _f64(mass), phi.shape[0], phi.shape[1], _f64(G), G.shape[1],
+                                                    int(k_out), _f64(out)))
+        return out
 
     def assign(self, rows, cols, return_duals=False):
         """Optimal one-to-one assignment on Euclidean costs (`pf_assign`): col_of_row (int64, n_rows) minimising
