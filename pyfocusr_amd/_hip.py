@@ -963,6 +963,7 @@ class DeviceCpd(object):
         _check(self._lib.pf_cpd_create(self.ctx._h, _f64(X), self.N, _f64(Y), self.M, self.D, C.byref(h)))
         self._h = h
         self._P1, self._Pt1, self._PX = np.empty(self.M), np.empty(self.N), np.empty((self.M, self.D))
+        self._H = np.empty((0, 0))  # until set_basis: the library refuses the basis calls (PfError), not Python
         _live_graphs.add(self)
         self.ctx._children.add(self)
 

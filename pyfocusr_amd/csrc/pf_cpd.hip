@@ -190,6 +190,7 @@ __global__ __launch_bounds__(PF_BLOCK) void k_gram(const double* __restrict__ A,
 // hpart[chunk][i][j] = sum over the chunk's m of w_m Q[m][i] Q[m][j]; 16 x 16 outputs per block
 constexpr int GRAM_TILE = 16;
 constexpr int GRAM_CHUNK = 512;
+static_assert(GRAM_CHUNK % GRAM_TILE == 0, "a chunk's last step of GRAM_TILE rows must not reach into the next chunk");
 __global__ __launch_bounds__(GRAM_TILE* GRAM_TILE) void k_weighted_gram(const double* __restrict__ Q, const double* __restrict__ w,
                                                                          int64_t M, int32_t K, double* __restrict__ part) {
     __shared__ double qi[GRAM_TILE][GRAM_TILE + 1], qj[GRAM_TILE][GRAM_TILE + 1];  // [m within step][column]
@@ -234,7 +235,9 @@ __global__ __launch_bounds__(PF_BLOCK) void k_affine_moments_m(const double* __r
     for (int k = threadIdx.x; k < cnt; k += PF_BLOCK) sp[k] = P1[m0 + k];
     for (int k = threadIdx.x; k < cnt * D; k += PF_BLOCK) {
         const int r = k / D, d = k - r * D;
-        spx[k] = PX[m0 * D + k] - P1[m0 + r] * cx[d];
+        // one rounding, of the centred value itself: with one fixed point PX is P1 cx up to its rounding, and a product
+        // rounded on its own would leave 0 in place of it
+        spx[k] = fma(-P1[m0 + r], cx[d], PX[m0 * D + k]);
         sy[k] = Y[m0 * D + k] - cy[d];
     }
     __syncthreads();
@@ -317,7 +320,7 @@ __global__ __launch_bounds__(PF_BLOCK) void k_deform_rhs(const double* __restric
     __shared__ double sf[MOM_ROWS * 16];
     const int64_t m0 = (int64_t)blockIdx.x * MOM_ROWS;
     const int cnt = (int)(M - m0 < MOM_ROWS ? M - m0 : MOM_ROWS);
-    for (int k = threadIdx.x; k < cnt * D; k += PF_BLOCK) sf[k] = PX[m0 * D + k] - P1[m0 + k / D] * Y[m0 * D + k];
+    for (int k = threadIdx.x; k < cnt * D; k += PF_BLOCK) sf[k] = fma(-P1[m0 + k / D], Y[m0 * D + k], PX[m0 * D + k]);
     __syncthreads();
     const int L = K * D;
     for (int o = threadIdx.x; o < L; o += PF_BLOCK) {
@@ -514,8 +517,9 @@ int pf_cpd_set_basis(pf_cpd* h, const double* Q, int32_t K) {
 }
 
 int pf_cpd_weighted_gram(pf_cpd* h, double* H) {
-    PF_CHECK(h && H, PF_E_ARG, "pf_cpd_weighted_gram: NULL argument");
+    PF_CHECK(h != nullptr, PF_E_ARG, "pf_cpd_weighted_gram: NULL handle");
     PF_CHECK(h->K > 0, PF_E_STATE, "pf_cpd_weighted_gram: no basis (pf_cpd_set_basis) on this handle");
+    PF_CHECK(H != nullptr, PF_E_ARG, "pf_cpd_weighted_gram: NULL argument");
     PF_HIP(hipSetDevice(h->ctx->device));
     hipStream_t st = h->ctx->stream;
     const unsigned tiles = (unsigned)((h->K + GRAM_TILE - 1) / GRAM_TILE);
@@ -577,8 +581,9 @@ int pf_cpd_apply_affine(pf_cpd* h, const double* B, const double* t) {
 }
 
 int pf_cpd_deform_sums(pf_cpd* h, double* H, double* R) {
-    PF_CHECK(h && H && R, PF_E_ARG, "pf_cpd_deform_sums: NULL argument");
+    PF_CHECK(h != nullptr, PF_E_ARG, "pf_cpd_deform_sums: NULL handle");
     PF_CHECK(h->K > 0, PF_E_STATE, "pf_cpd_deform_sums: no basis (pf_cpd_set_basis) on this handle");
+    PF_CHECK(H && R, PF_E_ARG, "pf_cpd_deform_sums: NULL argument");
     PF_HIP(hipSetDevice(h->ctx->device));
     hipStream_t st = h->ctx->stream;
     const int D = h->D, K = h->K;
@@ -656,15 +661,18 @@ int pf_cpd_gram(pf_ctx* ctx, const double* A, int64_t n_a, const double* B, int6
     double *dA = nullptr, *dB = nullptr, *dV = nullptr, *dO = nullptr;
     hipError_t e = hipSuccess;
     int rc = PF_OK;
+    // B rides on A's upload only when it is A or a leading part of it (low_rank_affinity: G(Y, Y) V, one upload per
+    // product saved).  Equal pointers alone do not say that: B = Y against A = Y[:k] has n_b > n_a rows.
+    const bool own_b = A != B || n_b > n_a;
     do {
         if ((e = pf_malloc(st, (void**)&dA, sizeof(double) * n_a * d)) != hipSuccess) break;
-        if (A != B && (e = pf_malloc(st, (void**)&dB, sizeof(double) * n_b * d)) != hipSuccess) break;
+        if (own_b && (e = pf_malloc(st, (void**)&dB, sizeof(double) * n_b * d)) != hipSuccess) break;
         if ((e = pf_malloc(st, (void**)&dV, sizeof(double) * n_b * n_cols)) != hipSuccess) break;
         if ((e = pf_malloc(st, (void**)&dO, sizeof(double) * n_a * n_cols)) != hipSuccess) break;
         if ((e = hipMemcpyAsync(dA, A, sizeof(double) * n_a * d, hipMemcpyHostToDevice, st)) != hipSuccess) break;
-        if (A != B && (e = hipMemcpyAsync(dB, B, sizeof(double) * n_b * d, hipMemcpyHostToDevice, st)) != hipSuccess) break;
+        if (own_b && (e = hipMemcpyAsync(dB, B, sizeof(double) * n_b * d, hipMemcpyHostToDevice, st)) != hipSuccess) break;
         if ((e = hipMemcpyAsync(dV, V, sizeof(double) * n_b * n_cols, hipMemcpyHostToDevice, st)) != hipSuccess) break;
-        rc = dispatch_gram(st, d, dA, n_a, A != B ? dB : dA, n_b, 1.0 / (2.0 * beta * beta), dV, n_cols, dO);
+        rc = dispatch_gram(st, d, dA, n_a, own_b ? dB : dA, n_b, 1.0 / (2.0 * beta * beta), dV, n_cols, dO);
         if (rc != PF_OK) break;
         if ((e = hipMemcpyAsync(out, dO, sizeof(double) * n_a * n_cols, hipMemcpyDeviceToHost, st)) != hipSuccess) break;
         e = hipStreamSynchronize(st);
