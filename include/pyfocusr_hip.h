@@ -32,7 +32,8 @@ extern "C" {
 #define PF_OK 0
 #define PF_E_ARG (-1)        /* bad argument (null pointer, size, slot range, face index out of range) */
 #define PF_E_HIP (-2)        /* HIP runtime error (allocation, launch, copy); see pf_last_error() */
-#define PF_E_DEGENERATE (-3) /* a face repeats a vertex: the reference would store W_ii = inf */
+#define PF_E_DEGENERATE (-3) /* a face repeats a vertex: the reference would store W_ii = inf; or the samples of
+                                pf_fmap_zoomout_sampled do not determine the fit */
 #define PF_E_STATE (-4)      /* call order violated (e.g. knn run before upload) */
 #define PF_E_PERSIST_TIMEOUT (-5) /* a wait inside the resident Chebyshev kernel ran out (device shared?): the filter
                                      applications since the last synchronising call are invalid; the stream has been
@@ -414,6 +415,34 @@ int pf_fmap_get_p2p(pf_fmap* h, int64_t* T_out, double* d2_out);
 int pf_fmap_project(pf_fmap* h, int32_t k_s, int32_t k_t, double* C_out);
 int pf_fmap_convert(pf_fmap* h, const double* C, int32_t k_s, int32_t k_t);
 int pf_fmap_zoomout(pf_fmap* h, int32_t k_start, int32_t k_end, int32_t step, int32_t n_iter_at_end, double* C_out);
+/* ZoomOut on sub-samples (Melzi et al. 2019, 4.2.3).  A = phi_s[S_s] (q_s rows), B = phi_t[S_t] (q_t rows), gathered once:
+ *   k = k_start;  C = project (k, k) of the handle's full point map;
+ *   loop { Tsub[i] = the row of B[:, :k] nearest to (A[:, :k] C)[i];  last = (k == k_end and the n_iter_at_end extra rounds
+ *          are used up);  k = min(k + step, k_end);  C = the least-squares fit on the samples at the new k, the solution of
+ *          (A_k^T A_k) C = A_k^T B[Tsub, :k];  stop if last }
+ *   convert (k_end, k_end) at full resolution: the handle's point map and distances are the full ones.
+ * Both Gram products are summed on the device in project's fixed order (two calls give the same bits); the k x k system
+ * is solved on the host by a Cholesky factorisation: one wait per round for k_end^2 doubles.
+ * pf_fmap_set_samples     indices into the target and the source (host), q_t, q_s >= 1; validated on the device: an entry
+ *                         out of range gives PF_E_ARG (no samples are set).
+ * pf_fmap_zoomout_sampled PF_E_STATE without samples or a point map; PF_E_ARG unless q_s >= k_end; PF_E_DEGENERATE when a pivot
+ *                         of the factorisation is not positive beyond its rounding, (q_s + k) eps times the diagonal
+ *                         entry (the samples are too few or degenerate for this k).
+ *                         C_out (nullable): the last fit, k_end x k_end. */
+int pf_fmap_set_samples(pf_fmap* h, const int64_t* S_t, int64_t q_t, const int64_t* S_s, int64_t q_s);
+int pf_fmap_zoomout_sampled(pf_fmap* h, int32_t k_start, int32_t k_end, int32_t step, int32_t n_iter_at_end, double* C_out);
+
+/* ---- farthest-point sampling (pf_fps.hip; the reference has none: an extra) ----------------------------------------
+ * m samples of the n x d points (host, row-major, 1 <= d <= 16, 1 <= m <= n < 2^31).  d2(i, c) = the sum over the
+ * coordinates, left to right, of (P[i][x] - c[x])^2, separate multiply and add.  start >= 0: the first sample; -1: the
+ * point with the largest d2 to the centroid (the per-coordinate mean, summed in index order), lowest index on ties.
+ * dmin = +inf, owner = 0; round j: sel[j] = cur; every i with d2(i, cur) < dmin[i] takes dmin[i] = d2(i, cur), owner[i] = j;
+ * cur = argmax dmin, lowest index on ties.  Samples repeat (index 0) once m exceeds the number of distinct points.
+ * sel_out [m]; owner_out [n] (nullable) the position in sel of the nearest sample, the earliest on ties; dmin_out [n]
+ * (nullable) the squared distance to it: its maximum is the squared covering radius.  2 m launches back to back, one
+ * download.  PF_E_ARG for d, m or start out of range or a coordinate that is not finite. */
+int pf_fps(pf_ctx* ctx, const double* points, int64_t n, int32_t d, int64_t m, int64_t start, int64_t* sel_out,
+           int32_t* owner_out, double* dmin_out);
 
 /* ---- spectral descriptors (pf_descriptors.hip; the reference has none: an extra) ---------------------------------
  * Every descriptor sum_a phi[i][a]^2 g_t(lambda_a) - heat kernel signature, wave kernel signature, ... - through one

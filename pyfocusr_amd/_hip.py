@@ -190,6 +190,9 @@ SIGNATURES = {
     "pf_fmap_project": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _f64p]),
     "pf_fmap_convert": (C.c_int, [C.c_void_p, _f64p, C.c_int32, C.c_int32]),
     "pf_fmap_zoomout": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _f64p]),
+    "pf_fmap_set_samples": (C.c_int, [C.c_void_p, _i64p, C.c_int64, _i64p, C.c_int64]),
+    "pf_fmap_zoomout_sampled": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _f64p]),
+    "pf_fps": (C.c_int, [C.c_void_p, _f64p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, _i64p, _i32p, _f64p]),
     "pf_spectral_descriptors": (C.c_int, [C.c_void_p, _f64p, C.c_int64, C.c_int32, _f64p, C.c_int32, _f64p]),
     "pf_descriptor_coefficients": (C.c_int, [C.c_void_p, _f64p, _f64p, C.c_int64, C.c_int32, _f64p, C.c_int32, C.c_int32, _f64p]),
     "pf_surface_nd_create": (C.c_int, [C.c_void_p, _f64p, C.c_int64, C.c_int32, _i32p, C.c_int64, C.c_int32,
@@ -496,6 +499,24 @@ class Context(object):
         pairs = C.c_int64()
         _check(self._lib.pf_knn1_wide_count(self._h, int(bool(enable_counting)), C.byref(pairs)))
         return int(pairs.value)
+
+    # ---- farthest-point sampling --------------------------------------------------------
+    def farthest_point_sampling(self, points, m, start=-1, return_owner=False, return_d2=False):
+        """`pf_fps`: sel (int64, m) of the (n, d) points, 1 <= d <= 16; `start` -1 begins at the point farthest from the
+        centroid.  With `return_owner` the position in sel of every point's nearest sample (int32, n), with `return_d2`
+        the squared distance to it.  Samples repeat once m exceeds the number of distinct points.  The library refuses
+        d, m or start out of range and non-finite coordinates with `PfError` (PF_E_ARG)."""
+        pts = _c_f64(points)
+        if pts.ndim != 2:
+            raise ValueError("points must be an (n, d) array")
+        n, m = pts.shape[0], int(m)
+        sel = np.empty(max(m, 0), dtype=np.int64)
+        owner = np.empty(n, dtype=np.int32) if return_owner else None
+        d2 = np.empty(n, dtype=np.float64) if return_d2 else None
+        _check(self._lib.pf_fps(self._h, _f64(pts), n, pts.shape[1], m, int(start), sel.ctypes.data_as(_i64p),
+                                owner.ctypes.data_as(_i32p) if return_owner else None, _f64(d2) if return_d2 else None))
+        out = (sel,) + ((owner,) if return_owner else ()) + ((d2,) if return_d2 else ())
+        return out if len(out) > 1 else sel
 
     # ---- spectral descriptors ----------------------------------------------------------
     def spectral_descriptors(self, phi, G):
@@ -928,6 +949,22 @@ class DeviceFunctionalMap(object):
     def zoomout(self, k_start, k_end, step=1, n_iter_at_end=0):
         Cm = np.empty((int(k_end), int(k_end)))
         _check(self._lib.pf_fmap_zoomout(self._h, int(k_start), int(k_end), int(step), int(n_iter_at_end), _f64(Cm)))
+        return Cm
+
+    def set_samples(self, S_t, S_s):
+        """Rows of the target's and of the source's basis that `zoomout_sampled` works on (`pf_fmap_set_samples`)."""
+        S_t, S_s = np.ascontiguousarray(S_t, dtype=np.int64), np.ascontiguousarray(S_s, dtype=np.int64)
+        if S_t.ndim != 1 or S_s.ndim != 1:
+            raise ValueError("S_t and S_s must be vectors of indices")
+        _check(self._lib.pf_fmap_set_samples(self._h, S_t.ctypes.data_as(_i64p), S_t.shape[0], S_s.ctypes.data_as(_i64p), S_s.shape[0]))
+
+    def zoomout_sampled(self, k_start, k_end, step=1, n_iter_at_end=0):
+        """ZoomOut on the samples, least-squares fits, one conversion at full resolution at the end
+        (`pf_fmap_zoomout_sampled`); returns the last fit, k_end x k_end."""
+        if not 1 <= int(k_end) <= self.K:
+            raise ValueError("k_end must lie in 1 .. K = %d" % self.K)
+        Cm = np.empty((int(k_end), int(k_end)))
+        _check(self._lib.pf_fmap_zoomout_sampled(self._h, int(k_start), int(k_end), int(step), int(n_iter_at_end), _f64(Cm)))
         return Cm
 
     def close(self):

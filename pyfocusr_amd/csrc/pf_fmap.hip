@@ -33,6 +33,14 @@
 // a block computes 64 x 64 outputs, 4 x 4 per lane, from LDS tiles of 32 z.  The projection cuts the rows into
 // fixed blocks of 512, each block's partial sum in its own slot; k_fmap_combine adds the slots in block order.  No
 // floating-point atomic: the order of every sum is fixed by the shapes alone, two calls give the same bits.
+//
+// ZoomOut on sub-samples (pf_fmap_set_samples, pf_fmap_zoomout_sampled).  The rows phi_s[S_s] and phi_t[S_t] are gathered
+// once into compact blocks A and B; the rounds run project's and convert's kernels on those (FmapView), so a round costs
+// q_s q_t k instead of n_s n_t k.  The fit on the samples is the least-squares one, (A_k^T A_k) C = A_k^T B[Tsub, :k]: both
+// Gram products are projections with unit weights (A^T A through the identity map into A itself), the k x k system is
+// solved on the host (chol_solve).  An entry of A^T A is the same sum in the same order whatever k, so the product is
+// formed once at k_end and its leading k x k block serves every round.
+#include <math.h>
 #include <string.h>
 
 #include <algorithm>
@@ -293,9 +301,63 @@ __global__ __launch_bounds__(PF_BLOCK) void k_fmap_take_knn(const int64_t* __res
     d2_out[i] = d2[i];
 }
 
+// dst[i][c] = src[rows[i]][c], K columns
+__global__ __launch_bounds__(PF_BLOCK) void k_fmap_gather_rows(const double* __restrict__ src, int32_t K, const int32_t* __restrict__ rows,
+                                                               int64_t q, double* __restrict__ dst) {
+    const int64_t e = (int64_t)blockIdx.x * PF_BLOCK + threadIdx.x;
+    if (e >= q * K) return;
+    const int64_t i = e / K, c = e - i * K;
+    dst[e] = src[(int64_t)rows[i] * K + c];
+}
+
+// unit weights and the identity map of the samples
+__global__ __launch_bounds__(PF_BLOCK) void k_fmap_unit(double* __restrict__ ones, int32_t* __restrict__ ident, int64_t q) {
+    const int64_t i = (int64_t)blockIdx.x * PF_BLOCK + threadIdx.x;
+    if (i < q) ones[i] = 1.0, ident[i] = (int32_t)i;
+}
+
 __global__ __launch_bounds__(PF_BLOCK) void k_fmap_widen(const int32_t* __restrict__ T, int64_t n, int64_t* __restrict__ out) {
     const int64_t i = (int64_t)blockIdx.x * PF_BLOCK + threadIdx.x;
     if (i < n) out[i] = T[i];
+}
+
+// R <- the solution X of G[:k, :k] X = R (k x k, row-major) for a symmetric positive definite G with leading dimension
+// ldg, of which the lower triangle is read: Cholesky G = L L^T, then a forward and a back substitution over the rows of R.
+// False when a pivot is not positive - not above tol times its diagonal entry of G, the rounding of the sums behind it
+// (a pivot that is zero in exact arithmetic comes out as noise of either sign).
+bool chol_solve(const double* G, int ldg, int k, double tol, double* R) {
+    std::vector<double> L((size_t)k * k, 0.0);
+    for (int j = 0; j < k; ++j) {
+        double s = G[(size_t)j * ldg + j];
+        for (int p = 0; p < j; ++p) s -= L[(size_t)j * k + p] * L[(size_t)j * k + p];
+        if (!(s > tol * G[(size_t)j * ldg + j])) return false;
+        const double ljj = sqrt(s);
+        L[(size_t)j * k + j] = ljj;
+        for (int i = j + 1; i < k; ++i) {
+            double t = G[(size_t)i * ldg + j];
+            for (int p = 0; p < j; ++p) t -= L[(size_t)i * k + p] * L[(size_t)j * k + p];
+            L[(size_t)i * k + j] = t / ljj;
+        }
+    }
+    for (int i = 0; i < k; ++i) {  // L Y = R
+        double* ri = R + (size_t)i * k;
+        for (int p = 0; p < i; ++p) {
+            const double l = L[(size_t)i * k + p];
+            const double* rp = R + (size_t)p * k;
+            for (int c = 0; c < k; ++c) ri[c] -= l * rp[c];
+        }
+        for (int c = 0; c < k; ++c) ri[c] /= L[(size_t)i * k + i];
+    }
+    for (int i = k - 1; i >= 0; --i) {  // L^T X = Y
+        double* ri = R + (size_t)i * k;
+        for (int p = i + 1; p < k; ++p) {
+            const double l = L[(size_t)p * k + i];
+            const double* rp = R + (size_t)p * k;
+            for (int c = 0; c < k; ++c) ri[c] -= l * rp[c];
+        }
+        for (int c = 0; c < k; ++c) ri[c] /= L[(size_t)i * k + i];
+    }
+    return true;
 }
 
 }  // namespace
@@ -313,52 +375,91 @@ struct pf_fmap {
     double* Q = nullptr;      // [n_s][k_t] (narrow search) or [pad(k_t)][ld_q] (wide search)
     int32_t c_ks = 0, c_kt = 0;
     bool has_T = false, has_d2 = false;
+    // the samples of pf_fmap_set_samples
+    int64_t q_t = 0, q_s = 0, ld_qs = 0;
+    double* A = nullptr;        // [q_s][K] phi_s[S_s]
+    double* B = nullptr;        // [q_t][K] phi_t[S_t]
+    double* ones = nullptr;     // [q_s] unit weights
+    int32_t* ident = nullptr;   // [q_s] the identity map (A^T A)
+    int32_t* T_sub = nullptr;   // [q_s] the samples' map into B
+    double* d2_sub = nullptr;   // [q_s]
+    double* Q_sub = nullptr;    // Q of the samples, laid out like Q
+    double* G = nullptr;        // [K][K] A^T A
+    double* R = nullptr;        // [K][K] A^T B[T_sub]
+    bool has_samples = false;
 };
 
-static int fmap_project(pf_fmap* h, int32_t k_s, int32_t k_t) {
+// what project and convert work on: the full bases, or the samples' compact blocks
+struct FmapView {
+    const double* phi_t;
+    int64_t n_t;
+    const double* phi_s;
+    int64_t n_s;
+    const double* mass;
+    int32_t* T;
+    double* d2;
+    double* Q;
+    int64_t ld_q;
+};
+static FmapView fmap_full(pf_fmap* h) { return {h->phi_t, h->n_t, h->phi_s, h->n_s, h->mass, h->T, h->d2, h->Q, h->ld_q}; }
+static FmapView fmap_sub(pf_fmap* h) { return {h->B, h->q_t, h->A, h->q_s, h->ones, h->T_sub, h->d2_sub, h->Q_sub, h->ld_qs}; }
+
+// out (k_s x k_t on the device); out == h->C makes it the resident functional map
+static int fmap_project(pf_fmap* h, const FmapView& v, int32_t k_s, int32_t k_t, double* out) {
     pf_ctx* c = h->ctx;
     Scratch s(c->stream);
-    const int64_t blocks = (h->n_s + PROJ_ROWS - 1) / PROJ_ROWS, count = (int64_t)k_s * k_t;
-    double* part = blocks > 1 ? s.get<double>((size_t)(blocks * count)) : h->C;
+    const int64_t blocks = (v.n_s + PROJ_ROWS - 1) / PROJ_ROWS, count = (int64_t)k_s * k_t;
+    double* part = blocks > 1 ? s.get<double>((size_t)(blocks * count)) : out;
     if (s.ok()) {
-        const ProjLoad ld{h->phi_s, h->phi_t, h->mass, h->T, h->K};
+        const ProjLoad ld{v.phi_s, v.phi_t, v.mass, v.T, h->K};
         const dim3 grid((unsigned)((k_s + TILE - 1) / TILE), (unsigned)((k_t + TILE - 1) / TILE), (unsigned)blocks);
-        k_fmap_tile<ProjLoad, false><<<grid, PF_BLOCK, 0, s.st>>>(ld, k_s, k_t, h->n_s, PROJ_ROWS, part, count, k_t, 1);
-        if (blocks > 1) k_fmap_combine<<<pf_blocks(count), PF_BLOCK, 0, s.st>>>(part, count, blocks, h->C);
+        k_fmap_tile<ProjLoad, false><<<grid, PF_BLOCK, 0, s.st>>>(ld, k_s, k_t, v.n_s, PROJ_ROWS, part, count, k_t, 1);
+        if (blocks > 1) k_fmap_combine<<<pf_blocks(count), PF_BLOCK, 0, s.st>>>(part, count, blocks, out);
         s.launched();
     }
     PF_CHECK(s.ok(), PF_E_HIP, "pf_fmap_project: %s", hipGetErrorString(s.err));
-    h->c_ks = k_s, h->c_kt = k_t;
+    if (out == h->C) h->c_ks = k_s, h->c_kt = k_t;
     return PF_OK;
 }
 
-static int fmap_convert(pf_fmap* h, int32_t k_s, int32_t k_t) {
+// the resident functional map (k_s x k_t) -> v.T, v.d2
+static int fmap_convert(pf_fmap* h, const FmapView& v, int32_t k_s, int32_t k_t) {
     pf_ctx* c = h->ctx;
     const bool wide = k_t > 16;
     {
         Scratch s(c->stream);
-        const QLoad ld{h->phi_s, h->C, h->K, k_t};
-        const dim3 grid((unsigned)((h->n_s + TILE - 1) / TILE), (unsigned)((k_t + TILE - 1) / TILE), 1);
+        const QLoad ld{v.phi_s, h->C, h->K, k_t};
+        const dim3 grid((unsigned)((v.n_s + TILE - 1) / TILE), (unsigned)((k_t + TILE - 1) / TILE), 1);
         const int32_t d_pad = pad_d(k_t);
         // the wide search reads zeros in the coordinates past k_t
-        if (wide && d_pad > k_t) s.zero(h->Q + (int64_t)k_t * h->ld_q, sizeof(double) * (size_t)((d_pad - k_t) * h->ld_q));
+        if (wide && d_pad > k_t) s.zero(v.Q + (int64_t)k_t * v.ld_q, sizeof(double) * (size_t)((d_pad - k_t) * v.ld_q));
         if (s.ok()) {
             if (wide)
-                k_fmap_tile<QLoad, true><<<grid, PF_BLOCK, 0, s.st>>>(ld, h->n_s, k_t, k_s, k_s, h->Q, 0, 1, h->ld_q);
+                k_fmap_tile<QLoad, true><<<grid, PF_BLOCK, 0, s.st>>>(ld, v.n_s, k_t, k_s, k_s, v.Q, 0, 1, v.ld_q);
             else
-                k_fmap_tile<QLoad, true><<<grid, PF_BLOCK, 0, s.st>>>(ld, h->n_s, k_t, k_s, k_s, h->Q, 0, k_t, 1);
+                k_fmap_tile<QLoad, true><<<grid, PF_BLOCK, 0, s.st>>>(ld, v.n_s, k_t, k_s, k_s, v.Q, 0, k_t, 1);
             s.launched();
         }
-        if (wide) PF_TRY(wide_search(c, s, h->phi_t, h->n_t, h->K, h->Q, h->n_s, h->ld_q, k_t, h->d2, h->T));
+        if (wide) PF_TRY(wide_search(c, s, v.phi_t, v.n_t, h->K, v.Q, v.n_s, v.ld_q, k_t, v.d2, v.T));
         PF_CHECK(s.ok(), PF_E_HIP, "pf_fmap_convert: %s", hipGetErrorString(s.err));
     }
     if (!wide) {
-        PF_TRY(pf_knn1_device(c, h->phi_t, h->n_t, h->K, h->Q, h->n_s, k_t, k_t));
-        k_fmap_take_knn<<<pf_blocks(h->n_s), PF_BLOCK, 0, c->stream>>>(c->knn_idx, c->knn_d2, h->n_s, h->T, h->d2);
+        PF_TRY(pf_knn1_device(c, v.phi_t, v.n_t, h->K, v.Q, v.n_s, k_t, k_t));
+        k_fmap_take_knn<<<pf_blocks(v.n_s), PF_BLOCK, 0, c->stream>>>(c->knn_idx, c->knn_d2, v.n_s, v.T, v.d2);
         PF_HIP(hipGetLastError());
     }
-    h->has_T = h->has_d2 = true;
+    if (v.T == h->T) h->has_T = h->has_d2 = true;
     return PF_OK;
+}
+
+static void fmap_free_samples(pf_fmap* h) {
+    hipStream_t st = h->ctx->stream;
+    for (void* p : {(void*)h->A, (void*)h->B, (void*)h->ones, (void*)h->ident, (void*)h->T_sub, (void*)h->d2_sub, (void*)h->Q_sub, (void*)h->G,
+                    (void*)h->R})
+        if (p) pf_free(st, p);
+    h->A = h->B = h->ones = h->d2_sub = h->Q_sub = h->G = h->R = nullptr;
+    h->ident = h->T_sub = nullptr;
+    h->has_samples = false;
 }
 
 extern "C" {
@@ -447,6 +548,7 @@ void pf_fmap_free(pf_fmap* h) {
     hipStream_t st = h->ctx->stream;
     for (void* p : {(void*)h->phi_t, (void*)h->phi_s, (void*)h->mass, (void*)h->T, (void*)h->d2, (void*)h->C, (void*)h->Q})
         if (p) pf_free(st, p);
+    fmap_free_samples(h);
     delete h;
 }
 
@@ -507,7 +609,7 @@ int pf_fmap_project(pf_fmap* h, int32_t k_s, int32_t k_t, double* C_out) {
              h->K);
     PF_CHECK(h->has_T, PF_E_STATE, "pf_fmap_project: no point map yet (pf_fmap_set_p2p or pf_fmap_convert)");
     PF_HIP(hipSetDevice(h->ctx->device));
-    PF_TRY(fmap_project(h, k_s, k_t));
+    PF_TRY(fmap_project(h, fmap_full(h), k_s, k_t, h->C));
     return fmap_download_c(h, C_out);
 }
 
@@ -523,7 +625,7 @@ int pf_fmap_convert(pf_fmap* h, const double* C, int32_t k_s, int32_t k_t) {
     }
     PF_CHECK(h->c_ks == k_s && h->c_kt == k_t, PF_E_STATE, "pf_fmap_convert: the resident functional map is %d x %d, not %d x %d", h->c_ks,
              h->c_kt, k_s, k_t);
-    return fmap_convert(h, k_s, k_t);
+    return fmap_convert(h, fmap_full(h), k_s, k_t);
 }
 
 int pf_fmap_zoomout(pf_fmap* h, int32_t k_start, int32_t k_end, int32_t step, int32_t n_iter_at_end, double* C_out) {
@@ -534,16 +636,119 @@ int pf_fmap_zoomout(pf_fmap* h, int32_t k_start, int32_t k_end, int32_t step, in
     PF_CHECK(h->has_T, PF_E_STATE, "pf_fmap_zoomout: no point map yet (pf_fmap_set_p2p)");
     PF_HIP(hipSetDevice(h->ctx->device));
     for (int32_t k = k_start;;) {
-        PF_TRY(fmap_project(h, k, k));
-        PF_TRY(fmap_convert(h, k, k));
+        PF_TRY(fmap_project(h, fmap_full(h), k, k, h->C));
+        PF_TRY(fmap_convert(h, fmap_full(h), k, k));
         if (k == k_end) break;
         k = std::min(k + step, k_end);
     }
     for (int32_t it = 0; it < n_iter_at_end; ++it) {
-        PF_TRY(fmap_project(h, k_end, k_end));
-        PF_TRY(fmap_convert(h, k_end, k_end));
+        PF_TRY(fmap_project(h, fmap_full(h), k_end, k_end, h->C));
+        PF_TRY(fmap_convert(h, fmap_full(h), k_end, k_end));
     }
     return fmap_download_c(h, C_out);
+}
+
+int pf_fmap_set_samples(pf_fmap* h, const int64_t* S_t, int64_t q_t, const int64_t* S_s, int64_t q_s) {
+    PF_CHECK(h && S_t && S_s, PF_E_ARG, "pf_fmap_set_samples: NULL argument");
+    PF_CHECK(q_t >= 1 && q_t < ((int64_t)1 << 31) && q_s >= 1 && q_s < ((int64_t)1 << 31), PF_E_ARG,
+             "pf_fmap_set_samples: q_t %lld, q_s %lld out of range (at least 1 each)", (long long)q_t, (long long)q_s);
+    pf_ctx* c = h->ctx;
+    PF_HIP(hipSetDevice(c->device));
+    fmap_free_samples(h);
+    int32_t bad = 0;
+    {
+        Scratch s(c->stream);
+        const int32_t K = h->K;
+        h->q_t = q_t, h->q_s = q_s;
+        h->ld_qs = (q_s + PF_WAVE - 1) & ~(int64_t)(PF_WAVE - 1);
+        const size_t q_count = (size_t)(h->ld_qs * pad_d(K));
+        h->A = s.keep<double>((size_t)(q_s * K));
+        h->B = s.keep<double>((size_t)(q_t * K));
+        h->ones = s.keep<double>((size_t)q_s);
+        h->ident = s.keep<int32_t>((size_t)q_s);
+        h->T_sub = s.keep<int32_t>((size_t)q_s);
+        h->d2_sub = s.keep<double>((size_t)q_s);
+        h->Q_sub = s.keep<double>(q_count);
+        h->G = s.keep<double>((size_t)K * K);
+        h->R = s.keep<double>((size_t)K * K);
+        int64_t* d_in_t = s.get<int64_t>((size_t)q_t);
+        int64_t* d_in_s = s.get<int64_t>((size_t)q_s);
+        int32_t* d_rows_t = s.get<int32_t>((size_t)q_t);
+        int32_t* d_rows_s = s.get<int32_t>((size_t)q_s);
+        int32_t* d_bad = s.get<int32_t>(1);
+        s.upload(d_in_t, S_t, (size_t)q_t);
+        s.upload(d_in_s, S_s, (size_t)q_s);
+        s.zero(d_bad, sizeof(int32_t));
+        s.zero(h->Q_sub, sizeof(double) * q_count);
+        if (s.ok()) {
+            // an index out of range is flagged and read as row 0: the gathers stay inside the bases either way
+            k_fmap_set_map<<<pf_blocks(q_t), PF_BLOCK, 0, s.st>>>(d_in_t, q_t, h->n_t, d_rows_t, d_bad);
+            k_fmap_set_map<<<pf_blocks(q_s), PF_BLOCK, 0, s.st>>>(d_in_s, q_s, h->n_s, d_rows_s, d_bad);
+            k_fmap_gather_rows<<<pf_blocks(q_t * K), PF_BLOCK, 0, s.st>>>(h->phi_t, K, d_rows_t, q_t, h->B);
+            k_fmap_gather_rows<<<pf_blocks(q_s * K), PF_BLOCK, 0, s.st>>>(h->phi_s, K, d_rows_s, q_s, h->A);
+            k_fmap_unit<<<pf_blocks(q_s), PF_BLOCK, 0, s.st>>>(h->ones, h->ident, q_s);
+            s.launched();
+        }
+        s.download(&bad, d_bad, 1);
+        s.sync();
+        if (!s.ok()) {
+            pf_set_error("pf_fmap_set_samples: %s", hipGetErrorString(s.err));
+            fmap_free_samples(h);
+            return PF_E_HIP;
+        }
+    }
+    if (bad != 0) {
+        pf_set_error("pf_fmap_set_samples: an index lies outside 0 .. n_t - 1 = %lld (target) or 0 .. n_s - 1 = %lld (source)",
+                     (long long)(h->n_t - 1), (long long)(h->n_s - 1));
+        fmap_free_samples(h);
+        return PF_E_ARG;
+    }
+    h->has_samples = true;
+    return PF_OK;
+}
+
+int pf_fmap_zoomout_sampled(pf_fmap* h, int32_t k_start, int32_t k_end, int32_t step, int32_t n_iter_at_end, double* C_out) {
+    PF_CHECK(h != nullptr, PF_E_ARG, "pf_fmap_zoomout_sampled: NULL handle");
+    PF_CHECK(k_start >= 1 && k_start <= k_end && k_end <= h->K && step >= 1 && n_iter_at_end >= 0, PF_E_ARG,
+             "pf_fmap_zoomout_sampled: k_start %d, k_end %d (K = %d), step %d, n_iter_at_end %d out of range", k_start, k_end, h->K, step,
+             n_iter_at_end);
+    PF_CHECK(h->has_samples, PF_E_STATE, "pf_fmap_zoomout_sampled: no samples yet (pf_fmap_set_samples)");
+    PF_CHECK(h->has_T, PF_E_STATE, "pf_fmap_zoomout_sampled: no point map yet (pf_fmap_set_p2p)");
+    PF_CHECK(h->q_s >= k_end, PF_E_ARG, "pf_fmap_zoomout_sampled: %lld source samples cannot determine a fit with k_end = %d functions",
+             (long long)h->q_s, k_end);
+    pf_ctx* c = h->ctx;
+    PF_HIP(hipSetDevice(c->device));
+    const FmapView sub = fmap_sub(h);
+    FmapView gram = sub;  // A^T A: the identity map into A itself
+    gram.phi_t = h->A, gram.n_t = h->q_s, gram.T = h->ident;
+    std::vector<double> G((size_t)k_end * k_end), X((size_t)k_end * k_end);
+    PF_TRY(fmap_project(h, gram, k_end, k_end, h->G));
+    PF_HIP(hipMemcpyAsync(G.data(), h->G, sizeof(double) * G.size(), hipMemcpyDeviceToHost, c->stream));
+    PF_HIP(hipStreamSynchronize(c->stream));  // once per call: no copy into G is in flight if a later step fails
+    int32_t k = k_start, extra = n_iter_at_end;
+    PF_TRY(fmap_project(h, fmap_full(h), k, k, h->C));
+    for (;;) {
+        PF_TRY(fmap_convert(h, sub, k, k));
+        const bool last = k == k_end && extra == 0;
+        if (k == k_end && !last) --extra;
+        k = std::min(k + step, k_end);
+        PF_TRY(fmap_project(h, sub, k, k, h->R));
+        const size_t count = (size_t)k * k;
+        PF_HIP(hipMemcpyAsync(X.data(), h->R, sizeof(double) * count, hipMemcpyDeviceToHost, c->stream));
+        PF_HIP(hipStreamSynchronize(c->stream));  // the one wait of the round
+        // G's entries carry the rounding of q_s terms each, the pivot's sum that of k more
+        PF_CHECK(chol_solve(G.data(), k_end, k, (double)(h->q_s + k) * 2.220446049250313e-16, X.data()), PF_E_DEGENERATE,
+                 "pf_fmap_zoomout_sampled: A^T A is not positive definite at k = %d: the %lld source samples are too few or degenerate for "
+                 "this many basis functions", k, (long long)h->q_s);
+        PF_HIP(hipMemcpyAsync(h->C, X.data(), sizeof(double) * count, hipMemcpyHostToDevice, c->stream));
+        PF_HIP(hipStreamSynchronize(c->stream));  // X is written again in the next round
+        h->c_ks = h->c_kt = k;
+        if (last) break;
+    }
+    PF_TRY(fmap_convert(h, fmap_full(h), k_end, k_end));
+    if (C_out) memcpy(C_out, X.data(), sizeof(double) * (size_t)k_end * k_end);
+    PF_HIP(hipStreamSynchronize(c->stream));
+    return PF_OK;
 }
 
 }  // extern "C"

@@ -323,18 +323,19 @@ class Focusr(object):
             self.graph_target.points, self.corresponding_target_vertices_for_each_source_pt,
             self.corresponding_target_bary_for_each_source_pt)
 
-    def refine_correspondences_zoomout(self, k_start=4, k_end=30, step=1):
+    def refine_correspondences_zoomout(self, k_start=4, k_end=30, step=1, n_samples=None):
         """ZoomOut refinement of `corresponding_target_idx_for_each_source_pt` on the two meshes' cotangent
         Laplace-Beltrami bases (`zoomout_correspondences`): sets `zoomout_target_idx_for_each_source_pt` (int64, one
         target vertex per source vertex) and `functional_map` (k_end x k_end).  Opt-in: `align_maps()` does not call it,
-        and it changes no other attribute."""
+        and it changes no other attribute.  `n_samples`: the rounds run on that many farthest-point samples of each
+        mesh (fast ZoomOut); None: on every vertex."""
         from .functional_maps import zoomout_correspondences
 
         if self.corresponding_target_idx_for_each_source_pt is None:
             raise ValueError("no correspondences yet: run align_maps() first")
         T, Cm = zoomout_correspondences(self.graph_target.vtk_mesh, self.graph_source.vtk_mesh,
                                         np.asarray(self.corresponding_target_idx_for_each_source_pt, dtype=np.int64),
-                                        k_start=k_start, k_end=k_end, step=step, ctx=self._ctx)
+                                        k_start=k_start, k_end=k_end, step=step, n_samples=n_samples, ctx=self._ctx)
         self.zoomout_target_idx_for_each_source_pt = T
         self.functional_map = Cm
 

@@ -17,12 +17,18 @@ uploaded once, the projection is a gathered weighted Gram matrix reduced in a fi
 two calls give the same bits), the search is exact (the library's 1-NN search for k_t <= 16, a register- and LDS-tiled
 exhaustive scan up to 128 dimensions), squared distances summed left to right, the lowest index on exact ties.
 At most 128 basis functions.
+
+Fast ZoomOut (Melzi et al. 2019, 4.2.3): the same loop on a few hundred or thousand farthest-point samples of each surface
+(`sampling.farthest_point_sampling`), C fitted there by least squares - exact for an exact map whatever the sampling - and
+one conversion to a full-resolution point map at the end: `zoomout_refine(..., samples=(S_t, S_s))`,
+`fast_zoomout_correspondences`.
 """
 import numpy as np
 
 from . import _hip
 
-__all__ = ["functional_map_from_p2p", "p2p_from_functional_map", "zoomout_refine", "zoomout_correspondences"]
+__all__ = ["functional_map_from_p2p", "p2p_from_functional_map", "zoomout_refine", "zoomout_correspondences",
+           "fast_zoomout_correspondences"]
 
 
 def _handle(phi_t, phi_s, mass_s, K, ctx):
@@ -75,26 +81,44 @@ def p2p_from_functional_map(phi_t, phi_s, C, return_d2=False, ctx=None):
         return h.get_p2p(return_d2=return_d2)
 
 
-def zoomout_refine(phi_t, phi_s, mass_s, T0, k_start, k_end, step=1, n_iter_at_end=0, ctx=None):
+def zoomout_refine(phi_t, phi_s, mass_s, T0, k_start, k_end, step=1, n_iter_at_end=0, samples=None, ctx=None):
     """(T, C): the point map T0 refined by ZoomOut from k_start to k_end basis functions (`n_iter_at_end` more rounds
     at k_end), and the last functional map, k_end x k_end.  k_start == k_end is one ICP-style round.  One upload, one
-    download; the loop runs in `pf_fmap_zoomout`."""
+    download; the loop runs in `pf_fmap_zoomout`.
+
+    `samples=(S_t, S_s)`, vertex indices into the target and into the source (at least k_end of the source), runs the
+    rounds on those rows alone (`pf_fmap_zoomout_sampled`): the first C is the projection of T0 at full resolution, every
+    later one the least-squares fit (A^T A) C = A^T B[Tsub] on the samples with A = phi_s[S_s], B = phi_t[S_t], and T is
+    the conversion of the last C at full resolution.  `PfError` if the samples do not determine the fit.  With `None`
+    nothing changes."""
     k_start, k_end, step = int(k_start), int(k_end), int(step)
     if not (1 <= k_start <= k_end and step >= 1 and n_iter_at_end >= 0):
         raise ValueError("need 1 <= k_start <= k_end, step >= 1, n_iter_at_end >= 0")
     with _handle(phi_t, phi_s, mass_s, k_end, ctx) as h:
         h.set_p2p(T0)
-        C = h.zoomout(k_start, k_end, step, int(n_iter_at_end))
+        if samples is None:
+            C = h.zoomout(k_start, k_end, step, int(n_iter_at_end))
+        else:
+            S_t, S_s = samples
+            h.set_samples(S_t, S_s)
+            C = h.zoomout_sampled(k_start, k_end, step, int(n_iter_at_end))
         return h.get_p2p(), C
 
 
-def zoomout_correspondences(target_mesh, source_mesh, T0, k_start=4, k_end=30, step=1, ctx=None):
+def zoomout_correspondences(target_mesh, source_mesh, T0, k_start=4, k_end=30, step=1, n_samples=None, ctx=None):
     """(T, C): `zoomout_refine` on the two meshes' own cotangent Laplace-Beltrami bases (`laplace_beltrami_spectrum`,
     k_end functions each) and the source's lumped vertex areas (`cotangent_laplacian`).  Raises `ValueError` if the
     eigensolver delivers fewer than k_end pairs for a mesh.  The largest k_end the tests ask for is 20 (a renumbered and
     moved 700-vertex blob, 30 % of T0 wrong, to be recovered at every vertex); that test has not run on an MI355X yet
-    (DESIGN.md 10b), and the solver is not tuned for more pairs here."""
+    (DESIGN.md 10b), and the solver is not tuned for more pairs here.  `n_samples`: the rounds run on that many
+    farthest-point samples of each mesh (`fast_zoomout_correspondences`); None: on every vertex."""
     from .laplace_beltrami import cotangent_laplacian, laplace_beltrami_spectrum
+    from .sampling import farthest_point_sampling
+
+    samples = None
+    if n_samples is not None:
+        samples = tuple(farthest_point_sampling(mesh, min(int(n_samples), len(mesh.points)), ctx=ctx)
+                        for mesh in (target_mesh, source_mesh))
 
     bases = []
     for name, mesh in (("target", target_mesh), ("source", source_mesh)):
@@ -104,4 +128,14 @@ def zoomout_correspondences(target_mesh, source_mesh, T0, k_start=4, k_end=30, s
                              % (vecs.shape[1], int(k_end), name))
         bases.append(vecs)
     _, mass_s = cotangent_laplacian(source_mesh, ctx=ctx)
-    return zoomout_refine(bases[0], bases[1], mass_s, T0, k_start, k_end, step=step, ctx=ctx)
+    return zoomout_refine(bases[0], bases[1], mass_s, T0, k_start, k_end, step=step, samples=samples, ctx=ctx)
+
+
+def fast_zoomout_correspondences(target_mesh, source_mesh, T0, k_start=4, k_end=30, step=1, n_samples=1000, ctx=None):
+    """(T, C): `zoomout_correspondences` with the rounds on min(n_samples, n) farthest-point samples of each mesh's 3-D
+    points: the work of a round no longer grows with the product of the vertex counts, only the one conversion at the end
+    does.  n_samples must be at least k_end (`PfError` otherwise)."""
+    if n_samples is None or int(n_samples) < 1:
+        raise ValueError("n_samples must be a positive number")
+    return zoomout_correspondences(target_mesh, source_mesh, T0, k_start=k_start, k_end=k_end, step=step, n_samples=int(n_samples),
+                                   ctx=ctx)

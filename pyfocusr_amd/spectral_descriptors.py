@@ -175,13 +175,15 @@ def functional_map_from_descriptors(vals_t, phi_t, mass_t, vals_s, phi_s, mass_s
 
 
 def descriptor_correspondences(target_mesh, source_mesh, k_init=8, k_end=20, kinds=("hks", "wks"), n_samples=100, mu=0.1,
-                               step=1, ctx=None):
+                               step=1, n_zoomout_samples=None, ctx=None):
     """(T, C): dense correspondences of two meshes from their Laplace-Beltrami spectra alone - no initial map.  Both
     spectra (`laplace_beltrami_spectrum`, k_end pairs) and lumped masses (`cotangent_laplacian`), a functional map
     fitted to the descriptors at k_init, its point map, and `zoomout_refine` from k_init to k_end.  T[i] is the target
     vertex of source vertex i; C is the last functional map, k_end x k_end.  Raises `ValueError` if the eigensolver
     delivers fewer than k_end pairs for a mesh.  Intrinsic symmetries of the surface are not resolved: a symmetric
-    shape can come back mirrored."""
+    shape can come back mirrored.  `n_zoomout_samples`: the refinement's rounds run on that many farthest-point
+    samples of each mesh (`zoomout_refine(samples=...)`; `n_samples` is taken: it counts the descriptors' samples); None:
+    on every vertex."""
     from .functional_maps import p2p_from_functional_map, zoomout_refine
     from .laplace_beltrami import cotangent_laplacian, laplace_beltrami_spectrum
 
@@ -200,7 +202,13 @@ def descriptor_correspondences(target_mesh, source_mesh, k_init=8, k_end=20, kin
     C0 = functional_map_from_descriptors(vals_t, phi_t, mass_t, vals_s, phi_s, mass_s, k_init, kinds=kinds, n_samples=n_samples,
                                          mu=mu, ctx=ctx)
     T0 = p2p_from_functional_map(phi_t, phi_s, C0, ctx=ctx)
-    return zoomout_refine(phi_t, phi_s, mass_s, T0, k_init, k_end, step=step, ctx=ctx)
+    samples = None
+    if n_zoomout_samples is not None:
+        from .sampling import farthest_point_sampling
+
+        samples = tuple(farthest_point_sampling(mesh, min(int(n_zoomout_samples), len(mesh.points)), ctx=ctx)
+                        for mesh in (target_mesh, source_mesh))
+    return zoomout_refine(phi_t, phi_s, mass_s, T0, k_init, k_end, step=step, samples=samples, ctx=ctx)
 
 
 def signature_on_mesh(mesh, F, name):
