@@ -367,7 +367,9 @@ int pf_knn1_blocks(pf_ctx* ctx, const double* ref_block, int64_t n_ref, int32_t 
  * m_t / m_s <= 16384 sampled rows of the target / source graph (rows_t / rows_s), the first k eigenmaps of each as
  * final[:, col[c]] * sign[c] (the column permutation and sign flips earlier eigsort calls left, identity at first).
  * out[4][k][k] = c_hist, c_hist_f, c_spatial, c_spatial_f (row = target map, column = source map); idx_out[m_t] = the
- * sampled source point nearest to each sampled target point (min-max normalised xyz, eigsort.py:203-204). */
+ * sampled source point nearest to each sampled target point (min-max normalised xyz, eigsort.py:203-204).
+ * A sample without extent along an axis (a planar mesh, one sampled row) normalises to NaN there: idx_out is then
+ * 0x7fffffff throughout (pf_knn1's answer for a query nothing compares with) and c_spatial / c_spatial_f are NaN. */
 int pf_eigsort_costs(pf_graph* g_target, pf_graph* g_source, const int64_t* rows_t, int64_t m_t, const int64_t* rows_s, int64_t m_s,
                      int32_t k, const int32_t* col_t, const double* sign_t, const int32_t* col_s, const double* sign_s, double* out,
                      int64_t* idx_out);

@@ -406,6 +406,21 @@ def _c_f64(a, shape=None):
     return a
 
 
+def degenerate_extent_message(target_points, source_points):
+    """The text of the ValueError eigsort raises when its spatial 1-NN found no neighbour: which sample has no extent
+    along which axis (raw points: max == min; min-max normalised points: NaN)."""
+    found = []
+    for name, pts in (("target", target_points), ("source", source_points)):
+        pts = np.asarray(pts, dtype=np.float64).reshape(-1, 3)
+        with np.errstate(invalid="ignore"):
+            flat = np.isnan(pts).any(axis=0) | ~(np.max(pts, axis=0) > np.min(pts, axis=0))
+        if flat.any():
+            found.append("the %s sample (%d points) has no extent along %s" % (name, len(pts), ", ".join("xyz"[a] for a in np.where(flat)[0])))
+    return ("eigsort: degenerate extent - %s: the min-max normalisation of the sampled points divides by zero (a planar "
+            "mesh, or a sample of one point), so no point has a nearest neighbour"
+            % ("; ".join(found) if found else "the sampled points do not compare"))
+
+
 class Context(object):
     """One HIP stream on one device."""
 
@@ -603,6 +618,10 @@ class Context(object):
         _check(self._lib.pf_eigsort_costs(dev_t._h, dev_s._h, rows_t.ctypes.data_as(_i64p), len(rows_t), rows_s.ctypes.data_as(_i64p),
                                           len(rows_s), int(k), col_t.ctypes.data_as(_i32p), _f64(sign_t), col_s.ctypes.data_as(_i32p),
                                           _f64(sign_s), _f64(out), idx.ctypes.data_as(_i64p)))
+        if len(idx) and (idx.min() < 0 or idx.max() >= len(rows_s)):
+            # a sample without extent along an axis normalises to NaN there; the search then answers every query with
+            # 0x7fffffff and the kernel makes the spatial costs NaN instead of reading at that index
+            raise ValueError(degenerate_extent_message(dev_t.point_rows(rows_t), dev_s.point_rows(rows_s)))
         return out, idx
 
     def knn1_blocks(self, ref_ptr, n_ref, ref_stride, qry_ptr, n_qry, qry_stride, col_ref, scale_ref, col_qry, scale_qry,

@@ -161,7 +161,9 @@ __global__ __launch_bounds__(ES_RED_THREADS) void k_es_w1(const double* __restri
     }
 }
 
-// block (i, j): out[2][i][j] = sqrt(sum (S_j[idx] - T_i)^2) / m, out[3][i][j] the same with -S_j
+// block (i, j): out[2][i][j] = sqrt(sum (S_j[idx] - T_i)^2) / m, out[3][i][j] the same with -S_j.  An index outside
+// [0, ms) - the search's 0x7fffffff for a query nothing compares with: a sample without extent on an axis normalises to
+// NaN - is never used as an address: its term, and with it the cost, is NaN (the Python side raises on it)
 __global__ __launch_bounds__(ES_RED_THREADS) void k_es_spatial(const double* __restrict__ vals_t, const double* __restrict__ vals_s,
                                                                const int64_t* __restrict__ idx, int64_t m, int64_t ms, int32_t k,
                                                                double* __restrict__ out) {
@@ -169,7 +171,8 @@ __global__ __launch_bounds__(ES_RED_THREADS) void k_es_spatial(const double* __r
     const int i = blockIdx.x / k, j = blockIdx.x - i * k;
     double a = 0.0, f = 0.0;
     for (int64_t r = threadIdx.x; r < m; r += ES_RED_THREADS) {
-        const double t = vals_t[(int64_t)i * m + r], s = vals_s[(int64_t)j * ms + idx[r]];
+        const int64_t nn = idx[r];
+        const double t = vals_t[(int64_t)i * m + r], s = (nn >= 0 && nn < ms) ? vals_s[(int64_t)j * ms + nn] : NAN;
         const double d0 = s - t, d1 = -s - t;
         a += d0 * d0;
         f += d1 * d1;

@@ -860,11 +860,11 @@ int sort_points(pf_ctx* c, const double* pts, int64_t n, int d, int morton, int 
 
 extern "C" {
 
-// device buffers and grid parameters of a (n_ref, n_qry, d) problem; the coordinates are filled in by the caller
-static int knn_prepare(pf_ctx* c, int64_t n_ref, int64_t n_qry, int32_t d) {
+// device buffers and grid parameters of a (n_ref, n_qry, d) problem with k neighbours per query; the coordinates are
+// filled in by the caller.  k is an argument and is stored (knn_k) only once every check has passed: a refused call
+// leaves nothing behind for the next one.
+static int knn_prepare(pf_ctx* c, int64_t n_ref, int64_t n_qry, int32_t d, int32_t k) {
     PF_CHECK(c != nullptr, PF_E_ARG, "pf_knn_upload: ctx is NULL");
-    const int32_t k = c->knn_k_next;
-    c->knn_k_next = 1;
     PF_CHECK(k >= 1 && k <= 4 && k <= n_ref, PF_E_ARG, "pf_knn: k = %d out of range (1..4, <= n_ref)", k);
     PF_CHECK(n_ref > 0 && n_ref < ((int64_t)1 << 31) && n_qry > 0 && n_qry < ((int64_t)1 << 31) && d >= 1 && d <= 16, PF_E_ARG,
              "pf_knn_upload: n_ref %lld, n_qry %lld, d %d out of range (1 <= d <= 16)", (long long)n_ref, (long long)n_qry, d);
@@ -913,15 +913,19 @@ __global__ __launch_bounds__(PF_BLOCK) void k_coords_from_final(const double* __
     out[e] = fin[i * fc + m.col[c]] * m.scale[c];
 }
 
-int pf_knn_upload(pf_ctx* c, const double* ref, int64_t n_ref, const double* qry, int64_t n_qry, int32_t d) {
+static int knn_upload_k(pf_ctx* c, const double* ref, int64_t n_ref, const double* qry, int64_t n_qry, int32_t d, int32_t k) {
     PF_CHECK(c && ref && qry, PF_E_ARG, "pf_knn_upload: NULL argument");
-    PF_TRY(knn_prepare(c, n_ref, n_qry, d));
+    PF_TRY(knn_prepare(c, n_ref, n_qry, d, k));
     hipStream_t st = c->stream;
     PF_HIP(hipMemcpyAsync(c->knn_ref, ref, sizeof(double) * n_ref * d, hipMemcpyHostToDevice, st));
     PF_HIP(hipMemcpyAsync(c->knn_qry, qry, sizeof(double) * n_qry * d, hipMemcpyHostToDevice, st));
     PF_HIP(hipStreamSynchronize(st));
     c->knn_ready = true;
     return PF_OK;
+}
+
+int pf_knn_upload(pf_ctx* c, const double* ref, int64_t n_ref, const double* qry, int64_t n_qry, int32_t d) {
+    return knn_upload_k(c, ref, n_ref, qry, n_qry, d, 1);
 }
 
 int pf_knn_run(pf_ctx* c) {
@@ -1086,9 +1090,7 @@ int pf_knn_download(pf_ctx* c, int64_t* idx_out, double* d2_out) {
 
 int pf_knn(pf_ctx* c, const double* ref, int64_t n_ref, const double* qry, int64_t n_qry, int32_t d, int32_t k,
            int64_t* idx_out, double* d2_out) {
-    PF_CHECK(c != nullptr, PF_E_ARG, "pf_knn: ctx is NULL");
-    c->knn_k_next = k;
-    PF_TRY(pf_knn_upload(c, ref, n_ref, qry, n_qry, d));
+    PF_TRY(knn_upload_k(c, ref, n_ref, qry, n_qry, d, k));
     PF_TRY(pf_knn_run(c));
     return pf_knn_download(c, idx_out, d2_out);
 }
@@ -1104,7 +1106,7 @@ int pf_knn1(pf_ctx* c, const double* ref, int64_t n_ref, const double* qry, int6
 static int knn1_blocks_run(pf_ctx* c, const double* ref_block, int64_t n_ref, int32_t ref_stride, const double* qry_block, int64_t n_qry,
                            int32_t qry_stride, int32_t d, const int32_t* col_ref, const double* scale_ref, const int32_t* col_qry,
                            const double* scale_qry) {
-    PF_TRY(knn_prepare(c, n_ref, n_qry, d));
+    PF_TRY(knn_prepare(c, n_ref, n_qry, d, 1));
     hipStream_t st = c->stream;
     CoordMap mr{}, mq{};
     for (int32_t k = 0; k < d; ++k) {

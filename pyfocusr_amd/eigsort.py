@@ -248,6 +248,8 @@ class eigsort(object):
             self.idx_source_for_each_target_pt = dev[1]
             return
         idx = self._ctx().knn1(self.rand_source_points, self.rand_target_points)
+        if len(idx) and (idx.min() < 0 or idx.max() >= len(self.rand_source_points)):  # the device path raises the same
+            raise ValueError(_hip.degenerate_extent_message(self.rand_target_points, self.rand_source_points))
         self.idx_source_for_each_target_pt = idx
         m = self.rand_target_eig_vecs.shape[0]
         k = self.n_features

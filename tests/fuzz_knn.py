@@ -11,25 +11,12 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from pyfocusr_amd import _hip  # noqa: E402
 
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from _knn_ref import brute  # noqa: E402  (the left-to-right brute force, shared with tests/test_tail_kernels.py)
+
 ctx = _hip.default_context()
 rng = np.random.default_rng(int(sys.argv[1]))
 N = int(sys.argv[2])
-
-
-def brute(ref, qry, K):
-    idx = np.empty((len(qry), K), dtype=np.int64)
-    d2 = np.empty((len(qry), K))
-    for lo in range(0, len(qry), 512):
-        q = qry[lo:lo + 512]
-        acc = None
-        for c in range(ref.shape[1]):  # left to right, separate multiply and add
-            df = q[:, None, c] - ref[None, :, c]
-            sq = df * df
-            acc = sq if acc is None else acc + sq
-        order = np.lexsort((np.broadcast_to(np.arange(len(ref)), acc.shape), acc), axis=1)[:, :K]
-        idx[lo:lo + 512] = order
-        d2[lo:lo + 512] = np.take_along_axis(acc, order, axis=1)
-    return idx, d2
 
 
 fails, t0 = 0, time.time()
