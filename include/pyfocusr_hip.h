@@ -351,6 +351,18 @@ int pf_knn_wave_stats(pf_ctx* ctx, double* sum_us, double* max_us, int64_t* wave
  * Focusr.get_weighted_final_node_locations (focusr.py:409-412).  idx_out / d2_out: n_qry x k row-major. */
 int pf_knn(pf_ctx* ctx, const double* ref, int64_t n_ref, const double* qry, int64_t n_qry, int32_t d, int32_t k,
            int64_t* idx_out, double* d2_out);
+/* k nearest neighbours for 1 <= k <= 64 (k <= n_ref) in 1 <= d <= 128 coordinates; n_ref and n_qry in 1 .. 2^31 - 1.
+ * d2(q, r) is the sum over the coordinates, from coordinate 0 on, of (q_c - r_c)^2 with separate multiply and add.  Per
+ * query: the k references with the smallest (d2, index), ascending - equal distances go to the lower index.  idx_out and
+ * d2_out (nullable) are n_qry x k row-major; indices and distances are the bits of a brute force, and two calls give
+ * the same bits.  A query with a NaN coordinate compares with nothing: its row is k times (0x7fffffff, +inf), pf_knn's
+ * rule.  Non-finite reference coordinates: unspecified result, no fault.  Outside the limits, or with a NULL pointer
+ * (d2_out excepted): PF_E_ARG, nothing is launched and the ctx stays usable.
+ * d <= 16: a list of the k best per query on the box hierarchy of pf_knn_tree.hip, which then takes n_ref <= 2^31 - 64
+ * as it does for pf_knn1; beyond: the same list over an exhaustive scan.  pf_knn (k <= 4, d <= 4) and pf_knn1_wide are
+ * unchanged.  pf_timing_get's knn_ms is the device time of the last call, transfers excluded. */
+int pf_knn_topk(pf_ctx* ctx, const double* ref, int64_t n_ref, const double* qry, int64_t n_qry, int32_t d, int32_t k,
+                int64_t* idx_out, double* d2_out);
 /* focusr.py:351-353 with the coordinates taken from the two graphs' resident pf_finalize_vectors blocks instead of
  * host arrays: ref[i][c] = final_ref[i][col_ref[c]] * scale_ref[c], qry likewise (c < d) - the column selection, sign
  * flips and permutation of eigsort (eigsort.py:108-122) and the spectral weights (focusr.py:481-501) are folded into

@@ -13,7 +13,8 @@ from .eigsort import eigsort
 from .focusr import *  # noqa: F401,F403
 from .graph import *  # noqa: F401,F403
 from .functional_maps import (fast_zoomout_correspondences, functional_map_from_p2p, p2p_from_functional_map,
-                              zoomout_correspondences, zoomout_refine)
+                              soft_p2p_from_functional_map, zoomout_correspondences, zoomout_refine)
+from .neighbours import inverse_distance_average, k_nearest_neighbours
 from .laplace_beltrami import cotangent_laplacian, laplace_beltrami_spectrum, mean_curvature, mean_curvature_normals
 from .sampling import farthest_point_sampling, voronoi_masses
 from .ray_casting import (hit_points, ray_crossings, ray_mesh_intersections, thickness_along_normals,

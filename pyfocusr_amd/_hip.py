@@ -138,6 +138,7 @@ SIGNATURES = {
     "pf_mean_filter": (C.c_int, [C.c_void_p, _f64p, C.c_int32, C.c_int32, _f64p]),
     "pf_knn1": (C.c_int, [C.c_void_p, _f64p, C.c_int64, _f64p, C.c_int64, C.c_int32, _i64p, _f64p]),
     "pf_knn": (C.c_int, [C.c_void_p, _f64p, C.c_int64, _f64p, C.c_int64, C.c_int32, C.c_int32, _i64p, _f64p]),
+    "pf_knn_topk": (C.c_int, [C.c_void_p, _f64p, C.c_int64, _f64p, C.c_int64, C.c_int32, C.c_int32, _i64p, _f64p]),
     "pf_knn1_graphs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, _i32p, _f64p, _i32p, _f64p, _i64p, _f64p]),
     "pf_knn1_blocks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_int32,
                                  _i32p, _f64p, _i32p, _f64p, _i64p, _f64p]),
@@ -421,6 +422,23 @@ def degenerate_extent_message(target_points, source_points):
             % ("; ".join(found) if found else "the sampled points do not compare"))
 
 
+KNN_TOPK_MAX_K = 64    # the limits of pf_knn_topk
+KNN_TOPK_MAX_D = 128
+
+
+def check_knn_topk(ref, qry, k):
+    """The argument checks of `Context.knn_topk`, which need no library: ValueError, or k as an int."""
+    ref_shape, qry_shape = np.shape(ref), np.shape(qry)
+    if len(ref_shape) != 2 or len(qry_shape) != 2 or ref_shape[1] != qry_shape[1]:
+        raise ValueError("ref and qry must be (n, d) arrays with equal d")
+    if not 1 <= ref_shape[1] <= KNN_TOPK_MAX_D:
+        raise ValueError("d = %d out of range (1 .. %d)" % (ref_shape[1], KNN_TOPK_MAX_D))
+    k = int(k)
+    if not 1 <= k <= min(KNN_TOPK_MAX_K, ref_shape[0]):
+        raise ValueError("k = %d out of range (1 .. min(%d, n_ref = %d))" % (k, KNN_TOPK_MAX_K, ref_shape[0]))
+    return k
+
+
 class Context(object):
     """One HIP stream on one device."""
 
@@ -586,6 +604,18 @@ class Context(object):
         _check(self._lib.pf_knn(self._h, _f64(ref), ref.shape[0], _f64(qry), qry.shape[0], ref.shape[1], int(k),
                                 idx.ctypes.data_as(_i64p), _f64(d2)))
         return idx, d2
+
+    def knn_topk(self, ref, qry, k, return_d2=True):
+        """The k nearest `ref` rows of every `qry` row (`pf_knn_topk`): idx (n_qry, k) int64 and, with `return_d2`, the
+        squared distances (n_qry, k), ascending by (distance, index); 1 <= k <= min(64, n_ref), 1 <= d <= 128.  The bits
+        of a brute force.  A query with a NaN coordinate gets k times (0x7fffffff, inf)."""
+        k = check_knn_topk(ref, qry, k)
+        ref, qry = _c_f64(ref), _c_f64(qry)
+        idx = np.empty((qry.shape[0], k), dtype=np.int64)
+        d2 = np.empty((qry.shape[0], k), dtype=np.float64) if return_d2 else None
+        _check(self._lib.pf_knn_topk(self._h, _f64(ref), ref.shape[0], _f64(qry), qry.shape[0], ref.shape[1], k,
+                                     idx.ctypes.data_as(_i64p), _f64(d2) if return_d2 else None))
+        return (idx, d2) if return_d2 else idx
 
     def knn1_graphs(self, dev_ref, dev_qry, col_ref, scale_ref, col_qry, scale_qry, return_d2=False):
         """`knn1` on coordinates built on the device from the two graphs' resident eigenvector blocks:

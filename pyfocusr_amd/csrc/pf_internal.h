@@ -449,6 +449,10 @@ static inline int32_t pf_window_rows(int64_t n_pad) { return n_pad <= 262144 ? 1
 int pf_knn1_device(pf_ctx* c, const double* ref_block, int64_t n_ref, int32_t ref_stride, const double* qry_block, int64_t n_qry,
                    int32_t qry_stride, int32_t d);
 
+// pf_knn.hip: the per-axis [min, max] of n row-major points of depth d <= 16, order-preserving integer encoding, queued on
+// st: ext[a] the minimum of axis a, ext[16 + a] its maximum
+int pf_knn_extent(hipStream_t st, const double* pts, int64_t n, int32_t d, unsigned long long* ext);
+
 // pf_knn_tree.hip: the 1-NN search of pf_knn_run through a bounding-box hierarchy over all d coordinates
 // (spectral coordinates of 250k blob pairs, ms grid / hierarchy: d = 6: 1.15 / 1.90, 7: 1.98 / 1.91, 8: 29.5 / 8.8, 10: 6.3 / 2.1;
 // 1M pair, d = 10: 133 / 19.6 - profiles/r03_knn_hierarchy.md)

@@ -957,13 +957,11 @@ int pf_knn_run(pf_ctx* c) {
         c->knn_done = true;
         return PF_OK;
     }
-    PF_HIP(hipMemsetAsync(c->knn_ext, 0xff, 16 * sizeof(unsigned long long), st));
-    PF_HIP(hipMemsetAsync(c->knn_ext + 16, 0x00, 16 * sizeof(unsigned long long), st));
+    PF_TRY(pf_knn_extent(st, c->knn_ref, c->knn_nref, d, c->knn_ext));
     const int res = c->knn_res;
     const int64_t n_cells = d == 1 ? res : (int64_t)res * res;
     int cell_bits = 1;
     while (((int64_t)1 << cell_bits) < n_cells) ++cell_bits;
-    k_extent<<<256, PF_BLOCK, 0, st>>>(c->knn_ref, c->knn_nref, d, c->knn_ext);
     // deep coordinates (k = 1): a grid over two axes prunes two of d coordinates; the box hierarchy prunes with all of them
     const bool tree = c->knn_k == 1 && (c->knn_mode == 2 || (c->knn_mode == 0 && d >= PF_KNN_TREE_MIN_D));
     if (tree) {
@@ -1152,6 +1150,13 @@ int pf_final_device(pf_graph* g, double** block, int64_t* n_rows, int32_t* n_col
 }
 
 }  // extern "C"
+
+int pf_knn_extent(hipStream_t st, const double* pts, int64_t n, int32_t d, unsigned long long* ext) {
+    PF_HIP(hipMemsetAsync(ext, 0xff, 16 * sizeof(unsigned long long), st));
+    PF_HIP(hipMemsetAsync(ext + 16, 0x00, 16 * sizeof(unsigned long long), st));
+    k_extent<<<256, PF_BLOCK, 0, st>>>(pts, n, d, ext);
+    return PF_OK;
+}
 
 int pf_knn1_device(pf_ctx* c, const double* ref_block, int64_t n_ref, int32_t ref_stride, const double* qry_block, int64_t n_qry,
                    int32_t qry_stride, int32_t d) {

@@ -25,6 +25,21 @@
 // rounding, so the computed box distance is <= the computed distance of every point in it: a box is skipped only when its
 // distance is > a query's bound - no candidate that could win or tie is ever dropped, and the minimum of (distance, index)
 // does not depend on the order of the visits.  Indices and distances are bit-identical to a brute force.
+//
+// k nearest neighbours (pf_knn_topk, 1 <= k <= 64).  The same hierarchy (tree_build, shared by both searches), the same
+// groups, the same box_d2; the single best of a query becomes a LIST of its 64 smallest (distance, index) pairs, kept
+// across the lanes of the wave: lane j holds the j-th smallest, (+inf, 0x7fffffff) while there is none.  The k-th entry is
+// the query's bound.  After a leaf's 64 distances are known the lanes whose (distance, index) is lexicographically below
+// the bound are collected with a ballot - empty for most leaves - and go in one at a time: the candidate is broadcast,
+// every lane compares it with its own entry, and the lanes at or behind its place take their left neighbour's entry.  No
+// LDS, no register array indexed at run time.
+// Exactness of the list.  A box is opened only if box_d2 <= the query's k-th best distance, which is +inf until k real
+// candidates are held: by the argument above every point that is skipped has a distance > the bound, so it is behind k
+// points already held.  The test is <=, not <: a point AT the bound's distance with a lower index still has to get in.
+// (distance, index) is a total order (an index occurs once: the first leaf is scanned once and skipped when its turn
+// comes again, and the copies that pad the last leaf - index 0x7fffffff - take the distance +inf and never enter), so the k
+// smallest do not depend on the order of the visits.  16 < d <= 128: the same list over an exhaustive scan, 64
+// references at a time from a coordinate-major copy, the depth a run-time value (k_knn_topk_wide).
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
@@ -317,6 +332,208 @@ __global__ __launch_bounds__(PF_BLOCK) void k_knn_tree(TreeArgs t) {
     }
 }
 
+// ---- the list of a query's 64 smallest (distance, index) pairs, one per lane, ascending (see the file header)
+
+// one candidate (wave-uniform) into the list: the lanes whose entry it precedes move one place to the right
+__device__ __forceinline__ void list_insert(double& nd, int32_t& ni, double cs, int32_t co, int lane) {
+    const bool before = cs < nd || (cs == nd && co < ni);
+    const double pd = __shfl_up(nd, 1, PF_WAVE);
+    const int32_t pi = __shfl_up(ni, 1, PF_WAVE);
+    const bool before_left = lane > 0 && (cs < pd || (cs == pd && co < pi));
+    if (before) {
+        nd = before_left ? pd : cs;
+        ni = before_left ? pi : co;
+    }
+}
+
+// the lanes' candidates (s, o) into the list; (kd, ki) is the list's k-th entry, wave-uniform: the bound.  A lane that
+// has no candidate offers s = +inf with o = 0x7fffffff, which is below no bound.
+__device__ __forceinline__ void list_offer(double& nd, int32_t& ni, double& kd, int32_t& ki, double s, int32_t o, int k, int lane) {
+    unsigned long long m = __ballot(s < kd || (s == kd && o < ki));
+    while (m) {
+        const int b = __ffsll((long long)m) - 1;
+        m &= m - 1ull;
+        const double cs = __shfl(s, b, PF_WAVE);
+        const int32_t co = __shfl(o, b, PF_WAVE);
+        if (!(cs < kd || (cs == kd && co < ki))) continue;  // (the bound has moved since the ballot)
+        list_insert(nd, ni, cs, co, lane);
+        kd = __shfl(nd, k - 1, PF_WAVE);
+        ki = __shfl(ni, k - 1, PF_WAVE);
+    }
+}
+
+// k_knn_tree with a list per query: t.idx_out / t.d2_out are [n_qry][k]
+template <int D>
+__global__ __launch_bounds__(PF_BLOCK) void k_knn_tree_topk(TreeArgs t, int k) {
+    constexpr int G = tree_group(D);
+    const int lane = threadIdx.x & (PF_WAVE - 1);
+    const int64_t group = (int64_t)blockIdx.x * (PF_BLOCK / PF_WAVE) + __builtin_amdgcn_readfirstlane((int)(threadIdx.x / PF_WAVE));
+    const int64_t q0 = group * G;
+    if (q0 >= t.n_qry) return;  // (wave-uniform)
+    const int nq = t.n_qry - q0 < G ? (int)(t.n_qry - q0) : G;
+    double q[G][D];  // wave-uniform (a short group replays its last query)
+    int32_t qdst[G];
+    double nd[G], kd[G];  // this lane's entry of each list; each list's k-th entry
+    int32_t ni[G], ki[G];
+#pragma unroll
+    for (int i = 0; i < G; ++i) {
+        qdst[i] = t.qry_order[q0 + (i < nq ? i : nq - 1)];
+#pragma unroll
+        for (int c = 0; c < D; ++c) q[i][c] = t.qry[(int64_t)qdst[i] * D + c];
+        nd[i] = kd[i] = INFINITY;
+        ni[i] = ki[i] = 0x7fffffff;
+    }
+
+    auto scan_leaf = [&](int32_t L) {
+        const double* p = t.pts + (int64_t)L * D * PF_WAVE + lane;
+        double x[D];
+#pragma unroll
+        for (int c = 0; c < D; ++c) x[c] = p[c * PF_WAVE];
+        const int32_t o = t.orig[(int64_t)L * PF_WAVE + lane];
+#pragma unroll
+        for (int i = 0; i < G; ++i) {
+            double s = 0.0;
+            constexpr int P = D >= 6 ? D / 2 : D;
+#pragma unroll
+            for (int c = 0; c < P; ++c) {
+                const double df = q[i][c] - x[c];
+                const double sq = df * df;
+                s = (c == 0) ? sq : s + sq;
+            }
+            if constexpr (P < D) {
+                if (!__any(s <= kd[i])) continue;  // (the partial sum is a prefix of the same accumulation and only grows)
+#pragma unroll
+                for (int c = P; c < D; ++c) {
+                    const double df = q[i][c] - x[c];
+                    s = s + df * df;
+                }
+            }
+            // the copies that fill the last leaf are no neighbours
+            list_offer(nd[i], ni[i], kd[i], ki[i], o == 0x7fffffff ? (double)INFINITY : s, o, k, lane);
+        }
+    };
+
+    // ---- the first candidates: the leaf nearest to the group's first query inside the super nearest to it
+    int32_t L0;
+    {
+        double sb = INFINITY;
+        int32_t sa = 0;
+        for (int32_t s0 = 0; s0 < t.ns_pad; s0 += PF_WAVE) {
+            const double dd = box_d2<D>(q[0], t.sup_lo + s0 + lane, t.sup_hi + s0 + lane, t.ns_pad);
+            if (dd < sb) sb = dd, sa = s0 + lane;
+        }
+        tree_argmin(sb, sa);
+        sa = sa < t.n_sup ? sa : 0;  // (the supers past the end are infinitely far and lose every tie: a guard, not a case)
+        const int64_t lb = (int64_t)sa * D * PF_WAVE + lane;
+        double lbest = box_d2<D>(q[0], t.leaf_lo + lb, t.leaf_hi + lb, PF_WAVE);
+        int32_t la = lane;
+        tree_argmin(lbest, la);
+        L0 = sa * PF_WAVE + la;
+        if (L0 < t.n_leaf)
+            scan_leaf(L0);
+        else
+            L0 = -1;
+    }
+    // ---- every super whose box is within a query's bound, every leaf of it whose box is; the bound may move with every leaf
+    for (int32_t s0 = 0; s0 < t.ns_pad; s0 += PF_WAVE) {
+        double sd[G];
+#pragma unroll
+        for (int i = 0; i < G; ++i) sd[i] = box_d2<D>(q[i], t.sup_lo + s0 + lane, t.sup_hi + s0 + lane, t.ns_pad);
+        unsigned long long sdone = 0ull;
+        while (true) {
+            bool need = false;
+#pragma unroll
+            for (int i = 0; i < G; ++i) need = need || sd[i] <= kd[i];
+            const unsigned long long sm = __ballot(need) & ~sdone;
+            if (!sm) break;
+            const int sbit = __ffsll((long long)sm) - 1;
+            sdone |= 1ull << sbit;
+            const int32_t S = s0 + sbit;
+            if (S >= t.n_sup) continue;
+            const int64_t lb = (int64_t)S * D * PF_WAVE + lane;
+            double bd[G];
+#pragma unroll
+            for (int i = 0; i < G; ++i) bd[i] = box_d2<D>(q[i], t.leaf_lo + lb, t.leaf_hi + lb, PF_WAVE);
+            unsigned long long ldone = 0ull;
+            while (true) {
+                bool ln = false;
+#pragma unroll
+                for (int i = 0; i < G; ++i) ln = ln || bd[i] <= kd[i];
+                const unsigned long long lm = __ballot(ln) & ~ldone;
+                if (!lm) break;
+                const int lbit = __ffsll((long long)lm) - 1;
+                ldone |= 1ull << lbit;
+                const int32_t L = S * PF_WAVE + lbit;
+                if (L < t.n_leaf && L != L0) scan_leaf(L);
+            }
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < G; ++i) {
+        if (i < nq && lane < k) {
+            t.idx_out[(int64_t)qdst[i] * k + lane] = ni[i];
+            t.d2_out[(int64_t)qdst[i] * k + lane] = nd[i];
+        }
+    }
+}
+
+// out[c][i] = in[i][c]: the references coordinate-major, so that a wave reads one coordinate of 64 of them as 512
+// contiguous bytes
+__global__ __launch_bounds__(PF_BLOCK) void k_topk_transpose(const double* __restrict__ in, int64_t n, int32_t d, double* __restrict__ out) {
+    const int64_t e = (int64_t)blockIdx.x * PF_BLOCK + threadIdx.x;
+    if (e >= n * d) return;
+    const int64_t c = e / n, i = e - c * n;
+    out[e] = in[i * d + c];
+}
+
+// 16 < d <= 128 (any d >= 1 is correct): the lists of WIDE_G consecutive queries per wave over ALL references, 64 at a
+// time, one per lane; the queries' coordinates are wave-uniform loads
+constexpr int WIDE_G = 4;
+__global__ __launch_bounds__(PF_BLOCK) void k_knn_topk_wide(const double* __restrict__ rt /* [d][n_ref] */, int64_t n_ref,
+                                                            const double* __restrict__ qry, int64_t n_qry, int d, int k,
+                                                            int64_t* __restrict__ idx_out, double* __restrict__ d2_out) {
+    const int lane = threadIdx.x & (PF_WAVE - 1);
+    const int64_t group = (int64_t)blockIdx.x * (PF_BLOCK / PF_WAVE) + __builtin_amdgcn_readfirstlane((int)(threadIdx.x / PF_WAVE));
+    const int64_t q0 = group * WIDE_G;
+    if (q0 >= n_qry) return;  // (wave-uniform)
+    const int nq = n_qry - q0 < WIDE_G ? (int)(n_qry - q0) : WIDE_G;
+    const double* qp[WIDE_G];  // (a short group replays its last query)
+    double nd[WIDE_G], kd[WIDE_G];
+    int32_t ni[WIDE_G], ki[WIDE_G];
+#pragma unroll
+    for (int i = 0; i < WIDE_G; ++i) {
+        qp[i] = qry + (q0 + (i < nq ? i : nq - 1)) * d;
+        nd[i] = kd[i] = INFINITY;
+        ni[i] = ki[i] = 0x7fffffff;
+    }
+    for (int64_t r0 = 0; r0 < n_ref; r0 += PF_WAVE) {
+        const bool real = r0 + lane < n_ref;
+        const double* p = rt + (real ? r0 + lane : n_ref - 1);  // (lanes past the end read the last reference and offer nothing)
+        double s[WIDE_G];
+#pragma unroll
+        for (int i = 0; i < WIDE_G; ++i) s[i] = 0.0;  // 0 + x^2 is x^2: the sum starts at coordinate 0
+#pragma unroll 4
+        for (int c = 0; c < d; ++c) {
+            const double x = p[(int64_t)c * n_ref];
+#pragma unroll
+            for (int i = 0; i < WIDE_G; ++i) {
+                const double df = qp[i][c] - x;
+                s[i] = s[i] + df * df;
+            }
+        }
+        const int32_t o = real ? (int32_t)(r0 + lane) : 0x7fffffff;
+#pragma unroll
+        for (int i = 0; i < WIDE_G; ++i) list_offer(nd[i], ni[i], kd[i], ki[i], real ? s[i] : (double)INFINITY, o, k, lane);
+    }
+#pragma unroll
+    for (int i = 0; i < WIDE_G; ++i) {
+        if (i < nq && lane < k) {
+            idx_out[(q0 + i) * k + lane] = ni[i];
+            d2_out[(q0 + i) * k + lane] = nd[i];
+        }
+    }
+}
+
 template <typename T>
 int tgrow(hipStream_t st, T** p, int64_t* cap, int64_t need) {
     if (need <= *cap) return PF_OK;
@@ -341,18 +558,21 @@ int sort_by_key(hipStream_t st, unsigned* k_in, int32_t* v_in, unsigned* k_out, 
 
 template <int D>
 void launch_tree(pf_ctx* c, const TreeArgs& a) {
-    const int64_t waves = (c->knn_nqry + tree_group(D) - 1) / tree_group(D);
+    const int64_t waves = (a.n_qry + tree_group(D) - 1) / tree_group(D);
     k_knn_tree<D><<<(unsigned)((waves + PF_BLOCK / PF_WAVE - 1) / (PF_BLOCK / PF_WAVE)), PF_BLOCK, 0, c->stream>>>(a);
 }
 
-}  // namespace
+template <int D>
+void launch_tree_topk(pf_ctx* c, const TreeArgs& a, int k) {
+    const int64_t waves = (a.n_qry + tree_group(D) - 1) / tree_group(D);
+    k_knn_tree_topk<D><<<(unsigned)((waves + PF_BLOCK / PF_WAVE - 1) / (PF_BLOCK / PF_WAVE)), PF_BLOCK, 0, c->stream>>>(a, k);
+}
 
-// The search of pf_knn_run for k = 1 through the box hierarchy: c->knn_ref / knn_qry hold the coordinates (row-major),
-// c->knn_ext the encoded extents of the references; results into c->knn_idx / knn_d2.
-int pf_knn_tree_run(pf_ctx* c) {
+// The hierarchy over the n references (row-major, d <= 16; ext: their encoded extents, as pf_knn_extent leaves them) and the
+// nq queries' order along the references' Morton curve, queued on the ctx's stream into the ctx's pf_knn_tree buffers:
+// keys, sort, leaves, leaf boxes, super boxes, query order.  Fills every field of `a` but the two outputs.
+int tree_build(pf_ctx* c, const double* ref, int64_t n, const double* qry, int64_t nq, int d, const unsigned long long* ext, TreeArgs* a) {
     hipStream_t st = c->stream;
-    const int d = c->knn_d;
-    const int64_t n = c->knn_nref, nq = c->knn_nqry;
     pf_knn_tree& T = c->knn_tree;
     const int64_t n_leaf = (n + PF_WAVE - 1) / PF_WAVE;
     const int64_t n_sup = (n_leaf + PF_WAVE - 1) / PF_WAVE;
@@ -381,46 +601,126 @@ int pf_knn_tree_run(pf_ctx* c) {
             rc = PF_E_HIP;
             break;
         }
-        k_tree_grid<<<1, 1, 0, st>>>(c->knn_ext, d, (TreeGrid*)T.grid);
-        k_tree_keys<<<pf_blocks(n), PF_BLOCK, 0, st>>>(c->knn_ref, n, d, (const TreeGrid*)T.grid, k0, v0);
+        k_tree_grid<<<1, 1, 0, st>>>(ext, d, (TreeGrid*)T.grid);
+        k_tree_keys<<<pf_blocks(n), PF_BLOCK, 0, st>>>(ref, n, d, (const TreeGrid*)T.grid, k0, v0);
         if ((rc = sort_by_key(st, k0, v0, k1, v1, n)) != PF_OK) break;
-        k_tree_leaves<<<pf_blocks(n_leaf * PF_WAVE), PF_BLOCK, 0, st>>>(c->knn_ref, v1, n, d, n_leaf * PF_WAVE, T.pts, T.orig);
+        k_tree_leaves<<<pf_blocks(n_leaf * PF_WAVE), PF_BLOCK, 0, st>>>(ref, v1, n, d, n_leaf * PF_WAVE, T.pts, T.orig);
         k_tree_leaf_boxes<<<pf_blocks(n_sup * PF_WAVE * d), PF_BLOCK, 0, st>>>(T.pts, (int32_t)n_leaf, (int32_t)n_sup, d, T.leaf_lo, leaf_hi);
         k_tree_super_boxes<<<pf_blocks(ns_pad * d), PF_BLOCK, 0, st>>>(T.leaf_lo, leaf_hi, (int32_t)n_sup, (int32_t)ns_pad, d, T.sup_lo, sup_hi);
-        k_tree_keys<<<pf_blocks(nq), PF_BLOCK, 0, st>>>(c->knn_qry, nq, d, (const TreeGrid*)T.grid, k0, v0);
+        k_tree_keys<<<pf_blocks(nq), PF_BLOCK, 0, st>>>(qry, nq, d, (const TreeGrid*)T.grid, k0, v0);
         if ((rc = sort_by_key(st, k0, v0, k1, T.qry_order, nq)) != PF_OK) break;
-        TreeArgs a{T.pts, T.orig, T.leaf_lo, leaf_hi, T.sup_lo, sup_hi, c->knn_qry, T.qry_order, nq, (int32_t)n_leaf, (int32_t)n_sup,
-                   (int32_t)ns_pad, c->knn_idx, c->knn_d2, T.count_visits ? T.counters : nullptr};
-        switch (d) {
-            case 1: launch_tree<1>(c, a); break;
-            case 2: launch_tree<2>(c, a); break;
-            case 3: launch_tree<3>(c, a); break;
-            case 4: launch_tree<4>(c, a); break;
-            case 5: launch_tree<5>(c, a); break;
-            case 6: launch_tree<6>(c, a); break;
-            case 7: launch_tree<7>(c, a); break;
-            case 8: launch_tree<8>(c, a); break;
-            case 9: launch_tree<9>(c, a); break;
-            case 10: launch_tree<10>(c, a); break;
-            case 11: launch_tree<11>(c, a); break;
-            case 12: launch_tree<12>(c, a); break;
-            case 13: launch_tree<13>(c, a); break;
-            case 14: launch_tree<14>(c, a); break;
-            case 15: launch_tree<15>(c, a); break;
-            case 16: launch_tree<16>(c, a); break;
-            default: rc = PF_E_ARG; break;
-        }
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) {
-            pf_set_error("pf_knn (box hierarchy): %s", hipGetErrorString(e));
-            rc = PF_E_HIP;
-        }
+        *a = TreeArgs{T.pts, T.orig, T.leaf_lo, leaf_hi, T.sup_lo, sup_hi, qry, T.qry_order, nq, (int32_t)n_leaf, (int32_t)n_sup,
+                      (int32_t)ns_pad, nullptr, nullptr, T.count_visits ? T.counters : nullptr};
     } while (0);
     pf_free(st, k0);
     pf_free(st, k1);
     pf_free(st, v0);
     pf_free(st, v1);
     return rc;
+}
+
+int tree_launched(const char* what) {
+    const hipError_t e = hipGetLastError();
+    PF_CHECK(e == hipSuccess, PF_E_HIP, "%s (box hierarchy): %s", what, hipGetErrorString(e));
+    return PF_OK;
+}
+
+}  // namespace
+
+// The search of pf_knn_run for k = 1 through the box hierarchy: c->knn_ref / knn_qry hold the coordinates (row-major),
+// c->knn_ext the encoded extents of the references; results into c->knn_idx / knn_d2.
+int pf_knn_tree_run(pf_ctx* c) {
+    const int d = c->knn_d;
+    TreeArgs a{};
+    PF_TRY(tree_build(c, c->knn_ref, c->knn_nref, c->knn_qry, c->knn_nqry, d, c->knn_ext, &a));
+    a.idx_out = c->knn_idx;
+    a.d2_out = c->knn_d2;
+    switch (d) {
+        case 1: launch_tree<1>(c, a); break;
+        case 2: launch_tree<2>(c, a); break;
+        case 3: launch_tree<3>(c, a); break;
+        case 4: launch_tree<4>(c, a); break;
+        case 5: launch_tree<5>(c, a); break;
+        case 6: launch_tree<6>(c, a); break;
+        case 7: launch_tree<7>(c, a); break;
+        case 8: launch_tree<8>(c, a); break;
+        case 9: launch_tree<9>(c, a); break;
+        case 10: launch_tree<10>(c, a); break;
+        case 11: launch_tree<11>(c, a); break;
+        case 12: launch_tree<12>(c, a); break;
+        case 13: launch_tree<13>(c, a); break;
+        case 14: launch_tree<14>(c, a); break;
+        case 15: launch_tree<15>(c, a); break;
+        case 16: launch_tree<16>(c, a); break;
+        default: return PF_E_ARG;
+    }
+    return tree_launched("pf_knn");
+}
+
+// k nearest neighbours, 1 <= k <= 64, 1 <= d <= 128 (include/pyfocusr_hip.h): the lists over the box hierarchy for
+// d <= 16, over an exhaustive scan beyond
+extern "C" int pf_knn_topk(pf_ctx* c, const double* ref, int64_t n_ref, const double* qry, int64_t n_qry, int32_t d, int32_t k,
+                           int64_t* idx_out, double* d2_out) {
+    PF_CHECK(c && ref && qry && idx_out, PF_E_ARG, "pf_knn_topk: NULL argument");
+    PF_CHECK(n_ref > 0 && n_ref < ((int64_t)1 << 31) && n_qry > 0 && n_qry < ((int64_t)1 << 31) && d >= 1 && d <= 128, PF_E_ARG,
+             "pf_knn_topk: n_ref %lld, n_qry %lld, d %d out of range (1 <= d <= 128)", (long long)n_ref, (long long)n_qry, d);
+    PF_CHECK(k >= 1 && k <= PF_WAVE && k <= n_ref, PF_E_ARG, "pf_knn_topk: k = %d out of range (1..64, <= n_ref)", k);
+    PF_HIP(hipSetDevice(c->device));
+    Scratch s(c->stream);
+    const size_t count = (size_t)n_qry * k;
+    double* d_ref = s.get<double>((size_t)(n_ref * d));
+    double* d_qry = s.get<double>((size_t)(n_qry * d));
+    int64_t* d_idx = s.get<int64_t>(count);
+    double* d_d2 = s.get<double>(count);
+    s.upload(d_ref, ref, (size_t)(n_ref * d));
+    s.upload(d_qry, qry, (size_t)(n_qry * d));
+    PF_CHECK(s.ok(), PF_E_HIP, "pf_knn_topk: %s", hipGetErrorString(s.err));
+    PF_HIP(hipEventRecord(c->ev0, s.st));
+    if (d <= PF_ND_MAX) {
+        unsigned long long* ext = s.get<unsigned long long>(32);
+        PF_CHECK(s.ok(), PF_E_HIP, "pf_knn_topk: %s", hipGetErrorString(s.err));
+        PF_TRY(pf_knn_extent(s.st, d_ref, n_ref, d, ext));
+        TreeArgs a{};
+        PF_TRY(tree_build(c, d_ref, n_ref, d_qry, n_qry, d, ext, &a));
+        a.idx_out = d_idx;
+        a.d2_out = d_d2;
+        switch (d) {
+            case 1: launch_tree_topk<1>(c, a, k); break;
+            case 2: launch_tree_topk<2>(c, a, k); break;
+            case 3: launch_tree_topk<3>(c, a, k); break;
+            case 4: launch_tree_topk<4>(c, a, k); break;
+            case 5: launch_tree_topk<5>(c, a, k); break;
+            case 6: launch_tree_topk<6>(c, a, k); break;
+            case 7: launch_tree_topk<7>(c, a, k); break;
+            case 8: launch_tree_topk<8>(c, a, k); break;
+            case 9: launch_tree_topk<9>(c, a, k); break;
+            case 10: launch_tree_topk<10>(c, a, k); break;
+            case 11: launch_tree_topk<11>(c, a, k); break;
+            case 12: launch_tree_topk<12>(c, a, k); break;
+            case 13: launch_tree_topk<13>(c, a, k); break;
+            case 14: launch_tree_topk<14>(c, a, k); break;
+            case 15: launch_tree_topk<15>(c, a, k); break;
+            default: launch_tree_topk<16>(c, a, k); break;
+        }
+    } else {
+        double* d_rt = s.get<double>((size_t)(n_ref * d));
+        PF_CHECK(s.ok(), PF_E_HIP, "pf_knn_topk: %s", hipGetErrorString(s.err));
+        k_topk_transpose<<<pf_blocks(n_ref * d), PF_BLOCK, 0, s.st>>>(d_ref, n_ref, d, d_rt);
+        const int64_t waves = (n_qry + WIDE_G - 1) / WIDE_G;
+        k_knn_topk_wide<<<(unsigned)((waves + PF_BLOCK / PF_WAVE - 1) / (PF_BLOCK / PF_WAVE)), PF_BLOCK, 0, s.st>>>(d_rt, n_ref, d_qry, n_qry, d, k,
+                                                                                                                  d_idx, d_d2);
+    }
+    PF_TRY(tree_launched("pf_knn_topk"));
+    PF_HIP(hipEventRecord(c->ev1, s.st));
+    // one read-back: both halves queued, one wait
+    s.download(idx_out, d_idx, count);
+    s.download(d2_out, d_d2, count);
+    s.sync();
+    PF_CHECK(s.ok(), PF_E_HIP, "pf_knn_topk: %s", hipGetErrorString(s.err));
+    float ms = 0.f;
+    PF_HIP(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    c->knn_ms = ms;
+    return PF_OK;
 }
 
 // diagnostics of the last box-hierarchy search (pf_knn_tree_count(ctx, 1) switches the counting on): leaves scanned and

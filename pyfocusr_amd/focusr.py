@@ -9,7 +9,8 @@ the same defaults, builds both graphs and their spectra eagerly (:134-170), and
 On the device: Laplacian assembly + eigensolve (`Graph`), the 3-D NN of `eigsort`,
 `get_kd_correspondence` (focusr.py:351-353 -> `pf_knn1`), the graph mean filter
 behind `get_smoothed_correspondences` (focusr.py:368-396) and the 3-NN query of
-`get_weighted_final_node_locations` (focusr.py:401-426 -> `pf_knn`, k = 3).
+`get_weighted_final_node_locations` (focusr.py:401-426 -> `pf_knn` for up to 4 neighbours in up to 4
+coordinates, `pf_knn_topk` for up to 64).
 
 "Next" rows of SURVEY.md §8f:
 * ICP pre-alignment (:110-131): `pyfocusr_amd/icp.py` (closest-point search on the
@@ -28,6 +29,7 @@ from .correspondence import closest_points_on_embedded_surface, interpolate_on_s
 from .eigsort import eigsort
 from .graph import Graph, compute_spectra, spectral_knn
 from .main import print_header
+from .neighbours import inverse_distance_average
 from .vtk_functions import PolyMesh, apply_transform, icp_transform, mesh_arrays, set_mesh_scalars, vtk_deep_copy
 
 from . import cpd as _native_cpd
@@ -342,24 +344,18 @@ class Focusr(object):
     def get_weighted_final_node_locations(self, n_closest_pts=3):
         """focusr.py:401-426: every source point goes to the inverse-distance-weighted average of the
         `n_closest_pts` target vertices nearest to its projection (a coincident vertex wins outright).
-        The reference loops over points with one `tree.query(k=3)` each; here one device call."""
-        idx, d2 = self._ctx.knn(self.smoothed_target_coords, self.source_projected_on_target, n_closest_pts)
-        dist = np.sqrt(d2)
-        pts = self.graph_target.points
-        with np.errstate(divide="ignore", invalid="ignore"):
-            w = 1.0 / dist
-            num = np.take(pts, idx[:, 0], axis=0) * w[:, 0:1]  # np.take: the fast path for whole-row gathers
-            den = w[:, 0:1].copy()
-            for j in range(1, idx.shape[1]):
-                num = num + np.take(pts, idx[:, j], axis=0) * w[:, j:j + 1]
-                den = den + w[:, j:j + 1]
-            out = num / den
-        coincident = dist == 0.0
-        rows = np.nonzero(coincident.any(axis=1))[0]
-        if len(rows):  # focusr.py:415-419: first zero-distance neighbour
-            first = np.argmax(coincident[rows], axis=1)
-            out[rows, :] = pts[idx[rows, first], :]
-        self.weighted_avg_transformed_points = out
+        The reference loops over points with one `tree.query(k=n_closest_pts)` each; here one device call: `pf_knn`
+        up to 4 neighbours in up to 4 coordinates, `pf_knn_topk` beyond (at most 64 neighbours)."""
+        ref, qry = self.smoothed_target_coords, self.source_projected_on_target
+        k, n_ref = int(n_closest_pts), np.shape(ref)[0]
+        if k > min(_hip.KNN_TOPK_MAX_K, n_ref):
+            raise ValueError("n_closest_pts = %d: at most %d neighbours (min(%d, the %d target vertices))"
+                             % (k, min(_hip.KNN_TOPK_MAX_K, n_ref), _hip.KNN_TOPK_MAX_K, n_ref))
+        if k <= 4 and np.shape(ref)[1] <= 4:
+            idx, d2 = self._ctx.knn(ref, qry, k)
+        else:
+            idx, d2 = self._ctx.knn_topk(ref, qry, k)
+        self.weighted_avg_transformed_points = inverse_distance_average(self.graph_target.points, idx, d2)
 
     def get_nearest_neighbour_final_node_locations(self):
         """focusr.py:428-431."""

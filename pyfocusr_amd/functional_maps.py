@@ -26,8 +26,9 @@ one conversion to a full-resolution point map at the end: `zoomout_refine(..., s
 import numpy as np
 
 from . import _hip
+from .neighbours import k_nearest_neighbours
 
-__all__ = ["functional_map_from_p2p", "p2p_from_functional_map", "zoomout_refine", "zoomout_correspondences",
+__all__ = ["functional_map_from_p2p", "p2p_from_functional_map", "soft_p2p_from_functional_map", "zoomout_refine", "zoomout_correspondences",
            "fast_zoomout_correspondences"]
 
 
@@ -79,6 +80,26 @@ def p2p_from_functional_map(phi_t, phi_s, C, return_d2=False, ctx=None):
     with _handle(_pad(phi_t, K), _pad(phi_s, K), None, K, ctx) as h:
         h.convert(k_s, k_t, C)
         return h.get_p2p(return_d2=return_d2)
+
+
+def soft_p2p_from_functional_map(phi_t, phi_s, C, k, ctx=None):
+    """(idx (n_s, k) int64, d2 (n_s, k)) of the k_s x k_t functional map C: for every source vertex the k rows of
+    phi_t[:, :k_t] nearest to its row of Q = phi_s[:, :k_s] C, ascending by (squared distance, index)
+    (`neighbours.k_nearest_neighbours`; 1 <= k <= 64, k_t <= 128).  Q is formed on the host, one term per basis
+    function in ascending order.  `neighbours.inverse_distance_average(values, idx, d2)` then carries per-vertex values
+    of the target - its points, point data - to the source as a smooth average; idx[:, 0] is
+    `p2p_from_functional_map`'s vertex."""
+    C = np.asarray(C, dtype=np.float64)
+    phi_t, phi_s = np.asarray(phi_t, dtype=np.float64), np.asarray(phi_s, dtype=np.float64)
+    if C.ndim != 2 or phi_t.ndim != 2 or phi_s.ndim != 2:
+        raise ValueError("C must be a k_s x k_t matrix, phi_t and phi_s (n, K) arrays")
+    k_s, k_t = C.shape
+    if k_s > phi_s.shape[1] or k_t > phi_t.shape[1] or k_s < 1:
+        raise ValueError("C is %d x %d, the bases have %d and %d functions" % (k_s, k_t, phi_s.shape[1], phi_t.shape[1]))
+    Q = phi_s[:, 0:1] * C[0:1, :]
+    for a in range(1, k_s):
+        Q = Q + phi_s[:, a:a + 1] * C[a:a + 1, :]
+    return k_nearest_neighbours(np.ascontiguousarray(phi_t[:, :k_t]), Q, k, ctx=ctx)
 
 
 def zoomout_refine(phi_t, phi_s, mass_s, T0, k_start, k_end, step=1, n_iter_at_end=0, samples=None, ctx=None):
