@@ -381,27 +381,6 @@ __global__ __launch_bounds__(PF_BLOCK) void k_as_cert(const double* __restrict__
     cost[i] = sqrt(as_d2(x, cols + (int64_t)col_of[i] * d, d));
 }
 
-struct AsBuffers {
-    hipStream_t st = nullptr;
-    std::vector<void*> blocks;
-    int64_t bytes = 0;
-    hipError_t err = hipSuccess;
-    template <typename T>
-    T* get(int64_t count) {
-        void* q = nullptr;
-        if (err != hipSuccess) return nullptr;
-        const size_t b = sizeof(T) * (size_t)(count > 0 ? count : 1);
-        err = pf_malloc(st, &q, b);
-        if (err != hipSuccess) return nullptr;
-        blocks.push_back(q);
-        bytes += (int64_t)b;
-        return (T*)q;
-    }
-    ~AsBuffers() {
-        for (void* q : blocks) pf_free(st, q);
-    }
-};
-
 double host_cost(const double* a, const double* b, int d) {
     double s = 0.0;
     for (int c = 0; c < d; ++c) {
@@ -466,8 +445,7 @@ int pf_assign(pf_ctx* ctx, const double* rows, int64_t n_rows, const double* col
     PF_HIP(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     const int64_t n_r = n_rows, n_c = n_cols;
-    AsBuffers B;
-    B.st = st;
+    Scratch B(st);
     double* dR = B.get<double>(n_r * d);
     double* dC = B.get<double>(n_c * d);
     int32_t* cand_j = B.get<int32_t>(n_r * AS_K);
@@ -485,12 +463,12 @@ int pf_assign(pf_ctx* ctx, const double* rows, int64_t n_rows, const double* col
     int32_t* queue = B.get<int32_t>(n_c);
     double* part = B.get<double>(4 * AS_PARTS);
     AsState* dst = B.get<AsState>(1);
-    if (B.err != hipSuccess) {
+    if (!B.ok()) {
         pf_set_error("pf_assign: device allocation: %s", hipGetErrorString(B.err));
         (void)hipGetLastError();
         return PF_E_HIP;
     }
-    S.device_bytes = B.bytes;
+    S.device_bytes = (int64_t)B.bytes;
     S.candidate_edges = n_r * (n_c < AS_K ? n_c : AS_K);
     AsState* hst = nullptr;
     PF_TRY(pf_pinned_scratch(ctx, sizeof(AsState), (void**)&hst));

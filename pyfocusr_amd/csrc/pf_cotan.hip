@@ -249,26 +249,12 @@ __global__ __launch_bounds__(PF_BLOCK) void k_cotan_apply(const int32_t* __restr
         if (c < ncols) out[i * ncols + c] = m > 0.0 ? acc[c] / m : 0.0;
 }
 
-// the caller's temporaries and, until the build has succeeded, the graph itself
+// until the build has succeeded, the graph itself is the build's to free
 struct CotanBuild {
     pf_graph* g = nullptr;
-    hipStream_t st = nullptr;
-    std::vector<void*> tmp;
     bool ok = false;
     ~CotanBuild() {
-        for (void* p : tmp) pf_free(st, p);
         if (!ok && g) pf_graph_free(g);
-    }
-    template <typename T>
-    int scratch(T** p, int64_t count) {
-        PF_HIP(pf_malloc(st, (void**)p, sizeof(T) * (size_t)std::max<int64_t>(count, 1)));
-        tmp.push_back((void*)*p);
-        return PF_OK;
-    }
-    template <typename T>
-    int keep(T** p, int64_t count) {
-        PF_HIP(pf_malloc(st, (void**)p, sizeof(T) * (size_t)std::max<int64_t>(count, 1)));
-        return PF_OK;
     }
 };
 
@@ -287,8 +273,8 @@ int pf_graph_build_cotan(pf_mesh* mesh, int32_t mass_kind, pf_graph** out) {
     PF_HIP(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     CotanBuild job;
-    job.st = st;
     pf_graph* g = job.g = new pf_graph();
+    Scratch sc(st);  // (declared after job: the temporaries go back before the graph of a failed build does)
     g->ctx = ctx;
     g->unit_g = 1;
     g->is_cotan = 1;
@@ -300,38 +286,35 @@ int pf_graph_build_cotan(pf_mesh* mesh, int32_t mass_kind, pf_graph** out) {
     g->n_slices = g->n_pad / PF_WAVE;
     g->n_chunks = (g->n_pad + PF_DOT_CHUNK - 1) / PF_DOT_CHUNK;
 
-    double *half_cot = nullptr, *area = nullptr, *val = nullptr, *rw = nullptr, *partial = nullptr;
-    int32_t *cnt = nullptr, *start = nullptr, *rank = nullptr, *rcol = nullptr, *ucnt = nullptr, *flags = nullptr;
-    long long* key = nullptr;
-    unsigned long long* hi_bits = nullptr;
     const unsigned face_blocks = pf_blocks(n_faces);
-    PF_TRY(job.scratch(&half_cot, 3 * n_faces));
-    PF_TRY(job.scratch(&area, n_faces));
-    PF_TRY(job.scratch(&partial, face_blocks));
-    PF_TRY(job.scratch(&cnt, n + 1));
-    PF_TRY(job.scratch(&start, n + 1));
-    PF_TRY(job.scratch(&rank, 3 * n_faces));
-    PF_TRY(job.scratch(&key, n_entries));
-    PF_TRY(job.scratch(&val, n_entries));
-    PF_TRY(job.scratch(&rcol, n_entries));
-    PF_TRY(job.scratch(&rw, n_entries));
-    PF_TRY(job.scratch(&ucnt, n + 1));
-    PF_TRY(job.scratch(&flags, 8));
-    PF_TRY(job.scratch(&hi_bits, 1));
-    PF_TRY(job.keep(&g->rowptr, n + 1));
-    PF_TRY(job.keep(&g->deg, g->n_pad));
-    PF_TRY(job.keep(&g->g, g->n_pad));
-    PF_TRY(job.keep(&g->sg, g->n_pad));
-    PF_TRY(job.keep(&g->diag, g->n_pad));
-    PF_TRY(job.keep(&g->label, g->n_pad));
-    PF_TRY(job.keep(&g->perm, g->n_pad));
-    PF_TRY(job.keep(&g->iperm, g->n_pad));
-    PF_TRY(job.keep(&g->smooth, g->n_pad));
-    PF_TRY(job.keep(&g->slice_ptr, g->n_slices + 1));
-    PF_TRY(job.keep(&g->cot_diag, n));
-    PF_TRY(job.keep(&g->cot_mass, n));
-    PF_TRY(job.keep(&g->cot_sqrtm, n));
-    PF_TRY(job.keep(&g->pts, 3 * n));
+    double* half_cot = sc.get<double>(3 * n_faces);
+    double* area = sc.get<double>(n_faces);
+    double* partial = sc.get<double>(face_blocks);
+    int32_t* cnt = sc.get<int32_t>(n + 1);
+    int32_t* start = sc.get<int32_t>(n + 1);
+    int32_t* rank = sc.get<int32_t>(3 * n_faces);
+    long long* key = sc.get<long long>(n_entries);
+    double* val = sc.get<double>(n_entries);
+    int32_t* rcol = sc.get<int32_t>(n_entries);
+    double* rw = sc.get<double>(n_entries);
+    int32_t* ucnt = sc.get<int32_t>(n + 1);
+    int32_t* flags = sc.get<int32_t>(8);
+    unsigned long long* hi_bits = sc.get<unsigned long long>(1);
+    g->rowptr = sc.keep<int32_t>(n + 1);
+    g->deg = sc.keep<double>(g->n_pad);
+    g->g = sc.keep<double>(g->n_pad);
+    g->sg = sc.keep<double>(g->n_pad);
+    g->diag = sc.keep<double>(g->n_pad);
+    g->label = sc.keep<int32_t>(g->n_pad);
+    g->perm = sc.keep<int32_t>(g->n_pad);
+    g->iperm = sc.keep<int32_t>(g->n_pad);
+    g->smooth = sc.keep<double>(g->n_pad);
+    g->slice_ptr = sc.keep<int64_t>(g->n_slices + 1);
+    g->cot_diag = sc.keep<double>(n);
+    g->cot_mass = sc.keep<double>(n);
+    g->cot_sqrtm = sc.keep<double>(n);
+    g->pts = sc.keep<double>(3 * n);
+    PF_HIP(sc.err);
     PF_HIP(hipMemsetAsync(cnt, 0, sizeof(int32_t) * (size_t)(n + 1), st));
     PF_HIP(hipMemsetAsync(flags, 0, sizeof(int32_t) * 8, st));
     PF_HIP(hipMemsetAsync(hi_bits, 0, sizeof(unsigned long long), st));
@@ -368,9 +351,10 @@ int pf_graph_build_cotan(pf_mesh* mesh, int32_t mass_kind, pf_graph** out) {
     for (double p : h_partial) total += p;
     g->cot_area = total;
     g->nnz_w = nnz32;
-    PF_TRY(job.keep(&g->col, g->nnz_w));
-    PF_TRY(job.keep(&g->w, g->nnz_w));
-    PF_TRY(job.keep(&g->cot_w, g->nnz_w));
+    g->col = sc.keep<int32_t>(g->nnz_w);
+    g->w = sc.keep<double>(g->nnz_w);
+    g->cot_w = sc.keep<double>(g->nnz_w);
+    PF_HIP(sc.err);
     k_cotan_compact<<<pf_blocks(n), PF_BLOCK, 0, st>>>(start, g->rowptr, n, rcol, rw, g->cot_diag, g->cot_mass, g->cot_sqrtm, g->col, g->cot_w,
                                                  g->w, g->deg, g->g, g->sg, hi_bits);
     PF_HIP(hipGetLastError());

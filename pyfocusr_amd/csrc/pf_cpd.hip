@@ -39,9 +39,8 @@ struct pf_cpd {
     // pf_cpd_variance_sums) and the transform kernels (pf_cpd_apply_affine / pf_cpd_apply_deform)
     double* Y = nullptr;      // [M][D] moving set as given (TY is its transformed copy)
     double* shift = nullptr;  // [3][16]: cx (mean of X), cy (mean of Y), zeros
-    double* mpart = nullptr;  // per-block partial sums of the moment kernels
-    double* msum = nullptr;   // their totals (device), also the staging area of small uploads
-    int64_t mpart_cap = 0, msum_cap = 0;
+    DevBuf<double> mpart;  // per-block partial sums of the moment kernels
+    DevBuf<double> msum;   // their totals (device), also the staging area of small uploads
 };
 
 namespace {
@@ -376,39 +375,15 @@ int run_gram(hipStream_t st, const double* A, int64_t n_a, const double* B, int6
     return PF_OK;
 }
 
-#define PF_DISPATCH_D(D_, CALL)                                           \
-    switch (D_) {                                                         \
-        case 1: return CALL(1);                                           \
-        case 2: return CALL(2);                                           \
-        case 3: return CALL(3);                                           \
-        case 4: return CALL(4);                                           \
-        case 5: return CALL(5);                                           \
-        case 6: return CALL(6);                                           \
-        case 7: return CALL(7);                                           \
-        case 8: return CALL(8);                                           \
-        case 9: return CALL(9);                                           \
-        case 10: return CALL(10);                                         \
-        case 11: return CALL(11);                                         \
-        case 12: return CALL(12);                                         \
-        case 13: return CALL(13);                                         \
-        case 14: return CALL(14);                                         \
-        case 15: return CALL(15);                                         \
-        case 16: return CALL(16);                                         \
-        default: pf_set_error("pf_cpd: d = %d out of range (1..16)", D_); \
-            return PF_E_ARG;                                              \
-    }
+const char* const CPD_BAD_D = "pf_cpd: d = %d out of range (1..16)";
 
 int dispatch_estep(pf_cpd* h, double inv2s, double c) {
-#define CALL_E(D_) run_estep<D_>(h, inv2s, c)
-    PF_DISPATCH_D(h->D, CALL_E)
-#undef CALL_E
+    return pf_dispatch_d<1, 16>(h->D, [&](auto D) { return run_estep<D()>(h, inv2s, c); }, CPD_BAD_D);
 }
 
 int dispatch_gram(hipStream_t st, int d, const double* A, int64_t n_a, const double* B, int64_t n_b, double inv2b, const double* V,
                   int32_t C, double* out) {
-#define CALL_G(D_) run_gram<D_>(st, A, n_a, B, n_b, inv2b, V, C, out)
-    PF_DISPATCH_D(d, CALL_G)
-#undef CALL_G
+    return pf_dispatch_d<1, 16>(d, [&](auto D) { return run_gram<D()>(st, A, n_a, B, n_b, inv2b, V, C, out); }, CPD_BAD_D);
 }
 
 }  // namespace
@@ -430,8 +405,8 @@ void pf_cpd_free(pf_cpd* h) {
     pf_free(st, h->H);
     pf_free(st, h->Y);
     pf_free(st, h->shift);
-    pf_free(st, h->mpart);
-    pf_free(st, h->msum);
+    h->mpart.release(st);
+    h->msum.release(st);
     delete h;
 }
 
@@ -447,33 +422,29 @@ int pf_cpd_create(pf_ctx* ctx, const double* X, int64_t N, const double* Y, int6
     h->chunks_m = (int32_t)((M + CPD_CHUNK - 1) / CPD_CHUNK);
     h->chunks_n = (int32_t)((N + CPD_CHUNK - 1) / CPD_CHUNK);
     const int64_t part = std::max<int64_t>((int64_t)h->chunks_m * N, (int64_t)h->chunks_n * M * (D + 1));
-    hipError_t e = hipSuccess;
-    do {
-        if ((e = pf_malloc(st, (void**)&h->X, sizeof(double) * N * D)) != hipSuccess) break;
-        if ((e = pf_malloc(st, (void**)&h->TY, sizeof(double) * M * D)) != hipSuccess) break;
-        if ((e = pf_malloc(st, (void**)&h->den, sizeof(double) * N)) != hipSuccess) break;
-        if ((e = pf_malloc(st, (void**)&h->part, sizeof(double) * part)) != hipSuccess) break;
-        if ((e = pf_malloc(st, (void**)&h->out, sizeof(double) * (N + M + M * D))) != hipSuccess) break;
-        if ((e = pf_malloc(st, (void**)&h->Y, sizeof(double) * M * D)) != hipSuccess) break;
-        if ((e = pf_malloc(st, (void**)&h->shift, sizeof(double) * 48)) != hipSuccess) break;
-        h->mpart_cap = (std::max(N, M) / MOM_ROWS + 1) * (1 + 2 * 16 + 2 * 256);
-        h->msum_cap = 1 + 2 * 16 + 2 * 256 + 16;
-        if ((e = pf_malloc(st, (void**)&h->mpart, sizeof(double) * h->mpart_cap)) != hipSuccess) break;
-        if ((e = pf_malloc(st, (void**)&h->msum, sizeof(double) * h->msum_cap)) != hipSuccess) break;
-        double sh[48] = {0.0};
-        for (int64_t i = 0; i < N; ++i)
-            for (int d = 0; d < D; ++d) sh[d] += X[i * D + d];
-        for (int64_t i = 0; i < M; ++i)
-            for (int d = 0; d < D; ++d) sh[16 + d] += Y[i * D + d];
-        for (int d = 0; d < D; ++d) sh[d] /= (double)N, sh[16 + d] /= (double)M;
-        if ((e = hipMemcpyAsync(h->shift, sh, sizeof(sh), hipMemcpyHostToDevice, st)) != hipSuccess) break;
-        if ((e = hipMemcpyAsync(h->X, X, sizeof(double) * N * D, hipMemcpyHostToDevice, st)) != hipSuccess) break;
-        if ((e = hipMemcpyAsync(h->Y, Y, sizeof(double) * M * D, hipMemcpyHostToDevice, st)) != hipSuccess) break;
-        if ((e = hipMemcpyAsync(h->TY, Y, sizeof(double) * M * D, hipMemcpyHostToDevice, st)) != hipSuccess) break;
-        e = hipStreamSynchronize(st);
-    } while (0);
-    if (e != hipSuccess) {
-        pf_set_error("pf_cpd_create: %s", hipGetErrorString(e));
+    Scratch s(st);  // every block is kept: the handle owns them, and pf_cpd_free gives back whatever a failure leaves
+    h->X = s.keep<double>(N * D);
+    h->TY = s.keep<double>(M * D);
+    h->den = s.keep<double>(N);
+    h->part = s.keep<double>(part);
+    h->out = s.keep<double>(N + M + M * D);
+    h->Y = s.keep<double>(M * D);
+    h->shift = s.keep<double>(48);
+    if (s.ok()) s.note(h->mpart.grow(st, (std::max(N, M) / MOM_ROWS + 1) * (1 + 2 * 16 + 2 * 256)));
+    if (s.ok()) s.note(h->msum.grow(st, 1 + 2 * 16 + 2 * 256 + 16));
+    double sh[48] = {0.0};
+    for (int64_t i = 0; i < N; ++i)
+        for (int d = 0; d < D; ++d) sh[d] += X[i * D + d];
+    for (int64_t i = 0; i < M; ++i)
+        for (int d = 0; d < D; ++d) sh[16 + d] += Y[i * D + d];
+    for (int d = 0; d < D; ++d) sh[d] /= (double)N, sh[16 + d] /= (double)M;
+    s.upload(h->shift, sh, 48);
+    s.upload(h->X, X, N * D);
+    s.upload(h->Y, Y, M * D);
+    s.upload(h->TY, Y, M * D);
+    s.sync();
+    if (!s.ok()) {
+        pf_set_error("pf_cpd_create: %s", hipGetErrorString(s.err));
         pf_cpd_free(h);
         return PF_E_HIP;
     }
@@ -492,25 +463,15 @@ int pf_cpd_set_basis(pf_cpd* h, const double* Q, int32_t K) {
     h->Q = h->hpart = h->H = nullptr;
     h->K = 0;
     h->chunks_h = (int32_t)((h->M + GRAM_CHUNK - 1) / GRAM_CHUNK);
-    PF_HIP(pf_malloc(st, (void**)&h->Q, sizeof(double) * h->M * K));
-    PF_HIP(pf_malloc(st, (void**)&h->hpart, sizeof(double) * (size_t)h->chunks_h * K * K));
-    PF_HIP(pf_malloc(st, (void**)&h->H, sizeof(double) * (size_t)K * K));
-    PF_HIP(hipMemcpyAsync(h->Q, Q, sizeof(double) * h->M * K, hipMemcpyHostToDevice, st));
+    Scratch s(st);
+    h->Q = s.keep<double>(h->M * K);
+    h->hpart = s.keep<double>((size_t)h->chunks_h * K * K);
+    h->H = s.keep<double>((size_t)K * K);
+    s.upload(h->Q, Q, h->M * K);
+    PF_HIP(s.err);
     // scratch of the device-resident M-step: K x d coefficients / right-hand side and their per-block partial sums
-    const int64_t need_sum = std::max<int64_t>(h->msum_cap, (int64_t)K * h->D);
-    const int64_t need_part = std::max<int64_t>(h->mpart_cap, ((h->M + MOM_ROWS - 1) / MOM_ROWS) * (int64_t)K * h->D);
-    if (need_sum > h->msum_cap) {
-        pf_free(st, h->msum);
-        h->msum = nullptr, h->msum_cap = 0;
-        PF_HIP(pf_malloc(st, (void**)&h->msum, sizeof(double) * need_sum));
-        h->msum_cap = need_sum;
-    }
-    if (need_part > h->mpart_cap) {
-        pf_free(st, h->mpart);
-        h->mpart = nullptr, h->mpart_cap = 0;
-        PF_HIP(pf_malloc(st, (void**)&h->mpart, sizeof(double) * need_part));
-        h->mpart_cap = need_part;
-    }
+    PF_HIP(h->msum.grow(st, (int64_t)K * h->D));
+    PF_HIP(h->mpart.grow(st, ((h->M + MOM_ROWS - 1) / MOM_ROWS) * (int64_t)K * h->D));
     PF_HIP(hipStreamSynchronize(st));
     h->K = K;
     return PF_OK;
@@ -555,13 +516,13 @@ int pf_cpd_affine_sums(pf_cpd* h, double* shifts, double* sums) {
     const int D = h->D, Lm = 1 + 2 * D + 2 * D * D, Ln = 2 + D;
     const unsigned bm = (unsigned)((h->M + MOM_ROWS - 1) / MOM_ROWS), bn = (unsigned)((h->N + MOM_ROWS - 1) / MOM_ROWS);
     double *Pt1 = h->out, *P1 = h->out + h->N, *PX = h->out + h->N + h->M;
-    k_affine_moments_m<<<bm, PF_BLOCK, 0, st>>>(P1, PX, h->Y, h->shift, h->shift + 16, h->M, D, h->mpart);
-    k_sum_chunks<<<pf_blocks(Lm), PF_BLOCK, 0, st>>>(h->mpart, (int)bm, Lm, h->msum);
-    PF_HIP(hipMemcpyAsync(sums, h->msum, sizeof(double) * Lm, hipMemcpyDeviceToHost, st));
-    k_moments_n<<<bn, PF_BLOCK, 0, st>>>(Pt1, h->X, h->shift, h->N, D, h->mpart);
-    k_sum_chunks<<<pf_blocks(Ln), PF_BLOCK, 0, st>>>(h->mpart, (int)bn, Ln, h->msum);
+    k_affine_moments_m<<<bm, PF_BLOCK, 0, st>>>(P1, PX, h->Y, h->shift, h->shift + 16, h->M, D, h->mpart.p);
+    k_sum_chunks<<<pf_blocks(Lm), PF_BLOCK, 0, st>>>(h->mpart.p, (int)bm, Lm, h->msum.p);
+    PF_HIP(hipMemcpyAsync(sums, h->msum.p, sizeof(double) * Lm, hipMemcpyDeviceToHost, st));
+    k_moments_n<<<bn, PF_BLOCK, 0, st>>>(Pt1, h->X, h->shift, h->N, D, h->mpart.p);
+    k_sum_chunks<<<pf_blocks(Ln), PF_BLOCK, 0, st>>>(h->mpart.p, (int)bn, Ln, h->msum.p);
     PF_HIP(hipGetLastError());
-    PF_HIP(hipMemcpyAsync(sums + Lm, h->msum, sizeof(double) * Ln, hipMemcpyDeviceToHost, st));
+    PF_HIP(hipMemcpyAsync(sums + Lm, h->msum.p, sizeof(double) * Ln, hipMemcpyDeviceToHost, st));
     PF_HIP(hipMemcpyAsync(shifts, h->shift, sizeof(double) * 32, hipMemcpyDeviceToHost, st));
     PF_HIP(hipStreamSynchronize(st));
     return PF_OK;
@@ -572,9 +533,9 @@ int pf_cpd_apply_affine(pf_cpd* h, const double* B, const double* t) {
     PF_HIP(hipSetDevice(h->ctx->device));
     hipStream_t st = h->ctx->stream;
     const int D = h->D;
-    PF_HIP(hipMemcpyAsync(h->msum, B, sizeof(double) * D * D, hipMemcpyHostToDevice, st));
-    PF_HIP(hipMemcpyAsync(h->msum + D * D, t, sizeof(double) * D, hipMemcpyHostToDevice, st));
-    k_apply_affine<<<pf_blocks(h->M * D), PF_BLOCK, 0, st>>>(h->Y, h->msum, h->M, D, h->TY);
+    PF_HIP(hipMemcpyAsync(h->msum.p, B, sizeof(double) * D * D, hipMemcpyHostToDevice, st));
+    PF_HIP(hipMemcpyAsync(h->msum.p + D * D, t, sizeof(double) * D, hipMemcpyHostToDevice, st));
+    k_apply_affine<<<pf_blocks(h->M * D), PF_BLOCK, 0, st>>>(h->Y, h->msum.p, h->M, D, h->TY);
     PF_HIP(hipGetLastError());
     PF_HIP(hipStreamSynchronize(st));  // B and t are the caller's again
     return PF_OK;
@@ -593,23 +554,12 @@ int pf_cpd_deform_sums(pf_cpd* h, double* H, double* R) {
     k_sum_chunks<<<pf_blocks((int64_t)K * K), PF_BLOCK, 0, st>>>(h->hpart, h->chunks_h, (int64_t)K * K, h->H);
     PF_HIP(hipMemcpyAsync(H, h->H, sizeof(double) * (size_t)K * K, hipMemcpyDeviceToHost, st));
     const unsigned bm = (unsigned)((h->M + MOM_ROWS - 1) / MOM_ROWS);
-    const int64_t need = (int64_t)bm * K * D;
-    if (need > h->mpart_cap) {
-        pf_free(st, h->mpart);
-        h->mpart = nullptr, h->mpart_cap = 0;
-        PF_HIP(pf_malloc(st, (void**)&h->mpart, sizeof(double) * need));
-        h->mpart_cap = need;
-    }
-    if ((int64_t)K * D > h->msum_cap) {
-        pf_free(st, h->msum);
-        h->msum = nullptr, h->msum_cap = 0;
-        PF_HIP(pf_malloc(st, (void**)&h->msum, sizeof(double) * K * D));
-        h->msum_cap = (int64_t)K * D;
-    }
-    k_deform_rhs<<<bm, PF_BLOCK, 0, st>>>(h->Q, P1, PX, h->Y, h->M, K, D, h->mpart);
-    k_sum_chunks<<<pf_blocks((int64_t)K * D), PF_BLOCK, 0, st>>>(h->mpart, (int)bm, (int64_t)K * D, h->msum);
+    PF_HIP(h->mpart.grow(st, (int64_t)bm * K * D));
+    PF_HIP(h->msum.grow(st, (int64_t)K * D));
+    k_deform_rhs<<<bm, PF_BLOCK, 0, st>>>(h->Q, P1, PX, h->Y, h->M, K, D, h->mpart.p);
+    k_sum_chunks<<<pf_blocks((int64_t)K * D), PF_BLOCK, 0, st>>>(h->mpart.p, (int)bm, (int64_t)K * D, h->msum.p);
     PF_HIP(hipGetLastError());
-    PF_HIP(hipMemcpyAsync(R, h->msum, sizeof(double) * K * D, hipMemcpyDeviceToHost, st));
+    PF_HIP(hipMemcpyAsync(R, h->msum.p, sizeof(double) * K * D, hipMemcpyDeviceToHost, st));
     PF_HIP(hipStreamSynchronize(st));
     return PF_OK;
 }
@@ -617,22 +567,22 @@ int pf_cpd_deform_sums(pf_cpd* h, double* H, double* R) {
 int pf_cpd_apply_deform(pf_cpd* h, const double* C, double* sums) {
     PF_CHECK(h && C && sums, PF_E_ARG, "pf_cpd_apply_deform: NULL argument");
     PF_CHECK(h->K > 0, PF_E_STATE, "pf_cpd_apply_deform: no basis (pf_cpd_set_basis) on this handle");
-    PF_CHECK((int64_t)h->K * h->D <= h->msum_cap, PF_E_STATE, "pf_cpd_apply_deform: scratch smaller than K x d");
+    PF_CHECK((int64_t)h->K * h->D <= h->msum.cap, PF_E_STATE, "pf_cpd_apply_deform: scratch smaller than K x d");
     PF_HIP(hipSetDevice(h->ctx->device));
     hipStream_t st = h->ctx->stream;
     const int D = h->D, K = h->K;
     double *Pt1 = h->out, *P1 = h->out + h->N, *PX = h->out + h->N + h->M;
-    PF_HIP(hipMemcpyAsync(h->msum, C, sizeof(double) * K * D, hipMemcpyHostToDevice, st));
-    k_apply_deform<<<pf_blocks(h->M * D), PF_BLOCK, 0, st>>>(h->Y, h->Q, h->msum, h->M, K, D, h->TY);
+    PF_HIP(hipMemcpyAsync(h->msum.p, C, sizeof(double) * K * D, hipMemcpyHostToDevice, st));
+    k_apply_deform<<<pf_blocks(h->M * D), PF_BLOCK, 0, st>>>(h->Y, h->Q, h->msum.p, h->M, K, D, h->TY);
     // variance sums with the new TY and the posterior of this iteration: [Np, yPy, trPXY | sum Pt1, xPx]
     const unsigned bm = pf_blocks(h->M), bn = (unsigned)((h->N + MOM_ROWS - 1) / MOM_ROWS);
-    k_variance_m<<<bm, PF_BLOCK, 0, st>>>(P1, PX, h->TY, h->M, D, h->mpart);
-    k_sum_chunks<<<1, PF_BLOCK, 0, st>>>(h->mpart, (int)bm, 3, h->msum);  // C has been consumed (stream order)
-    PF_HIP(hipMemcpyAsync(sums, h->msum, sizeof(double) * 3, hipMemcpyDeviceToHost, st));
-    k_moments_n<<<bn, PF_BLOCK, 0, st>>>(Pt1, h->X, h->shift + 32, h->N, D, h->mpart);
-    k_sum_chunks<<<1, PF_BLOCK, 0, st>>>(h->mpart, (int)bn, 2 + D, h->msum);
+    k_variance_m<<<bm, PF_BLOCK, 0, st>>>(P1, PX, h->TY, h->M, D, h->mpart.p);
+    k_sum_chunks<<<1, PF_BLOCK, 0, st>>>(h->mpart.p, (int)bm, 3, h->msum.p);  // C has been consumed (stream order)
+    PF_HIP(hipMemcpyAsync(sums, h->msum.p, sizeof(double) * 3, hipMemcpyDeviceToHost, st));
+    k_moments_n<<<bn, PF_BLOCK, 0, st>>>(Pt1, h->X, h->shift + 32, h->N, D, h->mpart.p);
+    k_sum_chunks<<<1, PF_BLOCK, 0, st>>>(h->mpart.p, (int)bn, 2 + D, h->msum.p);
     PF_HIP(hipGetLastError());
-    PF_HIP(hipMemcpyAsync(sums + 3, h->msum, sizeof(double) * 2, hipMemcpyDeviceToHost, st));
+    PF_HIP(hipMemcpyAsync(sums + 3, h->msum.p, sizeof(double) * 2, hipMemcpyDeviceToHost, st));
     PF_HIP(hipStreamSynchronize(st));
     return PF_OK;
 }
@@ -658,34 +608,22 @@ int pf_cpd_gram(pf_ctx* ctx, const double* A, int64_t n_a, const double* B, int6
              n_cols, beta);
     PF_HIP(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    double *dA = nullptr, *dB = nullptr, *dV = nullptr, *dO = nullptr;
-    hipError_t e = hipSuccess;
-    int rc = PF_OK;
     // B rides on A's upload only when it is A or a leading part of it (low_rank_affinity: G(Y, Y) V, one upload per
     // product saved).  Equal pointers alone do not say that: B = Y against A = Y[:k] has n_b > n_a rows.
     const bool own_b = A != B || n_b > n_a;
-    do {
-        if ((e = pf_malloc(st, (void**)&dA, sizeof(double) * n_a * d)) != hipSuccess) break;
-        if (own_b && (e = pf_malloc(st, (void**)&dB, sizeof(double) * n_b * d)) != hipSuccess) break;
-        if ((e = pf_malloc(st, (void**)&dV, sizeof(double) * n_b * n_cols)) != hipSuccess) break;
-        if ((e = pf_malloc(st, (void**)&dO, sizeof(double) * n_a * n_cols)) != hipSuccess) break;
-        if ((e = hipMemcpyAsync(dA, A, sizeof(double) * n_a * d, hipMemcpyHostToDevice, st)) != hipSuccess) break;
-        if (own_b && (e = hipMemcpyAsync(dB, B, sizeof(double) * n_b * d, hipMemcpyHostToDevice, st)) != hipSuccess) break;
-        if ((e = hipMemcpyAsync(dV, V, sizeof(double) * n_b * n_cols, hipMemcpyHostToDevice, st)) != hipSuccess) break;
-        rc = dispatch_gram(st, d, dA, n_a, own_b ? dB : dA, n_b, 1.0 / (2.0 * beta * beta), dV, n_cols, dO);
-        if (rc != PF_OK) break;
-        if ((e = hipMemcpyAsync(out, dO, sizeof(double) * n_a * n_cols, hipMemcpyDeviceToHost, st)) != hipSuccess) break;
-        e = hipStreamSynchronize(st);
-    } while (0);
-    pf_free(st, dA);
-    pf_free(st, dB);
-    pf_free(st, dV);
-    pf_free(st, dO);
-    if (e != hipSuccess) {
-        pf_set_error("pf_cpd_gram: %s", hipGetErrorString(e));
-        return PF_E_HIP;
-    }
-    return rc;
+    Scratch s(st);
+    double* dA = s.get<double>(n_a * d);
+    double* dB = own_b ? s.get<double>(n_b * d) : dA;
+    double* dV = s.get<double>(n_b * n_cols);
+    double* dO = s.get<double>(n_a * n_cols);
+    s.upload(dA, A, n_a * d);
+    if (own_b) s.upload(dB, B, n_b * d);
+    s.upload(dV, V, n_b * n_cols);
+    if (s.ok()) PF_TRY(dispatch_gram(st, d, dA, n_a, dB, n_b, 1.0 / (2.0 * beta * beta), dV, n_cols, dO));
+    s.download(out, dO, n_a * n_cols);
+    s.sync();
+    PF_CHECK(s.ok(), PF_E_HIP, "pf_cpd_gram: %s", hipGetErrorString(s.err));
+    return PF_OK;
 }
 
 }  // extern "C"

@@ -278,7 +278,7 @@ extern "C" int pf_eigsort_costs(pf_graph* gt, pf_graph* gs, const int64_t* rows_
         const double ones3[3] = {1.0, 1.0, 1.0};
         rc = pf_knn1_blocks(c, norm_s, ms, 3, norm_t, mt, 3, 3, cols3, ones3, cols3, ones3, idx_out, nullptr);
         if (rc != PF_OK) break;
-        k_es_spatial<<<(unsigned)(k * k), ES_RED_THREADS, 0, st>>>(vals_t, vals_s, c->knn_idx, mt, ms, k, d_out);
+        k_es_spatial<<<(unsigned)(k * k), ES_RED_THREADS, 0, st>>>(vals_t, vals_s, c->knn_idx.p, mt, ms, k, d_out);
         if (fail(hipGetLastError())) break;
         if ((rc = pf_copy_by_kernel(st, d_out, pin + up_bytes, out_bytes)) != PF_OK) break;
         if (fail(hipStreamSynchronize(st))) break;

@@ -445,7 +445,7 @@ static int fmap_convert(pf_fmap* h, const FmapView& v, int32_t k_s, int32_t k_t)
     }
     if (!wide) {
         PF_TRY(pf_knn1_device(c, v.phi_t, v.n_t, h->K, v.Q, v.n_s, k_t, k_t));
-        k_fmap_take_knn<<<pf_blocks(v.n_s), PF_BLOCK, 0, c->stream>>>(c->knn_idx, c->knn_d2, v.n_s, v.T, v.d2);
+        k_fmap_take_knn<<<pf_blocks(v.n_s), PF_BLOCK, 0, c->stream>>>(c->knn_idx.p, c->knn_d2.p, v.n_s, v.T, v.d2);
         PF_HIP(hipGetLastError());
     }
     if (v.T == h->T) h->has_T = h->has_d2 = true;

@@ -5,10 +5,12 @@
 #include <atomic>
 #include <map>
 #include <mutex>
+#include <type_traits>
 #include <unordered_map>
 #include <vector>
 
 #include "../../include/pyfocusr_hip.h"
+#include "pf_scratch.h"
 
 void pf_set_error(const char* fmt, ...);
 
@@ -36,6 +38,19 @@ void pf_set_error(const char* fmt, ...);
         if (r_ != PF_OK) return r_; \
     } while (0)
 
+// f(std::integral_constant<int, D>{}) for the D of LO..HI that equals d: the one place where a run-time depth picks a
+// template instance.  Any other d: PF_E_ARG with the caller's message (a format with one %d).
+template <int LO, int HI, class F>
+int pf_dispatch_d(int d, F&& f, const char* msg) {
+    if constexpr (LO > HI) {
+        pf_set_error(msg, d);
+        return PF_E_ARG;
+    } else {
+        if (d == LO) return f(std::integral_constant<int, LO>{});
+        return pf_dispatch_d<LO + 1, HI>(d, f, msg);
+    }
+}
+
 constexpr int PF_WAVE = 64;        // gfx950 wavefront
 constexpr int PF_BLOCK = 256;      // 4 waves: one per SIMD of a CU
 constexpr int PF_DOT_CHUNK = 4096; // rows per block in the reduction kernels
@@ -54,14 +69,13 @@ inline unsigned pf_blocks(int64_t n) { return (unsigned)((n + PF_BLOCK - 1) / PF
 
 // device buffers of the box hierarchy of pf_knn_tree.hip (1-NN for deep coordinates); they grow and stay with the ctx
 struct pf_knn_tree {
-    double* pts = nullptr;       // [n_leaf][d][64] leaves, coordinate-major
-    int32_t* orig = nullptr;     // [n_leaf][64] original reference indices
-    double* leaf_lo = nullptr;   // [2][n_sup][d][64] leaf boxes: lo, then hi
-    double* sup_lo = nullptr;    // [2][d][ns_pad] boxes of the supers
-    int32_t* qry_order = nullptr;  // queries along the references' Morton curve
-    void* grid = nullptr;        // TreeGrid
+    DevBuf<double> pts;         // [n_leaf][d][64] leaves, coordinate-major
+    DevBuf<int32_t> orig;       // [n_leaf][64] original reference indices
+    DevBuf<double> leaf_lo;     // [2][n_sup][d][64] leaf boxes: lo, then hi
+    DevBuf<double> sup_lo;      // [2][d][ns_pad] boxes of the supers
+    DevBuf<int32_t> qry_order;  // queries along the references' Morton curve
+    void* grid = nullptr;       // TreeGrid
     unsigned long long* counters = nullptr;
-    int64_t cap_pts = 0, cap_orig = 0, cap_leaf = 0, cap_sup = 0, cap_qry = 0;
     bool count_visits = false;
 };
 
@@ -87,34 +101,30 @@ struct pf_ctx {
     double knn_ms = 0.0;
     double build_ms = 0.0;
     bool build_pending = false;  // ev0 / ev1 bracket a build whose device time has not been read yet
-    // nearest-neighbour state (pf_knn_upload / run / download)
-    double* knn_ref = nullptr;   // [n_ref][d] as uploaded
-    double* knn_qry = nullptr;   // [n_qry][d]
-    double* knn_ref_s = nullptr; // rows sorted along the search axis
-    double* knn_ref_soa = nullptr;  // the same rows coordinate-major, [d][knn_ref_ld] (k_knn_coop)
-    int64_t knn_cap_ref_soa = 0, knn_ref_ld = 0;
-    double* knn_qry_s = nullptr;
-    unsigned* knn_ref_key = nullptr; // sorted grid-cell ids (references: row-major; queries: Morton)
-    unsigned* knn_qry_key = nullptr;
-    int32_t* knn_cell_start = nullptr; // [res*res + 1] first sorted reference of each cell
-    int64_t knn_cap_cell = 0;
+    // nearest-neighbour state (pf_knn_upload / run / download); the buffers grow and stay with the ctx
+    DevBuf<double> knn_ref;      // [n_ref][d] as uploaded
+    DevBuf<double> knn_qry;      // [n_qry][d]
+    DevBuf<double> knn_ref_s;    // rows sorted along the search axis
+    DevBuf<double> knn_ref_soa;  // the same rows coordinate-major, [d][knn_ref_ld] (k_knn_coop)
+    int64_t knn_ref_ld = 0;
+    DevBuf<double> knn_qry_s;
+    DevBuf<unsigned> knn_ref_key;  // sorted grid-cell ids (references: row-major; queries: Morton)
+    DevBuf<unsigned> knn_qry_key;
+    DevBuf<int32_t> knn_cell_start;  // [res*res + 1] first sorted reference of each cell
     int knn_res = 0;
     void* knn_grid = nullptr; // KnnGrid (pf_knn.hip)
-    int32_t* knn_ref_orig = nullptr; // sorted position -> original index
-    int32_t* knn_qry_orig = nullptr;
+    DevBuf<int32_t> knn_ref_orig;  // sorted position -> original index
+    DevBuf<int32_t> knn_qry_orig;
     unsigned long long* knn_ext = nullptr; // [16] per-axis min / max (encoded)
     int64_t knn_nref = 0, knn_nqry = 0;
-    int64_t knn_cap_ref = 0, knn_cap_qry = 0, knn_cap_ref_s = 0, knn_cap_qry_s = 0, knn_cap_ref_key = 0,
-            knn_cap_qry_key = 0, knn_cap_ref_orig = 0, knn_cap_qry_orig = 0, knn_cap_idx = 0, knn_cap_d2 = 0;
     int32_t knn_d = 0;
     int32_t knn_k = 1;                 // neighbours per query of the prepared problem (set by knn_prepare once its checks passed)
-    int64_t* knn_idx = nullptr; // [n_qry]
-    double* knn_d2 = nullptr;   // [n_qry]
+    DevBuf<int64_t> knn_idx;  // [n_qry][k]
+    DevBuf<double> knn_d2;    // [n_qry][k]
     bool knn_ready = false, knn_done = false;
     pf_knn_tree knn_tree;
     bool knn_count_on = false;              // pf_knn_count: the counting instantiation of k_knn_coop
-    unsigned long long* knn_visited = nullptr;
-    size_t knn_visited_words = 0;
+    DevBuf<unsigned long long> knn_visited;  // [0] pairs, then eight words per wave of the last counted search
     int64_t knn_visited_waves = 0;
     unsigned long long* wide_count = nullptr;  // pf_knn1_wide_count: chunks the last counted wide search went through (pf_fmap.hip)
     bool wide_count_on = false;
@@ -311,13 +321,7 @@ struct pf_mesh {
     int32_t vpf = 0;
 };
 
-// Caching device allocator, one cache per ctx (pf_api.hip).  Every use of a block is enqueued on
-// the ctx's single stream, so a block released at enqueue time can be handed out again at once:
-// later work is ordered behind earlier work by the stream.  After the first build the assembler's
-// ~30 temporaries are recycled without a driver call (hipMalloc/hipFree cost 0.1-1 ms each and
-// hipFree synchronises the device).  Blocks go back to the driver in pf_destroy.
 int pf_timing_collect(pf_ctx* c);  // pf_api.hip: fold finished spans into op_ms / op_launches / op_bytes
-hipError_t pf_malloc(hipStream_t st, void** p, size_t bytes);
 // the ctx's pinned host block for small transfers, at least `bytes` large (valid until the next call that asks for more;
 // users synchronise with the stream before they return)
 int pf_pinned_scratch(pf_ctx* c, size_t bytes, void** out, int which = 0);  // which 0: ctx stream, 1: the second mesh of a pair build, 2: the KNN read-back
@@ -328,58 +332,9 @@ int pf_downloads_release(pf_ctx* c);  // queue every download of the ctx that wa
 int pf_download_cancel(pf_graph* g);  // forget the image owed to the caller's buffer / wait for the one in flight (a call is about to fail)
 hipStream_t pf_stream_b(pf_ctx* c);  // created on first use (nullptr on failure)
 hipError_t pf_create_side_stream(hipStream_t* s, bool low = false);  // low: the least priority (a third pool of queues: the copy stream)  // a stream that never shares a hardware queue with a ctx's main stream
-void pf_free(hipStream_t st, void* p);
-
-// The device side of one call: scratch blocks from the ctx's cache, all given back when the call's scope ends (after
-// whatever synchronise the call made: as late as the blocks can matter), and the stream work itself.  The first failure is
-// kept in err and turns everything that follows into a no-op, so a call is written without branches: ok() before its
-// kernels, err at the end.
-struct Scratch {
-    const hipStream_t st;
-    hipError_t err = hipSuccess;
-    std::vector<void*> blocks;
-
-    explicit Scratch(hipStream_t stream) : st(stream) {}
-    Scratch(const Scratch&) = delete;
-    Scratch& operator=(const Scratch&) = delete;
-    ~Scratch() {
-        for (void* p : blocks) pf_free(st, p);
-    }
-    bool ok() const { return err == hipSuccess; }
-    void note(hipError_t e) {
-        if (ok()) err = e;
-    }
-    template <class T>
-    T* keep(size_t count) {  // a block that outlives the call: the caller owns it, also after a failure
-        void* p = nullptr;
-        if (ok()) err = pf_malloc(st, &p, sizeof(T) * count);
-        return (T*)p;
-    }
-    template <class T>
-    T* get(size_t count) {
-        T* p = keep<T>(count);
-        if (p) blocks.push_back(p);
-        return p;
-    }
-    template <class T>
-    void upload(T* dst, const T* src, size_t count) {
-        if (ok()) err = hipMemcpyAsync(dst, src, sizeof(T) * count, hipMemcpyHostToDevice, st);
-    }
-    template <class T>
-    void download(T* dst, const T* src, size_t count) {  // dst == NULL: the caller did not ask for it
-        if (ok() && dst) err = hipMemcpyAsync(dst, src, sizeof(T) * count, hipMemcpyDeviceToHost, st);
-    }
-    void zero(void* p, size_t bytes) {
-        if (ok()) err = hipMemsetAsync(p, 0, bytes, st);
-    }
-    void launched() { note(hipGetLastError()); }  // after the kernels of an ok() block
-    void sync() {
-        if (ok()) err = hipStreamSynchronize(st);
-    }
-};
 
 // pf_tri_hierarchy.hip: the chunk / super-chunk structure over the fan triangles of a surface in d coordinates that
-// pf_surface.hip (d = 3) and pf_surface_nd.hip search; pf_tri_hierarchy.h describes it and holds the device helpers
+// pf_surface.hip (d = 3) and pf_surface_nd.hip search; pf_tri_hierarchy.h describes it and holds its device helpers
 constexpr int PF_ND_MAX = 16;  // coordinates (the limit of pf_knn_upload and pf_assign)
 struct TriHierarchy {
     double* tri = nullptr;        // SoA [3 corners][d][n_tri], Morton order
@@ -403,6 +358,10 @@ KeyBox pf_key_box(const double* pts, int64_t n, int32_t d, bool finite_only);
 // Keys, values and the sort's temporary are scratch of sc; NULL after a failure.
 const int32_t* pf_surface_morton_order(Scratch& sc, const double* d_pts, int32_t d, const int32_t* d_faces, int32_t vpf, int64_t n,
                                        const KeyBox& bb);
+// The stable radix sort of n (unsigned key, int32 value) pairs on key bits [0, end_bit), queued on sc's stream; its
+// temporary is scratch of sc.  Sorts the Morton orders of the surfaces and of the k-NN box hierarchy, and the cells of
+// the k-NN grid's large point sets.
+void pf_sort_pairs(Scratch& sc, const unsigned* k_in, unsigned* k_out, const int32_t* v_in, int32_t* v_out, int64_t n, int end_bit);
 // keys -> stable sort -> gather -> chunk boxes -> super boxes, queued on sc's stream; h owns its four buffers from here on,
 // also after a failure (sc.err)
 void pf_tri_hierarchy_build(Scratch& sc, TriHierarchy& h, const double* d_pts, int32_t d, const int32_t* d_faces, int64_t n_faces,

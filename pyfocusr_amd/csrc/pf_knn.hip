@@ -31,6 +31,7 @@
 #include <algorithm>
 
 #include "pf_internal.h"
+#include "pf_wave.h"
 
 namespace {
 
@@ -42,14 +43,6 @@ struct KnnGrid {
     double lo0, lo1; // grid origin
     double s0, s1;   // cells per unit length (0 when the extent is 0)
 };
-
-__device__ __forceinline__ unsigned long long enc_f64(double d) {
-    const unsigned long long u = (unsigned long long)__double_as_longlong(d);
-    return (u >> 63) ? ~u : (u | (1ull << 63));
-}
-__device__ __forceinline__ double dec_f64(unsigned long long u) {
-    return __longlong_as_double((long long)((u >> 63) ? (u & ~(1ull << 63)) : ~u));
-}
 
 // monotone non-decreasing in x (same expression for references, queries and interval ends)
 __device__ __forceinline__ int cell_of(double x, double lo, double scale, int r) {
@@ -433,17 +426,6 @@ __global__ __launch_bounds__(BS) void k_knn_grid(const double* __restrict__ ref_
 // queries per wave: their coordinates stay in registers (G x d doubles, wave-uniform)
 constexpr int knn_group(int d) { return d <= 4 ? 8 : (d <= 8 ? 4 : 2); }
 
-__device__ __forceinline__ void wave_argmin(double& s, int32_t& o) {
-#pragma unroll
-    for (int off = PF_WAVE / 2; off > 0; off >>= 1) {
-        const double s2 = __shfl_xor(s, off, PF_WAVE);
-        const int32_t o2 = __shfl_xor(o, off, PF_WAVE);
-        const bool take = s2 < s || (s2 == s && o2 < o);
-        s = take ? s2 : s;
-        o = take ? o2 : o;
-    }
-}
-
 // COUNT (pf_knn_count; a separate instantiation, the search itself never pays for it): the candidate-query pairs whose
 // distance the search evaluates, summed into *visited - the work figure behind the roofline entry of the 1-NN stage.
 template <int D, bool COUNT = false>
@@ -692,7 +674,7 @@ template <int D>
 static int launch_knn_small(pf_ctx* c) {
     const int64_t groups = (c->knn_nqry + knn_small_group(D) - 1) / knn_small_group(D);
     k_knn_small<D><<<(unsigned)((groups + PF_BLOCK / PF_WAVE - 1) / (PF_BLOCK / PF_WAVE)), PF_BLOCK, 0, c->stream>>>(
-        c->knn_ref, c->knn_nref, c->knn_qry, c->knn_nqry, c->knn_idx, c->knn_d2);
+        c->knn_ref.p, c->knn_nref, c->knn_qry.p, c->knn_nqry, c->knn_idx.p, c->knn_d2.p);
     PF_HIP(hipGetLastError());
     return PF_OK;
 }
@@ -721,29 +703,22 @@ int launch_knn_k(pf_ctx* c) {
         const int64_t waves = (c->knn_nqry + knn_group(D) - 1) / knn_group(D);
         if (c->knn_count_on) {
             // [0] pairs, then from [8] on eight words per wave (pf_knn_wave_stats)
-            const size_t words = 8 + 8 * (size_t)waves;
-            if (c->knn_visited && c->knn_visited_words < words) {
-                pf_free(c->stream, c->knn_visited);
-                c->knn_visited = nullptr;
-            }
-            if (!c->knn_visited) {
-                PF_HIP(pf_malloc(c->stream, (void**)&c->knn_visited, words * sizeof(unsigned long long)));
-                c->knn_visited_words = words;
-            }
+            const int64_t words = 8 + 8 * waves;
+            PF_HIP(c->knn_visited.grow(c->stream, words));
             c->knn_visited_waves = waves;
-            PF_HIP(hipMemsetAsync(c->knn_visited, 0, words * sizeof(unsigned long long), c->stream));
+            PF_HIP(hipMemsetAsync(c->knn_visited.p, 0, words * sizeof(unsigned long long), c->stream));
             k_knn_coop<D, true><<<(unsigned)((waves + PF_BLOCK / PF_WAVE - 1) / (PF_BLOCK / PF_WAVE)), PF_BLOCK, 0, c->stream>>>(
-                c->knn_ref_soa, c->knn_ref_ld, c->knn_ref_orig, c->knn_cell_start, c->knn_qry_s, c->knn_qry_orig, c->knn_nqry,
-                (const KnnGrid*)c->knn_grid, c->knn_idx, c->knn_d2, c->knn_visited);
+                c->knn_ref_soa.p, c->knn_ref_ld, c->knn_ref_orig.p, c->knn_cell_start.p, c->knn_qry_s.p, c->knn_qry_orig.p, c->knn_nqry,
+                (const KnnGrid*)c->knn_grid, c->knn_idx.p, c->knn_d2.p, c->knn_visited.p);
         } else {
             k_knn_coop<D><<<(unsigned)((waves + PF_BLOCK / PF_WAVE - 1) / (PF_BLOCK / PF_WAVE)), PF_BLOCK, 0, c->stream>>>(
-                c->knn_ref_soa, c->knn_ref_ld, c->knn_ref_orig, c->knn_cell_start, c->knn_qry_s, c->knn_qry_orig, c->knn_nqry,
-                (const KnnGrid*)c->knn_grid, c->knn_idx, c->knn_d2);
+                c->knn_ref_soa.p, c->knn_ref_ld, c->knn_ref_orig.p, c->knn_cell_start.p, c->knn_qry_s.p, c->knn_qry_orig.p, c->knn_nqry,
+                (const KnnGrid*)c->knn_grid, c->knn_idx.p, c->knn_d2.p);
         }
     } else {
         k_knn_grid<D, K, BS, 512><<<(unsigned)((c->knn_nqry + BS - 1) / BS), BS, 0, c->stream>>>(
-            c->knn_ref_s, c->knn_ref_orig, c->knn_cell_start, c->knn_nref, c->knn_qry_s, c->knn_qry_orig, c->knn_nqry,
-            (const KnnGrid*)c->knn_grid, c->knn_idx, c->knn_d2);
+            c->knn_ref_s.p, c->knn_ref_orig.p, c->knn_cell_start.p, c->knn_nref, c->knn_qry_s.p, c->knn_qry_orig.p, c->knn_nqry,
+            (const KnnGrid*)c->knn_grid, c->knn_idx.p, c->knn_d2.p);
     }
     PF_HIP(hipGetLastError());
     return PF_OK;
@@ -759,17 +734,6 @@ int launch_knn(pf_ctx* c) {
     }
     pf_set_error("pf_knn: k = %d with d = %d is not supported (k <= 4 needs d <= 4)", c->knn_k, D);
     return PF_E_ARG;
-}
-
-template <typename T>
-int grow(hipStream_t st, T** p, int64_t* cap, int64_t need) {
-    if (need <= *cap) return PF_OK;
-    pf_free(st, *p);
-    *p = nullptr;
-    *cap = 0;
-    PF_HIP(pf_malloc(st, (void**)p, sizeof(T) * (size_t)need));
-    *cap = need;
-    return PF_OK;
 }
 
 // counting sort by cell key (keys < n_buckets): histogram, exclusive scan, scatter through per-bucket cursors.  The
@@ -793,13 +757,8 @@ __global__ __launch_bounds__(PF_BLOCK) void k_bucket_scatter(const unsigned* __r
 // launches where hipCUB's radix sort dispatches a merge sort of 17 launches (~107 us) for arrays below 1M items.
 int sort_points(pf_ctx* c, const double* pts, int64_t n, int d, int morton, int key_bits, unsigned* key_out, int32_t* orig_out,
                 double* rows_out) {
-    hipStream_t st = c->stream;
-    unsigned* k0 = nullptr;
-    int32_t* v0 = nullptr;
-    void* tmp = nullptr;
-    size_t bytes = 0;
-    int rc = PF_OK;
-    hipError_t e = pf_malloc(st, (void**)&k0, sizeof(unsigned) * n);
+    Scratch s(c->stream);
+    unsigned* k0 = s.get<unsigned>(n);
     // keys are cell ids (row-major: < res^2) or Morton codes of cells (< 4^ceil(log2 res))
     int64_t n_buckets = 1;
     {
@@ -816,44 +775,34 @@ int sort_points(pf_ctx* c, const double* pts, int64_t n, int d, int morton, int 
     // than 16M points take by themselves)
     int64_t bucket_max = (int64_t)1 << 22;
     if (const char* ev = getenv("PF_KNN_BUCKET_MAX")) bucket_max = atoll(ev);
-    if (e == hipSuccess && n_buckets <= bucket_max) {
-        int32_t* hist = nullptr;  // [n_buckets + 1] counts, [n_buckets + 1] starts, [n_buckets] cursors
-        e = pf_malloc(st, (void**)&hist, sizeof(int32_t) * (size_t)(3 * n_buckets + 2));
-        tmp = hist;
-        if (e == hipSuccess) e = hipMemsetAsync(hist, 0, sizeof(int32_t) * (size_t)(3 * n_buckets + 2), st);
-        if (e == hipSuccess) {
+    if (n_buckets <= bucket_max) {
+        int32_t* hist = s.get<int32_t>(3 * n_buckets + 2);  // [n_buckets + 1] counts, [n_buckets + 1] starts, [n_buckets] cursors
+        s.zero(hist, sizeof(int32_t) * (size_t)(3 * n_buckets + 2));
+        if (s.ok()) {
             int32_t* start = hist + n_buckets + 1;
             int32_t* cursor = start + n_buckets + 1;
-            k_cell_keys<<<pf_blocks(n), PF_BLOCK, 0, st>>>(pts, n, d, (const KnnGrid*)c->knn_grid, morton, k0, nullptr, hist);
-            e = hipGetLastError();
-            if (e == hipSuccess && pf_exclusive_scan_i32(st, hist, start, n_buckets + 1) != PF_OK) e = hipErrorUnknown;
-            if (e == hipSuccess) {
-                k_bucket_scatter<<<pf_blocks(n), PF_BLOCK, 0, st>>>(k0, n, start, cursor, key_out, orig_out, pts, d, rows_out);
-                e = hipGetLastError();
+            k_cell_keys<<<pf_blocks(n), PF_BLOCK, 0, s.st>>>(pts, n, d, (const KnnGrid*)c->knn_grid, morton, k0, nullptr, hist);
+            s.launched();
+            if (s.ok() && pf_exclusive_scan_i32(s.st, hist, start, n_buckets + 1) != PF_OK) s.note(hipErrorUnknown);
+            if (s.ok()) {
+                k_bucket_scatter<<<pf_blocks(n), PF_BLOCK, 0, s.st>>>(k0, n, start, cursor, key_out, orig_out, pts, d, rows_out);
+                s.launched();
             }
         }
     } else {
-        if (e == hipSuccess) e = pf_malloc(st, (void**)&v0, sizeof(int32_t) * n);
-        if (e == hipSuccess) {
-            k_cell_keys<<<pf_blocks(n), PF_BLOCK, 0, st>>>(pts, n, d, (const KnnGrid*)c->knn_grid, morton, k0, v0, nullptr);
-            e = hipGetLastError();
+        int32_t* v0 = s.get<int32_t>(n);
+        if (s.ok()) {
+            k_cell_keys<<<pf_blocks(n), PF_BLOCK, 0, s.st>>>(pts, n, d, (const KnnGrid*)c->knn_grid, morton, k0, v0, nullptr);
+            s.launched();
         }
-        if (e == hipSuccess) e = hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, k0, key_out, v0, orig_out, (int)n, 0, key_bits, st);
-        if (e == hipSuccess) e = pf_malloc(st, &tmp, bytes);
-        if (e == hipSuccess) e = hipcub::DeviceRadixSort::SortPairs(tmp, bytes, k0, key_out, v0, orig_out, (int)n, 0, key_bits, st);
-        if (e == hipSuccess) {
-            k_gather_rows<<<pf_blocks(n), PF_BLOCK, 0, st>>>(pts, orig_out, n, d, rows_out);
-            e = hipGetLastError();
+        pf_sort_pairs(s, k0, key_out, v0, orig_out, n, key_bits);
+        if (s.ok()) {
+            k_gather_rows<<<pf_blocks(n), PF_BLOCK, 0, s.st>>>(pts, orig_out, n, d, rows_out);
+            s.launched();
         }
     }
-    if (e != hipSuccess) {
-        pf_set_error("pf_knn: %s", hipGetErrorString(e));
-        rc = PF_E_HIP;
-    }
-    pf_free(st, k0);
-    pf_free(st, v0);
-    pf_free(st, tmp);
-    return rc;
+    PF_CHECK(s.ok(), PF_E_HIP, "pf_knn: %s", hipGetErrorString(s.err));
+    return PF_OK;
 }
 
 }  // namespace
@@ -871,27 +820,29 @@ static int knn_prepare(pf_ctx* c, int64_t n_ref, int64_t n_qry, int32_t d, int32
     PF_HIP(hipSetDevice(c->device));
     hipStream_t st = c->stream;
     c->knn_ready = c->knn_done = false;
-    PF_TRY(grow(st, &c->knn_ref, &c->knn_cap_ref, n_ref * 16));
-    PF_TRY(grow(st, &c->knn_ref_s, &c->knn_cap_ref_s, n_ref * 16));
-    PF_TRY(grow(st, &c->knn_ref_key, &c->knn_cap_ref_key, n_ref));
+    PF_HIP(c->knn_ref.grow(st, n_ref * 16));
+    PF_HIP(c->knn_ref_s.grow(st, n_ref * 16));
+    PF_HIP(c->knn_ref_key.grow(st, n_ref));
     c->knn_ref_ld = (n_ref + PF_WAVE - 1) & ~(int64_t)(PF_WAVE - 1);
-    PF_TRY(grow(st, &c->knn_ref_soa, &c->knn_cap_ref_soa, c->knn_ref_ld * d));
+    PF_HIP(c->knn_ref_soa.grow(st, c->knn_ref_ld * d));
     // grid resolution: ~4 references per cell if they were spread over the plane
     static const double per_cell = [] { const char* e = getenv("PF_KNN_PER_CELL"); const double v = e ? atof(e) : 0.0; return v > 0.0 ? v : 4.0; }();
     int res = (int)sqrt((double)n_ref / per_cell);
     res = res < 4 ? 4 : (res > 2048 ? 2048 : res);
     c->knn_res = res;
-    PF_TRY(grow(st, &c->knn_cell_start, &c->knn_cap_cell, (int64_t)res * res + 2));
-    PF_TRY(grow(st, &c->knn_ref_orig, &c->knn_cap_ref_orig, n_ref));
-    PF_TRY(grow(st, &c->knn_qry, &c->knn_cap_qry, n_qry * 16));
-    PF_TRY(grow(st, &c->knn_qry_s, &c->knn_cap_qry_s, n_qry * 16));
-    PF_TRY(grow(st, &c->knn_qry_key, &c->knn_cap_qry_key, n_qry));
-    PF_TRY(grow(st, &c->knn_qry_orig, &c->knn_cap_qry_orig, n_qry));
-    PF_TRY(grow(st, &c->knn_idx, &c->knn_cap_idx, n_qry * k));
-    PF_TRY(grow(st, &c->knn_d2, &c->knn_cap_d2, n_qry * k));
+    PF_HIP(c->knn_cell_start.grow(st, (int64_t)res * res + 2));
+    PF_HIP(c->knn_ref_orig.grow(st, n_ref));
+    PF_HIP(c->knn_qry.grow(st, n_qry * 16));
+    PF_HIP(c->knn_qry_s.grow(st, n_qry * 16));
+    PF_HIP(c->knn_qry_key.grow(st, n_qry));
+    PF_HIP(c->knn_qry_orig.grow(st, n_qry));
+    PF_HIP(c->knn_idx.grow(st, n_qry * k));
+    PF_HIP(c->knn_d2.grow(st, n_qry * k));
     c->knn_k = k;
-    if (!c->knn_ext) PF_HIP(pf_malloc(st, (void**)&c->knn_ext, 32 * sizeof(unsigned long long)));
-    if (!c->knn_grid) PF_HIP(pf_malloc(st, &c->knn_grid, sizeof(KnnGrid)));
+    Scratch once(st);  // the two small blocks that are taken once and stay
+    if (!c->knn_ext) c->knn_ext = once.keep<unsigned long long>(32);
+    if (!c->knn_grid) c->knn_grid = once.keep<KnnGrid>(1);
+    PF_HIP(once.err);
     c->knn_nref = n_ref;
     c->knn_nqry = n_qry;
     c->knn_d = d;
@@ -917,8 +868,8 @@ static int knn_upload_k(pf_ctx* c, const double* ref, int64_t n_ref, const doubl
     PF_CHECK(c && ref && qry, PF_E_ARG, "pf_knn_upload: NULL argument");
     PF_TRY(knn_prepare(c, n_ref, n_qry, d, k));
     hipStream_t st = c->stream;
-    PF_HIP(hipMemcpyAsync(c->knn_ref, ref, sizeof(double) * n_ref * d, hipMemcpyHostToDevice, st));
-    PF_HIP(hipMemcpyAsync(c->knn_qry, qry, sizeof(double) * n_qry * d, hipMemcpyHostToDevice, st));
+    PF_HIP(hipMemcpyAsync(c->knn_ref.p, ref, sizeof(double) * n_ref * d, hipMemcpyHostToDevice, st));
+    PF_HIP(hipMemcpyAsync(c->knn_qry.p, qry, sizeof(double) * n_qry * d, hipMemcpyHostToDevice, st));
     PF_HIP(hipStreamSynchronize(st));
     c->knn_ready = true;
     return PF_OK;
@@ -928,87 +879,46 @@ int pf_knn_upload(pf_ctx* c, const double* ref, int64_t n_ref, const double* qry
     return knn_upload_k(c, ref, n_ref, qry, n_qry, d, 1);
 }
 
-int pf_knn_run(pf_ctx* c) {
-    PF_CHECK(c != nullptr, PF_E_ARG, "pf_knn_run: ctx is NULL");
-    PF_CHECK(c->knn_ready, PF_E_STATE, "pf_knn_run: no uploaded problem");
-    PF_HIP(hipSetDevice(c->device));
+// the search of the prepared problem, queued on the ctx's stream: one launch for small sets, the box hierarchy for deep
+// coordinates, the grid otherwise
+static int knn_search(pf_ctx* c) {
     hipStream_t st = c->stream;
     const int d = c->knn_d;
-    PF_HIP(hipEventRecord(c->ev0, st));
-    if (c->knn_k == 1 && c->knn_mode == 0 && d <= 8 && c->knn_nref <= PF_KNN_SMALL && c->knn_nqry <= PF_KNN_SMALL) {
-        int r = PF_E_ARG;
-        switch (d) {
-            case 1: r = launch_knn_small<1>(c); break;
-            case 2: r = launch_knn_small<2>(c); break;
-            case 3: r = launch_knn_small<3>(c); break;
-            case 4: r = launch_knn_small<4>(c); break;
-            case 5: r = launch_knn_small<5>(c); break;
-            case 6: r = launch_knn_small<6>(c); break;
-            case 7: r = launch_knn_small<7>(c); break;
-            case 8: r = launch_knn_small<8>(c); break;
-            default: break;
-        }
-        PF_TRY(r);
-        PF_HIP(hipEventRecord(c->ev1, st));
-        PF_HIP(hipEventSynchronize(c->ev1));
-        float sms = 0.f;
-        PF_HIP(hipEventElapsedTime(&sms, c->ev0, c->ev1));
-        c->knn_ms = sms;
-        c->knn_done = true;
-        return PF_OK;
+    const char* bad_d = "pf_knn_run: no search for d = %d";
+    if (c->knn_k == 1 && c->knn_mode == 0 && d <= 8 && c->knn_nref <= PF_KNN_SMALL && c->knn_nqry <= PF_KNN_SMALL)
+        return pf_dispatch_d<1, 8>(d, [&](auto D) { return launch_knn_small<D()>(c); }, bad_d);
+    PF_TRY(pf_knn_extent(st, c->knn_ref.p, c->knn_nref, d, c->knn_ext));
+    // deep coordinates (k = 1): a grid over two axes prunes two of d coordinates; the box hierarchy prunes with all of them
+    if (c->knn_k == 1 && (c->knn_mode == 2 || (c->knn_mode == 0 && d >= PF_KNN_TREE_MIN_D))) {
+        if (c->knn_nqry >= 32768) PF_TRY(pf_downloads_release(c));
+        return pf_knn_tree_run(c);
     }
-    PF_TRY(pf_knn_extent(st, c->knn_ref, c->knn_nref, d, c->knn_ext));
     const int res = c->knn_res;
     const int64_t n_cells = d == 1 ? res : (int64_t)res * res;
     int cell_bits = 1;
     while (((int64_t)1 << cell_bits) < n_cells) ++cell_bits;
-    // deep coordinates (k = 1): a grid over two axes prunes two of d coordinates; the box hierarchy prunes with all of them
-    const bool tree = c->knn_k == 1 && (c->knn_mode == 2 || (c->knn_mode == 0 && d >= PF_KNN_TREE_MIN_D));
-    if (tree) {
-        if (c->knn_nqry >= 32768) PF_TRY(pf_downloads_release(c));
-        PF_TRY(pf_knn_tree_run(c));
-        PF_HIP(hipEventRecord(c->ev1, st));
-        PF_HIP(hipEventSynchronize(c->ev1));
-        float tms = 0.f;
-        PF_HIP(hipEventElapsedTime(&tms, c->ev0, c->ev1));
-        c->knn_ms = tms;
-        c->knn_done = true;
-        return PF_OK;
-    }
     k_make_grid<<<1, 1, 0, st>>>(c->knn_ext, d, res, (KnnGrid*)c->knn_grid);
     PF_HIP(hipGetLastError());
-    PF_TRY(sort_points(c, c->knn_ref, c->knn_nref, d, 0, cell_bits, c->knn_ref_key, c->knn_ref_orig, c->knn_ref_s));
-    k_cell_start<<<pf_blocks(n_cells + 1), PF_BLOCK, 0, st>>>(c->knn_ref_key, c->knn_nref, n_cells, c->knn_cell_start);
+    PF_TRY(sort_points(c, c->knn_ref.p, c->knn_nref, d, 0, cell_bits, c->knn_ref_key.p, c->knn_ref_orig.p, c->knn_ref_s.p));
+    k_cell_start<<<pf_blocks(n_cells + 1), PF_BLOCK, 0, st>>>(c->knn_ref_key.p, c->knn_nref, n_cells, c->knn_cell_start.p);
     PF_HIP(hipGetLastError());
     if (c->knn_k == 1) {
-        k_gather_rows_soa<<<pf_blocks(c->knn_nref), PF_BLOCK, 0, st>>>(c->knn_ref, c->knn_ref_orig, c->knn_nref, d, c->knn_ref_ld, c->knn_ref_soa);
+        k_gather_rows_soa<<<pf_blocks(c->knn_nref), PF_BLOCK, 0, st>>>(c->knn_ref.p, c->knn_ref_orig.p, c->knn_nref, d, c->knn_ref_ld, c->knn_ref_soa.p);
         PF_HIP(hipGetLastError());
     }
-    PF_TRY(sort_points(c, c->knn_qry, c->knn_nqry, d, 1, 32, c->knn_qry_key, c->knn_qry_orig, c->knn_qry_s));
+    PF_TRY(sort_points(c, c->knn_qry.p, c->knn_nqry, d, 1, 32, c->knn_qry_key.p, c->knn_qry_orig.p, c->knn_qry_s.p));
     // a large search is the long kernel behind which the eigenvector downloads that were held back may leave
     if (c->knn_nqry >= 32768) PF_TRY(pf_downloads_release(c));
-    int r = PF_E_ARG;
-    switch (d) {
-        case 1: r = launch_knn<1>(c); break;
-        case 2: r = launch_knn<2>(c); break;
-        case 3: r = launch_knn<3>(c); break;
-        case 4: r = launch_knn<4>(c); break;
-        case 5: r = launch_knn<5>(c); break;
-        case 6: r = launch_knn<6>(c); break;
-        case 7: r = launch_knn<7>(c); break;
-        case 8: r = launch_knn<8>(c); break;
-        case 9: r = launch_knn<9>(c); break;
-        case 10: r = launch_knn<10>(c); break;
-        case 11: r = launch_knn<11>(c); break;
-        case 12: r = launch_knn<12>(c); break;
-        case 13: r = launch_knn<13>(c); break;
-        case 14: r = launch_knn<14>(c); break;
-        case 15: r = launch_knn<15>(c); break;
-        case 16: r = launch_knn<16>(c); break;
-        default: break;
-    }
-    PF_TRY(r);
-    PF_HIP(hipEventRecord(c->ev1, st));
+    return pf_dispatch_d<1, 16>(d, [&](auto D) { return launch_knn<D()>(c); }, bad_d);
+}
+
+int pf_knn_run(pf_ctx* c) {
+    PF_CHECK(c != nullptr, PF_E_ARG, "pf_knn_run: ctx is NULL");
+    PF_CHECK(c->knn_ready, PF_E_STATE, "pf_knn_run: no uploaded problem");
+    PF_HIP(hipSetDevice(c->device));
+    PF_HIP(hipEventRecord(c->ev0, c->stream));
+    PF_TRY(knn_search(c));
+    PF_HIP(hipEventRecord(c->ev1, c->stream));
     PF_HIP(hipEventSynchronize(c->ev1));
     float ms = 0.f;
     PF_HIP(hipEventElapsedTime(&ms, c->ev0, c->ev1));
@@ -1022,8 +932,8 @@ int pf_knn_run(pf_ctx* c) {
 int pf_knn_count(pf_ctx* c, int32_t enable_counting, int64_t* pairs) {
     PF_CHECK(c != nullptr, PF_E_ARG, "pf_knn_count: ctx is NULL");
     unsigned long long h = 0ull;
-    if (c->knn_visited) {
-        PF_HIP(hipMemcpyAsync(&h, c->knn_visited, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+    if (c->knn_visited.p) {
+        PF_HIP(hipMemcpyAsync(&h, c->knn_visited.p, sizeof(h), hipMemcpyDeviceToHost, c->stream));
         PF_HIP(hipStreamSynchronize(c->stream));
     }
     if (pairs) *pairs = (int64_t)h;
@@ -1035,10 +945,10 @@ int pf_knn_count(pf_ctx* c, int32_t enable_counting, int64_t* pairs) {
  * their sum, the slowest wave, the number of waves - and the candidates of the wave that scanned most. */
 int pf_knn_wave_stats(pf_ctx* c, double* sum_us, double* max_us, int64_t* waves, int64_t* max_candidates, double* detail /* [5]: chunks, scans, scan us, bounds us, candidates that pass the off-plane coordinates (sums) */) {
     PF_CHECK(c != nullptr, PF_E_ARG, "pf_knn_wave_stats: ctx is NULL");
-    const int64_t nw = c->knn_visited ? c->knn_visited_waves : 0;
+    const int64_t nw = c->knn_visited.p ? c->knn_visited_waves : 0;
     std::vector<unsigned long long> h((size_t)(8 * nw), 0ull);
     if (nw > 0) {
-        PF_HIP(hipMemcpyAsync(h.data(), c->knn_visited + 8, sizeof(unsigned long long) * h.size(), hipMemcpyDeviceToHost, c->stream));
+        PF_HIP(hipMemcpyAsync(h.data(), c->knn_visited.p + 8, sizeof(unsigned long long) * h.size(), hipMemcpyDeviceToHost, c->stream));
         PF_HIP(hipStreamSynchronize(c->stream));
     }
     unsigned long long sum = 0, mx = 0, mc = 0, ch = 0, sc = 0, ts = 0, tb = 0, np = 0;
@@ -1073,15 +983,15 @@ int pf_knn_download(pf_ctx* c, int64_t* idx_out, double* d2_out) {
         // downloads in flight on the copy stream may be holding (pf_copy_by_kernel)
         unsigned char* pin = nullptr;
         PF_TRY(pf_pinned_scratch(c, bytes * (d2_out ? 2 : 1), reinterpret_cast<void**>(&pin), 2));
-        PF_TRY(pf_copy_by_kernel(c->stream, c->knn_idx, pin, bytes));
-        if (d2_out) PF_TRY(pf_copy_by_kernel(c->stream, c->knn_d2, pin + bytes, bytes));
+        PF_TRY(pf_copy_by_kernel(c->stream, c->knn_idx.p, pin, bytes));
+        if (d2_out) PF_TRY(pf_copy_by_kernel(c->stream, c->knn_d2.p, pin + bytes, bytes));
         PF_HIP(hipStreamSynchronize(c->stream));
         memcpy(idx_out, pin, bytes);
         if (d2_out) memcpy(d2_out, pin + bytes, bytes);
         return PF_OK;
     }
-    PF_HIP(hipMemcpyAsync(idx_out, c->knn_idx, bytes, hipMemcpyDeviceToHost, c->stream));
-    if (d2_out) PF_HIP(hipMemcpyAsync(d2_out, c->knn_d2, sizeof(double) * count, hipMemcpyDeviceToHost, c->stream));
+    PF_HIP(hipMemcpyAsync(idx_out, c->knn_idx.p, bytes, hipMemcpyDeviceToHost, c->stream));
+    if (d2_out) PF_HIP(hipMemcpyAsync(d2_out, c->knn_d2.p, sizeof(double) * count, hipMemcpyDeviceToHost, c->stream));
     PF_HIP(hipStreamSynchronize(c->stream));
     return PF_OK;
 }
@@ -1111,8 +1021,8 @@ static int knn1_blocks_run(pf_ctx* c, const double* ref_block, int64_t n_ref, in
         mr.col[k] = col_ref[k], mr.scale[k] = scale_ref[k];
         mq.col[k] = col_qry[k], mq.scale[k] = scale_qry[k];
     }
-    k_coords_from_final<<<pf_blocks(n_ref * d), PF_BLOCK, 0, st>>>(ref_block, n_ref, ref_stride, d, mr, c->knn_ref);
-    k_coords_from_final<<<pf_blocks(n_qry * d), PF_BLOCK, 0, st>>>(qry_block, n_qry, qry_stride, d, mq, c->knn_qry);
+    k_coords_from_final<<<pf_blocks(n_ref * d), PF_BLOCK, 0, st>>>(ref_block, n_ref, ref_stride, d, mr, c->knn_ref.p);
+    k_coords_from_final<<<pf_blocks(n_qry * d), PF_BLOCK, 0, st>>>(qry_block, n_qry, qry_stride, d, mq, c->knn_qry.p);
     PF_HIP(hipGetLastError());
     c->knn_ready = true;
     return pf_knn_run(c);

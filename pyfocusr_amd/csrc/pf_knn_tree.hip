@@ -45,6 +45,7 @@
 #include <algorithm>
 
 #include "pf_internal.h"
+#include "pf_wave.h"
 
 namespace {
 
@@ -58,17 +59,13 @@ struct TreeGrid {
     double scale[TREE_AXES];  // cells per unit length (0 when the extent is 0)
 };
 
-__device__ __forceinline__ double tdec_f64(unsigned long long u) {
-    return __longlong_as_double((long long)((u >> 63) ? (u & ~(1ull << 63)) : ~u));
-}
-
 // the (up to) five widest axes of the reference set, widest first; 30 key bits shared between them
 __global__ void k_tree_grid(const unsigned long long* __restrict__ ext /* [2][16]: encoded min, max */, int d, TreeGrid* g) {
     if (threadIdx.x | blockIdx.x) return;
     double w[16];
     bool used[16];
     for (int a = 0; a < d; ++a) {
-        w[a] = tdec_f64(ext[16 + a]) - tdec_f64(ext[a]);
+        w[a] = dec_f64(ext[16 + a]) - dec_f64(ext[a]);
         used[a] = false;
     }
     const int na = d < TREE_AXES ? d : TREE_AXES;
@@ -80,7 +77,7 @@ __global__ void k_tree_grid(const unsigned long long* __restrict__ ext /* [2][16
             if (!used[a] && (b < 0 || w[a] > w[b])) b = a;
         used[b] = true;
         g->axis[k] = b;
-        g->lo[k] = tdec_f64(ext[b]);
+        g->lo[k] = dec_f64(ext[b]);
         g->scale[k] = (w[b] > 0.0 && isfinite(w[b])) ? (double)(1 << g->bits) / w[b] : 0.0;
     }
 }
@@ -176,17 +173,6 @@ struct TreeArgs {
     unsigned long long* counters;  // nullable: [0] leaves scanned, [1] supers opened (diagnostics)
 };
 
-__device__ __forceinline__ void tree_argmin(double& s, int32_t& o) {
-#pragma unroll
-    for (int off = PF_WAVE / 2; off > 0; off >>= 1) {
-        const double s2 = __shfl_xor(s, off, PF_WAVE);
-        const int32_t o2 = __shfl_xor(o, off, PF_WAVE);
-        const bool take = s2 < s || (s2 == s && o2 < o);
-        s = take ? s2 : s;
-        o = take ? o2 : o;
-    }
-}
-
 // squared distance of q to the box [lo, hi] (one coordinate every `cs` doubles): the accumulation of the point distance
 template <int D>
 __device__ __forceinline__ double box_d2(const double (&q)[D], const double* __restrict__ lo, const double* __restrict__ hi, int64_t cs) {
@@ -259,7 +245,7 @@ __global__ __launch_bounds__(PF_BLOCK) void k_knn_tree(TreeArgs t) {
     };
     auto reduce = [&]() {
 #pragma unroll
-        for (int i = 0; i < G; ++i) tree_argmin(best[i], bidx[i]);
+        for (int i = 0; i < G; ++i) wave_argmin(best[i], bidx[i]);
     };
 
     // ---- the first bound: the leaf nearest to the group's first query inside the super nearest to it
@@ -271,11 +257,11 @@ __global__ __launch_bounds__(PF_BLOCK) void k_knn_tree(TreeArgs t) {
             const double dd = box_d2<D>(q[0], t.sup_lo + s0 + lane, t.sup_hi + s0 + lane, t.ns_pad);
             if (dd < sb) sb = dd, sa = s0 + lane;
         }
-        tree_argmin(sb, sa);
+        wave_argmin(sb, sa);
         const int64_t lb = (int64_t)sa * D * PF_WAVE + lane;
         double lbest = box_d2<D>(q[0], t.leaf_lo + lb, t.leaf_hi + lb, PF_WAVE);
         int32_t la = lane;
-        tree_argmin(lbest, la);
+        wave_argmin(lbest, la);
         L0 = sa * PF_WAVE + la;
         scan_leaf(L0);
         reduce();
@@ -422,12 +408,12 @@ __global__ __launch_bounds__(PF_BLOCK) void k_knn_tree_topk(TreeArgs t, int k) {
             const double dd = box_d2<D>(q[0], t.sup_lo + s0 + lane, t.sup_hi + s0 + lane, t.ns_pad);
             if (dd < sb) sb = dd, sa = s0 + lane;
         }
-        tree_argmin(sb, sa);
+        wave_argmin(sb, sa);
         sa = sa < t.n_sup ? sa : 0;  // (the supers past the end are infinitely far and lose every tie: a guard, not a case)
         const int64_t lb = (int64_t)sa * D * PF_WAVE + lane;
         double lbest = box_d2<D>(q[0], t.leaf_lo + lb, t.leaf_hi + lb, PF_WAVE);
         int32_t la = lane;
-        tree_argmin(lbest, la);
+        wave_argmin(lbest, la);
         L0 = sa * PF_WAVE + la;
         if (L0 < t.n_leaf)
             scan_leaf(L0);
@@ -534,38 +520,24 @@ __global__ __launch_bounds__(PF_BLOCK) void k_knn_topk_wide(const double* __rest
     }
 }
 
-template <typename T>
-int tgrow(hipStream_t st, T** p, int64_t* cap, int64_t need) {
-    if (need <= *cap) return PF_OK;
-    pf_free(st, *p);
-    *p = nullptr;
-    *cap = 0;
-    PF_HIP(pf_malloc(st, (void**)p, sizeof(T) * (size_t)need));
-    *cap = need;
-    return PF_OK;
-}
-
-int sort_by_key(hipStream_t st, unsigned* k_in, int32_t* v_in, unsigned* k_out, int32_t* v_out, int64_t n) {
-    size_t bytes = 0;
-    void* tmp = nullptr;
-    PF_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, k_in, k_out, v_in, v_out, (int)n, 0, 30, st));
-    PF_HIP(pf_malloc(st, &tmp, bytes));
-    const hipError_t e = hipcub::DeviceRadixSort::SortPairs(tmp, bytes, k_in, k_out, v_in, v_out, (int)n, 0, 30, st);
-    pf_free(st, tmp);
-    PF_HIP(e);
+int tree_launched(const char* what) {
+    const hipError_t e = hipGetLastError();
+    PF_CHECK(e == hipSuccess, PF_E_HIP, "%s (box hierarchy): %s", what, hipGetErrorString(e));
     return PF_OK;
 }
 
 template <int D>
-void launch_tree(pf_ctx* c, const TreeArgs& a) {
+int launch_tree(pf_ctx* c, const TreeArgs& a) {
     const int64_t waves = (a.n_qry + tree_group(D) - 1) / tree_group(D);
     k_knn_tree<D><<<(unsigned)((waves + PF_BLOCK / PF_WAVE - 1) / (PF_BLOCK / PF_WAVE)), PF_BLOCK, 0, c->stream>>>(a);
+    return tree_launched("pf_knn");
 }
 
 template <int D>
-void launch_tree_topk(pf_ctx* c, const TreeArgs& a, int k) {
+int launch_tree_topk(pf_ctx* c, const TreeArgs& a, int k) {
     const int64_t waves = (a.n_qry + tree_group(D) - 1) / tree_group(D);
     k_knn_tree_topk<D><<<(unsigned)((waves + PF_BLOCK / PF_WAVE - 1) / (PF_BLOCK / PF_WAVE)), PF_BLOCK, 0, c->stream>>>(a, k);
+    return tree_launched("pf_knn_topk");
 }
 
 // The hierarchy over the n references (row-major, d <= 16; ext: their encoded extents, as pf_knn_extent leaves them) and the
@@ -578,50 +550,35 @@ int tree_build(pf_ctx* c, const double* ref, int64_t n, const double* qry, int64
     const int64_t n_sup = (n_leaf + PF_WAVE - 1) / PF_WAVE;
     const int64_t ns_pad = (n_sup + PF_WAVE - 1) & ~(int64_t)(PF_WAVE - 1);
     PF_CHECK(n_leaf < ((int64_t)1 << 31) / PF_WAVE, PF_E_ARG, "pf_knn: too many references for the box hierarchy");
-    PF_TRY(tgrow(st, &T.pts, &T.cap_pts, n_leaf * PF_WAVE * d));
-    PF_TRY(tgrow(st, &T.orig, &T.cap_orig, n_leaf * PF_WAVE));
-    PF_TRY(tgrow(st, &T.leaf_lo, &T.cap_leaf, 2 * n_sup * PF_WAVE * d));
-    PF_TRY(tgrow(st, &T.sup_lo, &T.cap_sup, 2 * ns_pad * d));
-    PF_TRY(tgrow(st, &T.qry_order, &T.cap_qry, nq));
-    if (!T.grid) PF_HIP(pf_malloc(st, &T.grid, sizeof(TreeGrid)));
-    if (!T.counters) {
-        PF_HIP(pf_malloc(st, (void**)&T.counters, 2 * sizeof(unsigned long long)));
-    }
+    PF_HIP(T.pts.grow(st, n_leaf * PF_WAVE * d));
+    PF_HIP(T.orig.grow(st, n_leaf * PF_WAVE));
+    PF_HIP(T.leaf_lo.grow(st, 2 * n_sup * PF_WAVE * d));
+    PF_HIP(T.sup_lo.grow(st, 2 * ns_pad * d));
+    PF_HIP(T.qry_order.grow(st, nq));
+    Scratch s(st);
+    if (!T.grid) T.grid = s.keep<TreeGrid>(1);
+    if (!T.counters) T.counters = s.keep<unsigned long long>(2);
+    PF_HIP(s.err);
     PF_HIP(hipMemsetAsync(T.counters, 0, 2 * sizeof(unsigned long long), st));
-    double* leaf_hi = T.leaf_lo + n_sup * PF_WAVE * d;
-    double* sup_hi = T.sup_lo + ns_pad * d;
+    double* leaf_hi = T.leaf_lo.p + n_sup * PF_WAVE * d;
+    double* sup_hi = T.sup_lo.p + ns_pad * d;
     const int64_t nmax = std::max(n, nq);
-    unsigned *k0 = nullptr, *k1 = nullptr;
-    int32_t *v0 = nullptr, *v1 = nullptr;
-    int rc = PF_OK;
-    do {
-        if (pf_malloc(st, (void**)&k0, sizeof(unsigned) * nmax) != hipSuccess || pf_malloc(st, (void**)&k1, sizeof(unsigned) * nmax) != hipSuccess ||
-            pf_malloc(st, (void**)&v0, sizeof(int32_t) * nmax) != hipSuccess || pf_malloc(st, (void**)&v1, sizeof(int32_t) * nmax) != hipSuccess) {
-            pf_set_error("pf_knn: out of device memory (box hierarchy)");
-            rc = PF_E_HIP;
-            break;
-        }
-        k_tree_grid<<<1, 1, 0, st>>>(ext, d, (TreeGrid*)T.grid);
-        k_tree_keys<<<pf_blocks(n), PF_BLOCK, 0, st>>>(ref, n, d, (const TreeGrid*)T.grid, k0, v0);
-        if ((rc = sort_by_key(st, k0, v0, k1, v1, n)) != PF_OK) break;
-        k_tree_leaves<<<pf_blocks(n_leaf * PF_WAVE), PF_BLOCK, 0, st>>>(ref, v1, n, d, n_leaf * PF_WAVE, T.pts, T.orig);
-        k_tree_leaf_boxes<<<pf_blocks(n_sup * PF_WAVE * d), PF_BLOCK, 0, st>>>(T.pts, (int32_t)n_leaf, (int32_t)n_sup, d, T.leaf_lo, leaf_hi);
-        k_tree_super_boxes<<<pf_blocks(ns_pad * d), PF_BLOCK, 0, st>>>(T.leaf_lo, leaf_hi, (int32_t)n_sup, (int32_t)ns_pad, d, T.sup_lo, sup_hi);
+    unsigned *k0 = s.get<unsigned>(nmax), *k1 = s.get<unsigned>(nmax);
+    int32_t *v0 = s.get<int32_t>(nmax), *v1 = s.get<int32_t>(nmax);
+    PF_CHECK(s.ok(), PF_E_HIP, "pf_knn: out of device memory (box hierarchy)");
+    k_tree_grid<<<1, 1, 0, st>>>(ext, d, (TreeGrid*)T.grid);
+    k_tree_keys<<<pf_blocks(n), PF_BLOCK, 0, st>>>(ref, n, d, (const TreeGrid*)T.grid, k0, v0);
+    pf_sort_pairs(s, k0, k1, v0, v1, n, 30);
+    if (s.ok()) {
+        k_tree_leaves<<<pf_blocks(n_leaf * PF_WAVE), PF_BLOCK, 0, st>>>(ref, v1, n, d, n_leaf * PF_WAVE, T.pts.p, T.orig.p);
+        k_tree_leaf_boxes<<<pf_blocks(n_sup * PF_WAVE * d), PF_BLOCK, 0, st>>>(T.pts.p, (int32_t)n_leaf, (int32_t)n_sup, d, T.leaf_lo.p, leaf_hi);
+        k_tree_super_boxes<<<pf_blocks(ns_pad * d), PF_BLOCK, 0, st>>>(T.leaf_lo.p, leaf_hi, (int32_t)n_sup, (int32_t)ns_pad, d, T.sup_lo.p, sup_hi);
         k_tree_keys<<<pf_blocks(nq), PF_BLOCK, 0, st>>>(qry, nq, d, (const TreeGrid*)T.grid, k0, v0);
-        if ((rc = sort_by_key(st, k0, v0, k1, T.qry_order, nq)) != PF_OK) break;
-        *a = TreeArgs{T.pts, T.orig, T.leaf_lo, leaf_hi, T.sup_lo, sup_hi, qry, T.qry_order, nq, (int32_t)n_leaf, (int32_t)n_sup,
-                      (int32_t)ns_pad, nullptr, nullptr, T.count_visits ? T.counters : nullptr};
-    } while (0);
-    pf_free(st, k0);
-    pf_free(st, k1);
-    pf_free(st, v0);
-    pf_free(st, v1);
-    return rc;
-}
-
-int tree_launched(const char* what) {
-    const hipError_t e = hipGetLastError();
-    PF_CHECK(e == hipSuccess, PF_E_HIP, "%s (box hierarchy): %s", what, hipGetErrorString(e));
+    }
+    pf_sort_pairs(s, k0, k1, v0, T.qry_order.p, nq, 30);
+    PF_HIP(s.err);
+    *a = TreeArgs{T.pts.p, T.orig.p, T.leaf_lo.p, leaf_hi, T.sup_lo.p, sup_hi, qry, T.qry_order.p, nq, (int32_t)n_leaf, (int32_t)n_sup,
+                  (int32_t)ns_pad, nullptr, nullptr, T.count_visits ? T.counters : nullptr};
     return PF_OK;
 }
 
@@ -632,29 +589,10 @@ int tree_launched(const char* what) {
 int pf_knn_tree_run(pf_ctx* c) {
     const int d = c->knn_d;
     TreeArgs a{};
-    PF_TRY(tree_build(c, c->knn_ref, c->knn_nref, c->knn_qry, c->knn_nqry, d, c->knn_ext, &a));
-    a.idx_out = c->knn_idx;
-    a.d2_out = c->knn_d2;
-    switch (d) {
-        case 1: launch_tree<1>(c, a); break;
-        case 2: launch_tree<2>(c, a); break;
-        case 3: launch_tree<3>(c, a); break;
-        case 4: launch_tree<4>(c, a); break;
-        case 5: launch_tree<5>(c, a); break;
-        case 6: launch_tree<6>(c, a); break;
-        case 7: launch_tree<7>(c, a); break;
-        case 8: launch_tree<8>(c, a); break;
-        case 9: launch_tree<9>(c, a); break;
-        case 10: launch_tree<10>(c, a); break;
-        case 11: launch_tree<11>(c, a); break;
-        case 12: launch_tree<12>(c, a); break;
-        case 13: launch_tree<13>(c, a); break;
-        case 14: launch_tree<14>(c, a); break;
-        case 15: launch_tree<15>(c, a); break;
-        case 16: launch_tree<16>(c, a); break;
-        default: return PF_E_ARG;
-    }
-    return tree_launched("pf_knn");
+    PF_TRY(tree_build(c, c->knn_ref.p, c->knn_nref, c->knn_qry.p, c->knn_nqry, d, c->knn_ext, &a));
+    a.idx_out = c->knn_idx.p;
+    a.d2_out = c->knn_d2.p;
+    return pf_dispatch_d<1, 16>(d, [&](auto D) { return launch_tree<D()>(c, a); }, "pf_knn: no box hierarchy for d = %d");
 }
 
 // k nearest neighbours, 1 <= k <= 64, 1 <= d <= 128 (include/pyfocusr_hip.h): the lists over the box hierarchy for
@@ -684,24 +622,8 @@ extern "C" int pf_knn_topk(pf_ctx* c, const double* ref, int64_t n_ref, const do
         PF_TRY(tree_build(c, d_ref, n_ref, d_qry, n_qry, d, ext, &a));
         a.idx_out = d_idx;
         a.d2_out = d_d2;
-        switch (d) {
-            case 1: launch_tree_topk<1>(c, a, k); break;
-            case 2: launch_tree_topk<2>(c, a, k); break;
-            case 3: launch_tree_topk<3>(c, a, k); break;
-            case 4: launch_tree_topk<4>(c, a, k); break;
-            case 5: launch_tree_topk<5>(c, a, k); break;
-            case 6: launch_tree_topk<6>(c, a, k); break;
-            case 7: launch_tree_topk<7>(c, a, k); break;
-            case 8: launch_tree_topk<8>(c, a, k); break;
-            case 9: launch_tree_topk<9>(c, a, k); break;
-            case 10: launch_tree_topk<10>(c, a, k); break;
-            case 11: launch_tree_topk<11>(c, a, k); break;
-            case 12: launch_tree_topk<12>(c, a, k); break;
-            case 13: launch_tree_topk<13>(c, a, k); break;
-            case 14: launch_tree_topk<14>(c, a, k); break;
-            case 15: launch_tree_topk<15>(c, a, k); break;
-            default: launch_tree_topk<16>(c, a, k); break;
-        }
+        const int rc = pf_dispatch_d<1, 16>(d, [&](auto D) { return launch_tree_topk<D()>(c, a, k); }, "pf_knn_topk: no box hierarchy for d = %d");
+        PF_TRY(rc);
     } else {
         double* d_rt = s.get<double>((size_t)(n_ref * d));
         PF_CHECK(s.ok(), PF_E_HIP, "pf_knn_topk: %s", hipGetErrorString(s.err));
@@ -709,8 +631,8 @@ extern "C" int pf_knn_topk(pf_ctx* c, const double* ref, int64_t n_ref, const do
         const int64_t waves = (n_qry + WIDE_G - 1) / WIDE_G;
         k_knn_topk_wide<<<(unsigned)((waves + PF_BLOCK / PF_WAVE - 1) / (PF_BLOCK / PF_WAVE)), PF_BLOCK, 0, s.st>>>(d_rt, n_ref, d_qry, n_qry, d, k,
                                                                                                                   d_idx, d_d2);
+        PF_TRY(tree_launched("pf_knn_topk"));
     }
-    PF_TRY(tree_launched("pf_knn_topk"));
     PF_HIP(hipEventRecord(c->ev1, s.st));
     // one read-back: both halves queued, one wait
     s.download(idx_out, d_idx, count);

@@ -19,16 +19,9 @@
 
 #include "pf_internal.h"
 #include "pf_launch.h"
+#include "pf_wave.h"
 
 namespace {
-
-__device__ __forceinline__ unsigned long long enc_f64(double d) {
-    const unsigned long long u = (unsigned long long)__double_as_longlong(d);
-    return (u >> 63) ? ~u : (u | (1ull << 63));
-}
-__device__ __forceinline__ double dec_f64(unsigned long long u) {
-    return __longlong_as_double((long long)((u >> 63) ? (u & ~(1ull << 63)) : ~u));
-}
 
 struct k_bbox {
     static constexpr int BOUNDS = PF_BLOCK;
@@ -74,15 +67,6 @@ struct k_bbox {
     }
 }
 };
-
-__device__ __forceinline__ unsigned spread10(unsigned v) {  // 10 bits -> every third bit
-    v &= 0x3ffu;
-    v = (v | (v << 16)) & 0x030000ffu;
-    v = (v | (v << 8)) & 0x0300f00fu;
-    v = (v | (v << 4)) & 0x030c30c3u;
-    v = (v | (v << 2)) & 0x09249249u;
-    return v;
-}
 
 struct k_morton_keys {
     static constexpr int BOUNDS = PF_BLOCK;

@@ -1,5 +1,6 @@
 // The triangle hierarchy under every surface query (pf_surface.hip: d = 3; pf_surface_nd.hip: 1 <= d <= 16), and the
-// device helpers its searches share.  Built in pf_tri_hierarchy.hip (pf_tri_hierarchy_build, declared in pf_internal.h).
+// device helpers its searches share (the wave reductions and the tie rule `better` are pf_wave.h's).  Built in
+// pf_tri_hierarchy.hip (pf_tri_hierarchy_build, declared in pf_internal.h).
 //
 // Structure.  The fan triangles (0, j+1, j+2) of the faces are sorted along a Morton curve of their centroids (hipCUB
 // radix sort, stable) and cut into chunks of PF_TRI_CHUNK = 64 consecutive ones, each with its d-dimensional bounding
@@ -32,40 +33,12 @@
 #include <limits>
 
 #include "pf_internal.h"
+#include "pf_wave.h"
 
 constexpr int PF_TRI_CHUNK = 64;             // triangles per chunk: one per lane and scan
 constexpr double PF_BOX_SLACK = 1.0 + 1e-9;  // a box test must never reject on a rounding error (see above)
 
 #define PF_FOR_DEPTH(k) _Pragma("unroll") for (int k = 0; k < (D ? D : PF_ND_MAX); ++k) if (D != 0 || k < d)
-
-__device__ __forceinline__ double wave_min(double v) {
-    for (int off = PF_WAVE / 2; off > 0; off >>= 1) v = fmin(v, __shfl_xor(v, off, PF_WAVE));
-    return v;
-}
-
-__device__ __forceinline__ double wave_max(double v) {
-    for (int off = PF_WAVE / 2; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off, PF_WAVE));
-    return v;
-}
-
-__device__ __forceinline__ double wave_sum(double v) {  // fixed butterfly: the same order on every run
-    for (int off = PF_WAVE / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, PF_WAVE);
-    return v;
-}
-
-// the least d of the wave and its index, in every lane; lowest index on ties
-__device__ __forceinline__ void wave_argmin(double& d, int64_t& i) {
-    for (int off = PF_WAVE / 2; off > 0; off >>= 1) {
-        const double od = __shfl_xor(d, off, PF_WAVE);
-        const int64_t oi = __shfl_xor(i, off, PF_WAVE);
-        if (od < d || (od == d && oi < i)) d = od, i = oi;
-    }
-}
-
-// the tie rule of every search; a NaN d2 compares false: never wins
-__device__ __forceinline__ bool better(double d2, int32_t orig, double bd2, int32_t borig) {
-    return d2 < bd2 || (d2 == bd2 && orig < borig);
-}
 
 // corners of fan triangle t = face * (vpf - 2) + fan position
 __device__ __forceinline__ void tri_corners(const int32_t* __restrict__ faces, int32_t vpf, int64_t t, int32_t v[3]) {

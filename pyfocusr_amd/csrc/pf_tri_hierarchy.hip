@@ -9,15 +9,6 @@
 
 namespace {
 
-__device__ __forceinline__ unsigned spread10(unsigned v) {  // bit i -> bit 3 i
-    v &= 0x3ffu;
-    v = (v | (v << 16)) & 0x030000ffu;
-    v = (v | (v << 8)) & 0x0300f00fu;
-    v = (v | (v << 4)) & 0x030c30c3u;
-    v = (v | (v << 2)) & 0x09249249u;
-    return v;
-}
-
 // 30-bit Morton key of the leading coordinates of a point in box bb: 10 bits per axis, the first lowest; outside the box
 // clamps, NaN and a flat axis give 0.  The point comes as coord(axis), so that an axis is loaded where it is used
 // (registers: as few as the loops this replaces).
@@ -159,7 +150,6 @@ const int32_t* pf_surface_morton_order(Scratch& sc, const double* d_pts, int32_t
                                        const KeyBox& bb) {
     unsigned *k0 = sc.get<unsigned>(n), *k1 = sc.get<unsigned>(n);
     int32_t *v0 = sc.get<int32_t>(n), *v1 = sc.get<int32_t>(n);
-    size_t need = 0;
     if (sc.ok()) {
         if (d == 3)
             launch_keys<3>(sc.st, d_pts, d, d_faces, vpf, n, bb, k0, v0);
@@ -167,10 +157,15 @@ const int32_t* pf_surface_morton_order(Scratch& sc, const double* d_pts, int32_t
             launch_keys<0>(sc.st, d_pts, d, d_faces, vpf, n, bb, k0, v0);
         sc.launched();
     }
-    if (sc.ok()) sc.note(hipcub::DeviceRadixSort::SortPairs(nullptr, need, k0, k1, v0, v1, (int)n, 0, 30, sc.st));
-    void* tmp = sc.get<char>(need);
-    if (sc.ok()) sc.note(hipcub::DeviceRadixSort::SortPairs(tmp, need, k0, k1, v0, v1, (int)n, 0, 30, sc.st));
+    pf_sort_pairs(sc, k0, k1, v0, v1, n, 30);
     return sc.ok() ? v1 : nullptr;
+}
+
+void pf_sort_pairs(Scratch& sc, const unsigned* k_in, unsigned* k_out, const int32_t* v_in, int32_t* v_out, int64_t n, int end_bit) {
+    size_t need = 0;
+    if (sc.ok()) sc.note(hipcub::DeviceRadixSort::SortPairs(nullptr, need, k_in, k_out, v_in, v_out, (int)n, 0, end_bit, sc.st));
+    void* tmp = sc.get<char>(need);
+    if (sc.ok()) sc.note(hipcub::DeviceRadixSort::SortPairs(tmp, need, k_in, k_out, v_in, v_out, (int)n, 0, end_bit, sc.st));
 }
 
 void pf_tri_hierarchy_build(Scratch& sc, TriHierarchy& h, const double* d_pts, int32_t d, const int32_t* d_faces, int64_t n_faces,

@@ -447,6 +447,32 @@ def test_basis_replaced_on_one_handle(ctx):
 
 
 @pytest.mark.gpu
+def test_scratch_grows_and_is_reused_on_a_fresh_context():
+    """K = 8, then 200, then 8 again on one handle (N = M = 300, d = 3) of a context that has allocated nothing: K d = 600
+    is above the 561 doubles of the handle's first scratch, which grows, and the grown scratch then serves the small basis."""
+    from pyfocusr_amd import _hip
+
+    N = M = 300
+    X, Y = clouds(1200, N, M, 3)
+    fresh = _hip.Context(0)
+    try:
+        dev = device(fresh, X, Y)
+        for K in (8, 200, 8):
+            Q = np.random.default_rng(1200 + K).normal(size=(M, K))
+            dev.set_basis(Q)
+            _, P1, _, PX = posterior(dev, 0.2, 0.1)
+            H_alone = dev.weighted_gram().copy()
+            H, R = (a.copy() for a in dev.deform_sums())
+            (wH, wR), (H_abs, R_abs) = ref.deform_sums_ld(Q, P1, PX, Y)
+            assert np.array_equal(H_alone, H)
+            within("state", "fresh K=%d H" % K, H, wH, sum_bound(M, H_abs))
+            within("state", "fresh K=%d R" % K, R, wR, sum_bound(M, R_abs))
+        dev.close()
+    finally:
+        fresh.close()
+
+
+@pytest.mark.gpu
 def test_refusals_leave_the_handle_usable(ctx):
     from pyfocusr_amd import _hip
 

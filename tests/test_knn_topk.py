@@ -289,3 +289,23 @@ def test_soft_p2p_from_functional_map(ctx):
     assert np.array_equal(idx, ridx) and np.array_equal(d2, rd2)
     moved = inverse_distance_average(pts, idx, d2)
     assert moved.shape == (len(phi_s), 3) and np.all(np.isfinite(moved))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("mode,d", [(1, 3), (2, 8)], ids=["grid-d3", "hierarchy-d8"])
+def test_buffers_grow_and_are_reused_on_a_fresh_context(hip, mode, d):
+    """The k-NN state of a context that has never searched: 200 points, then 5000 (every buffer grows), then 200 again
+    (the grown buffers serve a smaller problem), different clouds each time.  In the hierarchy run a `knn_topk` between
+    the second and the third search builds its own hierarchy in the same buffers.  Bits of the brute force every time."""
+    ctx = hip.Context(0)
+    try:
+        ctx.knn_mode(mode)
+        for step, n in enumerate((200, 5000, 200)):
+            ref, qry = cloud(n, d, seed=10 + step), cloud(n, d, seed=20 + step)
+            idx, d2 = ctx.knn1(ref, qry, return_d2=True)
+            bidx, bd2 = kr.brute_argmin(ref, qry, 1)
+            assert np.array_equal(idx, bidx[:, 0]) and np.array_equal(d2, bd2[:, 0]), "search %d, n = %d" % (step, n)
+            if mode == 2 and step == 1:
+                check(ctx, cloud(1000, d, seed=30), cloud(1000, d, seed=31), (5,))
+    finally:
+        ctx.close()
