@@ -746,6 +746,39 @@ typedef struct pf_assign_stats {
 int pf_assign(pf_ctx* ctx, const double* rows, int64_t n_rows, const double* cols, int64_t n_cols, int32_t d,
               int64_t* col_of_row, double* u_out, double* v_out, pf_assign_stats* stats);
 
+/* ---- discrete curvatures of a triangle mesh (the quantities of vtkCurvatures, vtk_functions.py:40-74) --------------
+ * pts [n][3] f64, faces [n_faces][3] i32 (host; triangles only).  f64 throughout, separate multiplies and adds, dot
+ * products left to right.  Per triangle t = (v0, v1, v2): n_t = (x1 - x0) x (x2 - x0) / |..|, area_t = |..| / 2, corner
+ * angle at corner j = atan2(|e1 x e2|, e1 . e2) with e1, e2 the edges that leave the corner; all zero for a zero-area or
+ * non-finite triangle.  Half-edge h = 3 t + j leaves corner j of triangle t; every per-vertex sum runs over the
+ * half-edges that leave the vertex, in ascending h.
+ *   area      A_v = (sum area_t) / 3                                  (barycentric; 0: unreferenced, or only zero-area faces)
+ *   gauss     K_v = (2 pi - sum corner angles) / A_v                  (angle defect)
+ *   dihedral  of an edge shared by exactly two triangles with non-zero areas that traverse it in opposite directions, f the
+ *             lower-numbered one going a -> b, e = (x_b - x_a) / |x_b - x_a|: beta_e = atan2((n_f x n_g) . e, n_f . n_g).
+ *             Every other edge (boundary, three or more triangles, traversed twice the same way, zero length, a zero-area
+ *             triangle on either side) has beta_e = 0.
+ *   mean      H_v = (sum |e| beta_e) / (4 A_v): positive on a convex body with outward normals
+ *   tensor6   T_v = (1 / A_v) sum 1/2 |e| beta_e e e^T, stored xx yy zz xy xz yz; trace T_v = 2 H_v
+ *   kminmax   [n][4]: H - s, H + s with s = sqrt(max(H^2 - K, 0)); then the eigenvalues m - r, m + r of the tensor in the
+ *             tangent plane: n_v the normalised sum of corner angle x n_t, a the coordinate axis of the least |n_v component|
+ *             (lowest index on ties), t1 = normalise(a - (a . n_v) n_v), t2 = n_v x t1, S = [ti^T T tj],
+ *             m = (s11 + s22) / 2, r = sqrt(((s11 - s22) / 2)^2 + s12^2), theta = 1/2 atan2(2 s12, s11 - s22)
+ *   dirs      [n][6]: d_min = w = cos theta t1 + sin theta t2 (the eigenvector of m + r: the tensor collects an edge's
+ *             bending along the edge, which is bending across it), then d_max = n_v x w; each with its largest-|component|
+ *             entry positive (lowest index on ties)
+ *   normals   [n][3] n_v;  boundary [n] 1 where the vertex is an end of an edge with exactly one triangle
+ * A vertex with A_v = 0 gets 0 in every field; one whose normal sum is zero or non-finite gets a zero normal, zero tensor
+ * eigenvalues and zero directions.  Boundary vertices go through the same formulas: their values are no curvatures.
+ * topology [5] = edges | boundary edges | non-manifold edges (three or more triangles) | inconsistent edges (two triangles,
+ * same direction) | vertices where H^2 - K < 0 was clipped.  device_ms: the device time between the uploads and the
+ * downloads (HIP events).  Every output may be NULL.  One round trip: the uploads, three kernels and two stable radix sorts,
+ * the downloads, one wait.  No floating-point atomics: two calls give identical bits.  PF_E_ARG for a vertex id outside
+ * 0..n-1, n outside 1..2^31-1, n_faces < 1 or 3 n_faces >= 2^31. */
+int pf_curvatures(pf_ctx* ctx, const double* pts, int64_t n, const int32_t* faces, int64_t n_faces, double* out_area,
+                  double* out_gauss, double* out_mean, double* out_tensor6, double* out_kminmax, double* out_dirs,
+                  double* out_normals, uint8_t* out_boundary, int64_t* topology, double* device_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,6 +9,7 @@ missing — there is no CPU fallback.
 from . import vtk_functions
 from .assignment import euclidean_assignment
 from .correspondence import closest_points_on_embedded_surface, interpolate_on_surface, transfer_point_data
+from .curvature import (curvature_on_mesh, curvedness, discrete_curvatures, principal_curvatures, shape_index)
 from .eigsort import eigsort
 from .focusr import *  # noqa: F401,F403
 from .graph import *  # noqa: F401,F403

@@ -214,6 +214,8 @@ SIGNATURES = {
     "pf_cpd_gram": (C.c_int, [C.c_void_p, _f64p, C.c_int64, _f64p, C.c_int64, C.c_int32, C.c_double, _f64p, C.c_int32, _f64p]),
     "pf_assign": (C.c_int, [C.c_void_p, _f64p, C.c_int64, _f64p, C.c_int64, C.c_int32, _i64p, _f64p, _f64p,
                             C.POINTER(AssignStats)]),
+    "pf_curvatures": (C.c_int, [C.c_void_p, _f64p, C.c_int64, _i32p, C.c_int64, _f64p, _f64p, _f64p, _f64p, _f64p, _f64p, _f64p,
+                                C.POINTER(C.c_uint8), _i64p, _f64p]),
 }
 
 _lib = None
@@ -572,6 +574,30 @@ class Context(object):
         out = np.empty((max(int(k_out), 0), G.shape[1]), dtype=np.float64)
         _check(self._lib.pf_descriptor_coefficients(self._h, _f64(phi), _f64(mass), phi.shape[0], phi.shape[1], _f64(G), G.shape[1],
                                                     int(k_out), _f64(out)))
+        return out
+
+    # ---- discrete curvatures -----------------------------------------------------------
+    def curvatures(self, points, faces):
+        """`pf_curvatures` of the triangle mesh (points (n, 3) f64, faces (m, 3) i32): a dict with `area`, `gaussian`,
+        `mean` (n,), `tensor` (n, 6) xx yy zz xy xz yz, `k` (n, 4) = k_min, k_max from (H, K) | k_min, k_max of the
+        tensor, `dirs` (n, 6) = d_min | d_max, `normals` (n, 3), `boundary` (n,) bool, `topology` (5,) int64 = edges |
+        boundary | non-manifold | inconsistent edges | clipped vertices, and `device_ms`.  Only the shapes are checked
+        here (`curvature.discrete_curvatures` checks the values); the library refuses an index out of range (PF_E_ARG)."""
+        pts = _c_f64(points)
+        f = np.ascontiguousarray(faces, dtype=np.int32)
+        if pts.ndim != 2 or pts.shape[1] != 3 or f.ndim != 2 or f.shape[1] != 3:
+            raise ValueError("points must be (n, 3) and faces (m, 3)")
+        n = pts.shape[0]
+        out = {"area": np.empty(n), "gaussian": np.empty(n), "mean": np.empty(n), "tensor": np.empty((n, 6)), "k": np.empty((n, 4)),
+               "dirs": np.empty((n, 6)), "normals": np.empty((n, 3))}
+        boundary = np.empty(n, dtype=np.uint8)
+        topology = np.zeros(5, dtype=np.int64)
+        ms = C.c_double(0.0)
+        _check(self._lib.pf_curvatures(self._h, _f64(pts), n, f.ctypes.data_as(_i32p), f.shape[0], _f64(out["area"]),
+                                       _f64(out["gaussian"]), _f64(out["mean"]), _f64(out["tensor"]), _f64(out["k"]),
+                                       _f64(out["dirs"]), _f64(out["normals"]), boundary.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                       topology.ctypes.data_as(_i64p), C.byref(ms)))
+        out.update(boundary=boundary.astype(bool), topology=topology, device_ms=ms.value)
         return out
 
     def assign(self, rows, cols, return_duals=False):

@@ -16,7 +16,8 @@ ICP (`vtk_functions.py:12-37`): real `vtkPolyData` inputs go t
 VTK's own `vtkIterativeClosestPointTransform` when the `vtk` wheel is importable;
 everything else (always the case in the build image) runs the same iteration with
 the closest-point search on the MI355X (`pyfocusr_amd/icp.py`).  Curvature
-(`vtk_functions.py:40-74`) stays VTK-only.
+(`vtk_functions.py:40-74`): `get_min_curvature`, `get_max_curvature` and
+`get_min_max_curvature_values` run on the MI355X (`pyfocusr_amd/curvature.py`).
 """
 import numpy as np
 
@@ -365,6 +366,35 @@ def apply_transform(source, transform):
     f.SetTransform(transform)
     f.Update()
     return f.GetOutput()
+
+
+def get_min_max_curvature_values(mesh, ctx=None):
+    """`vtk_functions.py:67-74`: (k_min, k_max), the minimum and maximum principal curvature of every vertex of a
+    triangle mesh, computed on the MI355X: `curvature.principal_curvatures(mesh, "defect")`, that is
+    H -+ sqrt(max(H^2 - K, 0)) from the angle-defect Gaussian curvature K and the dihedral-angle mean curvature H over
+    the barycentric vertex area.  These are the same quantities as vtkCurvatures' minimum and maximum curvature, from a
+    different discretisation: VTK's mean curvature is an un-normalised edge average, not divided by a vertex area the
+    way H is here, so the values differ.  Parity with VTK is unpinned because VTK is not installed in the build image:
+    the same status as ICP and CPD.  Values at boundary vertices are not meaningful curvatures."""
+    from . import curvature
+
+    return curvature.principal_curvatures(mesh, method="defect", ctx=ctx)
+
+
+def get_min_curvature(mesh, ctx=None):
+    """`vtk_functions.py:59-64`: the minimum principal curvature k_min of every vertex, as the reference returns it: a
+    list of one array (it is appended to a list of node features).  The same quantity as vtkCurvatures' minimum
+    curvature from a different discretisation, parity with VTK unpinned (VTK is not installed in the build image; the
+    same status as ICP and CPD): see `get_min_max_curvature_values`."""
+    return [get_min_max_curvature_values(mesh, ctx=ctx)[0]]
+
+
+def get_max_curvature(mesh, ctx=None):
+    """`vtk_functions.py:51-56`: the maximum principal curvature k_max of every vertex, as the reference returns it: a
+    list of one array.  The same quantity as vtkCurvatures' maximum curvature from a different discretisation, parity
+    with VTK unpinned (VTK is not installed in the build image; the same status as ICP and CPD): see
+    `get_min_max_curvature_values`."""
+    return [get_min_max_curvature_values(mesh, ctx=ctx)[1]]
 
 
 def vtk_deep_copy(mesh):
