@@ -39,6 +39,7 @@ extern "C" {
                                      applications since the last synchronising call are invalid; the stream has been
                                      drained and the path switched off - repeat the solve (pf_eigs_smallest and the
                                      Python drivers do so by themselves) */
+#define PF_E_INTERNAL (-6)   /* a bound that the algorithm guarantees was exceeded (pf_mesh_topology's labelling rounds) */
 
 /* operator selector for the eigensolver kernels */
 #define PF_OP_RW 0  /* L = G (D - W), G = diag(1/(deg+1e-8))   graph.py:216-226 (as stored by the reference) */
@@ -778,6 +779,49 @@ int pf_assign(pf_ctx* ctx, const double* rows, int64_t n_rows, const double* col
 int pf_curvatures(pf_ctx* ctx, const double* pts, int64_t n, const int32_t* faces, int64_t n_faces, double* out_area,
                   double* out_gauss, double* out_mean, double* out_tensor6, double* out_kminmax, double* out_dirs,
                   double* out_normals, uint8_t* out_boundary, int64_t* topology, double* device_ms);
+
+/* ---- topology of a triangle mesh: face adjacency, patches, orientability, the faces to reverse, boundary loops ------
+ * n vertices, faces [n_faces][3] i32 (host; triangles only), pts [n][3] f64 (host) or NULL: the points only serve the
+ * outward rule.  Integers throughout, the signed volume excepted; vertex (bow-tie) manifoldness is not looked at.
+ *   half-edge  h = 3 t + j leaves corner j of face t for corner (j + 1) % 3; its edge is the unordered pair of vertices;
+ *              the half-edges of an edge are listed in ascending h
+ *   edges      one half-edge: boundary edge.  Two: two-face edge, with parity p = 1 when both half-edges run in the same
+ *              direction (inconsistent), else 0.  Three or more: non-manifold edge.
+ *   face_neighbours [n_faces][3]  the face across the edge of half-edge 3 t + j; -1 on a boundary edge, -2 on a
+ *              non-manifold edge
+ *   patch [n_faces]  patches are the connected components of the faces joined across two-face edges only, numbered
+ *              0 .. P-1 in ascending order of their smallest face (face 0 is in patch 0)
+ *   orientable a patch for which rel[t] in {0, 1} exists with rel[a] ^ rel[b] == p on each of its two-face edges; with
+ *              rel[root] = 0 for the patch's smallest face rel is unique
+ *   flip [n_faces]  0 on a patch that is not orientable (it is left as it is).  On an orientable patch flip = rel if that
+ *              reverses at most half of the patch's faces (a tie keeps the root), else rel ^ 1: a mesh with a few reversed
+ *              faces gets exactly those back.  Then the outward rule, with PF_TOPOLOGY_OUTWARD in flags and pts given, for
+ *              an orientable patch that is closed (none of its faces touches a boundary or non-manifold edge):
+ *              V = 1/6 sum over the patch's faces (a, b, c), as flip leaves them, of a . (b x c); V < 0 reverses the
+ *              whole patch (flip ^= 1, V = -V).  Only the sign of V decides.  The sum runs over the faces in ascending
+ *              order along a fixed tree (256 consecutive terms, 256 of those sums, the rest in order), separate
+ *              multiplies and adds, the cross product first, the dot product left to right; no floating-point atomics.
+ *   boundary_loop [n_faces][3]  within a patch two boundary edges are linked when they share a vertex; a loop is a
+ *              connected component of that relation; loops are numbered 0 .. B-1 in ascending order of their smallest
+ *              half-edge.  The loop of each half-edge, -1 for one that is not on a boundary edge.
+ *   patch_orientable, patch_volume  [n_faces] as capacity, the first P entries are written: 1 / 0, and V after the rule
+ *              (0.0 where the rule does not apply: not closed, not orientable, no pts, no PF_TOPOLOGY_OUTWARD)
+ *   report [8] edges | boundary edges | non-manifold edges | inconsistent edges (the first four of pf_curvatures' and
+ *              pf_surface_prepare_signed's topology) | P | B (-1 without boundary_loop) | labelling rounds of the patches
+ *              | labelling rounds of the loops (0 without boundary edges)
+ *   device_ms  between the uploads and the last download (HIP events): it contains the host's reads of the flag
+ * Every output may be NULL.  On the device: the half-edges sorted by edge (one stable radix sort), one thread per edge,
+ * then a union-find over the faces whose word (parent << 1 | parity) moves by one 64-bit atomicMin: per two-face edge the
+ * larger root goes under the smaller, then the paths are compressed, one round after another, each two ordinary launches,
+ * until a flag the host reads says that nothing changed.  No kernel waits for another block.  The loops are labelled
+ * the same way over the boundary half-edges sorted by (patch, vertex).  Two calls give the same bits in every output.
+ * PF_E_ARG for a vertex id outside 0..n-1, n outside 1..2^31-1, n_faces < 1, 3 n_faces >= 2^31 or unknown flags;
+ * PF_E_DEGENERATE for a face that repeats a vertex (the message names the first); a zero-area face of three distinct
+ * vertices is legal.  PF_E_INTERNAL if the labelling has not settled after n_faces + 1 rounds (it cannot). */
+#define PF_TOPOLOGY_OUTWARD 1u
+int pf_mesh_topology(pf_ctx* ctx, const double* pts, int64_t n, const int32_t* faces, int64_t n_faces, uint32_t flags,
+                     int32_t* face_neighbours, int32_t* patch, uint8_t* flip, int32_t* boundary_loop, uint8_t* patch_orientable,
+                     double* patch_volume, int64_t* report, double* device_ms);
 
 #ifdef __cplusplus
 }

@@ -26,6 +26,7 @@ from .surface_distance import (point_to_surface_distances, points_inside, signed
                                signed_point_to_surface_distances, summarize_distances, summarize_signed_distances,
                                surface_distance_metrics, winding_numbers)
 from .test import get_all_pairwise_surface_errors
+from .topology import extract_patches, is_consistently_oriented, mesh_topology, orient_faces
 from .vtk_functions import PolyMesh, read_vtk_mesh, write_vtk_mesh
 
 __version__ = "0.1.0"

@@ -216,6 +216,8 @@ SIGNATURES = {
                             C.POINTER(AssignStats)]),
     "pf_curvatures": (C.c_int, [C.c_void_p, _f64p, C.c_int64, _i32p, C.c_int64, _f64p, _f64p, _f64p, _f64p, _f64p, _f64p, _f64p,
                                 C.POINTER(C.c_uint8), _i64p, _f64p]),
+    "pf_mesh_topology": (C.c_int, [C.c_void_p, _f64p, C.c_int64, _i32p, C.c_int64, C.c_uint32, _i32p, _i32p, C.POINTER(C.c_uint8),
+                                   _i32p, C.POINTER(C.c_uint8), _f64p, _i64p, _f64p]),
 }
 
 _lib = None
@@ -256,6 +258,8 @@ def load_library():
 PF_E_DEGENERATE = -3
 PF_E_STATE = -4
 PF_E_PERSIST_TIMEOUT = -5
+PF_E_INTERNAL = -6
+PF_TOPOLOGY_OUTWARD = 1
 
 
 class _PinnedBlock(object):
@@ -599,6 +603,38 @@ class Context(object):
                                        topology.ctypes.data_as(_i64p), C.byref(ms)))
         out.update(boundary=boundary.astype(bool), topology=topology, device_ms=ms.value)
         return out
+
+    # ---- mesh topology -----------------------------------------------------------------
+    def mesh_topology(self, n_points, faces, points=None, outward=True):
+        """`pf_mesh_topology` of the triangle mesh (faces (m, 3) i32 over `n_points` vertices; points (n, 3) f64 or None:
+        they only serve the outward rule): a dict with `face_neighbours` (m, 3) int32 (-1 boundary, -2 non-manifold),
+        `patch` (m,) int32, `flip` (m,) bool, `boundary_loop` (m, 3) int32 (-1: not on a boundary), `patch_orientable`
+        (P,) bool, `patch_volume` (P,), `report` (8,) int64 = edges | boundary | non-manifold | inconsistent edges |
+        patches | loops | rounds | loop rounds, and `device_ms`.  Only the shapes are checked here; the library refuses
+        an index out of range (PF_E_ARG) and a face that repeats a vertex (PF_E_DEGENERATE)."""
+        f = np.ascontiguousarray(faces, dtype=np.int32)
+        if f.ndim != 2 or f.shape[1] != 3:
+            raise ValueError("faces must be (m, 3)")
+        n, m = int(n_points), f.shape[0]
+        pts = None
+        if points is not None:
+            pts = _c_f64(points)
+            if pts.shape != (n, 3):
+                raise ValueError("points must be (n_points, 3)")
+        u8p = C.POINTER(C.c_uint8)
+        nbr, loop = np.empty((m, 3), dtype=np.int32), np.empty((m, 3), dtype=np.int32)
+        patch, flip = np.empty(m, dtype=np.int32), np.empty(m, dtype=np.uint8)
+        orientable, volume = np.empty(m, dtype=np.uint8), np.empty(m)
+        report = np.zeros(8, dtype=np.int64)
+        ms = C.c_double(0.0)
+        _check(self._lib.pf_mesh_topology(self._h, None if pts is None else _f64(pts), n, f.ctypes.data_as(_i32p), m,
+                                          PF_TOPOLOGY_OUTWARD if outward else 0, nbr.ctypes.data_as(_i32p),
+                                          patch.ctypes.data_as(_i32p), flip.ctypes.data_as(u8p), loop.ctypes.data_as(_i32p),
+                                          orientable.ctypes.data_as(u8p), _f64(volume), report.ctypes.data_as(_i64p), C.byref(ms)))
+        P = int(report[4])
+        return {"face_neighbours": nbr, "patch": patch, "flip": flip.astype(bool), "boundary_loop": loop,
+                "patch_orientable": orientable[:P].astype(bool), "patch_volume": volume[:P].copy(), "report": report,
+                "device_ms": ms.value}
 
     def assign(self, rows, cols, return_duals=False):
         """Optimal one-to-one assignment on Euclidean costs (`pf_assign`): col_of_row (int64, n_rows) minimising

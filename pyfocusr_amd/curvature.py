@@ -73,7 +73,8 @@ def discrete_curvatures(mesh_or_points, faces=None, ctx=None):
     """`Curvatures` of a triangle mesh: a `PolyMesh`, a vtkPolyData, a `(points, faces)` pair, or points with `faces`.
     Keys: area, gaussian, mean, k_min, k_max (from H and K), tensor (n, 6), tensor_k_min, tensor_k_max, d_min, d_max
     (n, 3), normals (n, 3), boundary (n,) bool, topology (5,) int64, device_ms (the module's docstring has the
-    definitions).  Values at boundary vertices are not meaningful curvatures: mask them with `boundary`."""
+    definitions).  Values at boundary vertices are not meaningful curvatures: mask them with `boundary`.  The sign of
+    `mean` and the normals assume outward faces: `topology.orient_faces` makes them so."""
     pts, f = _triangle_mesh(mesh_or_points, faces)
     ctx = ctx or _hip.default_context()
     raw = ctx.curvatures(pts, f)

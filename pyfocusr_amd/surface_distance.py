@@ -158,8 +158,9 @@ def signed_point_to_surface_distances(points, mesh, ctx=None, check_orientation=
 
     `sign="pseudonormal"`: the side of the angle-weighted pseudonormal at the closest point.  With `check_orientation`
     a mesh whose triangles disagree on their orientation (inconsistent edges) or that has edges in three or more
-    triangles raises ValueError: the sign means nothing there.  Open boundaries are allowed (the sign then follows
-    the face normals nearby, and flips near every boundary loop).
+    triangles raises ValueError: the sign means nothing there (`topology.orient_faces` reverses the faces that
+    disagree).  Open boundaries are allowed (the sign then follows the face normals nearby, and flips near every
+    boundary loop).
 
     `sign="winding"`: negative where the generalized winding number (`winding_numbers`, exact mode) exceeds 0.5,
     positive otherwise, +0.0 at distance 0.  Meant for open and non-manifold meshes; with `check_orientation` only
