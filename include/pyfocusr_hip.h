@@ -85,6 +85,11 @@ typedef struct pf_timing {
 
 /* ---- context -------------------------------------------------------------------------- */
 int pf_version(void);
+/* Debugging aid, process-wide, off by default: on != 0 fills every block the library's device memory pool hands out with
+ * 0xFF bytes (NaN as a floating-point number, -1 as an integer) before its first use, on the stream that asked for it.
+ * Results do not change - nothing in the library reads pool memory it has not written - and a run that does change has
+ * found a reader of uninitialised memory.  Costs one fill launch per allocation while on, nothing while off. */
+int pf_pool_poison(int on);
 const char* pf_last_error(void);
 int pf_device_count(void);
 int pf_create(int device, pf_ctx** out);
@@ -148,6 +153,10 @@ int pf_cotan_apply(pf_graph* g, const double* x, int32_t ncols, double* out);
 /* (the three calls above return PF_E_ARG for a graph that pf_graph_build_cotan did not build) */
 void pf_graph_free(pf_graph* g);
 int pf_graph_get_info(pf_graph* g, pf_graph_info* out);
+/* 1 if the mesh this graph was built from listed a directed edge more than once (duplicated faces, non-manifold edges):
+ * the build then moved the rows of CSR(W) together after dropping the repeats.  0 for every closed manifold mesh - the
+ * sorted rows are CSR(W) as they stand and that pass returns at once - and for graphs not built from a mesh. */
+int pf_graph_rows_compacted(pf_graph* g);
 /* CSR(W): rowptr[n+1], colidx[nnz_w], w[nnz_w]; l_offdiag[nnz_w] = -w/(deg_i+1e-8);
  * per-vertex deg[n], l_diag[n] = deg/(deg+1e-8).  Any output may be NULL. */
 int pf_graph_download(pf_graph* g, int32_t* rowptr, int32_t* colidx, double* w, double* l_offdiag,

@@ -67,6 +67,7 @@ class AssignStats(C.Structure):
 # name -> (restype, argtypes): every symbol include/pyfocusr_hip.h declares.
 SIGNATURES = {
     "pf_version": (C.c_int, []),
+    "pf_pool_poison": (C.c_int, [C.c_int]),
     "pf_last_error": (C.c_char_p, []),
     "pf_device_count": (C.c_int, []),
     "pf_create": (C.c_int, [C.c_int, C.POINTER(C.c_void_p)]),
@@ -87,6 +88,7 @@ SIGNATURES = {
     "pf_cotan_apply": (C.c_int, [C.c_void_p, _f64p, C.c_int32, _f64p]),
     "pf_graph_free": (None, [C.c_void_p]),
     "pf_graph_get_info": (C.c_int, [C.c_void_p, C.POINTER(GraphInfo)]),
+    "pf_graph_rows_compacted": (C.c_int, [C.c_void_p]),
     "pf_graph_download": (C.c_int, [C.c_void_p, _i32p, _i32p, _f64p, _f64p, _f64p, _f64p, _i32p]),
     "pf_ws_ensure": (C.c_int, [C.c_void_p, C.c_int32]),
     "pf_ws_upload": (C.c_int, [C.c_void_p, C.c_int32, _f64p]),
@@ -350,6 +352,12 @@ def persist_enable(on=True):
     """Process-wide switch of the resident Chebyshev kernel (operator in registers, x in LDS, one kernel per filter
     application; on by default, see csrc/pf_persist.hip).  Results are bit-identical either way."""
     _check(load_library().pf_persist_enable(int(bool(on))))
+
+
+def pool_poison(on=True):
+    """Process-wide debugging switch (off by default): every block the device memory pool hands out is filled with
+    0xFF bytes (NaN / -1) before its first use.  Results are bit-identical either way; a difference is a bug."""
+    _check(load_library().pf_pool_poison(int(bool(on))))
 
 
 def orth_one_launch(on=True):
@@ -1268,6 +1276,7 @@ class DeviceLaplacian(object):
         self.n_components = int(info.n_components)
         self.max_degree = int(info.max_degree)
         self.n_oneway = int(info.n_oneway)
+        self.rows_compacted = bool(self._lib.pf_graph_rows_compacted(h))  # the mesh listed a directed edge more than once
         self.spectral_bound = float(info.spectral_bound) if 0.0 < float(info.spectral_bound) <= 2.0 else 2.0
         self.op = PF_OP_SYM if self.symmetric else PF_OP_RW
         self.has_points = matrix is None

@@ -5,6 +5,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <mutex>
 
@@ -96,7 +97,37 @@ hipStream_t pf_stream_b(pf_ctx* c) {
     return c->stream_b;
 }
 
+// pf_pool_poison: every block pf_malloc hands out is first filled with 0xFF bytes (a NaN as a double or a float, -1 as an
+// integer) on the stream it was asked for - at its place in the order when launches are being recorded.  Whoever reads
+// a block of the pool before writing it then shows.  A pair build takes blocks on the ctx stream for kernels of its side
+// stream (pf_reorder.hip) and the other way round: the ctx's other stream waits for the fill as well.
+static std::atomic<int> g_pool_poison{0};
+
+static hipError_t pf_malloc_block(hipStream_t st, void** p, size_t bytes);
+
+static hipError_t poison_block(hipStream_t st, void* p, size_t bytes) {
+    const int64_t words = (int64_t)(((std::max<size_t>(bytes, 1) + 255) & ~(size_t)255) / 4);  // (the block's own size)
+    pfl::launch<pfl::k_fill_words>(dim3((unsigned)((words + 1023) / 1024)), dim3(256), 0, st, static_cast<uint32_t*>(p), words, 0xFFFFFFFFu);
+    pf_ctx* c = ctx_of_stream(st);
+    if (c && c->stream_b) {
+        if (!c->poison_ev && hipEventCreateWithFlags(&c->poison_ev, hipEventDisableTiming) != hipSuccess) return hipGetLastError();
+        hipStream_t other = st == c->stream ? c->stream_b : c->stream;
+        hipEvent_t ev = c->poison_ev;
+        pfl::call(st, [=](hipStream_t s) {
+            (void)hipEventRecord(ev, s);
+            (void)hipStreamWaitEvent(other, ev, 0);
+        });
+    }
+    return pfl::tl_rec ? hipSuccess : hipGetLastError();
+}
+
 hipError_t pf_malloc(hipStream_t st, void** p, size_t bytes) {
+    const hipError_t e = pf_malloc_block(st, p, bytes);
+    if (e == hipSuccess && g_pool_poison.load(std::memory_order_relaxed)) return poison_block(st, *p, bytes);
+    return e;
+}
+
+static hipError_t pf_malloc_block(hipStream_t st, void** p, size_t bytes) {
     *p = nullptr;
     pf_ctx* c = ctx_of_stream(st);
     if (!c) return hipErrorInvalidValue;
@@ -229,6 +260,11 @@ extern "C" {
 
 int pf_version(void) { return PF_VERSION; }
 
+int pf_pool_poison(int on) {
+    g_pool_poison.store(on ? 1 : 0);
+    return PF_OK;
+}
+
 int pf_host_alloc(size_t bytes, void** out) {
     PF_CHECK(out != nullptr && bytes > 0, PF_E_ARG, "pf_host_alloc: bad argument");
     *out = nullptr;
@@ -316,6 +352,7 @@ void pf_destroy(pf_ctx* c) {
         if (c->fork_ev) hipEventDestroy(c->fork_ev);
         c->stream_b = nullptr;
     }
+    if (c->poison_ev) hipEventDestroy(c->poison_ev);
     if (c->pinned_scratch_b) hipHostFree(c->pinned_scratch_b);
     if (c->pinned_scratch_knn) hipHostFree(c->pinned_scratch_knn);
     for (auto& kv : c->free_blocks) hipFree(kv.second);

@@ -184,11 +184,31 @@ __device__ __forceinline__ int32_t sort_unique_segment(C* c, W* v, int32_t b, in
     return u;
 }
 
+// deg_i = the row's weights summed left to right in column order (lil_matrix.sum(axis=1)), g_i = 1 / (deg_i + 1e-8)
+// (graph.py:219), sg_i = sqrt(g_i): u sorted unique weights at v
+template <typename W>
+__device__ __forceinline__ void row_degree(const W* v, int32_t u, int64_t i, double* __restrict__ deg, double* __restrict__ g,
+                                           double* __restrict__ sg) {
+    double d = 0.0;
+    for (int32_t a = 0; a < u; ++a) d += v[a];
+    deg[i] = d;
+    const double gi = 1.0 / (d + 1e-8);
+    g[i] = gi;
+    sg[i] = sqrt(gi);
+}
+
+// The sorted rows go back to rcol / rw AND, at the same places, into col / w, the degrees are summed while the row is at
+// hand, and `shrunk` is raised when a row lost a repeated entry.  No row of a closed manifold mesh does: the rows then
+// begin where the scan of the unique counts says as well (rowptr == start), col / w are CSR(W) as they stand, and
+// k_compact_rows behind the scan returns at once.  Otherwise it moves the rows from rcol / rw to their places.
 struct k_sort_unique_rows {
     static constexpr int BOUNDS = PF_BLOCK;
     static __device__ __forceinline__ void run(const int32_t* __restrict__ start, int64_t n,
                                                                int32_t* __restrict__ rcol, double* __restrict__ rw,
-                                                               int32_t* __restrict__ ucnt, const int32_t* __restrict__ key) {
+                                                               int32_t* __restrict__ ucnt, const int32_t* __restrict__ key,
+                                                               int32_t* __restrict__ col, double* __restrict__ w,
+                                                               double* __restrict__ deg, double* __restrict__ g,
+                                                               double* __restrict__ sg, int32_t* __restrict__ shrunk) {
     __shared__ int32_t s_c[PF_SORT_CAP];
     __shared__ double s_v[PF_SORT_CAP];
     const int64_t i0 = (int64_t)blockIdx.x * PF_BLOCK;
@@ -196,7 +216,17 @@ struct k_sort_unique_rows {
     const int64_t i1 = i0 + PF_BLOCK < n ? i0 + PF_BLOCK : n;
     const int32_t lo = start[i0], hi = start[i1];  // (block-uniform)
     if (hi - lo > PF_SORT_CAP) {
-        if (i < n) ucnt[i] = sort_unique_segment(rcol, rw, start[i], start[i + 1], key);
+        if (i < n) {
+            const int32_t b = start[i], e = start[i + 1];
+            const int32_t u = sort_unique_segment(rcol, rw, b, e, key);
+            ucnt[i] = u;
+            for (int32_t a = b; a < b + u; ++a) {
+                col[a] = rcol[a];
+                w[a] = rw[a];
+            }
+            row_degree(rw + b, u, i, deg, g, sg);
+            if (u != e - b) atomicOr(shrunk, 1);
+        }
         return;
     }
     for (int32_t a = threadIdx.x; a < hi - lo; a += PF_BLOCK) {
@@ -204,11 +234,21 @@ struct k_sort_unique_rows {
         s_v[a] = rw[lo + a];
     }
     __syncthreads();
-    if (i < n) ucnt[i] = sort_unique_segment(s_c, s_v, start[i] - lo, start[i + 1] - lo, key);
+    if (i < n) {
+        const int32_t b = start[i] - lo, e = start[i + 1] - lo;
+        const int32_t u = sort_unique_segment(s_c, s_v, b, e, key);
+        ucnt[i] = u;
+        row_degree(s_v + b, u, i, deg, g, sg);
+        if (u != e - b) atomicOr(shrunk, 1);
+    }
     __syncthreads();
     for (int32_t a = threadIdx.x; a < hi - lo; a += PF_BLOCK) {
-        rcol[lo + a] = s_c[a];
-        rw[lo + a] = s_v[a];
+        const int32_t c = s_c[a];
+        const double v = s_v[a];
+        rcol[lo + a] = c;
+        rw[lo + a] = v;
+        col[lo + a] = c;
+        w[lo + a] = v;
     }
 }
 };
@@ -220,7 +260,9 @@ struct k_compact_rows {
                                                            const int32_t* __restrict__ rcol,
                                                            const double* __restrict__ rw, int32_t* __restrict__ col,
                                                            double* __restrict__ w, double* __restrict__ deg,
-                                                           double* __restrict__ g, double* __restrict__ sg) {
+                                                           double* __restrict__ g, double* __restrict__ sg,
+                                                           const int32_t* __restrict__ shrunk) {
+    if (!*shrunk) return;  // (k_sort_unique_rows: no row lost an entry - col / w / deg / g / sg are in place)
     const int64_t i = (int64_t)blockIdx.x * PF_BLOCK + threadIdx.x;
     if (i >= n) return;
     const int32_t src = start[i];
@@ -633,11 +675,17 @@ struct k_csr_split {
 // [16..16 + PF_ROOTS_AHEAD) the first component roots
 constexpr int PF_ROOTS_AHEAD = 16;
 constexpr int PF_REPORT_INTS = 16 + PF_ROOTS_AHEAD + 2;  // (+ the 64 bits of the face bound's P_min)
+// `out` and `host_slices` are PINNED host memory: the kernel is the read-back (the slice pointers by all blocks, the report by
+// block 0) - one launch that the two meshes of a pair share, instead of two copy commands per mesh through the runtime
 struct k_report {
     static constexpr int BOUNDS = 1024;
     static __device__ __forceinline__ void run(const int32_t* __restrict__ stats, const int32_t* __restrict__ last_round, const int32_t* __restrict__ rowptr_n,
                          const int32_t* __restrict__ extra, const int32_t* __restrict__ roots, const int32_t* __restrict__ pmin_bits,
-                         const int32_t* __restrict__ order_overflow, int32_t* __restrict__ out) {
+                         const int32_t* __restrict__ order_overflow, int32_t* __restrict__ out,
+                         const int64_t* __restrict__ slice_ptr, int64_t n_slice_words, int64_t* __restrict__ host_slices) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n_slice_words) host_slices[i] = slice_ptr[i];
+    if (blockIdx.x != 0) return;
     const int t = threadIdx.x;
     if (t < 5) out[t] = stats[t];
     if (t == 5) out[5] = *last_round;
@@ -662,6 +710,7 @@ struct FinishJob {
     const int32_t* d_extra = nullptr;
     int32_t* h_extra = nullptr;
     bool extra_hit = false;
+    int extra_info = -1;  // one of the caller's flags that tells something and is no error
     bool nnz_from_rowptr = false;
     const unsigned long long* d_pmin = nullptr;
     double* h_pmin = nullptr;
@@ -670,7 +719,7 @@ struct FinishJob {
     static constexpr int PF_CC_ROUNDS = 128;
     static constexpr int PF_CC_FIRST = 12;
     hipStream_t st = nullptr;
-    int32_t *flags = nullptr, *d_roots = nullptr, *round_flags = nullptr, *stats = nullptr, *report = nullptr, *h_report = nullptr;
+    int32_t *flags = nullptr, *d_roots = nullptr, *round_flags = nullptr, *stats = nullptr, *h_report = nullptr;
     int64_t* width64 = nullptr;
     void* pin = nullptr;
     size_t slice_bytes = 0;
@@ -691,6 +740,9 @@ struct FinishJob {
     int begin_stats_and_labels() {
         st = g->ctx->stream;
         const int64_t n = g->n;
+        // the resident filter's hand-off ring depends on n_pad alone: filled here, beside the labelling rounds where the
+        // build has forked, instead of in front of the solve's first filter application
+        PF_TRY(pf_persist_ring_prefill(g, g->side_stream ? g->side_stream : st));
         PF_TRY(dev_alloc(st, &flags, 8 + PF_CC_ROUNDS));  // the flags and the labelling rounds' flags: one block, one fill
         tmp.push_back(flags);
         round_flags = flags + 8;
@@ -747,18 +799,13 @@ struct FinishJob {
             });
             g->side_stream = nullptr;
         }
-        if (!report) {
-            PF_TRY(dev_alloc(st, &report, PF_REPORT_INTS));
-            tmp.push_back(report);
-        }
-        pfl::launch<k_report>(dim3(1), dim3(PF_WAVE), 0, st, stats, round_flags + PF_CC_FIRST - 1, nnz_from_rowptr ? g->rowptr + n : nullptr, d_extra, d_roots,
-                                        reinterpret_cast<const int32_t*>(d_pmin), flags, report);
-        PF_HIP(hipGetLastError());
         slice_bytes = sizeof(int64_t) * (size_t)(g->n_slices + 1);
         PF_TRY(pf_pinned_scratch(g->ctx, slice_bytes + sizeof(int32_t) * PF_REPORT_INTS, &pin, pos));
         h_report = reinterpret_cast<int32_t*>(static_cast<unsigned char*>(pin) + slice_bytes);
-        PF_HIP(pfl::memcpy_async(st, pin, g->slice_ptr, slice_bytes, hipMemcpyDeviceToHost));
-        PF_HIP(pfl::memcpy_async(st, h_report, report, sizeof(int32_t) * PF_REPORT_INTS, hipMemcpyDeviceToHost));
+        pfl::launch<k_report>(dim3(pf_blocks(g->n_slices + 1)), dim3(PF_BLOCK), 0, st, stats, round_flags + PF_CC_FIRST - 1, nnz_from_rowptr ? g->rowptr + n : nullptr,
+                              d_extra, d_roots, reinterpret_cast<const int32_t*>(d_pmin), flags, h_report, g->slice_ptr, g->n_slices + 1,
+                              static_cast<int64_t*>(pin));
+        PF_HIP(hipGetLastError());
         return PF_OK;
     }
 
@@ -788,7 +835,7 @@ struct FinishJob {
         if (nnz_from_rowptr) g->nnz_w = nnz32;
         if (d_extra) {
             extra_hit = false;
-            for (int i = 0; i < 8; ++i) extra_hit = extra_hit || h_extra[i] != 0;
+            for (int i = 0; i < 8; ++i) extra_hit = extra_hit || (h_extra[i] != 0 && i != extra_info);
             if (extra_hit) return PF_OK;
         }
         int32_t n_roots = h_stats[4];
@@ -990,12 +1037,16 @@ struct MeshBuild {
             return PF_OK;
         }
         if (k == 1) {  // CSR(W), degrees, the face bound
-            pfl::launch<k_sort_unique_rows>(dim3(pf_blocks(n)), dim3(PF_BLOCK), 0, st, b_start, n, b_rcol, b_rw, b_ucnt, g->morder);
-            PF_HIP(hipGetLastError());
-            PF_TRY(pf_exclusive_scan_i32(st, b_ucnt, g->rowptr, n + 1));
+            // (col / w are sized by the upper bound: the sorted rows land in them at once, see k_sort_unique_rows;
+            // b_flags[2]: a row lost a repeated entry - k_compact_rows has work, and the read-back tells the host)
             PF_TRY(dev_alloc(st, &g->col, n_edges));
             PF_TRY(dev_alloc(st, &g->w, n_edges));
-            pfl::launch<k_compact_rows>(dim3(pf_blocks(n)), dim3(PF_BLOCK), 0, st, b_start, g->rowptr, n, b_rcol, b_rw, g->col, g->w, g->deg, g->g, g->sg);
+            pfl::launch<k_sort_unique_rows>(dim3(pf_blocks(n)), dim3(PF_BLOCK), 0, st, b_start, n, b_rcol, b_rw, b_ucnt, g->morder, g->col, g->w, g->deg, g->g,
+                                            g->sg, b_flags + 2);
+            PF_HIP(hipGetLastError());
+            PF_TRY(pf_exclusive_scan_i32(st, b_ucnt, g->rowptr, n + 1));
+            pfl::launch<k_compact_rows>(dim3(pf_blocks(n)), dim3(PF_BLOCK), 0, st, b_start, g->rowptr, n, b_rcol, b_rw, g->col, g->w, g->deg, g->g, g->sg,
+                                        b_flags + 2);
             PF_HIP(hipGetLastError());
             // the face-by-face bound of the spectrum (k_face_bound); it holds if every undirected edge lies in exactly two
             // triangles: W symmetric and no directed edge listed twice - both known after the read-back
@@ -1017,6 +1068,7 @@ struct MeshBuild {
             }
             fin.g = g, fin.d_pts = d_pts, fin.numeric_symmetry = false, fin.d_extra = b_flags, fin.h_extra = h_flags;
             fin.nnz_from_rowptr = true, fin.d_pmin = pmin, fin.h_pmin = &h_pmin, fin.pos = pos;
+            fin.extra_info = 2;
             return PF_OK;
         }
         if (k == 2) return fin.begin_stats_and_labels();
@@ -1036,6 +1088,7 @@ struct MeshBuild {
                  "pf_graph_build: an edge has zero length or non-finite coordinates (the reference would store an "
                  "infinite weight, graph.py:177-178)");
         PF_CHECK(!fin.extra_hit, PF_E_HIP, "pf_graph_build: unexpected assembly flag");
+        g->rows_compacted = h_flags[2] != 0;
         g->spectral_bound = 2.0;
         if (pmin && g->is_symmetric && g->nnz_w == n_edges && h_pmin > 0.0 && h_pmin <= 0.25) {
             const double disc = 1.0 - 4.0 * h_pmin;
@@ -1250,6 +1303,9 @@ int pf_graph_build_device2(pf_mesh* mesh_a, pf_mesh* mesh_b, pf_graph** out_a, p
             rc = a.end();
             pfl::tl_rec = &rb;
             if (rc == PF_OK) rc = b.end();
+            // the SELL fills go out now: the device works on them while the host prepares the window structures
+            pfl::tl_rec = nullptr;
+            pfl::flush(ra, &rb);
             if (rc == PF_OK && !(a.needs_robust || b.needs_robust) && pf_persist_enabled()) {
                 // the window structures of the resident filter kernel, behind the fills (collected by the first application)
                 pfl::tl_rec = &ra;
@@ -1393,6 +1449,8 @@ int pf_graph_get_info(pf_graph* g, pf_graph_info* o) {
     o->n_oneway = g->n_oneway;
     return PF_OK;
 }
+
+int pf_graph_rows_compacted(pf_graph* g) { return g && g->rows_compacted ? 1 : 0; }
 
 int pf_graph_download(pf_graph* g, int32_t* rowptr, int32_t* colidx, double* w, double* l_offdiag, double* deg,
                       double* l_diag, int32_t* component_label) {

@@ -17,6 +17,7 @@
 
 #include "pf_internal.h"
 #include "pf_krylov.h"
+#include "pf_launch.h"
 
 namespace {
 
@@ -162,8 +163,26 @@ extern "C" int pf_eigs_smallest2(pf_graph* ga, pf_graph* gb, int32_t n_wanted_a,
         DeviceOps oa(ga), ob(gb);
         pfk::Solver a, b;
         *n_out_a = *n_out_b = 0;
-        rc = a.init(&oa, n_wanted_a, ellipse_hint());
-        if (rc == PF_OK) rc = b.init(&ob, n_wanted_b, ellipse_hint());
+        {
+            // The heads of the two solves - null vectors, their norms and scalings, the start vectors - are recorded per
+            // graph and queued zipped (pf_launch.h): one launch where both graphs ask for the same kernel, the rest (a
+            // second null vector that only one graph has) alone.  The start vectors' Gram-Schmidt steps are held back
+            // and queued by drive_pair, shared like every later one.  Per graph the kernels and their order are those
+            // of a single solve.
+            pfl::Recorder ra, rb;
+            a.defer_head_orth = b.defer_head_orth = true;
+            pfl::tl_rec = &ra;
+            rc = a.init(&oa, n_wanted_a, ellipse_hint());
+            pfl::tl_rec = &rb;
+            if (rc == PF_OK) rc = b.init(&ob, n_wanted_b, ellipse_hint());
+            pfl::tl_rec = nullptr;
+            a.defer_head_orth = b.defer_head_orth = false;
+            pfl::flush(ra, &rb);
+            if (rc == PF_OK && hipGetLastError() != hipSuccess) {
+                pf_set_error("pf_eigs_smallest2: a launch of the solves' heads failed");
+                rc = PF_E_HIP;
+            }
+        }
         if (rc == PF_OK) rc = pfk::drive_pair(a, b);
         // (both solves have synchronised with the stream in their extraction; a late PF_E_PERSIST_TIMEOUT of the partner's
         // last applications surfaces in pf_sync)

@@ -153,6 +153,7 @@ struct pf_ctx {
     // the side stream of a pair build (pf_graph_build_device2): chains of the build that run beside the others between a
     // fork and a join.  Blocks it uses come from the one cache: taken after the fork, released after the join is queued.
     hipStream_t stream_b = nullptr;
+    hipEvent_t poison_ev = nullptr;  // pf_pool_poison: orders a block's fill before its users on the ctx's other stream
     hipEvent_t join_ev = nullptr, fork_ev = nullptr;
     std::vector<pf_graph*> deferred;  // graphs with a download that is not queued yet ...
     std::mutex deferred_mutex;        // ... guarded: pf_host_free / pf_host_detach walk every ctx's list from whatever thread collects an array
@@ -248,6 +249,7 @@ struct pf_graph {
     int32_t persist_phase2 = 0;
     uint64_t persist_epoch2 = 0;
     int32_t is_symmetric = 0, n_isolated = 0, n_components = 0, max_degree = 0, n_oneway = 0;
+    bool rows_compacted = false;  // mesh builds: a row of W lost a repeated directed edge, so k_compact_rows had rows to move
     int32_t unit_g = 0;  // graph handed in as a matrix (pf_graph_from_matrix): G = I, the operator is the matrix itself
     std::vector<int32_t> roots; // roots of components with >= 2 vertices, ascending
     // workspace: n_slots vectors + 2 Chebyshev temporaries, stride n_pad
@@ -437,6 +439,7 @@ struct pf_persist_args {
 };
 int pf_persist_cheb(const pf_persist_args* a, const pf_persist_args* b /* nullable */, int* done, double* lds_bytes /* += */,
                     bool first_try = true /* false: a further attempt for the same filter application (pf_cheb2's single-graph launches) */);
+int pf_persist_ring_prefill(pf_graph* g, hipStream_t st);  // the hand-off ring, filled on a stream of the build (queued only)
 int pf_persist_check(pf_ctx* ctx);  // PF_E_PERSIST_TIMEOUT (stream drained, path switched off) if a wait of an earlier launch ran out
 int pf_persist_set(int on);
 void pf_persist_release(pf_ctx* ctx);  // pf_destroy: another ctx may take the resident path over

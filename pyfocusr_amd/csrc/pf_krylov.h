@@ -290,6 +290,9 @@ struct Solver {
     // norms | collect them); stepwise_extract: advance() returns between the phases with no request (drive_pair alternates
     // the two graphs' phases), `extracting` says so
     bool stepwise_extract = false, extracting = false;
+    // A pair's driver sets defer_head_orth around init(): the Gram-Schmidt step of the start vector is then owed
+    // (head_orth_pending) instead of queued, and drive_pair queues it for both graphs in shared launches.
+    bool defer_head_orth = false, head_orth_pending = false;
     // Lanczos with PARTIAL reorthogonalisation (symmetric graphs; H. Simon 1984): a step orthogonalises against the locked
     // null vectors and the last two basis vectors only - the three-term recurrence - while a recurrence over the
     // coefficients estimates w_{j+1,k} = <v_{j+1}, v_k>; when an estimate passes pro_thresh the next TWO steps are full
@@ -455,7 +458,8 @@ struct Solver {
         PFK_TRY(ops->lock_nulls(op, &locked));  // slots [0, c0)
         PFK_CHECK(locked == c0, PF_E_STATE, "pf_eigs_smallest: %d null vectors locked, %d components", locked, c0);
         PFK_TRY(ops->start_vector(A0 + j, seed++));
-        PFK_TRY(ops->orth_begin(A0 + j, A0, j));
+        if (defer_head_orth) head_orth_pending = true;
+        else PFK_TRY(ops->orth_begin(A0 + j, A0, j));
         start_pending = true;
         restarts = 0;
         begin_expand();
@@ -1178,6 +1182,15 @@ inline int drive_pair(Solver& a, Solver& b) {
     }
     a.inline_analysis = b.inline_analysis = false;
     a.stepwise_extract = b.stepwise_extract = true;
+    // the start vectors' Gram-Schmidt steps that init() held back: both graphs in shared launches
+    if (a.head_orth_pending && b.head_orth_pending) {
+        const int32_t orth[8] = {a.A0 + a.j, a.A0, a.j, 1, b.A0 + b.j, b.A0, b.j, 1};
+        PFK_TRY(a.ops->orth_begin_pair(*b.ops, orth));
+    } else {
+        for (Solver* s : {&a, &b})
+            if (s->head_orth_pending) PFK_TRY(s->ops->orth_begin(s->A0 + s->j, s->A0, s->j));
+    }
+    a.head_orth_pending = b.head_orth_pending = false;
     PFK_TRY(advance_pair(a, b, !a.done, !b.done, helper.get()));
     while (!a.done || !b.done) {
         if ((!a.done && a.req_launched) || (!b.done && b.req_launched)) {  // queued ahead of the partner's extraction: collect

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "pf_internal.h"
+#include "pf_launch.h"
 
 namespace {
 
@@ -113,9 +114,11 @@ __global__ __launch_bounds__(PF_OP_BLOCK) void k_sell_op2(OpArgs a, OpArgs b) {
 // partial[b][chunk] = sum over the chunk's rows of V_b[i] * w[i]   (fixed order -> deterministic)
 // partial[b][chunk] = <slot first+b, slot wslot> over the chunk; with self_col >= 0 column b == self_col is w itself
 // (|w|^2 rides along)
-__global__ __launch_bounds__(PF_BLOCK) void k_dot_partial(const double* __restrict__ ws, int64_t n_pad, int32_t first,
-                                                          int32_t wslot, int64_t n_chunks, double* __restrict__ partial,
-                                                          int32_t self_col = -1) {
+// (d_*: the body of k_* - the kernel itself, and the form pf_launch.h records when a pair's driver queues the heads of its
+// two solves in shared launches, f_*)
+__device__ __forceinline__ void d_dot_partial(const double* __restrict__ ws, int64_t n_pad, int32_t first,
+                                              int32_t wslot, int64_t n_chunks, double* __restrict__ partial,
+                                              int32_t self_col) {
     __shared__ double red[PF_BLOCK / PF_WAVE];
     const int b = blockIdx.y;
     const int64_t chunk = blockIdx.x;
@@ -136,10 +139,22 @@ __global__ __launch_bounds__(PF_BLOCK) void k_dot_partial(const double* __restri
     __syncthreads();
     if (threadIdx.x == 0) partial[(int64_t)b * n_chunks + chunk] = (red[0] + red[1]) + (red[2] + red[3]);
 }
+__global__ __launch_bounds__(PF_BLOCK) void k_dot_partial(const double* __restrict__ ws, int64_t n_pad, int32_t first,
+                                                          int32_t wslot, int64_t n_chunks, double* __restrict__ partial,
+                                                          int32_t self_col = -1) {
+    d_dot_partial(ws, n_pad, first, wslot, n_chunks, partial, self_col);
+}
+struct f_dot_partial {
+    static constexpr int BOUNDS = PF_BLOCK;
+    static __device__ __forceinline__ void run(const double* ws, int64_t n_pad, int32_t first, int32_t wslot, int64_t n_chunks, double* partial,
+                                               int32_t self_col) {
+        d_dot_partial(ws, n_pad, first, wslot, n_chunks, partial, self_col);
+    }
+};
 
 // out[b] = sum_chunks partial[b][chunk];  acc[b] (+)= out[b]
-__global__ __launch_bounds__(PF_WAVE) void k_dot_finish(const double* __restrict__ partial, int64_t n_chunks,
-                                                        double* __restrict__ out, double* __restrict__ acc, int accumulate) {
+__device__ __forceinline__ void d_dot_finish(const double* __restrict__ partial, int64_t n_chunks,
+                                             double* __restrict__ out, double* __restrict__ acc, int accumulate) {
     const int b = blockIdx.x;
     double s = 0.0;
     for (int64_t k = threadIdx.x; k < n_chunks; k += PF_WAVE) s += partial[(int64_t)b * n_chunks + k];
@@ -150,6 +165,16 @@ __global__ __launch_bounds__(PF_WAVE) void k_dot_finish(const double* __restrict
         if (acc) acc[b] = accumulate ? acc[b] + s : s;
     }
 }
+__global__ __launch_bounds__(PF_WAVE) void k_dot_finish(const double* __restrict__ partial, int64_t n_chunks,
+                                                        double* __restrict__ out, double* __restrict__ acc, int accumulate) {
+    d_dot_finish(partial, n_chunks, out, acc, accumulate);
+}
+struct f_dot_finish {
+    static constexpr int BOUNDS = PF_WAVE;
+    static __device__ __forceinline__ void run(const double* partial, int64_t n_chunks, double* out, double* acc, int accumulate) {
+        d_dot_finish(partial, n_chunks, out, acc, accumulate);
+    }
+};
 
 // w -= sum_b h[b] V_b
 __global__ __launch_bounds__(PF_BLOCK) void k_multi_axpy(double* __restrict__ ws, int64_t n_pad, int32_t first,
@@ -608,11 +633,18 @@ __global__ __launch_bounds__(PF_BLOCK) void k_scale(double* __restrict__ x, int6
 
 // x *= 1/sqrt(*nrm2) with the norm still on the device (no host round trip between a Lanczos step and the next
 // filter application); left alone when the norm is ~0 (invariant subspace: the host stops the iteration)
-__global__ __launch_bounds__(PF_BLOCK) void k_scale_rsqrt(double* __restrict__ x, int64_t n_pad, const double* __restrict__ nrm2) {
+__device__ __forceinline__ void d_scale_rsqrt(double* __restrict__ x, int64_t n_pad, const double* __restrict__ nrm2) {
     const int64_t i = (int64_t)blockIdx.x * PF_BLOCK + threadIdx.x;
     const double v = *nrm2;
     if (i < n_pad && v > 1e-280) x[i] *= 1.0 / sqrt(v);
 }
+__global__ __launch_bounds__(PF_BLOCK) void k_scale_rsqrt(double* __restrict__ x, int64_t n_pad, const double* __restrict__ nrm2) {
+    d_scale_rsqrt(x, n_pad, nrm2);
+}
+struct f_scale_rsqrt {
+    static constexpr int BOUNDS = PF_BLOCK;
+    static __device__ __forceinline__ void run(double* x, int64_t n_pad, const double* nrm2) { d_scale_rsqrt(x, n_pad, nrm2); }
+};
 
 __global__ __launch_bounds__(PF_BLOCK) void k_mask_isolated(double* __restrict__ x, const int32_t* __restrict__ rowptr,
                                                             const int32_t* __restrict__ perm, int64_t n) {
@@ -624,10 +656,10 @@ __global__ __launch_bounds__(PF_BLOCK) void k_mask_isolated(double* __restrict__
 
 // Krylov start vector, part 2: smooth part + counter-based noise (splitmix64 of (seed, vertex)), zero
 // on isolated vertices and padding.  Noise keeps every eigenmode present whatever the geometry.
-__global__ __launch_bounds__(PF_BLOCK) void k_start_vector(double* __restrict__ x, const double* __restrict__ smooth,
-                                                           const int32_t* __restrict__ perm, const int32_t* __restrict__ perm_m,
-                                                           const int32_t* __restrict__ rowptr,
-                                                           int64_t n_pad, unsigned long long seed, double noise) {
+__device__ __forceinline__ void d_start_vector(double* __restrict__ x, const double* __restrict__ smooth,
+                                               const int32_t* __restrict__ perm, const int32_t* __restrict__ perm_m,
+                                               const int32_t* __restrict__ rowptr,
+                                               int64_t n_pad, unsigned long long seed, double noise) {
     const int64_t r = (int64_t)blockIdx.x * PF_BLOCK + threadIdx.x;
     if (r >= n_pad) return;
     const int32_t i = perm[r];    // the caller's vertex number: what the noise is keyed by, whatever the internal order
@@ -643,6 +675,19 @@ __global__ __launch_bounds__(PF_BLOCK) void k_start_vector(double* __restrict__ 
     }
     x[r] = v;
 }
+__global__ __launch_bounds__(PF_BLOCK) void k_start_vector(double* __restrict__ x, const double* __restrict__ smooth,
+                                                           const int32_t* __restrict__ perm, const int32_t* __restrict__ perm_m,
+                                                           const int32_t* __restrict__ rowptr,
+                                                           int64_t n_pad, unsigned long long seed, double noise) {
+    d_start_vector(x, smooth, perm, perm_m, rowptr, n_pad, seed, noise);
+}
+struct f_start_vector {
+    static constexpr int BOUNDS = PF_BLOCK;
+    static __device__ __forceinline__ void run(double* x, const double* smooth, const int32_t* perm, const int32_t* perm_m, const int32_t* rowptr,
+                                               int64_t n_pad, unsigned long long seed, double noise) {
+        d_start_vector(x, smooth, perm, perm_m, rowptr, n_pad, seed, noise);
+    }
+};
 
 // host order <-> solver order
 __global__ __launch_bounds__(PF_BLOCK) void k_permute_in(const double* __restrict__ src_old, const int32_t* __restrict__ perm,
@@ -662,11 +707,11 @@ __global__ __launch_bounds__(PF_BLOCK) void k_permute_out(const double* __restri
     for (int c = 0; c < count; ++c) dst_old[(int64_t)c * n + i] = ws[(int64_t)(first + c) * n_pad + r];
 }
 
-__global__ __launch_bounds__(PF_BLOCK) void k_null_vector(double* __restrict__ x, const int32_t* __restrict__ label,
-                                                          const int32_t* __restrict__ rowptr,
-                                                          const double* __restrict__ deg, const int32_t* __restrict__ perm,
-                                                          int64_t n_pad, int32_t root, int32_t sym,
-                                                          const double* __restrict__ weight) {
+__device__ __forceinline__ void d_null_vector(double* __restrict__ x, const int32_t* __restrict__ label,
+                                              const int32_t* __restrict__ rowptr,
+                                              const double* __restrict__ deg, const int32_t* __restrict__ perm,
+                                              int64_t n_pad, int32_t root, int32_t sym,
+                                              const double* __restrict__ weight) {
     // null vector of the iterated operator on one component: 1_C for L = G (D - W) and for a general matrix with zero
     // row sums (G = I: sym == 0 is passed), G^-1/2 1_C = sqrt(deg + 1e-8) 1_C for S = G^1/2 (D - W) G^1/2 of a mesh graph;
     // `weight` (cotangent graphs: sqrt(m), the null vector of M^-1/2 (D - W) M^-1/2) replaces both
@@ -677,6 +722,20 @@ __global__ __launch_bounds__(PF_BLOCK) void k_null_vector(double* __restrict__ x
     if (i >= 0 && label[i] == root && rowptr[i + 1] > rowptr[i]) v = weight ? weight[i] : (sym ? sqrt(deg[i] + 1e-8) : 1.0);
     x[r] = v;
 }
+__global__ __launch_bounds__(PF_BLOCK) void k_null_vector(double* __restrict__ x, const int32_t* __restrict__ label,
+                                                          const int32_t* __restrict__ rowptr,
+                                                          const double* __restrict__ deg, const int32_t* __restrict__ perm,
+                                                          int64_t n_pad, int32_t root, int32_t sym,
+                                                          const double* __restrict__ weight) {
+    d_null_vector(x, label, rowptr, deg, perm, n_pad, root, sym, weight);
+}
+struct f_null_vector {
+    static constexpr int BOUNDS = PF_BLOCK;
+    static __device__ __forceinline__ void run(double* x, const int32_t* label, const int32_t* rowptr, const double* deg, const int32_t* perm,
+                                               int64_t n_pad, int32_t root, int32_t sym, const double* weight) {
+        d_null_vector(x, label, rowptr, deg, perm, n_pad, root, sym, weight);
+    }
+};
 
 // dst_c = sum_b src_b Y[b][c] for up to 8 output columns per launch (Y row-major m x k, in device memory)
 constexpr int COMBINE_COLS = 8;
@@ -1181,6 +1240,11 @@ int dots_device(pf_graph* g, int32_t w, int32_t first, int32_t count, double* d_
     hipStream_t st = g->ctx->stream;
     PF_TRY(pf_reduce_ensure(g, count));
     dim3 grid((unsigned)g->n_chunks, (unsigned)count);
+    if (pfl::tl_rec) {  // the head of a pair's solve is being recorded: the partner's dot products share the launches
+        pfl::launch<f_dot_partial>(grid, dim3(PF_BLOCK), 0, st, g->ws, g->n_pad, first, w, g->n_chunks, g->partials, -1);
+        pfl::launch<f_dot_finish>(dim3((unsigned)count), dim3(PF_WAVE), 0, st, g->partials, g->n_chunks, d_out, d_acc, accumulate);
+        return PF_OK;
+    }
     k_dot_partial<<<grid, PF_BLOCK, 0, st>>>(g->ws, g->n_pad, first, w, g->n_chunks, g->partials);
     PF_HIP(hipGetLastError());
     k_dot_finish<<<(unsigned)count, PF_WAVE, 0, st>>>(g->partials, g->n_chunks, d_out, d_acc, accumulate);
@@ -1218,8 +1282,12 @@ int pf_ws_ensure(pf_graph* g, int32_t n_slots) {
     hipStream_t st = g->ctx->stream;
     double* nw = nullptr;
     const size_t bytes = sizeof(double) * (size_t)(n_slots + PF_WS_TMPS) * (size_t)g->n_pad;
+    // Not cleared (250k rows x 100 slots: 200 MB per graph and solve, written through the cache the operator had just been
+    // assembled into): a slot is read only after a kernel has written all n_pad rows of it - k_null_vector, k_start_vector,
+    // k_permute_in, the operator kernels' out / dst (the Chebyshev temporaries behind the slots included: step 1 has no
+    // prev term), k_combine, the slot copies; the row kernels of the row-partitioned solve touch up slots that one of
+    // these has filled.  pf_pool_poison shows a reader that comes first (profiles/front_of_step.md, slot by slot).
     PF_HIP(pf_malloc(st, (void**)&nw, bytes));
-    PF_HIP(hipMemsetAsync(nw, 0, bytes, st));
     if (g->ws && g->n_slots > 0)
         PF_HIP(hipMemcpyAsync(nw, g->ws, sizeof(double) * (size_t)g->n_slots * g->n_pad, hipMemcpyDeviceToDevice, st));
     pf_free(st, g->ws);
@@ -1273,6 +1341,11 @@ int pf_mask_isolated(pf_graph* g, int32_t slot) {
 
 int pf_start_vector(pf_graph* g, int32_t slot, uint64_t seed) {
     PF_TRY(check_slots(g, slot, 1, "pf_start_vector"));
+    if (pfl::tl_rec) {  // (the head of a pair's solve: one launch for both graphs' start vectors)
+        pfl::launch<f_start_vector>(dim3(pf_blocks(g->n_pad)), dim3(PF_BLOCK), 0, g->ctx->stream, pf_slot(g, slot), g->smooth, g->perm, g->perm_m, g->rowptr,
+                                    g->n_pad, (unsigned long long)seed, 0.5);
+        return PF_OK;
+    }
     k_start_vector<<<pf_blocks(g->n_pad), PF_BLOCK, 0, g->ctx->stream>>>(pf_slot(g, slot), g->smooth, g->perm, g->perm_m, g->rowptr, g->n_pad,
                                                                     (unsigned long long)seed, 0.5);
     PF_HIP(hipGetLastError());
@@ -1288,14 +1361,18 @@ int pf_lock_null_vectors(pf_graph* g, int32_t op, int32_t* n_locked) {
     PF_TRY(pf_ws_ensure(g, nc + 1));
     hipStream_t st = g->ctx->stream;
     PF_TRY(pf_reduce_ensure(g, 1));
+    const bool rec = pfl::tl_rec != nullptr;  // the head of a pair's solve: recorded, the partner's launches share these
+    const int32_t sym_w = op == PF_OP_SYM && !g->unit_g;
+    const double* weight = g->is_cotan ? g->cot_sqrtm : nullptr;
     for (int32_t c = 0; c < nc; ++c) {
-        k_null_vector<<<pf_blocks(g->n_pad), PF_BLOCK, 0, st>>>(pf_slot(g, c), g->label, g->rowptr, g->deg, g->perm_m, g->n_pad,
-                                                          g->roots[c], op == PF_OP_SYM && !g->unit_g, g->is_cotan ? g->cot_sqrtm : nullptr);
+        if (rec) pfl::launch<f_null_vector>(dim3(pf_blocks(g->n_pad)), dim3(PF_BLOCK), 0, st, pf_slot(g, c), g->label, g->rowptr, g->deg, g->perm_m, g->n_pad, g->roots[c], sym_w, weight);
+        else k_null_vector<<<pf_blocks(g->n_pad), PF_BLOCK, 0, st>>>(pf_slot(g, c), g->label, g->rowptr, g->deg, g->perm_m, g->n_pad, g->roots[c], sym_w, weight);
         PF_HIP(hipGetLastError());
         // normalised with the norm still on the device (the same 1 / sqrt as on the host: the same bits; a component has at
         // least two vertices, so the norm is positive) - no wait at the head of a solve
         PF_TRY(dots_device(g, c, c, 1, g->coef, nullptr, 0));
-        k_scale_rsqrt<<<pf_blocks(g->n_pad), PF_BLOCK, 0, st>>>(pf_slot(g, c), g->n_pad, g->coef);
+        if (rec) pfl::launch<f_scale_rsqrt>(dim3(pf_blocks(g->n_pad)), dim3(PF_BLOCK), 0, st, pf_slot(g, c), g->n_pad, g->coef);
+        else k_scale_rsqrt<<<pf_blocks(g->n_pad), PF_BLOCK, 0, st>>>(pf_slot(g, c), g->n_pad, g->coef);
         PF_HIP(hipGetLastError());
     }
     *n_locked = nc;

@@ -54,6 +54,7 @@
 #include <vector>
 
 #include "pf_internal.h"
+#include "pf_launch.h"
 
 namespace {
 
@@ -984,6 +985,15 @@ int64_t lds_need2(pf_graph* g) {
     return worst;
 }
 
+// every slot of a hand-off ring empty: the library's own fill kernel (a build that records its launches shares it with
+// the partner graph's)
+int ring_fill(hipStream_t st, double* ring, int64_t n_pad) {
+    const int64_t words = 8 * n_pad;  // [4][n_pad] doubles
+    pfl::launch<pfl::k_fill_words>(dim3((unsigned)((words + 1023) / 1024)), dim3(256), 0, st, reinterpret_cast<uint32_t*>(ring), words, RX_EMPTY32);
+    if (!pfl::tl_rec) PF_HIP(hipGetLastError());
+    return PF_OK;
+}
+
 // two steps per exchange for a single graph, if the graph and its sizes allow it: *done = 1 when launched
 int persist_cheb2(const pf_persist_args* a, int64_t grid, int* done, double* lds_bytes) {
     *done = 0;
@@ -1008,7 +1018,7 @@ int persist_cheb2(const pf_persist_args* a, int64_t grid, int* done, double* lds
         g->persist_epoch2 = 0;
     }
     if (g->persist_epoch2 != epoch) {
-        PF_HIP(hipMemsetD32Async((hipDeviceptr_t)g->persist_ring2, (int)RX_EMPTY32, (size_t)8 * (size_t)g->n_pad, st));
+        PF_TRY(ring_fill(st, g->persist_ring2, g->n_pad));
         g->persist_epoch2 = epoch;
         g->persist_phase2 = 0;
     }
@@ -1394,7 +1404,7 @@ int pf_persist_cheb(const pf_persist_args* a, const pf_persist_args* b, int* don
             g->persist_epoch = 0;
         }
         if (g->persist_epoch != epoch) {  // new, or left in an unknown state by an aborted launch: all slots empty
-            PF_HIP(hipMemsetD32Async((hipDeviceptr_t)g->persist_ring, (int)RX_EMPTY32, (size_t)8 * (size_t)g->n_pad, st));
+            PF_TRY(ring_fill(st, g->persist_ring, g->n_pad));
             g->persist_epoch = epoch;
             g->persist_phase = 0;
         }
@@ -1463,6 +1473,19 @@ int pf_persist_cheb(const pf_persist_args* a, const pf_persist_args* b, int* don
         if (lds_bytes) *lds_bytes += (double)in[q]->degree * (8.0 * (double)g->sell_entries + 8.0 * (double)g->n_pad + 8.0 * (double)g->px_gh_total);
     }
     *done = 1;
+    return PF_OK;
+}
+
+// The ring of a graph that the resident path can take, allocated and filled while the graph is still being built: `st`
+// is a stream of the build on which the fill overlaps other work (the side stream beside the labelling rounds); the first
+// filter application then finds the ring ready instead of filling it in front of its launch.  A wait that runs out in
+// between moves the abort epoch on, and pf_persist_cheb fills again.
+int pf_persist_ring_prefill(pf_graph* g, hipStream_t st) {
+    if (g->persist_ring || !persist_enabled() || g->win_rows <= 0 || g->n_pad / g->win_rows > 256) return PF_OK;
+    PF_HIP(pf_malloc(st, (void**)&g->persist_ring, sizeof(double) * 4 * (size_t)g->n_pad));
+    PF_TRY(ring_fill(st, g->persist_ring, g->n_pad));
+    g->persist_epoch = g_abort_epoch.load();
+    g->persist_phase = 0;
     return PF_OK;
 }
 
