@@ -229,12 +229,30 @@ typedef struct pf_persist_info {
     int32_t hold_ticks;        /* the hold-back of the latest resident launch, 10 ns ticks after a step began (0: fixed sleep) */
 } pf_persist_info;
 int pf_persist_state(pf_ctx* ctx /* nullable */, pf_persist_info* out);
+/* The per-graph window structures the resident kernels run on, for tests and diagnostics (read-only; no kernel of its own;
+ * no result of any solve changes).  Prepares the first-ring structures if the graph has not yet (and, with want_rings, the
+ * second-ring structures too - at once instead of at the graph's third single application), then reports
+ *   win_rows, n_windows   rows per window (1024 / 2048 / 4096) and n_pad / win_rows;
+ *   state                 1: covered by the resident kernel, 0: not (more than 256 windows, no stored entry, a window with
+ *                         more than 4096 outside entries or more than 1024 distinct outside rows);
+ *   state2                1: two steps per exchange possible, 0: not (windows of more than 1024 rows, a window with more
+ *                         than 512 outside rows or more than 1024 in both rings, an outside row in a SELL slice wider
+ *                         than 16, windows that do not hold each other's rows symmetrically), -1: not asked for yet;
+ *   ghosts[n_windows]     outside rows each window reads (one-way repairs included)   - written only if state == 1;
+ *   need[n_windows]       leading rows each window publishes (one download)           - written only if state == 1;
+ *   ghosts2[n_windows]    second-ring rows of each window                            - written only if state2 == 1.
+ * The three arrays may be NULL. */
+int pf_graph_window_info(pf_graph* g, int32_t want_rings, int32_t* win_rows, int32_t* n_windows, int32_t* state,
+                         int32_t* state2, int32_t* ghosts /* nullable */, int32_t* ghosts2 /* nullable */,
+                         int32_t* need /* nullable */);
 /* Test hook: the next n resident launches start with their abort flag raised (they give up at once and the
  * PF_E_PERSIST_TIMEOUT recovery runs).  Never needed in production. */
 int pf_persist_test_hook(int n_launches);
 int pf_cheb(pf_graph* g, int32_t op, int32_t src, int32_t dst, int32_t degree, double c, double e, double rho);
 /* Two independent recurrences (graphs a and b of one ctx) advanced in lockstep: step k of both in
- * ONE launch while both have steps left, the longer one alone afterwards. */
+ * ONE launch while both have steps left, the longer one alone afterwards.  Resident: one launch for the pair where both
+ * graphs are covered and fit together; a launch per graph where they are covered but have no joint kernel (windows of
+ * 2048+ rows); with a graph that is not covered (pf_graph_window_info: state 0) the pair streams as a pair. */
 int pf_cheb2(pf_graph* ga, int32_t op_a, int32_t src_a, int32_t dst_a, int32_t degree_a, double c_a, double e_a, double rho_a,
              pf_graph* gb, int32_t op_b, int32_t src_b, int32_t dst_b, int32_t degree_b, double c_b, double e_b, double rho_b);
 int pf_dots(pf_graph* g, int32_t w, int32_t first, int32_t count, double* out);  /* out[b] = <slot first+b, slot w> */

@@ -106,6 +106,7 @@ SIGNATURES = {
     "pf_persist_pair_halves": (C.c_int, [C.c_int]),
     "pf_persist_clock": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int]),
     "pf_persist_state": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "pf_graph_window_info": (C.c_int, [C.c_void_p, C.c_int32] + [C.POINTER(C.c_int32)] * 4 + [_i32p, _i32p, _i32p]),
     "pf_persist_test_hook": (C.c_int, [C.c_int]),
     "pf_cheb": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double]),
     "pf_cheb2": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double,
@@ -1382,6 +1383,21 @@ class DeviceLaplacian(object):
 
     def cheb(self, src, dst, degree, c, e, rho=1.0):
         _check(self._lib.pf_cheb(self._h, self.op, int(src), int(dst), int(degree), float(c), float(e), float(rho)))
+
+    def window_info(self, rings=False):
+        """`pf_graph_window_info`: the window structures of the resident filter kernel as a dict - win_rows, n_windows,
+        state (1: covered), state2 (1: two steps per exchange possible, -1: not asked for), and per window ghosts and
+        need (None unless state == 1) and ghosts2 (None unless state2 == 1).  rings=True builds the second-ring
+        structures now instead of at the graph's third single application.  Read-only otherwise."""
+        n_max = int(self.info.n_pad) // 1024 + 1
+        scalars = [C.c_int32() for _ in range(4)]
+        ghosts, ghosts2, need = (np.full(n_max, -1, np.int32) for _ in range(3))
+        _check(self._lib.pf_graph_window_info(self._h, int(bool(rings)), *[C.byref(s) for s in scalars],
+                                              ghosts.ctypes.data_as(_i32p), ghosts2.ctypes.data_as(_i32p), need.ctypes.data_as(_i32p)))
+        win_rows, nw, state, state2 = (int(s.value) for s in scalars)
+        return dict(win_rows=win_rows, n_windows=nw, state=state, state2=state2,
+                    ghosts=ghosts[:nw].copy() if state == 1 else None, need=need[:nw].copy() if state == 1 else None,
+                    ghosts2=ghosts2[:nw].copy() if state2 == 1 else None)
 
     def cheb2(self, req_self, other, req_other):
         """One lockstep filter application for two graphs of the same context:

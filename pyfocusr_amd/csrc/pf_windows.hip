@@ -555,6 +555,32 @@ int pf_window_rings_prepare(pf_graph* g) {
     return PF_OK;
 }
 
+// A read-only view of the window structures for tests and diagnostics: prepares them (the second ring as well if
+// want_rings - NOW, not at the graph's third single application) and copies out what the host already holds, plus one
+// download of px_need.  No kernel of its own.  Arrays of a structure that is not ready (state != 1) are left untouched.
+extern "C" int pf_graph_window_info(pf_graph* g, int32_t want_rings, int32_t* win_rows, int32_t* n_windows, int32_t* state,
+                                    int32_t* state2, int32_t* ghosts, int32_t* ghosts2, int32_t* need) {
+    PF_CHECK(g && win_rows && n_windows && state && state2, PF_E_ARG, "pf_graph_window_info: NULL argument");
+    PF_HIP(hipSetDevice(g->ctx->device));
+    PF_TRY(pf_window_slots_prepare(g));
+    if (want_rings) PF_TRY(pf_window_rings_prepare(g));
+    const int64_t nw = g->win_rows > 0 ? g->n_pad / g->win_rows : 0;
+    *win_rows = g->win_rows;
+    *n_windows = (int32_t)nw;
+    *state = g->px_state;
+    *state2 = g->px2_state;
+    if (g->px_state == 1) {
+        if (ghosts) std::copy(g->h_px_gh_cnt.begin(), g->h_px_gh_cnt.end(), ghosts);
+        if (need) {
+            hipStream_t st = g->ctx->stream;
+            PF_HIP(pfl::memcpy_async(st, need, g->px_need, sizeof(int32_t) * (size_t)nw, hipMemcpyDeviceToHost));
+            PF_HIP(pfl::sync(st));
+        }
+    }
+    if (g->px2_state == 1 && ghosts2) std::copy(g->h_px_gh_cnt2.begin(), g->h_px_gh_cnt2.end(), ghosts2);
+    return PF_OK;
+}
+
 void pf_window_slots_free(pf_graph* g) {
     window_rings_free(g);
     hipStream_t st = g->ctx->stream;

@@ -14,6 +14,7 @@ import pytest
 from scipy import sparse
 
 import _exact as ex
+import _window_ref
 from oracle import reference_port as orc
 
 pytestmark = pytest.mark.gpu
@@ -82,6 +83,12 @@ def graphs(hip, ctx):
             M = random_matrix(n, seed=n + 7 * symmetric, symmetric=symmetric)
             g = hip.DeviceLaplacian(matrix=(M.indptr, M.indices, M.data), ctx=ctx)
             g.M = M
+            # does the resident filter kernel cover this graph?  Random columns: a 1024-row window of a graph with thousands
+            # of rows reads more outside rows than its list holds, so only the graphs of a few dozen rows are covered and
+            # every filter application on the others runs one step per launch - exactly where the restatement says so
+            ref = _window_ref.analyse(M, rings=False)
+            g.resident_covered = g.window_info()["state"] == 1
+            assert g.resident_covered == ref.covered, (n, symmetric, int(ref.ghosts.max()), int(ref.candidates.max()))
             cache[key] = g
         return cache[key]
 
