@@ -850,6 +850,50 @@ int pf_mesh_topology(pf_ctx* ctx, const double* pts, int64_t n, const int32_t* f
                      int32_t* face_neighbours, int32_t* patch, uint8_t* flip, int32_t* boundary_loop, uint8_t* patch_orientable,
                      double* patch_volume, int64_t* report, double* device_ms);
 
+/* ---- uniform resampling of a triangle mesh by clustering (pf_remesh.hip; the reference has none: an extra) ---------
+ * pts [n][3] f64, faces [n_faces][3] i32 (triangles; n_faces may be 0: no dual), mass [n] f64 (>= 0, finite), all host.
+ * Start from seeds [m] (vertex indices, C[j] = pts[seeds[j]]) or from centroids_in [m][3]; exactly one of the two is given.
+ * tests/_remesh_ref.py states the definition in numpy and the device returns its bits.
+ *   d2         d2(i, j) = ((dx dx + dy dy) + dz dz), dx = pts[i][0] - C[j][0], ...: separate multiplies and adds, as the
+ *              farthest-point sampling and the nearest-neighbour search compute it
+ *   assign     label[i] = argmin_j d2(i, j) over all m centroids, the lowest j on ties: exact, whatever the search skips
+ *   start      the labels are the assignment to the starting centroids; with n_iter = 0 the call ends here, and with seeds
+ *              that are farthest-point samples the labels are that sampling's owner
+ *   iteration  update: the members of a cluster in ascending vertex index, cut into consecutive runs of 64; a run is summed
+ *              left to right from 0.0 (mass[i] * pts[i][x] for the numerator, mass[i] for the denominator), the run sums
+ *              are added left to right from 0.0, C[j] = num / den per coordinate.  A cluster whose den is 0 (no members, or
+ *              none with a mass) keeps its centroid.  Then assign.  changed[t] = labels that differ from the iteration
+ *              before; the loop stops after the first iteration with changed == 0, or after n_iter
+ *   rep, count [m]: the member with the smallest d2 to the cluster's centroid, the lowest vertex on ties, -1 without
+ *              members; the number of members
+ *   dual       integers only.  A face whose three labels are pairwise distinct is a candidate; it is rotated so that its
+ *              smallest label comes first (which keeps its orientation).  The candidates of one set of three labels become
+ *              one output triangle, in the orientation most of them have, on a tie in that of the candidate with the lowest
+ *              face index.  Output triangles are in lexicographic order of their sorted label triple, which is packed
+ *              into one 64-bit key of 3 x 21 bits: m <= 2^21 - 1.  out_faces [n_faces][3], face_src [n_faces] (the lowest
+ *              face index among the candidates) and votes [n_faces][2] (candidates for | against the orientation) are
+ *              capacities; report[1] rows are written
+ *   labels_in  [n] or NULL: the search of the first assignment starts every vertex at the centroid of this label.  It
+ *              decides nothing: any labels in 0 .. m - 1 give the same result.  With PF_CLUSTER_UPDATE_ONLY in flags
+ *              (labels_in given, n_iter = 1) they are the labels: one update without any assignment, so that `centroids`
+ *              is one update step from given labels; labels, rep, count and the dual then describe labels_in
+ *   changed    [n_iter] as capacity, report[0] entries are written (none with PF_CLUSTER_UPDATE_ONLY)
+ *   report [8] iterations run | output faces | candidate faces | cells of the last assignment's grid | distances evaluated
+ *              by all assignments | assignments | 0 | 0
+ *   device_ms  between the uploads and the last download (HIP events): it contains the host's reads of changed[t]
+ * Every output may be NULL.  One upload, the loop on device buffers with one word read by the host per iteration, one
+ * download.  An assignment bins the centroids into a uniform grid of about 2 m cells, starts every vertex at the centroid
+ * of its previous label and visits the cells around it ring by ring until a ring's lower bound, taken with slack, is
+ * strictly greater than the best distance found.  No floating-point atomics, no kernel waits for another block: two calls
+ * give the same bits in every output.  PF_E_ARG for a vertex id, seed or label out of range, n outside 1..2^31-1, m outside
+ * 1..n or above 2^21 - 1, 3 n_faces >= 2^31, n_iter < 0, a coordinate or mass that is not finite, a negative mass, both
+ * or neither of seeds and centroids_in, unknown flags; PF_E_DEGENERATE for a face that repeats a vertex. */
+#define PF_CLUSTER_UPDATE_ONLY 1u
+int pf_mesh_cluster(pf_ctx* ctx, const double* pts, int64_t n, const int32_t* faces, int64_t n_faces, const double* mass,
+                    const int64_t* seeds, int64_t m, int32_t n_iter, uint32_t flags, const double* centroids_in,
+                    const int32_t* labels_in, int32_t* labels, double* centroids, int32_t* rep, int32_t* count, int32_t* changed,
+                    int32_t* out_faces, int32_t* face_src, int32_t* votes, int64_t* report, double* device_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -221,6 +221,8 @@ SIGNATURES = {
                                 C.POINTER(C.c_uint8), _i64p, _f64p]),
     "pf_mesh_topology": (C.c_int, [C.c_void_p, _f64p, C.c_int64, _i32p, C.c_int64, C.c_uint32, _i32p, _i32p, C.POINTER(C.c_uint8),
                                    _i32p, C.POINTER(C.c_uint8), _f64p, _i64p, _f64p]),
+    "pf_mesh_cluster": (C.c_int, [C.c_void_p, _f64p, C.c_int64, _i32p, C.c_int64, _f64p, _i64p, C.c_int64, C.c_int32, C.c_uint32,
+                                  _f64p, _i32p, _i32p, _f64p, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p, _i64p, _f64p]),
 }
 
 _lib = None
@@ -263,6 +265,7 @@ PF_E_STATE = -4
 PF_E_PERSIST_TIMEOUT = -5
 PF_E_INTERNAL = -6
 PF_TOPOLOGY_OUTWARD = 1
+PF_CLUSTER_UPDATE_ONLY = 1
 
 
 class _PinnedBlock(object):
@@ -644,6 +647,60 @@ class Context(object):
         return {"face_neighbours": nbr, "patch": patch, "flip": flip.astype(bool), "boundary_loop": loop,
                 "patch_orientable": orientable[:P].astype(bool), "patch_volume": volume[:P].copy(), "report": report,
                 "device_ms": ms.value}
+
+    # ---- mesh resampling ---------------------------------------------------------------
+    def cluster_mesh(self, points, faces, mass, seeds=None, n_iter=20, centroids=None, labels=None, update_only=False):
+        """`pf_mesh_cluster`: Lloyd clusters of the vertices and their dual triangulation (points (n, 3) f64, faces (f, 3)
+        i32 or None, mass (n,) f64).  Start from `seeds` (m vertex indices) or from `centroids` (m, 3); `labels` (n,) only
+        warm-starts the first search, except with `update_only`, where one update step runs from them and nothing is
+        assigned.  A dict with `labels` (n,) int32, `centroids` (m, 3), `rep`, `count` (m,) int32, `changed` (n_iter_run,)
+        int32, `n_iter_run`, `faces` (k, 3) int32, `face_src` (k,) int32, `votes` (k, 2) int32, `n_candidate_faces`,
+        `report` (8,) int64 and `device_ms`.  Only the shapes are checked here; the library refuses indices out of range,
+        non-finite input, negative masses and m above 2^21 - 1 (PF_E_ARG) and a face that repeats a vertex
+        (PF_E_DEGENERATE)."""
+        pts = _c_f64(points)
+        if pts.ndim != 2 or pts.shape[1] != 3:
+            raise ValueError("points must be (n, 3)")
+        n = pts.shape[0]
+        f = np.zeros((0, 3), dtype=np.int32) if faces is None else np.ascontiguousarray(faces, dtype=np.int32)
+        if f.ndim != 2 or f.shape[1] != 3:
+            raise ValueError("faces must be (f, 3)")
+        mass = _c_f64(mass, (n,))
+        if (seeds is None) == (centroids is None):
+            raise ValueError("give either seeds or centroids")
+        sel = cen = lab = None
+        if seeds is not None:
+            sel = np.ascontiguousarray(seeds, dtype=np.int64)
+            if sel.ndim != 1:
+                raise ValueError("seeds must be a vector of vertex indices")
+            m = sel.shape[0]
+        else:
+            cen = _c_f64(centroids)
+            if cen.ndim != 2 or cen.shape[1] != 3:
+                raise ValueError("centroids must be (m, 3)")
+            m = cen.shape[0]
+        if labels is not None:
+            lab = np.ascontiguousarray(labels, dtype=np.int32)
+            if lab.shape != (n,):
+                raise ValueError("labels must be (n,)")
+        n_iter, k = int(n_iter), f.shape[0]
+        out_labels, out_c = np.empty(n, dtype=np.int32), np.empty((m, 3))
+        rep, count = np.empty(m, dtype=np.int32), np.empty(m, dtype=np.int32)
+        changed = np.zeros(max(n_iter, 0), dtype=np.int32)
+        out_f, src, votes = np.empty((k, 3), dtype=np.int32), np.empty(k, dtype=np.int32), np.empty((k, 2), dtype=np.int32)
+        report = np.zeros(8, dtype=np.int64)
+        ms = C.c_double(0.0)
+        _check(self._lib.pf_mesh_cluster(
+            self._h, _f64(pts), n, f.ctypes.data_as(_i32p) if k else None, k, _f64(mass),
+            None if sel is None else sel.ctypes.data_as(_i64p), m, n_iter, PF_CLUSTER_UPDATE_ONLY if update_only else 0,
+            None if cen is None else _f64(cen), None if lab is None else lab.ctypes.data_as(_i32p),
+            out_labels.ctypes.data_as(_i32p), _f64(out_c), rep.ctypes.data_as(_i32p), count.ctypes.data_as(_i32p),
+            changed.ctypes.data_as(_i32p), out_f.ctypes.data_as(_i32p), src.ctypes.data_as(_i32p), votes.ctypes.data_as(_i32p),
+            report.ctypes.data_as(_i64p), C.byref(ms)))
+        run, kept = (0 if update_only else int(report[0])), int(report[1])
+        return {"labels": out_labels, "centroids": out_c, "rep": rep, "count": count, "changed": changed[:run].copy(),
+                "n_iter_run": int(report[0]), "faces": out_f[:kept].copy(), "face_src": src[:kept].copy(),
+                "votes": votes[:kept].copy(), "n_candidate_faces": int(report[2]), "report": report, "device_ms": ms.value}
 
     def assign(self, rows, cols, return_duals=False):
         """Optimal one-to-one assignment on Euclidean costs (`pf_assign`): col_of_row (int64, n_rows) minimising
