@@ -3,36 +3,24 @@
 // curvature tensor with its principal curvatures and directions, the unit vertex normal and a boundary mask.  The
 // definitions are in include/pyfocusr_hip.h; tests/_curvature_ref.py restates them in numpy.
 //
-// The structure is the one of the signed distances (pf_surface.hip: k_tri_normals, k_edge_normals, k_vertex_normals):
-// half-edge h = 3 t + j leaves corner j of triangle t; one stable radix sort of the half-edges by their edge's key
-// (min << nb | max) makes the half-edges of an edge a run in triangle order, a second one by the corner's vertex makes
-// the half-edges that leave a vertex a run in ascending h.  No device code crosses translation units, so the triangle
-// pass is written here again, with the areas it needs in addition.
+// The structure is the half-edge pass of pf_halfedge.h, as in the signed distances of pf_surface.hip: the half-edges
+// sorted by their edge's key are walked one run per edge, sorted by their corner's vertex one run per vertex.  The
+// triangle pass, the run walks and the edge counts are that header's; the kernels here add what is curvature's own.
 //   k_curv_triangles  one thread per triangle: unit normal, corner angles, area; keys and values of both sorts
 //   k_curv_edges      one thread per run of equal edge keys: |e| beta_e and the unit edge vector, written to each of the
 //                     run's half-edges; whether the edge is a boundary edge; the four edge counts
 //   k_curv_vertices   one thread per vertex over its run: every sum in ascending h, then the derived fields in registers
 // Every floating-point sum has a fixed order and the counts are integer atomics: two calls give the same bits.
 // Arithmetic: separate multiplies and adds (-ffp-contract=off), dot products left to right.
-#include <hipcub/hipcub.hpp>
-
 #include <cmath>
 
-#include "pf_internal.h"
+#include "pf_halfedge.h"
 
 namespace {
 
 constexpr double PF_TWO_PI = 6.283185307179586;
 
-__device__ __forceinline__ double cdot3(const double a[3], const double b[3]) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
-__device__ __forceinline__ void ccross3(const double a[3], const double b[3], double c[3]) {
-    c[0] = a[1] * b[2] - a[2] * b[1];
-    c[1] = a[2] * b[0] - a[0] * b[2];
-    c[2] = a[0] * b[1] - a[1] * b[0];
-}
-
-// per triangle: unit normal, corner angles atan2(|e1 x e2|, e1 . e2) and area, all zero for a zero-area or non-finite
-// triangle; per half-edge h = 3t + j (corner j -> corner j+1): the key of its edge, its corner's vertex, and h itself
+// one thread per triangle: he_triangle, with the area
 __global__ __launch_bounds__(PF_BLOCK) void k_curv_triangles(const double* __restrict__ pts, const int32_t* __restrict__ faces,
                                                              int64_t n_tri, int nb, double* __restrict__ tnrm,
                                                              double* __restrict__ tang, double* __restrict__ tarea,
@@ -41,41 +29,14 @@ __global__ __launch_bounds__(PF_BLOCK) void k_curv_triangles(const double* __res
     const int64_t t = (int64_t)blockIdx.x * PF_BLOCK + threadIdx.x;
     if (t >= n_tri) return;
     const int32_t v[3] = {faces[3 * t], faces[3 * t + 1], faces[3 * t + 2]};
-    double x[3][3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c)
-#pragma unroll
-        for (int a = 0; a < 3; ++a) x[c][a] = pts[3 * (int64_t)v[c] + a];
-    const double u[3] = {x[1][0] - x[0][0], x[1][1] - x[0][1], x[1][2] - x[0][2]};
-    const double w[3] = {x[2][0] - x[0][0], x[2][1] - x[0][1], x[2][2] - x[0][2]};
-    double cr[3];
-    ccross3(u, w, cr);
-    const double len = sqrt(cdot3(cr, cr));
-    const bool area = len > 0.0 && std::isfinite(len);
-#pragma unroll
-    for (int a = 0; a < 3; ++a) tnrm[3 * t + a] = area ? cr[a] / len : 0.0;
-    tarea[t] = area ? len / 2.0 : 0.0;
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        const int j1 = j == 2 ? 0 : j + 1, j2 = j == 0 ? 2 : j - 1;
-        const double e1[3] = {x[j1][0] - x[j][0], x[j1][1] - x[j][1], x[j1][2] - x[j][2]};
-        const double e2[3] = {x[j2][0] - x[j][0], x[j2][1] - x[j][1], x[j2][2] - x[j][2]};
-        double c[3];
-        ccross3(e1, e2, c);
-        tang[3 * t + j] = area ? atan2(sqrt(cdot3(c, c)), cdot3(e1, e2)) : 0.0;
-        const unsigned lo = (unsigned)min(v[j], v[j1]), hi = (unsigned)max(v[j], v[j1]);
-        ekey[3 * t + j] = ((unsigned long long)lo << nb) | hi;
-        vkey[3 * t + j] = (unsigned)v[j];
-        hval[3 * t + j] = (int32_t)(3 * t + j);
-    }
+    he_triangle(pts, v, t, nb, tnrm, tang, tarea, ekey, vkey, hval);
 }
 
 // One thread per edge: the first half-edge of each run of equal keys; a run is in ascending h, the sort being stable, so
 // its first half-edge belongs to the lower-numbered triangle f.  For an edge of exactly two triangles with areas that
 // traverse it in opposite directions, with f going a -> b: e = (x_b - x_a) / |x_b - x_a| and
 // beta = atan2((n_f x n_g) . e, n_f . n_g); every other edge has beta = 0 and e = 0.  wb = |e| beta and e go to each
-// half-edge of the run, bnd says whether the run is a single half-edge.  counts: edges | boundary | non-manifold |
-// inconsistent, as k_edge_normals of pf_surface.hip counts them.
+// half-edge of the run, bnd says whether the run is a single half-edge.  counts: he_count_edge.
 __global__ __launch_bounds__(PF_BLOCK) void k_curv_edges(const unsigned long long* __restrict__ ekey, const int32_t* __restrict__ hedge,
                                                          int64_t n_half, const double* __restrict__ pts,
                                                          const int32_t* __restrict__ faces, const double* __restrict__ tnrm,
@@ -83,38 +44,34 @@ __global__ __launch_bounds__(PF_BLOCK) void k_curv_edges(const unsigned long lon
                                                          double* __restrict__ evec, uint8_t* __restrict__ bnd,
                                                          unsigned long long* __restrict__ counts) {
     const int64_t i = (int64_t)blockIdx.x * PF_BLOCK + threadIdx.x;
-    if (i >= n_half || (i > 0 && ekey[i - 1] == ekey[i])) return;
-    const unsigned long long key = ekey[i];
-    int64_t end = i + 1;
-    while (end < n_half && ekey[end] == key) ++end;
+    const int64_t end = he_run_end(ekey, n_half, i);
+    if (end == i) return;
     const int64_t m = end - i;
     double w = 0.0, e[3] = {0.0, 0.0, 0.0};
-    atomicAdd(&counts[0], 1ull);  // integer counts: the same on every run
-    if (m == 1) atomicAdd(&counts[1], 1ull);
-    if (m > 2) atomicAdd(&counts[2], 1ull);
+    bool fwd0 = false, fwd1 = false;
     if (m == 2) {
         const int32_t h0 = hedge[i], h1 = hedge[i + 1];
         const int64_t t0 = h0 / 3, t1 = h1 / 3;
         const int j0 = h0 % 3, j1 = h1 % 3;
-        const int32_t a0 = faces[3 * t0 + j0], b0 = faces[3 * t0 + (j0 == 2 ? 0 : j0 + 1)];
-        const int32_t a1 = faces[3 * t1 + j1], b1 = faces[3 * t1 + (j1 == 2 ? 0 : j1 + 1)];
-        if ((a0 < b0) == (a1 < b1)) {
-            atomicAdd(&counts[3], 1ull);
-        } else if (tarea[t0] > 0.0 && tarea[t1] > 0.0) {
+        const int32_t a0 = faces[3 * t0 + j0], b0 = faces[3 * t0 + he_next(j0)];
+        const int32_t a1 = faces[3 * t1 + j1], b1 = faces[3 * t1 + he_next(j1)];
+        fwd0 = a0 < b0, fwd1 = a1 < b1;
+        if (fwd0 != fwd1 && tarea[t0] > 0.0 && tarea[t1] > 0.0) {
             const double d[3] = {pts[3 * (int64_t)b0] - pts[3 * (int64_t)a0], pts[3 * (int64_t)b0 + 1] - pts[3 * (int64_t)a0 + 1],
                                  pts[3 * (int64_t)b0 + 2] - pts[3 * (int64_t)a0 + 2]};
-            const double len = sqrt(cdot3(d, d));
+            const double len = sqrt(dot3(d, d));
             if (len > 0.0 && std::isfinite(len)) {
                 const double nf[3] = {tnrm[3 * t0], tnrm[3 * t0 + 1], tnrm[3 * t0 + 2]};
                 const double ng[3] = {tnrm[3 * t1], tnrm[3 * t1 + 1], tnrm[3 * t1 + 2]};
                 double c[3];
-                ccross3(nf, ng, c);
+                cross3(nf, ng, c);
 #pragma unroll
                 for (int a = 0; a < 3; ++a) e[a] = d[a] / len;
-                w = len * atan2(cdot3(c, e), cdot3(nf, ng));
+                w = len * atan2(dot3(c, e), dot3(nf, ng));
             }
         }
     }
+    he_count_edge(counts, m, fwd0, fwd1);
     for (int64_t k = i; k < end; ++k) {
         const int64_t h = hedge[k];
         wb[h] = w;
@@ -148,12 +105,7 @@ __global__ __launch_bounds__(PF_BLOCK) void k_curv_vertices(const unsigned* __re
                                                             uint8_t* __restrict__ out_bnd, unsigned long long* __restrict__ counts) {
     const int64_t v = (int64_t)blockIdx.x * PF_BLOCK + threadIdx.x;
     if (v >= n_points) return;
-    int64_t lo = 0, hi = n_half;  // first position with key >= v
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (vkey[mid] < (unsigned)v) lo = mid + 1;
-        else hi = mid;
-    }
+    int64_t lo = he_vertex_run(vkey, n_half, v);
     double asum = 0.0, angsum = 0.0, hsum = 0.0, ns[3] = {0.0, 0.0, 0.0}, T[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     bool boundary = false;
     for (; lo < n_half && vkey[lo] == (unsigned)v; ++lo) {
@@ -168,7 +120,7 @@ __global__ __launch_bounds__(PF_BLOCK) void k_curv_vertices(const unsigned* __re
         for (int a = 0; a < 3; ++a) ns[a] += ang * tnrm[3 * t + a];
         T[0] += (c * e[0]) * e[0], T[1] += (c * e[1]) * e[1], T[2] += (c * e[2]) * e[2];
         T[3] += (c * e[0]) * e[1], T[4] += (c * e[0]) * e[2], T[5] += (c * e[1]) * e[2];
-        boundary = boundary || bnd[h] || bnd[3 * t + (j == 0 ? 2 : j - 1)];
+        boundary = boundary || bnd[h] || bnd[3 * t + he_prev(j)];
     }
     const double A = asum / 3.0;
     const bool have = A > 0.0;
@@ -185,7 +137,7 @@ __global__ __launch_bounds__(PF_BLOCK) void k_curv_vertices(const unsigned* __re
         }
         const double s = sqrt(disc);
         k[0] = H - s, k[1] = H + s;
-        const double nl = sqrt(cdot3(ns, ns));
+        const double nl = sqrt(dot3(ns, ns));
         if (nl > 0.0 && std::isfinite(nl)) {
 #pragma unroll
             for (int a = 0; a < 3; ++a) n[a] = ns[a] / nl;
@@ -194,16 +146,16 @@ __global__ __launch_bounds__(PF_BLOCK) void k_curv_vertices(const unsigned* __re
             if (fabs(n[2]) < fabs(n[ax])) ax = 2;
             const double na = ax == 0 ? n[0] : (ax == 1 ? n[1] : n[2]);
             double t1[3] = {(ax == 0 ? 1.0 : 0.0) - na * n[0], (ax == 1 ? 1.0 : 0.0) - na * n[1], (ax == 2 ? 1.0 : 0.0) - na * n[2]};
-            const double tl = sqrt(cdot3(t1, t1));
+            const double tl = sqrt(dot3(t1, t1));
 #pragma unroll
             for (int a = 0; a < 3; ++a) t1[a] = t1[a] / tl;
             double t2[3];
-            ccross3(n, t1, t2);
+            cross3(n, t1, t2);
             const double Tt1[3] = {T[0] * t1[0] + T[3] * t1[1] + T[4] * t1[2], T[3] * t1[0] + T[1] * t1[1] + T[5] * t1[2],
                                    T[4] * t1[0] + T[5] * t1[1] + T[2] * t1[2]};
             const double Tt2[3] = {T[0] * t2[0] + T[3] * t2[1] + T[4] * t2[2], T[3] * t2[0] + T[1] * t2[1] + T[5] * t2[2],
                                    T[4] * t2[0] + T[5] * t2[1] + T[2] * t2[2]};
-            const double s11 = cdot3(t1, Tt1), s12 = cdot3(t2, Tt1), s22 = cdot3(t2, Tt2);
+            const double s11 = dot3(t1, Tt1), s12 = dot3(t2, Tt1), s22 = dot3(t2, Tt2);
             const double mid = (s11 + s22) / 2.0, dif = (s11 - s22) / 2.0;
             const double r = sqrt(dif * dif + s12 * s12);
             const double theta = 0.5 * atan2(2.0 * s12, s11 - s22);
@@ -211,7 +163,7 @@ __global__ __launch_bounds__(PF_BLOCK) void k_curv_vertices(const unsigned* __re
             k[2] = mid - r, k[3] = mid + r;
             double wv[3] = {ct * t1[0] + st * t2[0], ct * t1[1] + st * t2[1], ct * t1[2] + st * t2[2]};
             double dm[3];
-            ccross3(n, wv, dm);
+            cross3(n, wv, dm);
             sign_rule(wv);
             sign_rule(dm);
 #pragma unroll
@@ -249,23 +201,11 @@ extern "C" int pf_curvatures(pf_ctx* ctx, const double* pts, int64_t n, const in
     PF_CHECK(n_faces > 0 && 3 * n_faces < ((int64_t)1 << 31), PF_E_ARG, "pf_curvatures: %lld faces out of range (3 n_faces < 2^31)",
              (long long)n_faces);
     const int64_t T = n_faces, H = 3 * T;
-    for (int64_t i = 0; i < H; ++i)
-        PF_CHECK(faces[i] >= 0 && faces[i] < n, PF_E_ARG, "pf_curvatures: face %lld references vertex %d of %lld", (long long)(i / 3),
-                 faces[i], (long long)n);
-    int nb = 1;  // bits of a vertex index
-    while (nb < 31 && ((int64_t)1 << nb) < n) ++nb;
+    PF_TRY(pf_check_faces("pf_curvatures", faces, T, 3, n, false));
+    const int nb = pf_index_bits(n);  // bits of a vertex index
     PF_HIP(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    if (device_ms) {
-        PF_HIP(hipEventCreate(&ev[0]));
-        if (hipEventCreate(&ev[1]) != hipSuccess) {
-            hipEventDestroy(ev[0]);
-            (void)hipGetLastError();
-            pf_set_error("pf_curvatures: hipEventCreate failed");
-            return PF_E_HIP;
-        }
-    }
+    StreamTimer timer(device_ms != nullptr);
     unsigned long long counts[5] = {0, 0, 0, 0, 0};
     hipError_t err;
     {
@@ -291,29 +231,25 @@ extern "C" int pf_curvatures(pf_ctx* ctx, const double* pts, int64_t n, const in
         sc.upload(d_pts, pts, 3 * n);
         sc.upload(d_faces, faces, H);
         sc.zero(cnt, sizeof(unsigned long long) * 5);
-        if (sc.ok() && device_ms) sc.note(hipEventRecord(ev[0], st));
+        timer.start(sc);
         if (sc.ok()) {
             k_curv_triangles<<<pf_blocks(T), PF_BLOCK, 0, st>>>(d_pts, d_faces, T, nb, tnrm, tang, tarea, ek0, vk0, h0);
             sc.launched();
         }
         // both sorts are stable and start from half-edge order: equal keys stay in ascending h.  They share the value
-        // arrays and the temporary, so the vertex sort runs after k_curv_edges has read the edge sort's h1.
-        size_t need_e = 0, need_v = 0;
-        if (sc.ok()) sc.note(hipcub::DeviceRadixSort::SortPairs(nullptr, need_e, ek0, ek1, h0, h1, (int)H, 0, 2 * nb, st));
-        if (sc.ok()) sc.note(hipcub::DeviceRadixSort::SortPairs(nullptr, need_v, vk0, vk1, h0, h1, (int)H, 0, nb, st));
-        void* tmp = sc.get<char>(need_e > need_v ? need_e : need_v);
-        if (sc.ok()) sc.note(hipcub::DeviceRadixSort::SortPairs(tmp, need_e, ek0, ek1, h0, h1, (int)H, 0, 2 * nb, st));
+        // arrays, and the stream runs the vertex sort after k_curv_edges has read the edge sort's h1.
+        pf_sort_pairs(sc, ek0, ek1, h0, h1, H, 2 * nb);
         if (sc.ok()) {
             k_curv_edges<<<pf_blocks(H), PF_BLOCK, 0, st>>>(ek1, h1, H, d_pts, d_faces, tnrm, tarea, wb, evec, bnd, cnt);
             sc.launched();
         }
-        if (sc.ok()) sc.note(hipcub::DeviceRadixSort::SortPairs(tmp, need_v, vk0, vk1, h0, h1, (int)H, 0, nb, st));
+        pf_sort_pairs(sc, vk0, vk1, h0, h1, H, nb);
         if (sc.ok()) {
             k_curv_vertices<<<pf_blocks(n), PF_BLOCK, 0, st>>>(vk1, h1, H, n, tnrm, tang, tarea, wb, evec, bnd, o_area, o_gauss, o_mean,
                                                                o_tensor, o_k, o_dirs, o_nrm, o_bnd, cnt);
             sc.launched();
         }
-        if (sc.ok() && device_ms) sc.note(hipEventRecord(ev[1], st));
+        timer.stop(sc);
         sc.download(out_area, o_area, n);
         sc.download(out_gauss, o_gauss, n);
         sc.download(out_mean, o_mean, n);
@@ -324,19 +260,10 @@ extern "C" int pf_curvatures(pf_ctx* ctx, const double* pts, int64_t n, const in
         sc.download(out_boundary, o_bnd, n);
         sc.download(counts, cnt, 5);
         sc.sync();
-        if (sc.ok() && device_ms) {
-            float ms = 0.0f;
-            sc.note(hipEventElapsedTime(&ms, ev[0], ev[1]));
-            *device_ms = (double)ms;
-        }
+        timer.read(sc, device_ms);
         err = sc.err;
     }
-    if (device_ms) hipEventDestroy(ev[0]), hipEventDestroy(ev[1]);
-    if (err != hipSuccess) {
-        (void)hipGetLastError();
-        pf_set_error("pf_curvatures: %s", hipGetErrorString(err));
-        return PF_E_HIP;
-    }
+    if (err != hipSuccess) return pf_hip_failed("pf_curvatures", err);
     if (topology)
         for (int k = 0; k < 5; ++k) topology[k] = (int64_t)counts[k];
     return PF_OK;

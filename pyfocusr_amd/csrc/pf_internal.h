@@ -67,6 +67,36 @@ constexpr int PF_WS_TMPS = 4;      // temporaries behind the workspace slots (Ch
 // blocks of PF_BLOCK threads that cover n items
 inline unsigned pf_blocks(int64_t n) { return (unsigned)((n + PF_BLOCK - 1) / PF_BLOCK); }
 
+// bits of an index below count: the least b >= 1 with 2^b >= count
+inline int pf_index_bits(int64_t count) {
+    int b = 1;
+    while (b < 62 && ((int64_t)1 << b) < count) ++b;
+    return b;
+}
+
+// Every vertex of n_faces faces of vpf vertices lies in 0 .. n - 1 (else PF_E_ARG) and, with distinct (triangles only),
+// no face repeats one (else PF_E_DEGENERATE); the first face that fails is the one reported, with its first failure,
+// under the name fn of the calling entry point.  (One flat loop without distinct: a third faster than a loop per face.)
+inline int pf_check_faces(const char* fn, const int32_t* faces, int64_t n_faces, int32_t vpf, int64_t n, bool distinct) {
+    for (int64_t i = 0; !distinct && i < n_faces * vpf; ++i)
+        PF_CHECK(faces[i] >= 0 && faces[i] < n, PF_E_ARG, "%s: face %lld references vertex %d of %lld", fn, (long long)(i / vpf),
+                 faces[i], (long long)n);
+    for (int64_t t = 0; distinct && t < n_faces; ++t) {
+        const int32_t* f = faces + 3 * t;
+        for (int j = 0; j < 3; ++j)
+            PF_CHECK(f[j] >= 0 && f[j] < n, PF_E_ARG, "%s: face %lld references vertex %d of %lld", fn, (long long)t, f[j], (long long)n);
+        PF_CHECK(f[0] != f[1] && f[1] != f[2] && f[0] != f[2], PF_E_DEGENERATE, "%s: face %lld repeats a vertex", fn, (long long)t);
+    }
+    return PF_OK;
+}
+
+// the end of an entry point fn whose stream work failed with e: the sticky error is cleared, "fn: what" is the message
+inline int pf_hip_failed(const char* fn, hipError_t e) {
+    (void)hipGetLastError();
+    pf_set_error("%s: %s", fn, hipGetErrorString(e));
+    return PF_E_HIP;
+}
+
 // device buffers of the box hierarchy of pf_knn_tree.hip (1-NN for deep coordinates); they grow and stay with the ctx
 struct pf_knn_tree {
     DevBuf<double> pts;         // [n_leaf][d][64] leaves, coordinate-major
@@ -360,10 +390,6 @@ KeyBox pf_key_box(const double* pts, int64_t n, int32_t d, bool finite_only);
 // Keys, values and the sort's temporary are scratch of sc; NULL after a failure.
 const int32_t* pf_surface_morton_order(Scratch& sc, const double* d_pts, int32_t d, const int32_t* d_faces, int32_t vpf, int64_t n,
                                        const KeyBox& bb);
-// The stable radix sort of n (unsigned key, int32 value) pairs on key bits [0, end_bit), queued on sc's stream; its
-// temporary is scratch of sc.  Sorts the Morton orders of the surfaces and of the k-NN box hierarchy, and the cells of
-// the k-NN grid's large point sets.
-void pf_sort_pairs(Scratch& sc, const unsigned* k_in, unsigned* k_out, const int32_t* v_in, int32_t* v_out, int64_t n, int end_bit);
 // keys -> stable sort -> gather -> chunk boxes -> super boxes, queued on sc's stream; h owns its four buffers from here on,
 // also after a failure (sc.err)
 void pf_tri_hierarchy_build(Scratch& sc, TriHierarchy& h, const double* d_pts, int32_t d, const int32_t* d_faces, int64_t n_faces,
@@ -387,6 +413,18 @@ static inline double* pf_tmp(pf_graph* g, int which) { return g->ws + (int64_t)(
 // pf_graph_build_cotan): numeric symmetry, row statistics, component labels, the solver's renumbering (along the Morton
 // curve of d_pts when given), the SELL-64 storage; closes the ctx's build timer (ev0 recorded by the caller) and waits.
 int pf_graph_finish_general(pf_graph* g, const double* d_pts);
+
+// pf_sort.hip: the stable radix sort of n < 2^31 (key, 32-bit value) pairs on key bits [0, end_bit), queued on sc's stream;
+// its temporary is scratch of sc, and it does nothing once sc has failed.  Sorts the Morton orders of the surfaces and of
+// the k-NN box hierarchy, the cells of the k-NN grid's large point sets, and the half-edges, patches, loop ends, cells,
+// labels and dual faces of the mesh units.  Values are only moved, so unsigned ones go through the same instance.
+void pf_sort_pairs(Scratch& sc, const unsigned* k_in, unsigned* k_out, const int32_t* v_in, int32_t* v_out, int64_t n, int end_bit);
+void pf_sort_pairs(Scratch& sc, const unsigned long long* k_in, unsigned long long* k_out, const int32_t* v_in, int32_t* v_out,
+                   int64_t n, int end_bit);
+inline void pf_sort_pairs(Scratch& sc, const unsigned long long* k_in, unsigned long long* k_out, const unsigned* v_in, unsigned* v_out,
+                          int64_t n, int end_bit) {
+    pf_sort_pairs(sc, k_in, k_out, (const int32_t*)v_in, (int32_t*)v_out, n, end_bit);
+}
 
 // pf_scan.hip
 int pf_exclusive_scan_i32(hipStream_t st, const int32_t* in, int32_t* out, int64_t n);

@@ -350,12 +350,6 @@ __global__ __launch_bounds__(PF_BLOCK) void k_dual_emit(const u64* __restrict__ 
     votes[2 * o] = swapped ? n1 : n0, votes[2 * o + 1] = swapped ? n0 : n1;
 }
 
-int bits_for(int64_t count) {  // the least b >= 1 with 2^b >= count
-    int b = 1;
-    while (b < 62 && ((int64_t)1 << b) < count) ++b;
-    return b;
-}
-
 int32_t root_up(int64_t value, int k, int32_t cap) {  // the least g >= 1 with g^k >= value, at most cap
     int32_t g = 1;
     for (;;) {
@@ -401,29 +395,14 @@ extern "C" int pf_mesh_cluster(pf_ctx* ctx, const double* pts, int64_t n, const 
             PF_CHECK(std::isfinite(centroids_in[3 * j + x]), PF_E_ARG, "pf_mesh_cluster: a coordinate of centroid %lld is not finite",
                      (long long)j);
     }
-    for (int64_t t = 0; t < T; ++t) {
-        const int32_t* f = faces + 3 * t;
-        for (int j = 0; j < 3; ++j)
-            PF_CHECK(f[j] >= 0 && f[j] < n, PF_E_ARG, "pf_mesh_cluster: face %lld references vertex %d of %lld", (long long)t, f[j],
-                     (long long)n);
-        PF_CHECK(f[0] != f[1] && f[1] != f[2] && f[0] != f[2], PF_E_DEGENERATE, "pf_mesh_cluster: face %lld repeats a vertex", (long long)t);
-    }
+    PF_TRY(pf_check_faces("pf_mesh_cluster", faces, T, 3, n, true));
     // the grid: about 2 m cells; gk^k and every refinement the device accepts stay within the capacity
     const int64_t target = 2 * m, capacity = 8 * m + 64;
     const int32_t g1 = root_up(target, 1, RM_AXIS_CELLS), g2 = root_up(target, 2, 1024), g3 = root_up(target, 3, 128);
-    const int cell_bits = bits_for(capacity), label_bits = bits_for(m);
+    const int cell_bits = pf_index_bits(capacity), label_bits = pf_index_bits(m);
     PF_HIP(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    if (device_ms) {
-        PF_HIP(hipEventCreate(&ev[0]));
-        if (hipEventCreate(&ev[1]) != hipSuccess) {
-            hipEventDestroy(ev[0]);
-            (void)hipGetLastError();
-            pf_set_error("pf_mesh_cluster: hipEventCreate failed");
-            return PF_E_HIP;
-        }
-    }
+    StreamTimer timer(device_ms != nullptr);
     std::vector<int32_t> h_changed((size_t)n_iter + 1, 0);
     int32_t iters = 0, passes = 0, h_counts[2] = {0, 0};  // output faces | candidates
     u64 h_evals = 0;
@@ -451,11 +430,6 @@ extern "C" int pf_mesh_cluster(pf_ctx* ctx, const double* pts, int64_t n, const 
         int32_t* d_counts = (int32_t*)(d_evals + 1);  // output faces | candidates
         u64 *d2_bits = sc.get<u64>(n), *rep_d2 = sc.get<u64>(m);
         int32_t *d_rep = sc.get<int32_t>(m), *d_count = sc.get<int32_t>(m);
-        size_t need_c = 0, need_l = 0;
-        if (sc.ok()) sc.note(hipcub::DeviceRadixSort::SortPairs(nullptr, need_c, cell0, cell1, cidx0, cidx1, (int)m, 0, cell_bits, st));
-        if (sc.ok())
-            sc.note(hipcub::DeviceRadixSort::SortPairs(nullptr, need_l, (unsigned*)d_lab, lkey, iota, member, (int)n, 0, label_bits, st));
-        void *tmp_c = sc.get<char>(need_c), *tmp_l = sc.get<char>(need_l);
         sc.upload(d_P, pts, 3 * n);
         sc.upload(d_mass, mass, n);
         if (T) sc.upload(d_faces, faces, 3 * T);
@@ -465,7 +439,7 @@ extern "C" int pf_mesh_cluster(pf_ctx* ctx, const double* pts, int64_t n, const 
         sc.zero(words, sizeof(u64) * ((size_t)(n_iter + 2) / 2 + 2));
         sc.zero(d_count, sizeof(int32_t) * m);
         if (sc.ok()) sc.note(hipMemsetAsync(rep_d2, 0xff, sizeof(u64) * m, st));
-        if (sc.ok() && device_ms) sc.note(hipEventRecord(ev[0], st));
+        timer.start(sc);
         if (sc.ok()) {
             if (seeds) k_seed_centroids<<<pf_blocks(m), PF_BLOCK, 0, st>>>(d_P, d_seeds, m, d_C);
             if (!labels_in) k_iota<<<pf_blocks(n), PF_BLOCK, 0, st>>>(d_lab, n, 0, false);
@@ -479,7 +453,7 @@ extern "C" int pf_mesh_cluster(pf_ctx* ctx, const double* pts, int64_t n, const 
             k_grid_spec<<<1, PF_BLOCK, 0, st>>>(d_C, m, g1, g2, g3, target, capacity, d_spec);
             k_cell_ids<<<pf_blocks(m), PF_BLOCK, 0, st>>>(d_C, m, d_spec, cell0, cidx0);
             sc.launched();
-            if (sc.ok()) sc.note(hipcub::DeviceRadixSort::SortPairs(tmp_c, need_c, cell0, cell1, cidx0, cidx1, (int)m, 0, cell_bits, st));
+            pf_sort_pairs(sc, cell0, cell1, cidx0, cidx1, m, cell_bits);
             if (!sc.ok()) return;
             k_cell_starts<<<pf_blocks(m), PF_BLOCK, 0, st>>>(cell1, cidx1, m, d_C, d_spec, cstart, sorted);
             k_assign<<<pf_blocks(n), PF_BLOCK, 0, st>>>(d_P, n, d_C, d_spec, cstart, sorted, d_lab, d_changed + slot, d_evals);
@@ -487,8 +461,7 @@ extern "C" int pf_mesh_cluster(pf_ctx* ctx, const double* pts, int64_t n, const 
             ++passes;
         };
         auto update = [&]() {
-            if (sc.ok())
-                sc.note(hipcub::DeviceRadixSort::SortPairs(tmp_l, need_l, (unsigned*)d_lab, lkey, iota, member, (int)n, 0, label_bits, st));
+            pf_sort_pairs(sc, (const unsigned*)d_lab, lkey, iota, member, n, label_bits);
             if (!sc.ok()) return;
             k_label_starts<<<pf_blocks(n), PF_BLOCK, 0, st>>>(lkey, n, m, lstart);
             k_run_sums<<<pf_blocks(n), PF_BLOCK, 0, st>>>(lkey, member, n, lstart, d_P, d_mass, sums);
@@ -501,10 +474,12 @@ extern "C" int pf_mesh_cluster(pf_ctx* ctx, const double* pts, int64_t n, const 
         } else {
             assign(n_iter);
             for (int32_t t = 0; sc.ok() && t < n_iter; ++t) {
+                const size_t mark = sc.blocks.size();  // the two sorts' temporaries go back with every iteration
                 update();
                 assign(t);
                 sc.download(&h_changed[t], d_changed + t, 1);  // the one word the host reads per iteration
                 sc.sync();
+                sc.release_from(mark);
                 if (!sc.ok()) break;
                 ++iters;
                 if (h_changed[t] == 0) break;
@@ -522,15 +497,14 @@ extern "C" int pf_mesh_cluster(pf_ctx* ctx, const double* pts, int64_t n, const 
             unsigned *dv0 = sc.get<unsigned>(T), *dv1 = sc.get<unsigned>(T);
             int32_t *flag = sc.get<int32_t>(T), *pos = sc.get<int32_t>(T);
             d_out = sc.get<int32_t>(3 * T), d_src = sc.get<int32_t>(T), d_votes = sc.get<int32_t>(2 * T);
-            size_t need_d = 0, need_s = 0;
-            if (sc.ok()) sc.note(hipcub::DeviceRadixSort::SortPairs(nullptr, need_d, dk0, dk1, dv0, dv1, (int)T, 0, 3 * RM_LABEL_BITS, st));
+            size_t need_s = 0;
             if (sc.ok()) sc.note(hipcub::DeviceScan::ExclusiveSum(nullptr, need_s, flag, pos, (int)T, st));
-            void *tmp_d = sc.get<char>(need_d), *tmp_s = sc.get<char>(need_s);
+            void* tmp_s = sc.get<char>(need_s);
             if (sc.ok()) {
                 k_dual_keys<<<pf_blocks(T), PF_BLOCK, 0, st>>>(d_faces, T, d_lab, dk0, dv0, d_counts + 1);
                 sc.launched();
             }
-            if (sc.ok()) sc.note(hipcub::DeviceRadixSort::SortPairs(tmp_d, need_d, dk0, dk1, dv0, dv1, (int)T, 0, 3 * RM_LABEL_BITS, st));
+            pf_sort_pairs(sc, dk0, dk1, dv0, dv1, T, 3 * RM_LABEL_BITS);
             if (sc.ok()) {
                 k_dual_flags<<<pf_blocks(T), PF_BLOCK, 0, st>>>(dk1, T, flag);
                 sc.launched();
@@ -554,21 +528,12 @@ extern "C" int pf_mesh_cluster(pf_ctx* ctx, const double* pts, int64_t n, const 
             sc.download(face_src, d_src, (size_t)h_counts[0]);
             sc.download(votes, d_votes, 2 * (size_t)h_counts[0]);
         }
-        if (sc.ok() && device_ms) sc.note(hipEventRecord(ev[1], st));
+        timer.stop(sc);
         sc.sync();
-        if (sc.ok() && device_ms) {
-            float ms = 0.0f;
-            sc.note(hipEventElapsedTime(&ms, ev[0], ev[1]));
-            *device_ms = (double)ms;
-        }
+        timer.read(sc, device_ms);
         err = sc.err;
     }
-    if (device_ms) hipEventDestroy(ev[0]), hipEventDestroy(ev[1]);
-    if (err != hipSuccess) {
-        (void)hipGetLastError();
-        pf_set_error("pf_mesh_cluster: %s", hipGetErrorString(err));
-        return PF_E_HIP;
-    }
+    if (err != hipSuccess) return pf_hip_failed("pf_mesh_cluster", err);
     if (changed && !update_only)
         for (int32_t t = 0; t < iters; ++t) changed[t] = h_changed[t];
     if (report) {

@@ -1,6 +1,7 @@
 // Device memory as the host code of the library holds it: the scratch of one call (Scratch) and a buffer that grows and
-// stays (DevBuf), both on top of the ctx's caching allocator (pf_api.hip).  Only the HIP C API is needed here, so the
-// failure paths of both run on the CPU over a test double of the allocator (tests/csrc/scratch_paths.cpp).
+// stays (DevBuf), both on top of the ctx's caching allocator (pf_api.hip); and the timer of a call's stream work
+// (StreamTimer).  Only the HIP C API is needed here, so the failure paths of all three run on the CPU over test doubles
+// of the allocator and of the event calls (tests/csrc/scratch_paths.cpp).
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include <stddef.h>
@@ -65,6 +66,43 @@ struct Scratch {
     void launched() { note(hipGetLastError()); }  // after the kernels of an ok() block
     void sync() {
         if (ok()) err = hipStreamSynchronize(st);
+    }
+    // the blocks got since blocks.size() was `mark` go back now (the stream orders their next user behind the work queued
+    // so far): for a loop whose every round gets temporaries of its own
+    void release_from(size_t mark) {
+        for (; blocks.size() > mark; blocks.pop_back()) pf_free(st, blocks.back());
+    }
+};
+
+// The device time of a call's stream work, for the entry points that report it (device_ms): two events around the work.
+// Constructed with whether the caller wants the time - if not, nothing below does anything.  start creates the events
+// and records the first, stop records the second, read (after the call's sync) gives the milliseconds between them;
+// a failure is the Scratch's like any other.  The destructor destroys whatever was created.
+struct StreamTimer {
+    const bool wanted;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+
+    explicit StreamTimer(bool wanted_) : wanted(wanted_) {}
+    StreamTimer(const StreamTimer&) = delete;
+    StreamTimer& operator=(const StreamTimer&) = delete;
+    ~StreamTimer() {
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+    void start(Scratch& sc) {
+        if (!wanted) return;
+        for (hipEvent_t& e : ev)
+            if (sc.ok()) sc.note(hipEventCreate(&e));
+        if (sc.ok()) sc.note(hipEventRecord(ev[0], sc.st));
+    }
+    void stop(Scratch& sc) {
+        if (wanted && sc.ok()) sc.note(hipEventRecord(ev[1], sc.st));
+    }
+    void read(Scratch& sc, double* ms) {
+        if (!wanted || !sc.ok()) return;
+        float f = 0.0f;
+        sc.note(hipEventElapsedTime(&f, ev[0], ev[1]));
+        *ms = (double)f;
     }
 };
 

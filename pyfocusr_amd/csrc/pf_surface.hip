@@ -23,8 +23,8 @@
 // hierarchy one packet of neighbouring queries per wave, with the same exact tests and tie rule as k_closest.
 //
 // Signed distances (pf_surface_prepare_signed / pf_surface_signed_distance): angle-weighted pseudonormals, built once
-// per surface on request, and one per-query kernel after the unchanged k_distance search that names the feature (face,
-// edge, vertex) of the winning triangle the closest point lies on.
+// per surface on request by the half-edge pass of pf_halfedge.h, and one per-query kernel after the unchanged k_distance
+// search that names the feature (face, edge, vertex) of the winning triangle the closest point lies on.
 //
 // Generalized winding numbers (pf_surface_prepare_winding / pf_surface_winding): the solid angles of all triangles,
 // summed over the same chunks, exactly or with far clusters replaced by their dipoles.
@@ -35,11 +35,10 @@
 //
 // Each section's own comment has the details.  The entry points (extern "C", at the end) keep their device scratch in a
 // Scratch, and sort along the Morton curve through pf_surface_morton_order.
-#include <hipcub/hipcub.hpp>
-
 #include <cmath>
 #include <limits>
 
+#include "pf_halfedge.h"
 #include "pf_tri_hierarchy.h"
 
 struct pf_surface {
@@ -59,8 +58,6 @@ struct pf_surface {
 };
 
 namespace {
-
-__device__ __forceinline__ double dot3(const double a[3], const double b[3]) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
 
 // Ericson, Real-Time Collision Detection 5.1.5; same operation order as oracle/icp_port.py.  Returns the Voronoi region
 // of the result: 0 1 2 = corner a b c, 3 = edge ab, 4 = edge bc, 5 = edge ca, 6 = interior (PF_REGION_*); only k_signed
@@ -438,10 +435,9 @@ __global__ __launch_bounds__(PF_BLOCK) void k_distance_stats(const double* __res
 // feature (interior, edge, corner) of the winning triangle that the closest point c lies on is the exact inside /
 // outside sign on a closed, consistently oriented mesh.  Fan diagonals are edges like any other.  Every sum runs in a
 // fixed order (triangle order for an edge, sorted (vertex, half-edge) order for a vertex): no floating-point atomics.
+// The half-edge pass itself - the triangle pass, the run walks, the edge counts - is pf_halfedge.h's.
 
-// per triangle: unit normal (zero for a zero-area or non-finite triangle), corner angles atan2(|u x v|, u . v) (zero
-// there too); per half-edge h = 3t + j (corner j -> corner j+1): the key (min << nb | max) of its edge, and its corner's
-// vertex (for the vertex sums)
+// one thread per fan triangle: he_triangle, without the area
 __global__ __launch_bounds__(PF_BLOCK) void k_tri_normals(const double* __restrict__ pts, const int32_t* __restrict__ faces,
                                                           int32_t vpf, int64_t n_tri, int nb, double* __restrict__ tnrm,
                                                           double* __restrict__ tang, unsigned long long* __restrict__ ekey,
@@ -450,46 +446,21 @@ __global__ __launch_bounds__(PF_BLOCK) void k_tri_normals(const double* __restri
     if (t >= n_tri) return;
     int32_t v[3];
     tri_corners(faces, vpf, t, v);
-    double x[3][3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c)
-#pragma unroll
-        for (int a = 0; a < 3; ++a) x[c][a] = pts[3 * (int64_t)v[c] + a];
-    const double u[3] = {x[1][0] - x[0][0], x[1][1] - x[0][1], x[1][2] - x[0][2]};
-    const double w[3] = {x[2][0] - x[0][0], x[2][1] - x[0][1], x[2][2] - x[0][2]};
-    const double cr[3] = {u[1] * w[2] - u[2] * w[1], u[2] * w[0] - u[0] * w[2], u[0] * w[1] - u[1] * w[0]};
-    const double len = sqrt(dot3(cr, cr));
-    const bool area = len > 0.0 && std::isfinite(len);
-#pragma unroll
-    for (int a = 0; a < 3; ++a) tnrm[3 * t + a] = area ? cr[a] / len : 0.0;
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        const int j1 = j == 2 ? 0 : j + 1, j2 = j == 0 ? 2 : j - 1;
-        const double e1[3] = {x[j1][0] - x[j][0], x[j1][1] - x[j][1], x[j1][2] - x[j][2]};
-        const double e2[3] = {x[j2][0] - x[j][0], x[j2][1] - x[j][1], x[j2][2] - x[j][2]};
-        const double c[3] = {e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0]};
-        tang[3 * t + j] = area ? atan2(sqrt(dot3(c, c)), dot3(e1, e2)) : 0.0;
-        const unsigned lo = (unsigned)min(v[j], v[j1]), hi = (unsigned)max(v[j], v[j1]);
-        ekey[3 * t + j] = ((unsigned long long)lo << nb) | hi;
-        vkey[3 * t + j] = (unsigned)v[j];
-        hval[3 * t + j] = (int32_t)(3 * t + j);
-    }
+    he_triangle(pts, v, t, nb, tnrm, tang, nullptr, ekey, vkey, hval);
 }
 
 // one thread per edge (the first half-edge of each run of equal keys; runs are in triangle order, the sort being
-// stable): the sum of its triangles' normals, stored for each of its half-edges; counts edges | boundary | non-manifold
-// | inconsistent (two triangles that traverse it in the same direction)
+// stable): the sum of its triangles' normals, stored for each of its half-edges; counts: he_count_edge
 __global__ __launch_bounds__(PF_BLOCK) void k_edge_normals(const unsigned long long* __restrict__ ekey, const int32_t* __restrict__ hedge,
                                                            int64_t n_half, const int32_t* __restrict__ faces, int32_t vpf,
                                                            const double* __restrict__ tnrm, double* __restrict__ enrm,
                                                            unsigned long long* __restrict__ counts) {
     const int64_t i = (int64_t)blockIdx.x * PF_BLOCK + threadIdx.x;
-    if (i >= n_half || (i > 0 && ekey[i - 1] == ekey[i])) return;
-    const unsigned long long key = ekey[i];
-    int64_t end = i;
+    const int64_t end = he_run_end(ekey, n_half, i);
+    if (end == i) return;
     double s[3] = {0.0, 0.0, 0.0};
-    for (; end < n_half && ekey[end] == key; ++end) {
-        const int64_t t = hedge[end] / 3;
+    for (int64_t k = i; k < end; ++k) {
+        const int64_t t = hedge[k] / 3;
 #pragma unroll
         for (int a = 0; a < 3; ++a) s[a] += tnrm[3 * t + a];
     }
@@ -497,20 +468,15 @@ __global__ __launch_bounds__(PF_BLOCK) void k_edge_normals(const unsigned long l
 #pragma unroll
         for (int a = 0; a < 3; ++a) enrm[3 * (int64_t)hedge[k] + a] = s[a];
     const int64_t m = end - i;
-    atomicAdd(&counts[0], 1ull);  // integer counts: the same on every run
-    if (m == 1) atomicAdd(&counts[1], 1ull);
-    if (m > 2) atomicAdd(&counts[2], 1ull);
-    if (m == 2) {
-        bool fwd[2];
-        for (int k = 0; k < 2; ++k) {
-            const int32_t h = hedge[i + k];
-            int32_t v[3];
-            tri_corners(faces, vpf, h / 3, v);
-            const int j = h % 3;
-            fwd[k] = v[j] < v[j == 2 ? 0 : j + 1];
-        }
-        if (fwd[0] == fwd[1]) atomicAdd(&counts[3], 1ull);
+    bool fwd[2] = {false, false};
+    for (int k = 0; m == 2 && k < 2; ++k) {
+        const int32_t h = hedge[i + k];
+        int32_t v[3];
+        tri_corners(faces, vpf, h / 3, v);
+        const int j = h % 3;
+        fwd[k] = v[j] < v[he_next(j)];
     }
+    he_count_edge(counts, m, fwd[0], fwd[1]);
 }
 
 // one thread per vertex: sum of corner angle x unit normal over its corners, in sorted (vertex, half-edge) order
@@ -519,14 +485,8 @@ __global__ __launch_bounds__(PF_BLOCK) void k_vertex_normals(const unsigned* __r
                                                              const double* __restrict__ tang, double* __restrict__ vnrm) {
     const int64_t v = (int64_t)blockIdx.x * PF_BLOCK + threadIdx.x;
     if (v >= n_points) return;
-    int64_t lo = 0, hi = n_half;  // first position with key >= v
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (vkey[mid] < (unsigned)v) lo = mid + 1;
-        else hi = mid;
-    }
     double s[3] = {0.0, 0.0, 0.0};
-    for (; lo < n_half && vkey[lo] == (unsigned)v; ++lo) {
+    for (int64_t lo = he_vertex_run(vkey, n_half, v); lo < n_half && vkey[lo] == (unsigned)v; ++lo) {
         const int32_t h = hedge[lo];
         const double ang = tang[h];
 #pragma unroll
@@ -1112,9 +1072,7 @@ int pf_surface_create(pf_ctx* ctx, const double* pts, int64_t n, const int32_t* 
     PF_CHECK(n > 0 && n < ((int64_t)1 << 31), PF_E_ARG, "pf_surface_create: n = %lld out of range", (long long)n);
     PF_CHECK(vpf >= 3 && vpf <= 16 && n_faces > 0 && n_faces * (vpf - 2) < ((int64_t)1 << 31), PF_E_ARG,
              "pf_surface_create: faces %lld x %d out of range", (long long)n_faces, vpf);
-    for (int64_t i = 0; i < n_faces * vpf; ++i)
-        PF_CHECK(faces[i] >= 0 && faces[i] < n, PF_E_ARG, "pf_surface_create: face %lld references vertex %d of %lld",
-                 (long long)(i / vpf), faces[i], (long long)n);
+    PF_TRY(pf_check_faces("pf_surface_create", faces, n_faces, vpf, n, false));
     const KeyBox bb = pf_key_box(pts, n, 3, false);
     PF_HIP(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
@@ -1196,11 +1154,9 @@ int pf_surface_prepare_signed(pf_surface* s, const double* points, const int32_t
     PF_CHECK(s && points && faces, PF_E_ARG, "pf_surface_prepare_signed: NULL argument");
     const int64_t n = s->n_points, T = s->h.n_tri, H = 3 * T, nf = s->n_faces * s->vpf;
     PF_CHECK(H < ((int64_t)1 << 31), PF_E_ARG, "pf_surface_prepare_signed: %lld half-edges out of range", (long long)H);
-    for (int64_t i = 0; i < nf; ++i)  // the same arrays as at pf_surface_create, or at least indices within them
-        PF_CHECK(faces[i] >= 0 && faces[i] < n, PF_E_ARG, "pf_surface_prepare_signed: face %lld references vertex %d of %lld",
-                 (long long)(i / s->vpf), faces[i], (long long)n);
-    int nb = 1;  // bits of a vertex index
-    while (nb < 31 && ((int64_t)1 << nb) < n) ++nb;
+    // the same arrays as at pf_surface_create, or at least indices within them
+    PF_TRY(pf_check_faces("pf_surface_prepare_signed", faces, s->n_faces, s->vpf, n, false));
+    const int nb = pf_index_bits(n);  // bits of a vertex index
     PF_HIP(hipSetDevice(s->ctx->device));
     hipStream_t st = s->ctx->stream;
     release_signed(s, st);  // a second call builds afresh from the arrays it is given
@@ -1226,17 +1182,13 @@ int pf_surface_prepare_signed(pf_surface* s, const double* points, const int32_t
             sc.launched();
         }
         // both sorts are stable and start from half-edge order: equal keys stay in triangle order.  They share the value
-        // arrays and the temporary, so the vertex sort runs after k_edge_normals has read the edge sort's h1.
-        size_t need_e = 0, need_v = 0;
-        if (sc.ok()) sc.note(hipcub::DeviceRadixSort::SortPairs(nullptr, need_e, ek0, ek1, h0, h1, (int)H, 0, 2 * nb, st));
-        if (sc.ok()) sc.note(hipcub::DeviceRadixSort::SortPairs(nullptr, need_v, vk0, vk1, h0, h1, (int)H, 0, nb, st));
-        void* tmp = sc.get<char>(need_e > need_v ? need_e : need_v);
-        if (sc.ok()) sc.note(hipcub::DeviceRadixSort::SortPairs(tmp, need_e, ek0, ek1, h0, h1, (int)H, 0, 2 * nb, st));
+        // arrays, and the stream runs the vertex sort after k_edge_normals has read the edge sort's h1.
+        pf_sort_pairs(sc, ek0, ek1, h0, h1, H, 2 * nb);
         if (sc.ok()) {
             k_edge_normals<<<pf_blocks(H), PF_BLOCK, 0, st>>>(ek1, h1, H, s->faces, s->vpf, s->tnrm, s->enrm, cnt);
             sc.launched();
         }
-        if (sc.ok()) sc.note(hipcub::DeviceRadixSort::SortPairs(tmp, need_v, vk0, vk1, h0, h1, (int)H, 0, nb, st));
+        pf_sort_pairs(sc, vk0, vk1, h0, h1, H, nb);
         if (sc.ok()) {
             k_vertex_normals<<<pf_blocks(n), PF_BLOCK, 0, st>>>(vk1, h1, H, n, s->tnrm, tang, s->vnrm);
             sc.launched();

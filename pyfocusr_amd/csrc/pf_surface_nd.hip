@@ -261,9 +261,7 @@ int pf_surface_nd_create(pf_ctx* ctx, const double* coords, int64_t n, int32_t d
     PF_CHECK(n > 0 && n < ((int64_t)1 << 31) / d, PF_E_ARG, "pf_surface_nd_create: n = %lld out of range", (long long)n);
     PF_CHECK(vpf >= 3 && vpf <= 16 && n_faces > 0 && n_faces * (vpf - 2) < ((int64_t)1 << 31) / (3 * d), PF_E_ARG,
              "pf_surface_nd_create: faces %lld x %d out of range", (long long)n_faces, vpf);
-    for (int64_t i = 0; i < n_faces * vpf; ++i)
-        PF_CHECK(faces[i] >= 0 && faces[i] < n, PF_E_ARG, "pf_surface_nd_create: face %lld references vertex %d of %lld",
-                 (long long)(i / vpf), faces[i], (long long)n);
+    PF_TRY(pf_check_faces("pf_surface_nd_create", faces, n_faces, vpf, n, false));
     const KeyBox bb = pf_key_box(coords, n, d, false);
     PF_HIP(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;

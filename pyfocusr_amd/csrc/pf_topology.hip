@@ -3,8 +3,8 @@
 // closed patch with points, point outward - and the boundary loops.  The definitions are in include/pyfocusr_hip.h;
 // tests/_topology_ref.py restates them in numpy / scipy.
 //
-// Half-edge h = 3 t + j leaves corner j of face t; one stable radix sort of the half-edges by their edge's key
-// (min << nb | max) makes the half-edges of an edge a run in ascending h (as in pf_curvature.hip and pf_surface.hip).
+// The half-edges sorted by their edge's key are walked one run per edge (pf_halfedge.h has the keys, the run walk and
+// the edge counts).
 //   k_topo_halfedges  one thread per face: the three keys, and (h << 1 | direction) as the sort's value
 //   k_topo_edges      one thread per run of equal keys: the edge's class, face_neighbours, the parity of a two-face
 //                     edge on both of its half-edges, the four counts, the faces that touch an edge of one or of
@@ -30,11 +30,9 @@
 //                     share a vertex and are hooked as the faces are, without parity.  Skipped without boundary edges.
 // The host turns roots into dense ascending ids (patches by their smallest face, loops by their smallest half-edge).
 // No floating-point atomics, no kernel waits for another block: two calls give the same bits.
-#include <hipcub/hipcub.hpp>
-
 #include <vector>
 
-#include "pf_internal.h"
+#include "pf_halfedge.h"
 
 namespace {
 
@@ -50,37 +48,31 @@ __global__ __launch_bounds__(PF_BLOCK) void k_topo_halfedges(const int32_t* __re
     const int32_t v[3] = {faces[3 * t], faces[3 * t + 1], faces[3 * t + 2]};
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
-        const int32_t a = v[j], b = v[j == 2 ? 0 : j + 1];
-        const unsigned lo = (unsigned)min(a, b), hi = (unsigned)max(a, b);
-        ekey[3 * t + j] = ((u64)lo << nb) | hi;
+        const int32_t a = v[j], b = v[he_next(j)];
+        ekey[3 * t + j] = he_edge_key(a, b, nb);
         hval[3 * t + j] = ((unsigned)(3 * t + j) << 1) | (a < b ? 0u : 1u);
     }
 }
 
-// One thread per edge: the first half-edge of each run of equal keys; the run is in ascending h.
-// counts: edges | boundary | non-manifold | inconsistent, as k_curv_edges and k_edge_normals count them.
+// One thread per edge: the first half-edge of each run of equal keys; the run is in ascending h.  counts: he_count_edge.
 __global__ __launch_bounds__(PF_BLOCK) void k_topo_edges(const u64* __restrict__ ekey, const unsigned* __restrict__ hval, int64_t n_half,
                                                          int32_t* __restrict__ nbr, uint8_t* __restrict__ hpar,
                                                          uint8_t* __restrict__ fopen, u64* __restrict__ counts) {
     const int64_t i = (int64_t)blockIdx.x * PF_BLOCK + threadIdx.x;
-    if (i >= n_half || (i > 0 && ekey[i - 1] == ekey[i])) return;
-    const u64 key = ekey[i];
-    int64_t end = i + 1;
-    while (end < n_half && ekey[end] == key) ++end;
+    const int64_t end = he_run_end(ekey, n_half, i);
+    if (end == i) return;
     const int64_t m = end - i;
-    atomicAdd(&counts[0], 1ull);
+    const unsigned w0 = hval[i], w1 = m == 2 ? hval[i + 1] : 0u;
+    he_count_edge(counts, m, !(w0 & 1u), !(w1 & 1u));
     if (m == 2) {
-        const unsigned w0 = hval[i], w1 = hval[i + 1];
         const int64_t h0 = w0 >> 1, h1 = w1 >> 1;
         const uint8_t p = (w0 & 1u) == (w1 & 1u) ? 1 : 0;
-        if (p) atomicAdd(&counts[3], 1ull);
         nbr[h0] = (int32_t)(h1 / 3);
         nbr[h1] = (int32_t)(h0 / 3);
         hpar[h0] = p;
         hpar[h1] = p;
         return;
     }
-    atomicAdd(&counts[m == 1 ? 1 : 2], 1ull);
     for (int64_t k = i; k < end; ++k) {
         const int64_t h = hval[k] >> 1;
         nbr[h] = m == 1 ? -1 : -2;
@@ -269,7 +261,7 @@ __global__ __launch_bounds__(PF_BLOCK) void k_loop_keys(const int32_t* __restric
     }
     const u64 root = pw[t] >> 1;
     lkey[2 * h] = (root << nb) | (u64)(unsigned)faces[h];
-    lkey[2 * h + 1] = (root << nb) | (u64)(unsigned)faces[3 * t + (j == 2 ? 0 : j + 1)];
+    lkey[2 * h + 1] = (root << nb) | (u64)(unsigned)faces[3 * t + he_next(j)];
     lw[h] = (int32_t)h;
 }
 
@@ -299,12 +291,6 @@ __global__ __launch_bounds__(PF_BLOCK) void k_loop_compress(int32_t* lw, int64_t
     __hip_atomic_store(&lw[h], loop_find(lw, (int32_t)h), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-int bits_for(int64_t count) {  // the least b >= 1 with 2^b >= count
-    int b = 1;
-    while (b < 62 && ((int64_t)1 << b) < count) ++b;
-    return b;
-}
-
 }  // namespace
 
 extern "C" int pf_mesh_topology(pf_ctx* ctx, const double* pts, int64_t n, const int32_t* faces, int64_t n_faces, uint32_t flags,
@@ -316,29 +302,13 @@ extern "C" int pf_mesh_topology(pf_ctx* ctx, const double* pts, int64_t n, const
              "pf_mesh_topology: %lld faces out of range (3 n_faces < 2^31)", (long long)n_faces);
     PF_CHECK((flags & ~(uint32_t)PF_TOPOLOGY_OUTWARD) == 0, PF_E_ARG, "pf_mesh_topology: unknown flags 0x%x", (unsigned)flags);
     const int64_t T = n_faces, H = 3 * T;
-    for (int64_t t = 0; t < T; ++t) {
-        const int32_t* f = faces + 3 * t;
-        for (int j = 0; j < 3; ++j)
-            PF_CHECK(f[j] >= 0 && f[j] < n, PF_E_ARG, "pf_mesh_topology: face %lld references vertex %d of %lld", (long long)t, f[j],
-                     (long long)n);
-        PF_CHECK(f[0] != f[1] && f[1] != f[2] && f[0] != f[2], PF_E_DEGENERATE, "pf_mesh_topology: face %lld repeats a vertex",
-                 (long long)t);
-    }
-    const int nb = bits_for(n);       // bits of a vertex index
-    const int rb = bits_for(T + 1);   // bits of a face index and of the value T
+    PF_TRY(pf_check_faces("pf_mesh_topology", faces, T, 3, n, true));
+    const int nb = pf_index_bits(n);       // bits of a vertex index
+    const int rb = pf_index_bits(T + 1);   // bits of a face index and of the value T
     const bool volumes = pts && (flags & PF_TOPOLOGY_OUTWARD);
     PF_HIP(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    if (device_ms) {
-        PF_HIP(hipEventCreate(&ev[0]));
-        if (hipEventCreate(&ev[1]) != hipSuccess) {
-            hipEventDestroy(ev[0]);
-            (void)hipGetLastError();
-            pf_set_error("pf_mesh_topology: hipEventCreate failed");
-            return PF_E_HIP;
-        }
-    }
+    StreamTimer timer(device_ms != nullptr);
     u64 counts[4] = {0, 0, 0, 0};
     int64_t rounds = 0, loop_rounds = 0;
     bool capped = false;
@@ -376,15 +346,12 @@ extern "C" int pf_mesh_topology(pf_ctx* ctx, const double* pts, int64_t n, const
         sc.zero(fopen, T);
         sc.zero(nonor, T);
         sc.zero(inv, T);
-        if (sc.ok() && device_ms) sc.note(hipEventRecord(ev[0], st));
+        timer.start(sc);
         if (sc.ok()) {
             k_topo_halfedges<<<pf_blocks(T), PF_BLOCK, 0, st>>>(d_faces, T, nb, ek0, hv0);
             sc.launched();
         }
-        size_t need = 0;
-        if (sc.ok()) sc.note(hipcub::DeviceRadixSort::SortPairs(nullptr, need, ek0, ek1, hv0, hv1, (int)H, 0, 2 * nb, st));
-        void* tmp = sc.get<char>(need);
-        if (sc.ok()) sc.note(hipcub::DeviceRadixSort::SortPairs(tmp, need, ek0, ek1, hv0, hv1, (int)H, 0, 2 * nb, st));
+        pf_sort_pairs(sc, ek0, ek1, hv0, hv1, H, 2 * nb);
         if (sc.ok()) {
             k_topo_edges<<<pf_blocks(H), PF_BLOCK, 0, st>>>(ek1, hv1, H, nbr, hpar, fopen, cnt);
             k_topo_init<<<pf_blocks(T), PF_BLOCK, 0, st>>>(pw, T);
@@ -424,10 +391,7 @@ extern "C" int pf_mesh_topology(pf_ctx* ctx, const double* pts, int64_t n, const
                 k_topo_terms<<<pf_blocks(T), PF_BLOCK, 0, st>>>(pw, T, rk0, fv0);
                 sc.launched();
             }
-            size_t need_r = 0;
-            if (sc.ok()) sc.note(hipcub::DeviceRadixSort::SortPairs(nullptr, need_r, rk0, rk1, fv0, fv1, (int)T, 0, rb, st));
-            void* tmp_r = sc.get<char>(need_r);
-            if (sc.ok()) sc.note(hipcub::DeviceRadixSort::SortPairs(tmp_r, need_r, rk0, rk1, fv0, fv1, (int)T, 0, rb, st));
+            pf_sort_pairs(sc, rk0, rk1, fv0, fv1, T, rb);
             if (sc.ok()) {
                 k_seg_start<<<pf_blocks(T), PF_BLOCK, 0, st>>>(rk1, fv1, T, d_pts, d_faces, pw, inv, start, sa);
                 k_seg_sum<<<pf_blocks(T), PF_BLOCK, 0, st>>>(rk1, start, T, sa, sb, 1, 256);
@@ -455,10 +419,7 @@ extern "C" int pf_mesh_topology(pf_ctx* ctx, const double* pts, int64_t n, const
                 k_loop_keys<<<pf_blocks(H), PF_BLOCK, 0, st>>>(d_faces, nbr, pw, H, T, nb, lk0, lv0, lw);
                 sc.launched();
             }
-            size_t need_l = 0;
-            if (sc.ok()) sc.note(hipcub::DeviceRadixSort::SortPairs(nullptr, need_l, lk0, lk1, lv0, lv1, E, 0, nb + rb, st));
-            void* tmp_l = sc.get<char>(need_l);
-            if (sc.ok()) sc.note(hipcub::DeviceRadixSort::SortPairs(tmp_l, need_l, lk0, lk1, lv0, lv1, E, 0, nb + rb, st));
+            pf_sort_pairs(sc, lk0, lk1, lv0, lv1, E, nb + rb);
             for (bool more = true; sc.ok() && more;) {
                 if (loop_rounds > H) {
                     capped = true;
@@ -478,21 +439,12 @@ extern "C" int pf_mesh_topology(pf_ctx* ctx, const double* pts, int64_t n, const
             }
             sc.download(h_loop.data(), lw, H);
         }
-        if (sc.ok() && device_ms) sc.note(hipEventRecord(ev[1], st));
+        timer.stop(sc);
         sc.sync();
-        if (sc.ok() && device_ms) {
-            float ms = 0.0f;
-            sc.note(hipEventElapsedTime(&ms, ev[0], ev[1]));
-            *device_ms = (double)ms;
-        }
+        timer.read(sc, device_ms);
         err = sc.err;
     }
-    if (device_ms) hipEventDestroy(ev[0]), hipEventDestroy(ev[1]);
-    if (err != hipSuccess) {
-        (void)hipGetLastError();
-        pf_set_error("pf_mesh_topology: %s", hipGetErrorString(err));
-        return PF_E_HIP;
-    }
+    if (err != hipSuccess) return pf_hip_failed("pf_mesh_topology", err);
     PF_CHECK(!capped, PF_E_INTERNAL, "pf_mesh_topology: the labelling did not settle within %lld rounds (faces) / %lld rounds (loops)",
              (long long)rounds, (long long)loop_rounds);
     // dense ids in ascending order of the smallest member: a root is its set's smallest member, and never follows a member

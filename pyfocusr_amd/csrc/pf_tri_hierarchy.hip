@@ -1,8 +1,6 @@
 // The build of the triangle hierarchy (pf_tri_hierarchy.h has the structure): Morton keys of centroids or points, the
 // stable sort, the gather into SoA, the chunk and super-chunk boxes; and its release.  Every kernel has the instance
 // D = 3 of the 3-D surface and the instance D = 0 for any other depth.
-#include <hipcub/hipcub.hpp>
-
 #include <cmath>
 
 #include "pf_tri_hierarchy.h"
@@ -159,13 +157,6 @@ const int32_t* pf_surface_morton_order(Scratch& sc, const double* d_pts, int32_t
     }
     pf_sort_pairs(sc, k0, k1, v0, v1, n, 30);
     return sc.ok() ? v1 : nullptr;
-}
-
-void pf_sort_pairs(Scratch& sc, const unsigned* k_in, unsigned* k_out, const int32_t* v_in, int32_t* v_out, int64_t n, int end_bit) {
-    size_t need = 0;
-    if (sc.ok()) sc.note(hipcub::DeviceRadixSort::SortPairs(nullptr, need, k_in, k_out, v_in, v_out, (int)n, 0, end_bit, sc.st));
-    void* tmp = sc.get<char>(need);
-    if (sc.ok()) sc.note(hipcub::DeviceRadixSort::SortPairs(tmp, need, k_in, k_out, v_in, v_out, (int)n, 0, end_bit, sc.st));
 }
 
 void pf_tri_hierarchy_build(Scratch& sc, TriHierarchy& h, const double* d_pts, int32_t d, const int32_t* d_faces, int64_t n_faces,

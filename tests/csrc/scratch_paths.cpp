@@ -1,4 +1,4 @@
-// The failure paths of Scratch and DevBuf (pyfocusr_amd/csrc/pf_scratch.h), run on the CPU.
+// The failure paths of Scratch, DevBuf and StreamTimer (pyfocusr_amd/csrc/pf_scratch.h), run on the CPU.
 //
 // On a GPU an allocation only fails when the device is out of memory, so no GPU test can walk these paths.  Here the
 // header is compiled by the host compiler over a test double of the library's allocator: pf_malloc / pf_free are backed
@@ -9,7 +9,12 @@
 //   * the first error is the one the call reports, whatever is noted after it;
 //   * every request after it is a no-op that returns NULL: no allocation, no copy, no wait;
 //   * when the call's scope ends every get block has been freed exactly once and the keep block is still live;
-//   * a DevBuf whose grow failed is empty, and can be grown or released again.
+//   * a DevBuf whose grow failed is empty, and can be grown or released again;
+//   * blocks released in the middle of a call (release_from) are freed once, and only they.
+// StreamTimer runs over stand-ins of the four event calls - an event is a heap block, so the sanitizer sees one destroyed
+// twice, used after it, or never destroyed - with the n-th hipEventCreate failing, wanted and not wanted, through start,
+// stop and read and through every early end of a call: each event created is destroyed exactly once, the failure is the
+// call's error, and a timer that is not wanted makes no event call at all.
 // Built with -fsanitize=address,undefined (tests/test_scratch_paths.py): a block freed twice, used after its release or
 // overrun by a copy stops the program there.  Exit status 0 and "ok" on the last line: every check held.
 #include <stdio.h>
@@ -86,6 +91,52 @@ hipError_t hipStreamSynchronize(hipStream_t) {
 hipError_t hipGetLastError(void) { return hipSuccess; }
 }
 
+// ---- the event calls of StreamTimer: an event is a heap block of one int
+namespace {
+int g_event_fail_at = -1;  // the hipEventCreate call (counted from 0) that fails; -1: none
+int g_event_creates = 0, g_event_calls = 0, g_event_bad = 0;  // bad: a destroy, record or read of an event that is not live
+std::map<void*, int> g_events;  // live event -> times recorded
+const hipError_t EVENT_ERROR = hipErrorInvalidResourceHandle;
+}  // namespace
+
+extern "C" {
+hipError_t hipEventCreate(hipEvent_t* e) {
+    ++g_event_calls;
+    if (g_event_creates++ == g_event_fail_at) return EVENT_ERROR;
+    *e = reinterpret_cast<hipEvent_t>(malloc(sizeof(int)));
+    g_events[*e] = 0;
+    return hipSuccess;
+}
+hipError_t hipEventDestroy(hipEvent_t e) {
+    ++g_event_calls;
+    if (g_events.erase(e) != 1) {
+        ++g_event_bad;
+        return hipErrorInvalidResourceHandle;
+    }
+    free(e);
+    return hipSuccess;
+}
+hipError_t hipEventRecord(hipEvent_t e, hipStream_t) {
+    ++g_event_calls;
+    const auto it = g_events.find(e);
+    if (it == g_events.end()) {
+        ++g_event_bad;
+        return hipErrorInvalidResourceHandle;
+    }
+    *reinterpret_cast<int*>(e) = ++it->second;
+    return hipSuccess;
+}
+hipError_t hipEventElapsedTime(float* ms, hipEvent_t a, hipEvent_t b) {
+    ++g_event_calls;
+    if (g_events.count(a) != 1 || g_events.count(b) != 1 || g_events[a] != 1 || g_events[b] != 1) {
+        ++g_event_bad;
+        return hipErrorInvalidResourceHandle;
+    }
+    *ms = 1.5f;
+    return hipSuccess;
+}
+}
+
 namespace {
 
 constexpr int N_ALLOC = 6;  // allocations of one call: get, get, keep, get, grow, grow
@@ -148,6 +199,16 @@ hipError_t call(DevBuf<double>& buf, double** kept) {
             CHECK(s.get<double>(N) == nullptr && s.keep<char>(1) == nullptr && g_malloc_calls == malloc_late);
         }
         for (void* p : blocks) CHECK(p == nullptr || g_live.count(p) == 1);  // still the call's until its scope ends
+        if (s.ok()) {  // a round's temporaries go back in the middle of the call: they, and nothing else
+            g_fail_at = -1;  // (this is the sequence in which no allocation fails)
+            const size_t mark = s.blocks.size(), live = g_live.size();
+            char *t0 = s.get<char>(10), *t1 = s.get<char>(20);
+            CHECK(t0 && t1 && g_live.size() == live + 2);
+            s.release_from(mark);
+            CHECK(s.blocks.size() == mark && g_live.size() == live && g_live.count(t0) == 0 && g_live.count(t1) == 0);
+            s.release_from(mark);  // nothing left to release
+            CHECK(g_bad_frees == 0 && g_live.count(a) == 1);
+        }
         if (!s.ok()) return s.err;  // (the early return of PF_HIP: the scope ends here as well)
     }
     return hipSuccess;
@@ -189,10 +250,47 @@ void run(int fail_at) {
     CHECK(g_bad_frees == 0 && g_live.empty());
 }
 
+// One timed call in miniature: stop_early leaves before stop (a kernel failed), or before read.
+void timed(bool wanted, int event_fail_at, int stop_early) {
+    g_fail_at = -1;
+    g_event_fail_at = event_fail_at;
+    g_event_creates = g_event_calls = g_event_bad = 0;
+    double ms = -1.0;
+    hipError_t err;
+    {
+        StreamTimer timer(wanted);
+        {
+            Scratch s(ST);
+            timer.start(s);
+            const bool failed = wanted && event_fail_at >= 0 && event_fail_at < 2;
+            CHECK(s.ok() == !failed);
+            CHECK(g_events.size() == (size_t)(!wanted ? 0 : (failed ? event_fail_at : 2)));  // nothing is created after a failure
+            if (stop_early == 1) s.note(hipErrorLaunchFailure);
+            timer.stop(s);
+            if (stop_early == 2) s.note(hipErrorLaunchFailure);
+            s.sync();
+            timer.read(s, &ms);
+            CHECK((ms == 1.5) == (wanted && !failed && !stop_early));
+            CHECK(ms == 1.5 || ms == -1.0);  // not written unless it was measured
+            err = s.err;
+            CHECK(err == (failed ? EVENT_ERROR : (stop_early ? hipErrorLaunchFailure : hipSuccess)));
+        }
+    }
+    CHECK(g_events.empty());    // every event that was created has been destroyed ...
+    for (auto& kv : g_events) free(kv.first);  // (a leaked event is this sequence's failed check, not the next one's too)
+    g_events.clear();
+    CHECK(g_event_bad == 0);    // ... once, and none was touched that was not live
+    if (!wanted) CHECK(g_event_calls == 0);
+}
+
 }  // namespace
 
 int main() {
     for (int fail_at = 0; fail_at <= N_ALLOC; ++fail_at) run(fail_at);
+    g_fail_at = -1;
+    for (int wanted = 0; wanted < 2; ++wanted)
+        for (int event_fail_at = -1; event_fail_at < 2; ++event_fail_at)
+            for (int stop_early = 0; stop_early < 3; ++stop_early) timed(wanted != 0, event_fail_at, stop_early);
     for (auto& kv : g_live) free(kv.first);
     printf("%d sequences, %d checks failed\n", N_ALLOC + 1, g_failures);
     if (g_failures) return 1;

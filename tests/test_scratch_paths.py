@@ -1,5 +1,5 @@
-"""The failure paths of the host code's scratch and buffer types (pyfocusr_amd/csrc/pf_scratch.h) on the CPU: the header over
-a test double of the device allocator that fails on the n-th call, built with the address and undefined-behaviour
+"""The failure paths of the host code's scratch, buffer and timer types (pyfocusr_amd/csrc/pf_scratch.h) on the CPU: the header
+over test doubles of the device allocator and of the event calls that fail on the n-th call, built with the address and undefined-behaviour
 sanitizers and run as a program of its own (tests/csrc/scratch_paths.cpp says what it checks).  No GPU, no HIP runtime."""
 import os
 import subprocess
