@@ -894,6 +894,57 @@ int pf_mesh_cluster(pf_ctx* ctx, const double* pts, int64_t n, const int32_t* fa
                     const int32_t* labels_in, int32_t* labels, double* centroids, int32_t* rep, int32_t* count, int32_t* changed,
                     int32_t* out_faces, int32_t* face_src, int32_t* votes, int64_t* report, double* device_ms);
 
+/* ---- distortion and coverage of a correspondence as a map between surfaces (pf_map_quality.hip; an extra) -----------
+ * src_pts [n_src][3] f64, src_faces [n_faces][3] i32 (triangles), tgt_pts [n_tgt][3] f64, tgt_normals [n_tgt][3] f64 or
+ * NULL, the map as map_vertices [n_src][c] i32 and map_weights [n_src][c] f64, all host.  c = 1: a vertex map, the weights
+ * are not read (NULL).  c = 3: the vertices / bary of pf_surface_nd_closest.  A source vertex whose first map vertex is -1
+ * is unmapped; the rest of its row is not read.  f64 throughout, separate multiplies and adds, dot products left to
+ * right, cross products component by component.  tests/_map_quality_ref.py states the definition in numpy.
+ *   image      c = 1: y_i = tgt_pts[T_i].  c = 3: y_i = (w0 x_a + w1 x_b) + w2 x_c per coordinate.  The image normal m_i the
+ *              same way from tgt_normals.  The owner of i is T_i; for c = 3 the corner with the largest weight, the lowest
+ *              corner on ties.
+ *   face       (i0, i1, i2): u = x1 - x0, w = x2 - x0, U = y1 - y0, W = y2 - y0; E = u . u, F = u . w, G = w . w and E', F',
+ *              G' likewise from U, W; a_s = |u x w|, a_i = |U x W|.
+ *              invalid    a_s is 0 or not finite, or a corner is unmapped: sigma = (0, 0), ratio 0, flags 0, or 8 with an
+ *                         unmapped corner
+ *              collapsed  valid and a_i == 0: sigma1 = sqrt(((G E' - (2 F) F') + E G') / (a_s a_s)), a numerator below 0
+ *                         counting as 0; sigma2 = 0, ratio 0
+ *              otherwise  l = sqrt(E), l' = sqrt(E'), p = l' / l, q = ((F' l) / l' - (l' F) / l) / a_s,
+ *                         s = (a_i l) / (l' a_s), Q = sqrt(((p + s) / 2)^2 + (q / 2)^2), R = sqrt(((p - s) / 2)^2 + (q / 2)^2),
+ *                         sigma1 = Q + R, sigma2 = |Q - R|, ratio = a_i / a_s: the singular values of the linear map
+ *                         between the two triangles in their own planes.  The identity gives (1, 1) and 1 exactly, a
+ *                         scaling by a power of two that power.
+ *              flipped    with tgt_normals only: valid, not collapsed and (U x W) . ((m0 + m1) + m2) < 0
+ *   face_sigma [n_faces][2], face_area_ratio [n_faces], face_flags [n_faces] u8: 1 valid | 2 collapsed | 4 flipped |
+ *              8 unmapped corner
+ *   vertex     over the half-edges h = 3 t + j that leave the vertex, in ascending h, as pf_curvatures sums:
+ *              vertex_area A_i = (sum a_s / 2) / 3 over the faces whose a_s is finite and not 0, mapped or not: the area of
+ *              pf_curvatures, bit for bit.  vertex_sigma [n_src][2] = (sum (a_s / 2) sigma) / (sum a_s / 2) over the valid
+ *              incident faces, 0 without any.  vertex_flags [n_src] u8: the OR of the incident faces' flags.
+ *   coverage   target_count [n_tgt] i32: the mapped source vertices the target vertex owns.  target_premass [n_tgt]: the
+ *              sum of their A_i, the owned vertices in ascending i cut into consecutive runs of 64, a run summed left to
+ *              right from 0.0, the run sums added left to right from 0.0 (the order of pf_mesh_cluster's update).
+ *   totals [8] each a sum over the faces in ascending order along the fixed tree of pf_mesh_topology (256 consecutive
+ *              terms, 256 of those sums, the rest in order), invalid faces adding 0: source area of the valid faces
+ *              sum a_s / 2 | image area sum a_i / 2 | Dirichlet energy 1/2 sum (a_s / 2) (sigma1^2 + sigma2^2) | sum (a_s / 2)
+ *              sigma1 | sum (a_s / 2) sigma2 | source area of the collapsed faces | of the flipped faces | 0
+ *   report [8] faces: valid | collapsed | flipped (-1 without tgt_normals) | invalid | with an unmapped corner | target
+ *              vertices with count > 0 | the largest count | source vertices with a flipped incident face (-1 without
+ *              tgt_normals)
+ *   device_ms  between the uploads and the downloads (HIP events)
+ * Every output may be NULL.  One round trip: the uploads, seven kernels and two stable radix sorts (the half-edges by
+ * vertex, the source vertices by owner), the downloads, one wait.  No floating-point atomics (the counts are integer sums
+ * and one integer maximum), no kernel waits for another block: two calls give the same bits in every output.  PF_E_ARG
+ * for a face index outside 0..n_src-1, a map vertex of a mapped row outside 0..n_tgt-1, c other than 1 or 3, c = 3
+ * without weights, n_src or n_tgt outside 1..2^31-1, n_faces < 1 or 3 n_faces >= 2^31, and for a mapped row whose source
+ * point, target points, target normals or weights are not finite; PF_E_DEGENERATE for a source face that repeats a
+ * vertex.  These checks run on the host before anything is launched. */
+int pf_map_distortion(pf_ctx* ctx, const double* src_pts, int64_t n_src, const int32_t* src_faces, int64_t n_faces,
+                      const double* tgt_pts, int64_t n_tgt, const double* tgt_normals, const int32_t* map_vertices,
+                      const double* map_weights, int32_t c, double* face_sigma, double* face_area_ratio, uint8_t* face_flags,
+                      double* vertex_area, double* vertex_sigma, uint8_t* vertex_flags, int32_t* target_count,
+                      double* target_premass, double* totals, int64_t* report, double* device_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,6 +15,8 @@ from .focusr import *  # noqa: F401,F403
 from .graph import *  # noqa: F401,F403
 from .functional_maps import (fast_zoomout_correspondences, functional_map_from_p2p, p2p_from_functional_map,
                               soft_p2p_from_functional_map, zoomout_correspondences, zoomout_refine)
+from .map_quality import (conformal_distortion, distortion_on_mesh, isometric_distortion, map_distortion,
+                          symmetric_dirichlet)
 from .neighbours import inverse_distance_average, k_nearest_neighbours
 from .laplace_beltrami import cotangent_laplacian, laplace_beltrami_spectrum, mean_curvature, mean_curvature_normals
 from .sampling import farthest_point_sampling, voronoi_masses

@@ -223,6 +223,9 @@ SIGNATURES = {
                                    _i32p, C.POINTER(C.c_uint8), _f64p, _i64p, _f64p]),
     "pf_mesh_cluster": (C.c_int, [C.c_void_p, _f64p, C.c_int64, _i32p, C.c_int64, _f64p, _i64p, C.c_int64, C.c_int32, C.c_uint32,
                                   _f64p, _i32p, _i32p, _f64p, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p, _i64p, _f64p]),
+    "pf_map_distortion": (C.c_int, [C.c_void_p, _f64p, C.c_int64, _i32p, C.c_int64, _f64p, C.c_int64, _f64p, _i32p, _f64p, C.c_int32,
+                                    _f64p, _f64p, C.POINTER(C.c_uint8), _f64p, _f64p, C.POINTER(C.c_uint8), _i32p, _f64p, _f64p,
+                                    _i64p, _f64p]),
 }
 
 _lib = None
@@ -701,6 +704,48 @@ class Context(object):
         return {"labels": out_labels, "centroids": out_c, "rep": rep, "count": count, "changed": changed[:run].copy(),
                 "n_iter_run": int(report[0]), "faces": out_f[:kept].copy(), "face_src": src[:kept].copy(),
                 "votes": votes[:kept].copy(), "n_candidate_faces": int(report[2]), "report": report, "device_ms": ms.value}
+
+    # ---- map distortion and coverage ---------------------------------------------------
+    def map_distortion(self, src_points, src_faces, tgt_points, map_vertices, map_weights=None, tgt_normals=None):
+        """`pf_map_distortion` of a correspondence from the triangle mesh (src_points (n, 3) f64, src_faces (m, 3) i32) onto
+        tgt_points (k, 3) f64: map_vertices (n,) or (n, 1) i32 is a vertex map, (n, 3) with map_weights (n, 3) f64 a surface
+        map (vertices / bary); a row that starts with -1 is unmapped.  tgt_normals (k, 3) f64 or None: without them nothing is
+        flagged as flipped.  A dict with `face_sigma` (m, 2), `face_area_ratio` (m,), `face_flags` (m,) uint8 (1 valid |
+        2 collapsed | 4 flipped | 8 unmapped corner), `vertex_area` (n,), `vertex_sigma` (n, 2), `vertex_flags` (n,) uint8,
+        `target_count` (k,) int32, `target_premass` (k,), `totals` (8,), `report` (8,) int64 and `device_ms`.  Only the
+        shapes are checked here; the library refuses indices out of range and non-finite values of mapped rows (PF_E_ARG)
+        and a face that repeats a vertex (PF_E_DEGENERATE)."""
+        pts, tgt = _c_f64(src_points), _c_f64(tgt_points)
+        f = np.ascontiguousarray(src_faces, dtype=np.int32)
+        if pts.ndim != 2 or pts.shape[1] != 3 or tgt.ndim != 2 or tgt.shape[1] != 3 or f.ndim != 2 or f.shape[1] != 3:
+            raise ValueError("points must be (n, 3) and faces (m, 3)")
+        n, m, k = pts.shape[0], f.shape[0], tgt.shape[0]
+        mv = np.ascontiguousarray(map_vertices, dtype=np.int32)
+        if mv.ndim == 1:
+            mv = mv.reshape(-1, 1)
+        if mv.ndim != 2 or mv.shape[0] != n or mv.shape[1] not in (1, 3):
+            raise ValueError("map_vertices must be (n,), (n, 1) or (n, 3)")
+        c = mv.shape[1]
+        mw = None
+        if c == 3:
+            if map_weights is None:
+                raise ValueError("a map of 3 corners needs map_weights (n, 3)")
+            mw = _c_f64(map_weights, (n, 3))
+        nrm = None if tgt_normals is None else _c_f64(tgt_normals, (k, 3))
+        u8p = C.POINTER(C.c_uint8)
+        out = {"face_sigma": np.empty((m, 2)), "face_area_ratio": np.empty(m), "face_flags": np.empty(m, dtype=np.uint8),
+               "vertex_area": np.empty(n), "vertex_sigma": np.empty((n, 2)), "vertex_flags": np.empty(n, dtype=np.uint8),
+               "target_count": np.empty(k, dtype=np.int32), "target_premass": np.empty(k), "totals": np.zeros(8),
+               "report": np.zeros(8, dtype=np.int64)}
+        ms = C.c_double(0.0)
+        _check(self._lib.pf_map_distortion(
+            self._h, _f64(pts), n, f.ctypes.data_as(_i32p), m, _f64(tgt), k, None if nrm is None else _f64(nrm),
+            mv.ctypes.data_as(_i32p), None if mw is None else _f64(mw), c, _f64(out["face_sigma"]), _f64(out["face_area_ratio"]),
+            out["face_flags"].ctypes.data_as(u8p), _f64(out["vertex_area"]), _f64(out["vertex_sigma"]),
+            out["vertex_flags"].ctypes.data_as(u8p), out["target_count"].ctypes.data_as(_i32p), _f64(out["target_premass"]),
+            _f64(out["totals"]), out["report"].ctypes.data_as(_i64p), C.byref(ms)))
+        out["device_ms"] = ms.value
+        return out
 
     def assign(self, rows, cols, return_duals=False):
         """Optimal one-to-one assignment on Euclidean costs (`pf_assign`): col_of_row (int64, n_rows) minimising

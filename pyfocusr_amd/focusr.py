@@ -341,6 +341,29 @@ class Focusr(object):
         self.zoomout_target_idx_for_each_source_pt = T
         self.functional_map = Cm
 
+    def map_quality(self, kind="nearest", orientation=True):
+        """`map_distortion` of a correspondence this object holds, from the source mesh onto the target mesh: "nearest"
+        judges `corresponding_target_idx_for_each_source_pt`, "surface" the vertices and weights that
+        `get_surface_correspondence` left.  Opt-in: `align_maps()` does not call it, and it changes no attribute.
+        ValueError when the correspondence asked for has not been computed."""
+        from .map_quality import map_distortion
+
+        if kind not in ("nearest", "surface"):
+            raise ValueError("kind must be \"nearest\" or \"surface\", not %r" % (kind,))
+        if kind == "nearest":
+            if self.corresponding_target_idx_for_each_source_pt is None:
+                raise ValueError("no correspondences yet: run align_maps() first")
+            source, target = self.graph_source.vtk_mesh, self.graph_target.vtk_mesh
+            idx = np.asarray(self.corresponding_target_idx_for_each_source_pt)
+            return map_distortion(source, target, vertex_map=idx, orientation=orientation, ctx=self._ctx)
+        vertices = getattr(self, "corresponding_target_vertices_for_each_source_pt", None)
+        bary = getattr(self, "corresponding_target_bary_for_each_source_pt", None)
+        if vertices is None or bary is None:
+            raise ValueError("no surface correspondence yet: run get_surface_correspondence() or "
+                             "get_surface_final_node_locations() first")
+        source, target = self.graph_source.vtk_mesh, self.graph_target.vtk_mesh
+        return map_distortion(source, target, surface_map=(vertices, bary), orientation=orientation, ctx=self._ctx)
+
     def get_weighted_final_node_locations(self, n_closest_pts=3):
         """focusr.py:401-426: every source point goes to the inverse-distance-weighted average of the
         `n_closest_pts` target vertices nearest to its projection (a coincident vertex wins outright).
