@@ -85,8 +85,10 @@ typedef struct pf_timing {
 
 /* ---- context -------------------------------------------------------------------------- */
 int pf_version(void);
-/* Debugging aid, process-wide, off by default: on != 0 fills every block the library's device memory pool hands out with
- * 0xFF bytes (NaN as a floating-point number, -1 as an integer) before its first use, on the stream that asked for it.
+/* Debugging aid, process-wide, off by default: on = 1 fills every block the library's device memory pool hands out with
+ * 0xFF bytes (NaN as a floating-point number, -1 as an integer) before its first use, on the stream that asked for it;
+ * on = 2 fills it with zero bytes instead (for readers of blocks that are set to all-ones on purpose); 0 is off, any
+ * other value acts like 1.
  * Results do not change - nothing in the library reads pool memory it has not written - and a run that does change has
  * found a reader of uninitialised memory.  Costs one fill launch per allocation while on, nothing while off. */
 int pf_pool_poison(int on);

@@ -363,8 +363,12 @@ def persist_enable(on=True):
 
 def pool_poison(on=True):
     """Process-wide debugging switch (off by default): every block the device memory pool hands out is filled with
-    0xFF bytes (NaN / -1) before its first use.  Results are bit-identical either way; a difference is a bug."""
-    _check(load_library().pf_pool_poison(int(bool(on))))
+    0xFF bytes (NaN / -1) before its first use with `on` = 1 or True, with zero bytes with `on` = 2; 0 or False is off.
+    Results are bit-identical in every mode; a difference is a bug."""
+    on = int(on)
+    if on not in (0, 1, 2):
+        raise ValueError("pool_poison: 0 (off), 1 (0xFF bytes) or 2 (zero bytes), got %r" % (on,))
+    _check(load_library().pf_pool_poison(on))
 
 
 def orth_one_launch(on=True):

@@ -97,17 +97,21 @@ hipStream_t pf_stream_b(pf_ctx* c) {
     return c->stream_b;
 }
 
-// pf_pool_poison: every block pf_malloc hands out is first filled with 0xFF bytes (a NaN as a double or a float, -1 as an
-// integer) on the stream it was asked for - at its place in the order when launches are being recorded.  Whoever reads
-// a block of the pool before writing it then shows.  A pair build takes blocks on the ctx stream for kernels of its side
-// stream (pf_reorder.hip) and the other way round: the ctx's other stream waits for the fill as well.
+// pf_pool_poison: every block pf_malloc hands out is first filled - mode 1 with 0xFF bytes (a NaN as a double or a float,
+// -1 as an integer), mode 2 with zero bytes - on the stream it was asked for, at its place in the order when launches are
+// being recorded.  Whoever reads a block of the pool before writing it then shows: a reader that needs zeros breaks under
+// 0xFF, one that needs all-ones (the blocks set to 0xFF or 0x7F on purpose: pf_assign's owner / win, pf_mesh_cluster's
+// rep_d2, the 1-NN grid's ext words) breaks under zeros, and zero as an index stays in bounds.  A pair build takes blocks
+// on the ctx stream for kernels of its side stream (pf_reorder.hip) and the other way round: the ctx's other stream waits
+// for the fill as well.
 static std::atomic<int> g_pool_poison{0};
 
 static hipError_t pf_malloc_block(hipStream_t st, void** p, size_t bytes);
 
-static hipError_t poison_block(hipStream_t st, void* p, size_t bytes) {
+static hipError_t poison_block(hipStream_t st, void* p, size_t bytes, int mode) {
     const int64_t words = (int64_t)(((std::max<size_t>(bytes, 1) + 255) & ~(size_t)255) / 4);  // (the block's own size)
-    pfl::launch<pfl::k_fill_words>(dim3((unsigned)((words + 1023) / 1024)), dim3(256), 0, st, static_cast<uint32_t*>(p), words, 0xFFFFFFFFu);
+    pfl::launch<pfl::k_fill_words>(dim3((unsigned)((words + 1023) / 1024)), dim3(256), 0, st, static_cast<uint32_t*>(p), words,
+                                    mode == 2 ? 0u : 0xFFFFFFFFu);
     pf_ctx* c = ctx_of_stream(st);
     if (c && c->stream_b) {
         if (!c->poison_ev && hipEventCreateWithFlags(&c->poison_ev, hipEventDisableTiming) != hipSuccess) return hipGetLastError();
@@ -123,7 +127,8 @@ static hipError_t poison_block(hipStream_t st, void* p, size_t bytes) {
 
 hipError_t pf_malloc(hipStream_t st, void** p, size_t bytes) {
     const hipError_t e = pf_malloc_block(st, p, bytes);
-    if (e == hipSuccess && g_pool_poison.load(std::memory_order_relaxed)) return poison_block(st, *p, bytes);
+    const int mode = g_pool_poison.load(std::memory_order_relaxed);
+    if (e == hipSuccess && mode) return poison_block(st, *p, bytes, mode);
     return e;
 }
 
@@ -261,7 +266,7 @@ extern "C" {
 int pf_version(void) { return PF_VERSION; }
 
 int pf_pool_poison(int on) {
-    g_pool_poison.store(on ? 1 : 0);
+    g_pool_poison.store(on == 2 ? 2 : on ? 1 : 0);  // 0 off, 2 zero bytes, anything else 0xFF bytes
     return PF_OK;
 }
 

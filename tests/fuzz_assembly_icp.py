@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Randomised sweep: (i) Laplacian assembly on random polygon soups (3-6 vertices per face, duplicates, degenerate
 edges, unreferenced points) bit-exact against the oracle; (ii) the ICP loop on small random pairs against the CPU
-restatement.  Not collected by pytest:  python tests/fuzz_assembly_icp.py SEED N_CASES   on the GPU box."""
+restatement.  Not collected by pytest:  python tests/fuzz_assembly_icp.py SEED N_CASES [--poison]   on the GPU box.
+`--poison`: case i runs under `pf_pool_poison(i % 3)` (off, 0xFF bytes, zero bytes); the checks are the same."""
 import os
 import sys
 import time
@@ -19,8 +20,11 @@ from pyfocusr_amd.meshgen import blob_mesh  # noqa: E402
 ctx = _hip.default_context()
 rng = np.random.default_rng(int(sys.argv[1]))
 N = int(sys.argv[2])
+POISON = "--poison" in sys.argv[3:]
 fails, t0 = 0, time.time()
 for it in range(N):
+    if POISON:
+        _hip.pool_poison(it % 3)
     try:
         n, vpf = int(rng.integers(3, 4000)), int(rng.integers(3, 7))
         F = int(rng.integers(1, 9000))

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Randomised sweep of the "next"-row kernels against their CPU restatements: CPD (E-step, affine and deformable
 registrations), closest point on a surface, graph mean filter.  Uses oracle/ as the checker, hence lives under tests/
-(not collected by pytest):  python tests/fuzz_kernels.py SEED N_ROUNDS   on the GPU box."""
+(not collected by pytest):  python tests/fuzz_kernels.py SEED N_ROUNDS [--poison]   on the GPU box.
+`--poison`: round i runs under `pf_pool_poison(i % 3)` (off, 0xFF bytes, zero bytes); the checks are the same."""
 import os
 import sys
 import time
@@ -18,6 +19,7 @@ from pyfocusr_amd.meshgen import blob_mesh  # noqa: E402
 ctx = _hip.default_context()
 rng = np.random.default_rng(int(sys.argv[1]))
 N = int(sys.argv[2])
+POISON = "--poison" in sys.argv[3:]
 fails, t0 = 0, time.time()
 
 
@@ -31,6 +33,8 @@ def check(label, fn):
 
 
 for it in range(N):
+    if POISON:
+        _hip.pool_poison(it % 3)
     D = int(rng.integers(1, 17))
     Nx, M = int(rng.integers(1, 2500)), int(rng.integers(1, 2500))
     X = rng.normal(size=(Nx, D)) * rng.uniform(0.1, 3)

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Randomised sweep of the exact KNN kernel against a left-to-right numpy brute force (indices AND squared distances
 bit-exact), over dimensions, sizes, K, alignment regimes, duplicates and degenerate extents.  Not collected by pytest:
-python tests/fuzz_knn.py SEED N_CASES   on the GPU box."""
+python tests/fuzz_knn.py SEED N_CASES [--poison]   on the GPU box.
+`--poison`: case i runs under `pf_pool_poison(i % 3)` (off, 0xFF bytes, zero bytes); the checks are the same."""
 import os
 import sys
 import time
@@ -17,10 +18,13 @@ from _knn_ref import brute  # noqa: E402  (the left-to-right brute force, shared
 ctx = _hip.default_context()
 rng = np.random.default_rng(int(sys.argv[1]))
 N = int(sys.argv[2])
+POISON = "--poison" in sys.argv[3:]
 
 
 fails, t0 = 0, time.time()
 for it in range(N):
+    if POISON:
+        _hip.pool_poison(it % 3)
     d = int(rng.integers(1, 17))
     K = int(rng.integers(1, 5)) if d <= 4 else 1
     n_ref, n_qry = int(rng.integers(K, 6000)), int(rng.integers(1, 3000))

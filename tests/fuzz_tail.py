@@ -2,7 +2,8 @@
 """Randomised sweep of the post-processing tail of `align_maps` (focusr.py:368-431) against the oracle: graph mean
 filters, second NN query, 3-NN inverse-distance locations (including exactly coincident points), on random blob pairs
 of different sizes with random initial correspondences.  Not collected by pytest:
-python tests/fuzz_tail.py SEED N_CASES   on the GPU box."""
+python tests/fuzz_tail.py SEED N_CASES [--poison]   on the GPU box.
+`--poison`: case i runs under `pf_pool_poison(i % 3)` (off, 0xFF bytes, zero bytes); the checks are the same."""
 import os
 import sys
 import time
@@ -18,8 +19,11 @@ from pyfocusr_amd.meshgen import blob_mesh  # noqa: E402
 ctx = _hip.default_context()
 rng = np.random.default_rng(int(sys.argv[1]))
 N = int(sys.argv[2])
+POISON = "--poison" in sys.argv[3:]
 fails, t0 = 0, time.time()
 for it in range(N):
+    if POISON:
+        _hip.pool_poison(it % 3)
     try:
         nt, ns = int(rng.integers(100, 3000)), int(rng.integers(100, 3000))
         a, b = blob_mesh(nt, seed=int(rng.integers(0, 10**6))), blob_mesh(ns, seed=int(rng.integers(0, 10**6)))

@@ -2,7 +2,8 @@
 rings - on the device (run with `-m gpu` on an MI355X):
 
 * nothing reads memory of the library's pool before writing it: with `pf_pool_poison(1)` every block the pool hands out
-  starts as 0xFF bytes (NaN), and single, paired, multi-component, Lanczos and Arnoldi solves give the same bits;
+  starts as 0xFF bytes (NaN), with `pf_pool_poison(2)` as zero bytes, and single, paired, multi-component, Lanczos and
+  Arnoldi solves give the same bits (the other units: tests/test_pool_hygiene.py);
 * the head of a pair solve in shared launches leaves each graph's arithmetic alone: `eigs_smallest2` equals two
   `eigs_smallest` calls, in both orders, with one null vector beside two;
 * CSR(W) with and without rows that lose a repeated directed edge: against the oracle, alone and in pair builds, and the
@@ -130,17 +131,18 @@ def test_poisoned_pool_changes_nothing(golden, hip, ctx, case):
     lib = hip.load_library()
     results = {}
     try:
-        for on in (0, 1):
+        for on in (0, 1, 2):  # off, 0xFF bytes, zero bytes
             assert lib.pf_pool_poison(on) == 0
             results[on] = run()
     finally:
         lib.pf_pool_poison(0)
-    assert len(results[0]) == len(results[1])
-    for (v0, x0, m0, r0), (v1, x1, m1, r1) in zip(results[0], results[1]):
-        assert len(v0) > 0 and np.array_equal(v0, v1)
-        assert np.array_equal(x0, x1)
-        assert m0 == m1
-        assert np.all(np.isfinite(r0)) and np.all(np.isfinite(r1)) and np.all(np.isfinite(x1))
+    for on in (1, 2):
+        assert len(results[0]) == len(results[on])
+        for (v0, x0, m0, r0), (v1, x1, m1, r1) in zip(results[0], results[on]):
+            assert len(v0) > 0 and np.array_equal(v0, v1)
+            assert np.array_equal(x0, x1)
+            assert m0 == m1
+            assert np.all(np.isfinite(r0)) and np.all(np.isfinite(r1)) and np.all(np.isfinite(x1))
 
 
 # ------------------------------------------------------------------------------------------------ the pair's head
