@@ -33,35 +33,39 @@ class PfError(RuntimeError):
         self.code = code
 
 
-class GraphInfo(C.Structure):
+class _Struct(C.Structure):
+    """A structure the library fills in; `as_dict()` gives its fields as Python ints and floats."""
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+class GraphInfo(_Struct):
     _fields_ = [("n", C.c_int64), ("n_faces", C.c_int64), ("nnz_w", C.c_int64), ("nnz_l", C.c_int64),
                 ("is_symmetric", C.c_int32), ("n_isolated", C.c_int32), ("n_components", C.c_int32),
                 ("max_degree", C.c_int32), ("sell_entries", C.c_int64), ("n_pad", C.c_int64), ("n_oneway", C.c_int64),
                 ("spectral_bound", C.c_double)]
 
 
-class EigsStats(C.Structure):
+class EigsStats(_Struct):
     _fields_ = [("matvecs", C.c_int64), ("outer_steps", C.c_int32), ("restarts", C.c_int32), ("filter_resets", C.c_int32),
                 ("degree", C.c_int32), ("n_null", C.c_int32), ("cut", C.c_double), ("max_residual", C.c_double),
                 ("second_passes", C.c_int32), ("mode", C.c_int32), ("local_steps", C.c_int32), ("reserved", C.c_int32)]
 
 
-class Timing(C.Structure):
+class Timing(_Struct):
     _fields_ = [("op_ms", C.c_double), ("op_launches", C.c_int64), ("op_bytes", C.c_double), ("knn_ms", C.c_double),
                 ("build_ms", C.c_double), ("persist_ms", C.c_double), ("persist_launches", C.c_int64),
                 ("persist_steps", C.c_int64), ("persist_bytes", C.c_double), ("persist_lds_bytes", C.c_double)]
 
 
-class AssignStats(C.Structure):
+class AssignStats(_Struct):
     _fields_ = [("phases", C.c_int32), ("dense_passes", C.c_int32), ("rounds", C.c_int64), ("bids", C.c_int64),
                 ("dense_bids", C.c_int64), ("candidate_edges", C.c_int64), ("launches", C.c_int64),
                 ("device_bytes", C.c_int64), ("k", C.c_int32), ("eps_floor_hit", C.c_int32), ("eps_initial", C.c_double),
                 ("eps_final", C.c_double), ("eps_floor", C.c_double), ("total_cost", C.c_double),
                 ("gap_bound", C.c_double), ("lower_bound", C.c_double), ("ms_candidates", C.c_double),
                 ("ms_auction", C.c_double), ("ms_certificate", C.c_double)]
-
-    def as_dict(self):
-        return {name: getattr(self, name) for name, _ in self._fields_}
 
 
 # name -> (restype, argtypes): every symbol include/pyfocusr_hip.h declares.
@@ -287,7 +291,9 @@ class _PinnedBlock(object):
 
 _pinned_free = {}  # nbytes -> [ptr]: blocks of collected arrays, reused by the next result of the same size
 _pinned_cached = [0]
-_pinned_lock = threading.Lock()  # (compute_spectra runs one host thread per context; arrays are collected on any thread)
+# (compute_spectra runs one host thread per context; arrays are collected on any thread.)  Re-entrant: the locked region of
+# _pinned_release allocates, a collection started there can finalise another block on the same thread, and that comes back here
+_pinned_lock = threading.RLock()
 # page-locked memory kept for reuse.  A 1M-vertex pair with k = 10 turns over four 84 MB blocks per pipeline step: with the
 # 256 MiB of round 3 whether they fitted beside what smaller workloads had left behind decided between 80 and 90 ms per
 # step (two hipHostMalloc / hipHostFree of 84 MB each) - 1 GiB, and blocks of OTHER sizes make room first.
@@ -398,7 +404,7 @@ def persist_clock(ctx, reset=False):
     return ms.value, n.value
 
 
-class _PersistInfo(C.Structure):
+class _PersistInfo(_Struct):
     _fields_ = [("enabled", C.c_int32), ("two_step", C.c_int32), ("owner", C.c_int32), ("timeouts", C.c_int32),
                 ("launches", C.c_int64), ("launches_two_step", C.c_int64), ("suspended_for", C.c_int32), ("rearms", C.c_int32),
                 ("owner_switches", C.c_int32), ("hold_ticks", C.c_int32)]
@@ -408,7 +414,7 @@ def persist_state(ctx=None):
     """pf_persist_state as a dict: is the resident path on, who owns it, how many waits ran out, launch counters."""
     info = _PersistInfo()
     _check(load_library().pf_persist_state(None if ctx is None else ctx._h, C.byref(info)))
-    return {name: int(getattr(info, name)) for name, _ in _PersistInfo._fields_}
+    return info.as_dict()
 
 
 def persist_test_hook(n_launches=1):
@@ -421,8 +427,29 @@ def _check(code):
         raise PfError(code, load_library().pf_last_error().decode("utf-8", "replace"))
 
 
+_POINTER_OF = {np.dtype(t): C.POINTER(c) for t, c in ((np.float64, C.c_double), (np.int32, C.c_int32), (np.int64, C.c_int64),
+                                                        (np.uint8, C.c_uint8), (np.uint64, C.c_uint64))}
+
+
+def _ptr(a):
+    """The typed pointer to a C-contiguous array, chosen by its dtype, so that the `argtypes` of SIGNATURES check what
+    the library is handed (ctypes.ArgumentError on a mismatch); None (an output nobody asked for) stays None."""
+    if a is None:
+        return None
+    try:
+        ptype = _POINTER_OF[a.dtype]
+    except KeyError:
+        raise TypeError("no pointer type for dtype %s: the library takes float64, int32, int64, uint8 and uint64" % a.dtype)
+    if not a.flags.c_contiguous:
+        raise ValueError("the library needs a C-contiguous array, not a strided view")
+    return a.ctypes.data_as(ptype)
+
+
 def _f64(a):
-    return a.ctypes.data_as(_f64p)
+    """`_ptr` of an array that must hold float64."""
+    if a is not None and a.dtype != np.float64:
+        raise TypeError("a float64 array is needed, not %s" % a.dtype)
+    return _ptr(a)
 
 
 def _c_f64(a, shape=None):
@@ -430,6 +457,49 @@ def _c_f64(a, shape=None):
     if shape is not None and a.shape != shape:
         raise ValueError("expected shape %r, got %r" % (shape, a.shape))
     return a
+
+
+def _c_i32(a):
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def _c_i64(a):
+    return np.ascontiguousarray(a, dtype=np.int64)
+
+
+_EQUAL_D = "%s must be (n, d) arrays with equal d"
+
+
+def _same_d(a, b, message=_EQUAL_D % "ref and qry"):
+    """Two point sets as contiguous f64 (n, d) arrays of one d."""
+    a, b = _c_f64(a), _c_f64(b)
+    if a.ndim != 2 or b.ndim != 2 or a.shape[1] != b.shape[1]:
+        raise ValueError(message)
+    return a, b
+
+
+def _queries(a, noun="queries", message=None):
+    """Query points as a contiguous f64 array that must be (n, 3) with n > 0."""
+    a = _c_f64(a)
+    if a.ndim != 2 or a.shape[1] != 3 or a.shape[0] == 0:
+        raise ValueError(message or "%s must be a non-empty (n, 3) array" % noun)
+    return a
+
+
+def _rays(origins, directions):
+    message = "origins and directions must be non-empty (n, 3) arrays of the same length"
+    o, d = _queries(origins, message=message), _c_f64(directions)
+    if d.shape != o.shape:
+        raise ValueError(message)
+    return o, d
+
+
+def _upload_arrays(points, faces, empty_ok=True):
+    """(points (n, 3) f64, faces (F, v) i32, v) of a mesh that goes to the device; v is 3 where there is no face."""
+    pts, f = _c_f64(points).reshape(-1, 3), _c_i32(faces)
+    if f.ndim != 2 or not (empty_ok or f.shape[0]):
+        raise ValueError("faces must be %s" % ("(F, verts_per_face)" if empty_ok else "a non-empty (F, verts_per_face) array"))
+    return pts, f, f.shape[1] if f.shape[0] else 3
 
 
 def degenerate_extent_message(target_points, source_points):
@@ -455,7 +525,7 @@ def check_knn_topk(ref, qry, k):
     """The argument checks of `Context.knn_topk`, which need no library: ValueError, or k as an int."""
     ref_shape, qry_shape = np.shape(ref), np.shape(qry)
     if len(ref_shape) != 2 or len(qry_shape) != 2 or ref_shape[1] != qry_shape[1]:
-        raise ValueError("ref and qry must be (n, d) arrays with equal d")
+        raise ValueError(_EQUAL_D % "ref and qry")
     if not 1 <= ref_shape[1] <= KNN_TOPK_MAX_D:
         raise ValueError("d = %d out of range (1 .. %d)" % (ref_shape[1], KNN_TOPK_MAX_D))
     k = int(k)
@@ -508,9 +578,7 @@ class Context(object):
     def timing(self, reset=False):
         t = Timing()
         _check(self._lib.pf_timing_get(self._h, C.byref(t), int(bool(reset))))
-        return dict(op_ms=t.op_ms, op_launches=int(t.op_launches), op_bytes=t.op_bytes, knn_ms=t.knn_ms,
-                    build_ms=t.build_ms, persist_ms=t.persist_ms, persist_launches=int(t.persist_launches),
-                    persist_steps=int(t.persist_steps), persist_bytes=t.persist_bytes, persist_lds_bytes=t.persist_lds_bytes)
+        return t.as_dict()
 
     # ---- nearest neighbour -------------------------------------------------------------
     def knn_mode(self, mode):
@@ -532,24 +600,20 @@ class Context(object):
 
     def knn1(self, ref, qry, return_d2=False):
         """Index (int64) of the nearest `ref` row for every `qry` row."""
-        ref, qry = _c_f64(ref), _c_f64(qry)
-        if ref.ndim != 2 or qry.ndim != 2 or ref.shape[1] != qry.shape[1]:
-            raise ValueError("ref and qry must be (n, d) arrays with equal d")
+        ref, qry = _same_d(ref, qry)
         idx = np.empty(qry.shape[0], dtype=np.int64)
         d2 = np.empty(qry.shape[0], dtype=np.float64) if return_d2 else None
         _check(self._lib.pf_knn1(self._h, _f64(ref), ref.shape[0], _f64(qry), qry.shape[0], ref.shape[1],
-                                 idx.ctypes.data_as(_i64p), _f64(d2) if return_d2 else None))
+                                 _ptr(idx), _f64(d2)))
         return (idx, d2) if return_d2 else idx
 
     def knn1_wide(self, ref, qry, return_d2=False):
         """`knn1` for 1 <= d <= 128 by the tiled exhaustive scan (`pf_knn1_wide`): the same arithmetic, the same bits."""
-        ref, qry = _c_f64(ref), _c_f64(qry)
-        if ref.ndim != 2 or qry.ndim != 2 or ref.shape[1] != qry.shape[1]:
-            raise ValueError("ref and qry must be (n, d) arrays with equal d")
+        ref, qry = _same_d(ref, qry)
         idx = np.empty(qry.shape[0], dtype=np.int64)
         d2 = np.empty(qry.shape[0], dtype=np.float64) if return_d2 else None
         _check(self._lib.pf_knn1_wide(self._h, _f64(ref), ref.shape[0], _f64(qry), qry.shape[0], ref.shape[1],
-                                      idx.ctypes.data_as(_i64p), _f64(d2) if return_d2 else None))
+                                      _ptr(idx), _f64(d2)))
         return (idx, d2) if return_d2 else idx
 
     def knn1_wide_count(self, enable_counting=False):
@@ -571,8 +635,7 @@ class Context(object):
         sel = np.empty(max(m, 0), dtype=np.int64)
         owner = np.empty(n, dtype=np.int32) if return_owner else None
         d2 = np.empty(n, dtype=np.float64) if return_d2 else None
-        _check(self._lib.pf_fps(self._h, _f64(pts), n, pts.shape[1], m, int(start), sel.ctypes.data_as(_i64p),
-                                owner.ctypes.data_as(_i32p) if return_owner else None, _f64(d2) if return_d2 else None))
+        _check(self._lib.pf_fps(self._h, _f64(pts), n, pts.shape[1], m, int(start), _ptr(sel), _ptr(owner), _f64(d2)))
         out = (sel,) + ((owner,) if return_owner else ()) + ((d2,) if return_d2 else ())
         return out if len(out) > 1 else sel
 
@@ -607,7 +670,7 @@ class Context(object):
         boundary | non-manifold | inconsistent edges | clipped vertices, and `device_ms`.  Only the shapes are checked
         here (`curvature.discrete_curvatures` checks the values); the library refuses an index out of range (PF_E_ARG)."""
         pts = _c_f64(points)
-        f = np.ascontiguousarray(faces, dtype=np.int32)
+        f = _c_i32(faces)
         if pts.ndim != 2 or pts.shape[1] != 3 or f.ndim != 2 or f.shape[1] != 3:
             raise ValueError("points must be (n, 3) and faces (m, 3)")
         n = pts.shape[0]
@@ -616,10 +679,9 @@ class Context(object):
         boundary = np.empty(n, dtype=np.uint8)
         topology = np.zeros(5, dtype=np.int64)
         ms = C.c_double(0.0)
-        _check(self._lib.pf_curvatures(self._h, _f64(pts), n, f.ctypes.data_as(_i32p), f.shape[0], _f64(out["area"]),
+        _check(self._lib.pf_curvatures(self._h, _f64(pts), n, _ptr(f), f.shape[0], _f64(out["area"]),
                                        _f64(out["gaussian"]), _f64(out["mean"]), _f64(out["tensor"]), _f64(out["k"]),
-                                       _f64(out["dirs"]), _f64(out["normals"]), boundary.ctypes.data_as(C.POINTER(C.c_uint8)),
-                                       topology.ctypes.data_as(_i64p), C.byref(ms)))
+                                       _f64(out["dirs"]), _f64(out["normals"]), _ptr(boundary), _ptr(topology), C.byref(ms)))
         out.update(boundary=boundary.astype(bool), topology=topology, device_ms=ms.value)
         return out
 
@@ -631,7 +693,7 @@ class Context(object):
         (P,) bool, `patch_volume` (P,), `report` (8,) int64 = edges | boundary | non-manifold | inconsistent edges |
         patches | loops | rounds | loop rounds, and `device_ms`.  Only the shapes are checked here; the library refuses
         an index out of range (PF_E_ARG) and a face that repeats a vertex (PF_E_DEGENERATE)."""
-        f = np.ascontiguousarray(faces, dtype=np.int32)
+        f = _c_i32(faces)
         if f.ndim != 2 or f.shape[1] != 3:
             raise ValueError("faces must be (m, 3)")
         n, m = int(n_points), f.shape[0]
@@ -640,16 +702,14 @@ class Context(object):
             pts = _c_f64(points)
             if pts.shape != (n, 3):
                 raise ValueError("points must be (n_points, 3)")
-        u8p = C.POINTER(C.c_uint8)
         nbr, loop = np.empty((m, 3), dtype=np.int32), np.empty((m, 3), dtype=np.int32)
         patch, flip = np.empty(m, dtype=np.int32), np.empty(m, dtype=np.uint8)
         orientable, volume = np.empty(m, dtype=np.uint8), np.empty(m)
         report = np.zeros(8, dtype=np.int64)
         ms = C.c_double(0.0)
-        _check(self._lib.pf_mesh_topology(self._h, None if pts is None else _f64(pts), n, f.ctypes.data_as(_i32p), m,
-                                          PF_TOPOLOGY_OUTWARD if outward else 0, nbr.ctypes.data_as(_i32p),
-                                          patch.ctypes.data_as(_i32p), flip.ctypes.data_as(u8p), loop.ctypes.data_as(_i32p),
-                                          orientable.ctypes.data_as(u8p), _f64(volume), report.ctypes.data_as(_i64p), C.byref(ms)))
+        _check(self._lib.pf_mesh_topology(self._h, _f64(pts), n, _ptr(f), m, PF_TOPOLOGY_OUTWARD if outward else 0, _ptr(nbr),
+                                          _ptr(patch), _ptr(flip), _ptr(loop), _ptr(orientable), _f64(volume), _ptr(report),
+                                          C.byref(ms)))
         P = int(report[4])
         return {"face_neighbours": nbr, "patch": patch, "flip": flip.astype(bool), "boundary_loop": loop,
                 "patch_orientable": orientable[:P].astype(bool), "patch_volume": volume[:P].copy(), "report": report,
@@ -669,7 +729,7 @@ class Context(object):
         if pts.ndim != 2 or pts.shape[1] != 3:
             raise ValueError("points must be (n, 3)")
         n = pts.shape[0]
-        f = np.zeros((0, 3), dtype=np.int32) if faces is None else np.ascontiguousarray(faces, dtype=np.int32)
+        f = np.zeros((0, 3), dtype=np.int32) if faces is None else _c_i32(faces)
         if f.ndim != 2 or f.shape[1] != 3:
             raise ValueError("faces must be (f, 3)")
         mass = _c_f64(mass, (n,))
@@ -677,7 +737,7 @@ class Context(object):
             raise ValueError("give either seeds or centroids")
         sel = cen = lab = None
         if seeds is not None:
-            sel = np.ascontiguousarray(seeds, dtype=np.int64)
+            sel = _c_i64(seeds)
             if sel.ndim != 1:
                 raise ValueError("seeds must be a vector of vertex indices")
             m = sel.shape[0]
@@ -687,7 +747,7 @@ class Context(object):
                 raise ValueError("centroids must be (m, 3)")
             m = cen.shape[0]
         if labels is not None:
-            lab = np.ascontiguousarray(labels, dtype=np.int32)
+            lab = _c_i32(labels)
             if lab.shape != (n,):
                 raise ValueError("labels must be (n,)")
         n_iter, k = int(n_iter), f.shape[0]
@@ -698,12 +758,9 @@ class Context(object):
         report = np.zeros(8, dtype=np.int64)
         ms = C.c_double(0.0)
         _check(self._lib.pf_mesh_cluster(
-            self._h, _f64(pts), n, f.ctypes.data_as(_i32p) if k else None, k, _f64(mass),
-            None if sel is None else sel.ctypes.data_as(_i64p), m, n_iter, PF_CLUSTER_UPDATE_ONLY if update_only else 0,
-            None if cen is None else _f64(cen), None if lab is None else lab.ctypes.data_as(_i32p),
-            out_labels.ctypes.data_as(_i32p), _f64(out_c), rep.ctypes.data_as(_i32p), count.ctypes.data_as(_i32p),
-            changed.ctypes.data_as(_i32p), out_f.ctypes.data_as(_i32p), src.ctypes.data_as(_i32p), votes.ctypes.data_as(_i32p),
-            report.ctypes.data_as(_i64p), C.byref(ms)))
+            self._h, _f64(pts), n, _ptr(f if k else None), k, _f64(mass), _ptr(sel), m, n_iter,
+            PF_CLUSTER_UPDATE_ONLY if update_only else 0, _f64(cen), _ptr(lab), _ptr(out_labels), _f64(out_c), _ptr(rep),
+            _ptr(count), _ptr(changed), _ptr(out_f), _ptr(src), _ptr(votes), _ptr(report), C.byref(ms)))
         run, kept = (0 if update_only else int(report[0])), int(report[1])
         return {"labels": out_labels, "centroids": out_c, "rep": rep, "count": count, "changed": changed[:run].copy(),
                 "n_iter_run": int(report[0]), "faces": out_f[:kept].copy(), "face_src": src[:kept].copy(),
@@ -720,11 +777,11 @@ class Context(object):
         shapes are checked here; the library refuses indices out of range and non-finite values of mapped rows (PF_E_ARG)
         and a face that repeats a vertex (PF_E_DEGENERATE)."""
         pts, tgt = _c_f64(src_points), _c_f64(tgt_points)
-        f = np.ascontiguousarray(src_faces, dtype=np.int32)
+        f = _c_i32(src_faces)
         if pts.ndim != 2 or pts.shape[1] != 3 or tgt.ndim != 2 or tgt.shape[1] != 3 or f.ndim != 2 or f.shape[1] != 3:
             raise ValueError("points must be (n, 3) and faces (m, 3)")
         n, m, k = pts.shape[0], f.shape[0], tgt.shape[0]
-        mv = np.ascontiguousarray(map_vertices, dtype=np.int32)
+        mv = _c_i32(map_vertices)
         if mv.ndim == 1:
             mv = mv.reshape(-1, 1)
         if mv.ndim != 2 or mv.shape[0] != n or mv.shape[1] not in (1, 3):
@@ -736,18 +793,16 @@ class Context(object):
                 raise ValueError("a map of 3 corners needs map_weights (n, 3)")
             mw = _c_f64(map_weights, (n, 3))
         nrm = None if tgt_normals is None else _c_f64(tgt_normals, (k, 3))
-        u8p = C.POINTER(C.c_uint8)
         out = {"face_sigma": np.empty((m, 2)), "face_area_ratio": np.empty(m), "face_flags": np.empty(m, dtype=np.uint8),
                "vertex_area": np.empty(n), "vertex_sigma": np.empty((n, 2)), "vertex_flags": np.empty(n, dtype=np.uint8),
                "target_count": np.empty(k, dtype=np.int32), "target_premass": np.empty(k), "totals": np.zeros(8),
                "report": np.zeros(8, dtype=np.int64)}
         ms = C.c_double(0.0)
         _check(self._lib.pf_map_distortion(
-            self._h, _f64(pts), n, f.ctypes.data_as(_i32p), m, _f64(tgt), k, None if nrm is None else _f64(nrm),
-            mv.ctypes.data_as(_i32p), None if mw is None else _f64(mw), c, _f64(out["face_sigma"]), _f64(out["face_area_ratio"]),
-            out["face_flags"].ctypes.data_as(u8p), _f64(out["vertex_area"]), _f64(out["vertex_sigma"]),
-            out["vertex_flags"].ctypes.data_as(u8p), out["target_count"].ctypes.data_as(_i32p), _f64(out["target_premass"]),
-            _f64(out["totals"]), out["report"].ctypes.data_as(_i64p), C.byref(ms)))
+            self._h, _f64(pts), n, _ptr(f), m, _f64(tgt), k, _f64(nrm), _ptr(mv), _f64(mw), c, _f64(out["face_sigma"]),
+            _f64(out["face_area_ratio"]), _ptr(out["face_flags"]), _f64(out["vertex_area"]), _f64(out["vertex_sigma"]),
+            _ptr(out["vertex_flags"]), _ptr(out["target_count"]), _f64(out["target_premass"]), _f64(out["totals"]),
+            _ptr(out["report"]), C.byref(ms)))
         out["device_ms"] = ms.value
         return out
 
@@ -756,9 +811,7 @@ class Context(object):
         sum_i ||rows[i] - cols[col_of_row[i]]||, n_rows <= n_cols, 1 <= d <= 16, and the call's AssignStats (total_cost,
         gap_bound, ...).  return_duals: also u (n_rows) and v (n_cols) with u_i + v_j <= C_ij, v <= 0, whose slacks on the
         assigned pairs sum to stats.gap_bound.  Non-finite coordinates raise ValueError."""
-        rows, cols = _c_f64(rows), _c_f64(cols)
-        if rows.ndim != 2 or cols.ndim != 2 or rows.shape[1] != cols.shape[1]:
-            raise ValueError("rows and cols must be (n, d) arrays with equal d")
+        rows, cols = _same_d(rows, cols, _EQUAL_D % "rows and cols")
         if not (np.isfinite(rows).all() and np.isfinite(cols).all()):
             raise ValueError("coordinates must be finite")
         n_r, n_c = rows.shape[0], cols.shape[0]
@@ -766,20 +819,17 @@ class Context(object):
         u = np.empty(n_r) if return_duals else None
         v = np.empty(n_c) if return_duals else None
         stats = AssignStats()
-        _check(self._lib.pf_assign(self._h, _f64(rows), n_r, _f64(cols), n_c, rows.shape[1], col.ctypes.data_as(_i64p),
-                                   _f64(u) if return_duals else None, _f64(v) if return_duals else None,
+        _check(self._lib.pf_assign(self._h, _f64(rows), n_r, _f64(cols), n_c, rows.shape[1], _ptr(col), _f64(u), _f64(v),
                                    C.byref(stats)))
         return (col, stats, u, v) if return_duals else (col, stats)
 
     def knn(self, ref, qry, k):
         """(idx (n_qry, k) int64, squared distances (n_qry, k)), ascending by (distance, index); k <= 4, d <= 4."""
-        ref, qry = _c_f64(ref), _c_f64(qry)
-        if ref.ndim != 2 or qry.ndim != 2 or ref.shape[1] != qry.shape[1]:
-            raise ValueError("ref and qry must be (n, d) arrays with equal d")
+        ref, qry = _same_d(ref, qry)
         idx = np.empty((qry.shape[0], int(k)), dtype=np.int64)
         d2 = np.empty((qry.shape[0], int(k)), dtype=np.float64)
         _check(self._lib.pf_knn(self._h, _f64(ref), ref.shape[0], _f64(qry), qry.shape[0], ref.shape[1], int(k),
-                                idx.ctypes.data_as(_i64p), _f64(d2)))
+                                _ptr(idx), _f64(d2)))
         return idx, d2
 
     def knn_topk(self, ref, qry, k, return_d2=True):
@@ -791,40 +841,34 @@ class Context(object):
         idx = np.empty((qry.shape[0], k), dtype=np.int64)
         d2 = np.empty((qry.shape[0], k), dtype=np.float64) if return_d2 else None
         _check(self._lib.pf_knn_topk(self._h, _f64(ref), ref.shape[0], _f64(qry), qry.shape[0], ref.shape[1], k,
-                                     idx.ctypes.data_as(_i64p), _f64(d2) if return_d2 else None))
+                                     _ptr(idx), _f64(d2)))
         return (idx, d2) if return_d2 else idx
 
     def knn1_graphs(self, dev_ref, dev_qry, col_ref, scale_ref, col_qry, scale_qry, return_d2=False):
         """`knn1` on coordinates built on the device from the two graphs' resident eigenvector blocks:
         ref[:, c] = final_ref[:, col_ref[c]] * scale_ref[c], qry likewise."""
-        col_ref = np.ascontiguousarray(col_ref, dtype=np.int32)
-        col_qry = np.ascontiguousarray(col_qry, dtype=np.int32)
+        col_ref, col_qry = _c_i32(col_ref), _c_i32(col_qry)
         scale_ref, scale_qry = _c_f64(scale_ref), _c_f64(scale_qry)
         d = len(col_ref)
         if not (len(col_qry) == len(scale_ref) == len(scale_qry) == d):
             raise ValueError("col / scale arrays must share one length d")
         idx = np.empty(dev_qry.n, dtype=np.int64)
         d2 = np.empty(dev_qry.n, dtype=np.float64) if return_d2 else None
-        _check(self._lib.pf_knn1_graphs(dev_ref._h, dev_qry._h, d, col_ref.ctypes.data_as(_i32p), _f64(scale_ref),
-                                        col_qry.ctypes.data_as(_i32p), _f64(scale_qry), idx.ctypes.data_as(_i64p),
-                                        _f64(d2) if return_d2 else None))
+        _check(self._lib.pf_knn1_graphs(dev_ref._h, dev_qry._h, d, _ptr(col_ref), _f64(scale_ref), _ptr(col_qry), _f64(scale_qry),
+                                        _ptr(idx), _f64(d2)))
         return (idx, d2) if return_d2 else idx
 
     def eigsort_costs(self, dev_t, dev_s, rows_t, rows_s, k, col_t, sign_t, col_s, sign_s):
         """eigsort's c_hist, c_hist_f, c_spatial, c_spatial_f (each k x k) and the 3-D 1-NN indices of the sampled points,
         computed on the device from the two graphs' resident eigenvector blocks (`pf_eigsort_costs`)."""
-        rows_t = np.ascontiguousarray(rows_t, dtype=np.int64)
-        rows_s = np.ascontiguousarray(rows_s, dtype=np.int64)
-        col_t = np.ascontiguousarray(col_t, dtype=np.int32)
-        col_s = np.ascontiguousarray(col_s, dtype=np.int32)
+        rows_t, rows_s, col_t, col_s = _c_i64(rows_t), _c_i64(rows_s), _c_i32(col_t), _c_i32(col_s)
         sign_t, sign_s = _c_f64(sign_t), _c_f64(sign_s)
         if min(len(col_t), len(col_s), len(sign_t), len(sign_s)) < k:
             raise ValueError("eigsort_costs: k columns / signs per graph are needed")
         out = np.empty((4, int(k), int(k)), dtype=np.float64)
         idx = np.empty(len(rows_t), dtype=np.int64)
-        _check(self._lib.pf_eigsort_costs(dev_t._h, dev_s._h, rows_t.ctypes.data_as(_i64p), len(rows_t), rows_s.ctypes.data_as(_i64p),
-                                          len(rows_s), int(k), col_t.ctypes.data_as(_i32p), _f64(sign_t), col_s.ctypes.data_as(_i32p),
-                                          _f64(sign_s), _f64(out), idx.ctypes.data_as(_i64p)))
+        _check(self._lib.pf_eigsort_costs(dev_t._h, dev_s._h, _ptr(rows_t), len(rows_t), _ptr(rows_s), len(rows_s), int(k),
+                                          _ptr(col_t), _f64(sign_t), _ptr(col_s), _f64(sign_s), _f64(out), _ptr(idx)))
         if len(idx) and (idx.min() < 0 or idx.max() >= len(rows_s)):
             # a sample without extent along an axis normalises to NaN there; the search then answers every query with
             # 0x7fffffff and the kernel makes the spatial costs NaN instead of reading at that index
@@ -835,8 +879,7 @@ class Context(object):
                     return_d2=False):
         """`knn1` on coordinates built from two row-major float64 blocks already in this device's memory (integer
         addresses, row strides in doubles): block[:, col[c]] * scale[c] for c < d."""
-        col_ref = np.ascontiguousarray(col_ref, dtype=np.int32)
-        col_qry = np.ascontiguousarray(col_qry, dtype=np.int32)
+        col_ref, col_qry = _c_i32(col_ref), _c_i32(col_qry)
         scale_ref, scale_qry = _c_f64(scale_ref), _c_f64(scale_qry)
         d = len(col_ref)
         if not (len(col_qry) == len(scale_ref) == len(scale_qry) == d):
@@ -844,9 +887,8 @@ class Context(object):
         idx = np.empty(int(n_qry), dtype=np.int64)
         d2 = np.empty(int(n_qry), dtype=np.float64) if return_d2 else None
         _check(self._lib.pf_knn1_blocks(self._h, C.c_void_p(int(ref_ptr)), int(n_ref), int(ref_stride), C.c_void_p(int(qry_ptr)),
-                                        int(n_qry), int(qry_stride), d, col_ref.ctypes.data_as(_i32p), _f64(scale_ref),
-                                        col_qry.ctypes.data_as(_i32p), _f64(scale_qry), idx.ctypes.data_as(_i64p),
-                                        _f64(d2) if return_d2 else None))
+                                        int(n_qry), int(qry_stride), d, _ptr(col_ref), _f64(scale_ref), _ptr(col_qry),
+                                        _f64(scale_qry), _ptr(idx), _f64(d2)))
         return (idx, d2) if return_d2 else idx
 
     def knn_upload(self, ref, qry):
@@ -860,7 +902,7 @@ class Context(object):
     def knn_download(self):
         idx = np.empty(self._knn_nq, dtype=np.int64)
         d2 = np.empty(self._knn_nq, dtype=np.float64)
-        _check(self._lib.pf_knn_download(self._h, idx.ctypes.data_as(_i64p), _f64(d2)))
+        _check(self._lib.pf_knn_download(self._h, _ptr(idx), _f64(d2)))
         return idx, d2
 
 
@@ -879,28 +921,40 @@ def default_context(device=None):
     return _default_ctx[device]
 
 
-class DeviceMesh(object):
-    """points (n,3) f64 + faces (F,v) i32 resident in HBM (input side of the assembler)."""
+class _Handle(object):
+    """One object of the library that lives in a context's device memory.  A subclass names the library's function that
+    frees it (`_free`) and builds it with `_create`; `close()` frees it once, and so do `with`, the collector, the
+    context's own `close()` and the end of the process, whichever comes first."""
 
-    def __init__(self, points, faces, ctx=None):
+    _free = None
+    _h = None  # (also of an instance whose constructor raised before the library returned a handle: nothing to free)
+
+    def __init__(self, ctx=None):
         self.ctx = ctx if ctx is not None else default_context()
         self._lib = self.ctx._lib
-        pts = _c_f64(points).reshape(-1, 3)
-        f = np.ascontiguousarray(faces, dtype=np.int32)
-        if f.ndim != 2:
-            raise ValueError("faces must be (F, verts_per_face)")
-        h = C.c_void_p()
-        _check(self._lib.pf_mesh_upload(self.ctx._h, _f64(pts), pts.shape[0], f.ctypes.data_as(_i32p), f.shape[0],
-                                        f.shape[1] if f.shape[0] else 3, C.byref(h)))
+
+    def _adopt(self, h):
         self._h = h
-        self.n, self.n_faces = pts.shape[0], f.shape[0]
         _live_graphs.add(self)
         self.ctx._children.add(self)
 
+    def _create(self, name, *args):
+        """Call the library's constructor `name`(*args, &handle) and own the handle."""
+        h = C.c_void_p()
+        _check(getattr(self._lib, name)(*(args + (C.byref(h),))))
+        self._adopt(h)
+
     def close(self):
-        if getattr(self, "_h", None):
-            self._lib.pf_mesh_free(self._h)
-            self._h = None
+        h, self._h = self._h, None
+        if h:
+            getattr(self._lib, self._free)(h)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
 
     def __del__(self):
         try:
@@ -909,39 +963,43 @@ class DeviceMesh(object):
             pass
 
 
+class DeviceMesh(_Handle):
+    """points (n,3) f64 + faces (F,v) i32 resident in HBM (input side of the assembler)."""
+
+    _free = "pf_mesh_free"
+
+    def __init__(self, points, faces, ctx=None):
+        _Handle.__init__(self, ctx)
+        pts, f, v = _upload_arrays(points, faces)
+        self._create("pf_mesh_upload", self.ctx._h, _f64(pts), pts.shape[0], _ptr(f), f.shape[0], v)
+        self.n, self.n_faces = pts.shape[0], f.shape[0]
+
+
 def _fan_triangles(faces):
     """(F,v) polygons -> (F*(v-2), 3) triangles (0,j+1,j+2), face-major, as the device fan-triangulates them."""
     v = faces.shape[1]
     return np.stack([faces[:, [0, j + 1, j + 2]] for j in range(v - 2)], axis=1).reshape(-1, 3)
 
 
-class DeviceSurface(object):
+class DeviceSurface(_Handle):
     """Triangle soup of one mesh in HBM (Morton-sorted, chunk boxes) for exact closest-point queries
     (`pf_surface_*`): the search inside the ICP pre-alignment."""
 
+    _free = "pf_surface_free"
+
     def __init__(self, points, faces, ctx=None):
-        self.ctx = ctx if ctx is not None else default_context()
-        self._lib = self.ctx._lib
-        pts = _c_f64(points).reshape(-1, 3)
-        f = np.ascontiguousarray(faces, dtype=np.int32)
-        if f.ndim != 2 or f.shape[0] == 0:
-            raise ValueError("faces must be a non-empty (F, verts_per_face) array")
-        h = C.c_void_p()
-        _check(self._lib.pf_surface_create(self.ctx._h, _f64(pts), pts.shape[0], f.ctypes.data_as(_i32p), f.shape[0],
-                                           f.shape[1], C.byref(h)))
-        self._h = h
+        _Handle.__init__(self, ctx)
+        pts, f, v = _upload_arrays(points, faces, empty_ok=False)
+        self._create("pf_surface_create", self.ctx._h, _f64(pts), pts.shape[0], _ptr(f), f.shape[0], v)
         self.n, self.n_faces = pts.shape[0], f.shape[0]
         self.points, self.faces = pts, f  # host arrays, for pf_surface_prepare_signed and topology()
         self._topology = None  # edge counts once the signed structure is built
         self._winding_ready = False  # the dipole data of pf_surface_prepare_winding
-        _live_graphs.add(self)
-        self.ctx._children.add(self)
 
     def _prepare_signed(self):
         if self._topology is None:
             t = np.zeros(4, dtype=np.int64)
-            _check(self._lib.pf_surface_prepare_signed(self._h, _f64(self.points), self.faces.ctypes.data_as(_i32p),
-                                                       t.ctypes.data_as(_i64p)))
+            _check(self._lib.pf_surface_prepare_signed(self._h, _f64(self.points), _ptr(self.faces), _ptr(t)))
             self._topology = t
         return self._topology
 
@@ -963,16 +1021,13 @@ class DeviceSurface(object):
         (outside of an outward-oriented closed mesh).  feature: 0 face, 1 edge, 2 vertex the closest point lies on (-1
         for a non-finite query, which gives NaN).  n_ambiguous: queries off the surface with a zero pseudonormal
         component (returned positive).  Builds the signed structure on first use."""
-        q = _c_f64(queries)
-        if q.ndim != 2 or q.shape[1] != 3 or q.shape[0] == 0:
-            raise ValueError("queries must be a non-empty (n, 3) array")
+        q = _queries(queries)
         self._prepare_signed()
         sd = np.empty(len(q), dtype=np.float64)
         face = np.empty(len(q), dtype=np.int32)
         feature = np.empty(len(q), dtype=np.int32)
         amb = C.c_int64(0)
-        _check(self._lib.pf_surface_signed_distance(self._h, _f64(q), len(q), _f64(sd), face.ctypes.data_as(_i32p),
-                                                    feature.ctypes.data_as(_i32p), C.byref(amb)))
+        _check(self._lib.pf_surface_signed_distance(self._h, _f64(q), len(q), _f64(sd), _ptr(face), _ptr(feature), C.byref(amb)))
         return sd, face, feature, int(amb.value)
 
     def winding_number(self, queries, beta=0.0):
@@ -981,9 +1036,7 @@ class DeviceSurface(object):
         triangle exactly, bound 0.  `beta > 1`: clusters of triangles at least `beta` radii away contribute their dipole
         term, and `bound` is a rigorous bound of |w - exact w|.  Two calls give identical bits.  Builds the dipole data on
         first use."""
-        q = _c_f64(queries)
-        if q.ndim != 2 or q.shape[1] != 3 or q.shape[0] == 0:
-            raise ValueError("queries must be a non-empty (n, 3) array")
+        q = _queries(queries)
         if not self._winding_ready:
             _check(self._lib.pf_surface_prepare_winding(self._h))
             self._winding_ready = True
@@ -1000,16 +1053,13 @@ class DeviceSurface(object):
         `facing`: 0 any side, 1 only faces whose normal points against the ray (det > 0), -1 only the others.  A miss gives
         +inf, -1, NaN; a ray with a non-finite component or a zero direction NaN, -1, NaN, count 0.  Equal to a brute-force
         loop over all triangles bit for bit; two calls give identical bits."""
-        o, d = _c_f64(origins), _c_f64(directions)
-        if o.ndim != 2 or o.shape[1] != 3 or o.shape[0] == 0 or d.shape != o.shape:
-            raise ValueError("origins and directions must be non-empty (n, 3) arrays of the same length")
+        o, d = _rays(origins, directions)
         t = np.empty(len(o), dtype=np.float64)
         face = np.empty(len(o), dtype=np.int32)
         uv = np.empty((len(o), 2), dtype=np.float64)
         n_hit = np.empty(len(o), dtype=np.int32) if count else None
         _check(self._lib.pf_surface_raycast(self._h, _f64(o), _f64(d), len(o), float(t_min), float(t_max), int(facing), _f64(t),
-                                            face.ctypes.data_as(_i32p), _f64(uv),
-                                            n_hit.ctypes.data_as(_i32p) if count else None))
+                                            _ptr(face), _f64(uv), _ptr(n_hit)))
         return (t, face, uv, n_hit) if count else (t, face, uv)
 
     def vertex_normals(self):
@@ -1026,7 +1076,7 @@ class DeviceSurface(object):
         pts = np.empty_like(q)
         face = np.empty(len(q), dtype=np.int32)
         d2 = np.empty(len(q), dtype=np.float64)
-        _check(self._lib.pf_surface_closest(self._h, _f64(q), len(q), _f64(pts), face.ctypes.data_as(_i32p), _f64(d2)))
+        _check(self._lib.pf_surface_closest(self._h, _f64(q), len(q), _f64(pts), _ptr(face), _f64(d2)))
         return pts, face, d2
 
     def distance(self, queries, per_point=True):
@@ -1034,53 +1084,34 @@ class DeviceSurface(object):
         many queries, no closest points).  A query with a non-finite coordinate gives NaN and face -1.  stats:
         n_finite, n_nan, sum_d, sum_d2, max_d, argmax (-1 if none) over d = sqrt(d2).  per_point=False downloads the
         stats only and returns (None, None, stats)."""
-        q = _c_f64(queries)
-        if q.ndim != 2 or q.shape[1] != 3 or q.shape[0] == 0:
-            raise ValueError("queries must be a non-empty (n, 3) array")
+        q = _queries(queries)
         d2 = np.empty(len(q), dtype=np.float64) if per_point else None
         face = np.empty(len(q), dtype=np.int32) if per_point else None
         st = np.empty(6, dtype=np.float64)
-        _check(self._lib.pf_surface_distance(self._h, _f64(q), len(q), _f64(d2) if per_point else None,
-                                             face.ctypes.data_as(_i32p) if per_point else None, _f64(st)))
+        _check(self._lib.pf_surface_distance(self._h, _f64(q), len(q), _f64(d2), _ptr(face), _f64(st)))
         stats = {"n_finite": int(st[0]), "n_nan": int(st[1]), "sum_d": float(st[2]), "sum_d2": float(st[3]),
                  "max_d": float(st[4]), "argmax": int(st[5])}
         return d2, face, stats
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.pf_surface_free(self._h)
-            self._h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001
-            pass
-
-
-class DeviceSurfaceND(object):
+class DeviceSurfaceND(_Handle):
     """Triangulated surface embedded in d dimensions (1 <= d <= 16) in HBM, for exact closest-point queries that return
     the face, its corners and barycentric weights (`pf_surface_nd_*`): sub-vertex correspondences in spectral
     coordinates.  `close()` frees it; usable as a context manager."""
 
     MAX_DIM = 16
+    _free = "pf_surface_nd_free"
 
     def __init__(self, coords, faces, ctx=None):
         x = _c_f64(coords)
-        f = np.ascontiguousarray(faces, dtype=np.int32)
+        f = _c_i32(faces)
         if x.ndim != 2 or x.shape[0] == 0 or not 1 <= x.shape[1] <= self.MAX_DIM:
             raise ValueError("coords must be a non-empty (n, d) array with 1 <= d <= %d" % self.MAX_DIM)
         if f.ndim != 2 or f.shape[0] == 0 or f.shape[1] < 3:
             raise ValueError("faces must be a non-empty (F, verts_per_face >= 3) array")
-        self.ctx = ctx if ctx is not None else default_context()
-        self._lib = self.ctx._lib
-        h = C.c_void_p()
-        _check(self._lib.pf_surface_nd_create(self.ctx._h, _f64(x), x.shape[0], x.shape[1], f.ctypes.data_as(_i32p), f.shape[0],
-                                              f.shape[1], C.byref(h)))
-        self._h = h
+        _Handle.__init__(self, ctx)
+        self._create("pf_surface_nd_create", self.ctx._h, _f64(x), x.shape[0], x.shape[1], _ptr(f), f.shape[0], f.shape[1])
         self.n, self.d, self.n_faces = x.shape[0], x.shape[1], f.shape[0]
-        _live_graphs.add(self)
-        self.ctx._children.add(self)
 
     def closest(self, queries, exhaustive=False):
         """(face (q,) i32, vertices (q,3) i32, bary (q,3) f64, d2 (q,) f64) of the closest surface point of every query
@@ -1095,7 +1126,7 @@ class DeviceSurfaceND(object):
         verts = np.empty((len(q), 3), dtype=np.int32)
         bary = np.empty((len(q), 3), dtype=np.float64)
         d2 = np.empty(len(q), dtype=np.float64)
-        _check(self._lib.pf_surface_nd_closest(self._h, _f64(q), len(q), face.ctypes.data_as(_i32p), verts.ctypes.data_as(_i32p),
+        _check(self._lib.pf_surface_nd_closest(self._h, _f64(q), len(q), _ptr(face), _ptr(verts),
                                                _f64(bary), _f64(d2), 1 if exhaustive else 0))
         return face, verts, bary, d2
 
@@ -1106,31 +1137,14 @@ class DeviceSurfaceND(object):
         _check(self._lib.pf_surface_nd_last_search(self._h, *[C.byref(x) for x in v]))
         return {"chunks_opened": int(v[0].value), "packets": int(v[1].value), "n_chunks": int(v[2].value)}
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.pf_surface_nd_free(self._h)
-            self._h = None
 
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001
-            pass
-
-
-class DeviceFunctionalMap(object):
+class DeviceFunctionalMap(_Handle):
     """Two Laplace-Beltrami bases, the source's vertex areas and a point map T (T[i] in [0, n_t) for every source vertex)
     in HBM for functional-map iterations (`pf_fmap_*`): `project` (point map -> C), `convert` (C -> point map),
     `zoomout`.  `close()` frees it; usable as a context manager."""
 
     MAX_K = 128
+    _free = "pf_fmap_free"
 
     def __init__(self, phi_t, phi_s, mass_s, ctx=None):
         pt, ps, m = _c_f64(phi_t), _c_f64(phi_s), _c_f64(mass_s)
@@ -1140,25 +1154,20 @@ class DeviceFunctionalMap(object):
             raise ValueError("1 <= K <= %d basis functions, got %d" % (self.MAX_K, pt.shape[1]))
         if m.shape != (ps.shape[0],):
             raise ValueError("mass_s must have one entry per source vertex")
-        self.ctx = ctx if ctx is not None else default_context()
-        self._lib = self.ctx._lib
-        h = C.c_void_p()
-        _check(self._lib.pf_fmap_create(self.ctx._h, _f64(pt), pt.shape[0], _f64(ps), ps.shape[0], _f64(m), pt.shape[1], C.byref(h)))
-        self._h = h
+        _Handle.__init__(self, ctx)
+        self._create("pf_fmap_create", self.ctx._h, _f64(pt), pt.shape[0], _f64(ps), ps.shape[0], _f64(m), pt.shape[1])
         self.n_t, self.n_s, self.K = pt.shape[0], ps.shape[0], pt.shape[1]
-        _live_graphs.add(self)
-        self.ctx._children.add(self)
 
     def set_p2p(self, T):
-        T = np.ascontiguousarray(T, dtype=np.int64)
+        T = _c_i64(T)
         if T.shape != (self.n_s,):
             raise ValueError("T must have one target index per source vertex")
-        _check(self._lib.pf_fmap_set_p2p(self._h, T.ctypes.data_as(_i64p)))
+        _check(self._lib.pf_fmap_set_p2p(self._h, _ptr(T)))
 
     def get_p2p(self, return_d2=False):
         T = np.empty(self.n_s, dtype=np.int64)
         d2 = np.empty(self.n_s) if return_d2 else None
-        _check(self._lib.pf_fmap_get_p2p(self._h, T.ctypes.data_as(_i64p), _f64(d2) if return_d2 else None))
+        _check(self._lib.pf_fmap_get_p2p(self._h, _ptr(T), _f64(d2)))
         return (T, d2) if return_d2 else T
 
     def project(self, k_s, k_t):
@@ -1170,7 +1179,7 @@ class DeviceFunctionalMap(object):
         """The resident functional map (Cm None) or the given k_s x k_t one -> the point map, which stays on the device."""
         if Cm is not None:
             Cm = _c_f64(Cm, (int(k_s), int(k_t)))
-        _check(self._lib.pf_fmap_convert(self._h, _f64(Cm) if Cm is not None else None, int(k_s), int(k_t)))
+        _check(self._lib.pf_fmap_convert(self._h, _f64(Cm), int(k_s), int(k_t)))
 
     def zoomout(self, k_start, k_end, step=1, n_iter_at_end=0):
         Cm = np.empty((int(k_end), int(k_end)))
@@ -1179,10 +1188,10 @@ class DeviceFunctionalMap(object):
 
     def set_samples(self, S_t, S_s):
         """Rows of the target's and of the source's basis that `zoomout_sampled` works on (`pf_fmap_set_samples`)."""
-        S_t, S_s = np.ascontiguousarray(S_t, dtype=np.int64), np.ascontiguousarray(S_s, dtype=np.int64)
+        S_t, S_s = _c_i64(S_t), _c_i64(S_s)
         if S_t.ndim != 1 or S_s.ndim != 1:
             raise ValueError("S_t and S_s must be vectors of indices")
-        _check(self._lib.pf_fmap_set_samples(self._h, S_t.ctypes.data_as(_i64p), S_t.shape[0], S_s.ctypes.data_as(_i64p), S_s.shape[0]))
+        _check(self._lib.pf_fmap_set_samples(self._h, _ptr(S_t), S_t.shape[0], _ptr(S_s), S_s.shape[0]))
 
     def zoomout_sampled(self, k_start, k_end, step=1, n_iter_at_end=0):
         """ZoomOut on the samples, least-squares fits, one conversion at full resolution at the end
@@ -1193,42 +1202,19 @@ class DeviceFunctionalMap(object):
         _check(self._lib.pf_fmap_zoomout_sampled(self._h, int(k_start), int(k_end), int(step), int(n_iter_at_end), _f64(Cm)))
         return Cm
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.pf_fmap_free(self._h)
-            self._h = None
 
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001
-            pass
-
-
-class DeviceCpd(object):
+class DeviceCpd(_Handle):
     """Fixed set X (N,d) and moving set Y (M,d) resident in HBM for the E-steps of a CPD registration."""
 
+    _free = "pf_cpd_free"
+
     def __init__(self, X, Y, ctx=None):
-        self.ctx = ctx if ctx is not None else default_context()
-        self._lib = self.ctx._lib
-        X, Y = _c_f64(X), _c_f64(Y)
-        if X.ndim != 2 or Y.ndim != 2 or X.shape[1] != Y.shape[1]:
-            raise ValueError("X (N,d) and Y (M,d) must share d")
+        _Handle.__init__(self, ctx)
+        X, Y = _same_d(X, Y, "X (N,d) and Y (M,d) must share d")
         self.N, self.M, self.D = X.shape[0], Y.shape[0], X.shape[1]
-        h = C.c_void_p()
-        _check(self._lib.pf_cpd_create(self.ctx._h, _f64(X), self.N, _f64(Y), self.M, self.D, C.byref(h)))
-        self._h = h
+        self._create("pf_cpd_create", self.ctx._h, _f64(X), self.N, _f64(Y), self.M, self.D)
         self._P1, self._Pt1, self._PX = np.empty(self.M), np.empty(self.N), np.empty((self.M, self.D))
         self._H = np.empty((0, 0))  # until set_basis: the library refuses the basis calls (PfError), not Python
-        _live_graphs.add(self)
-        self.ctx._children.add(self)
 
     def estep(self, TY, sigma2, w=0.0):
         """(P1 (M,), Pt1 (N,), PX (M,d)) for the moving set at TY; the arrays are reused by the next call."""
@@ -1290,17 +1276,6 @@ class DeviceCpd(object):
         _check(self._lib.pf_cpd_weighted_gram(self._h, _f64(self._H)))
         return self._H
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.pf_cpd_free(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001
-            pass
-
 
 def gaussian_gram_product(A, B, beta, V, ctx=None):
     """G(A,B) @ V with G_ij = exp(-|a_i - b_j|^2 / (2 beta^2)), evaluated on the device without forming G."""
@@ -1314,77 +1289,61 @@ def gaussian_gram_product(A, B, beta, V, ctx=None):
     return out
 
 
-class _Rows(object):
+class _Rows(_Handle):
     """A fixed subset of a graph's rows on the device (`pf_rows_*`)."""
 
-    def __init__(self, owner, h, n):
-        self._lib, self._h, self.n = owner._lib, h, n
+    _free = "pf_rows_free"
 
-    def close(self):
-        if self._h:
-            self._lib.pf_rows_free(self._h)
-            self._h = None
+    def __init__(self, graph, idx):
+        _Handle.__init__(self, graph.ctx)
+        idx = _c_i64(idx)
+        self._create("pf_rows_create", graph._h, _ptr(idx), len(idx))
+        self.n = len(idx)
 
 
-class DeviceLaplacian(object):
+class DeviceLaplacian(_Handle):
     """Device-resident graph of one mesh: CSR(W), deg, SELL-64 operators, workspace.
     Also the `ops` object the Krylov driver (`_krylov.filtered_eigs`) drives."""
 
+    _free = "pf_graph_free"
+    _rows = ()
     cotangent = False  # True: built by pf_graph_build_cotan - the operator is S = M^-1/2 (D - W) M^-1/2 of the cotangent weights
 
     def __init__(self, points=None, faces=None, ctx=None, device_mesh=None, matrix=None, _handle=None, cotangent=False):
-        h = C.c_void_p()
         if cotangent:
             if matrix is not None or _handle is not None:
                 raise ValueError("cotangent=True needs a mesh (points and faces, or device_mesh)")
             mesh = device_mesh if device_mesh is not None else DeviceMesh(points, faces, ctx=ctx)
-            self.ctx = mesh.ctx
-            self._lib = self.ctx._lib
+            _Handle.__init__(self, mesh.ctx)
             try:
-                _check(self._lib.pf_graph_build_cotan(mesh._h, 0, C.byref(h)))
+                self._create("pf_graph_build_cotan", mesh._h, 0)
             finally:
                 if device_mesh is None:
                     mesh.close()
         elif _handle is not None:  # (ctx, pf_graph*) of a graph the library has already built (build_pair)
-            self.ctx, h = _handle
-            self._lib = self.ctx._lib
+            _Handle.__init__(self, _handle[0])
+            self._adopt(_handle[1])
         elif matrix is not None:  # (rowptr, colidx, values) of a general CSR matrix, canonical format
-            self.ctx = ctx if ctx is not None else default_context()
-            self._lib = self.ctx._lib
-            rp = np.ascontiguousarray(matrix[0], dtype=np.int32)
-            ci = np.ascontiguousarray(matrix[1], dtype=np.int32)
-            va = _c_f64(matrix[2])
-            _check(self._lib.pf_graph_from_matrix(self.ctx._h, len(rp) - 1, rp.ctypes.data_as(_i32p),
-                                                  ci.ctypes.data_as(_i32p), _f64(va), C.byref(h)))
+            _Handle.__init__(self, ctx)
+            rp, ci, va = _c_i32(matrix[0]), _c_i32(matrix[1]), _c_f64(matrix[2])
+            self._create("pf_graph_from_matrix", self.ctx._h, len(rp) - 1, _ptr(rp), _ptr(ci), _f64(va))
         elif device_mesh is not None:
-            self.ctx = device_mesh.ctx
-            self._lib = self.ctx._lib
-            _check(self._lib.pf_graph_build_device(device_mesh._h, C.byref(h)))
+            _Handle.__init__(self, device_mesh.ctx)
+            self._create("pf_graph_build_device", device_mesh._h)
         else:
-            self.ctx = ctx if ctx is not None else default_context()
-            self._lib = self.ctx._lib
-            pts = _c_f64(points).reshape(-1, 3)
-            f = np.ascontiguousarray(faces, dtype=np.int32)
-            if f.ndim != 2:
-                raise ValueError("faces must be (F, verts_per_face)")
-            _check(self._lib.pf_graph_build(self.ctx._h, _f64(pts), pts.shape[0], f.ctypes.data_as(_i32p), f.shape[0],
-                                            f.shape[1] if f.shape[0] else 3, C.byref(h)))
-        self._h = h
-        _live_graphs.add(self)
-        self.ctx._children.add(self)
+            _Handle.__init__(self, ctx)
+            pts, f, v = _upload_arrays(points, faces)
+            self._create("pf_graph_build", self.ctx._h, _f64(pts), pts.shape[0], _ptr(f), f.shape[0], v)
+        h = self._h
         info = GraphInfo()
         _check(self._lib.pf_graph_get_info(h, C.byref(info)))
         self.info = info
-        self.n = int(info.n)
-        self.nnz_w = int(info.nnz_w)
-        self.nnz_l = int(info.nnz_l)
+        fields = info.as_dict()
+        for name in ("n", "nnz_w", "nnz_l", "n_isolated", "n_components", "max_degree", "n_oneway"):
+            setattr(self, name, fields[name])
         self.symmetric = bool(info.is_symmetric)
-        self.n_isolated = int(info.n_isolated)
-        self.n_components = int(info.n_components)
-        self.max_degree = int(info.max_degree)
-        self.n_oneway = int(info.n_oneway)
         self.rows_compacted = bool(self._lib.pf_graph_rows_compacted(h))  # the mesh listed a directed edge more than once
-        self.spectral_bound = float(info.spectral_bound) if 0.0 < float(info.spectral_bound) <= 2.0 else 2.0
+        self.spectral_bound = info.spectral_bound if 0.0 < info.spectral_bound <= 2.0 else 2.0
         self.op = PF_OP_SYM if self.symmetric else PF_OP_RW
         self.has_points = matrix is None
         self._rows = []
@@ -1407,18 +1366,10 @@ class DeviceLaplacian(object):
         return cls(_handle=(mesh_a.ctx, ha)), cls(_handle=(mesh_b.ctx, hb))
 
     def close(self):
-        if getattr(self, "_h", None):
-            for rows in getattr(self, "_rows", []):
-                rows.close()
-            self._lib.pf_graph_free(self._h)  # (collects a download that is still owed or in flight)
-            self._h = None
-            self._final_out = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001
-            pass
+        for rows in self._rows:
+            rows.close()
+        _Handle.close(self)  # (pf_graph_free collects a download that is still owed or in flight)
+        self._final_out = None
 
     # ---- matrices back to the host (scipy views for the reference-style attributes) ----------
     def download(self, labels=False):
@@ -1426,10 +1377,8 @@ class DeviceLaplacian(object):
         out = dict(rowptr=np.empty(n + 1, np.int32), colidx=np.empty(nnz, np.int32), w=np.empty(nnz),
                    l_offdiag=np.empty(nnz), deg=np.empty(n), l_diag=np.empty(n))
         lab = np.empty(n, np.int32) if labels else None
-        _check(self._lib.pf_graph_download(self._h, out["rowptr"].ctypes.data_as(_i32p),
-                                           out["colidx"].ctypes.data_as(_i32p), _f64(out["w"]), _f64(out["l_offdiag"]),
-                                           _f64(out["deg"]), _f64(out["l_diag"]),
-                                           lab.ctypes.data_as(_i32p) if labels else None))
+        _check(self._lib.pf_graph_download(self._h, _ptr(out["rowptr"]), _ptr(out["colidx"]), _f64(out["w"]), _f64(out["l_offdiag"]),
+                                           _f64(out["deg"]), _f64(out["l_diag"]), _ptr(lab)))
         if labels:
             out["labels"] = lab
         return out
@@ -1443,7 +1392,7 @@ class DeviceLaplacian(object):
             out["diag"] = np.empty(self.n)
         if mass:
             out["mass"] = np.empty(self.n)
-        _check(self._lib.pf_graph_cotan_download(self._h, *[_f64(out[k]) if k in out else None for k in ("w", "diag", "mass")]))
+        _check(self._lib.pf_graph_cotan_download(self._h, *[_f64(out.get(k)) for k in ("w", "diag", "mass")]))
         return out
 
     def cotan_apply(self, x):
@@ -1499,7 +1448,7 @@ class DeviceLaplacian(object):
         scalars = [C.c_int32() for _ in range(4)]
         ghosts, ghosts2, need = (np.full(n_max, -1, np.int32) for _ in range(3))
         _check(self._lib.pf_graph_window_info(self._h, int(bool(rings)), *[C.byref(s) for s in scalars],
-                                              ghosts.ctypes.data_as(_i32p), ghosts2.ctypes.data_as(_i32p), need.ctypes.data_as(_i32p)))
+                                              _ptr(ghosts), _ptr(ghosts2), _ptr(need)))
         win_rows, nw, state, state2 = (int(s.value) for s in scalars)
         return dict(win_rows=win_rows, n_windows=nw, state=state, state2=state2,
                     ghosts=ghosts[:nw].copy() if state == 1 else None, need=need[:nw].copy() if state == 1 else None,
@@ -1624,10 +1573,10 @@ class DeviceLaplacian(object):
     def final_remap(self, cols, signs, out):
         """out[:, c] <- (device-resident block)[:, cols[c]] * signs[c], by a kernel and one DMA on the copy stream (`out`: the
         pinned array `finalize_vectors` returned, all of its columns); `finalize_wait()` before anybody reads it."""
-        cols = np.ascontiguousarray(cols, dtype=np.int32)
+        cols = _c_i32(cols)
         signs = np.ascontiguousarray(signs, dtype=np.float64)
         assert out.flags.c_contiguous and out.shape == (self.n, len(cols))
-        _check(self._lib.pf_final_remap_begin(self._h, cols.ctypes.data_as(_i32p), _f64(signs), len(cols), _f64(out)))
+        _check(self._lib.pf_final_remap_begin(self._h, _ptr(cols), _f64(signs), len(cols), _f64(out)))
         self._final_pending = True
         self._final_out = out
 
@@ -1642,9 +1591,9 @@ class DeviceLaplacian(object):
 
     def final_rows(self, rows):
         """Rows of the block the last `finalize_vectors` left on the device -> (len(rows), count) array."""
-        rows = np.ascontiguousarray(rows, dtype=np.int64)
+        rows = _c_i64(rows)
         out = np.empty((len(rows), self._final_count), dtype=np.float64)
-        _check(self._lib.pf_final_rows(self._h, rows.ctypes.data_as(_i64p), len(rows), _f64(out)))
+        _check(self._lib.pf_final_rows(self._h, _ptr(rows), len(rows), _f64(out)))
         return out
 
     def final_device(self):
@@ -1655,9 +1604,9 @@ class DeviceLaplacian(object):
 
     def point_rows(self, rows):
         """Rows of the mesh's points as they sit on the device -> (len(rows), 3) array (mesh-built graphs only)."""
-        rows = np.ascontiguousarray(rows, dtype=np.int64)
+        rows = _c_i64(rows)
         out = np.empty((len(rows), 3), dtype=np.float64)
-        _check(self._lib.pf_point_rows(self._h, rows.ctypes.data_as(_i64p), len(rows), _f64(out)))
+        _check(self._lib.pf_point_rows(self._h, _ptr(rows), len(rows), _f64(out)))
         return out
 
     def spmv_host(self, x, op=None):
@@ -1683,7 +1632,7 @@ class DeviceLaplacian(object):
             if self._final_pending:
                 self.finalize_wait()
             vecs = np.ascontiguousarray(vecs.reshape(-1)[: self.n * m].reshape(self.n, m))
-        stats = {f: getattr(st, f) for f, _ in EigsStats._fields_}
+        stats = st.as_dict()
         stats["residuals"] = resid[:m].copy()
         return vals[:m].copy(), vecs, stats
 
@@ -1718,10 +1667,7 @@ class DeviceLaplacian(object):
         _check(self._lib.pf_axpy(self._h, int(w), int(first), int(count), _f64(coef)))
 
     def rows_create(self, idx):
-        idx = np.ascontiguousarray(idx, dtype=np.int64)
-        h = C.c_void_p()
-        _check(self._lib.pf_rows_create(self._h, idx.ctypes.data_as(_i64p), len(idx), C.byref(h)))
-        rows = _Rows(self, h, len(idx))
+        rows = _Rows(self, idx)
         self._rows.append(rows)
         return rows
 
@@ -1742,10 +1688,10 @@ class DeviceLaplacian(object):
         _check(self._lib.pf_rows_scatter_dev(rows._h, int(slot), C.c_void_p(int(device_ptr))))
 
     def rows_set_sources(self, rows, offsets):
-        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        offsets = _c_i64(offsets)
         if len(offsets) != rows.n:
             raise ValueError("one offset per row")
-        _check(self._lib.pf_rows_set_sources(rows._h, offsets.ctypes.data_as(_i64p)))
+        _check(self._lib.pf_rows_set_sources(rows._h, _ptr(offsets)))
 
     def rows_gather2_dev(self, slot_a, slot_b, rows, device_ptr, stride):
         _check(self._lib.pf_rows_gather2_dev(rows._h, int(slot_a), -1 if slot_b is None else int(slot_b),

@@ -9,20 +9,21 @@ point data, labels - is carried over without quantisation (`interpolate_on_surfa
 The search runs on the MI355X (`pf_surface_nd_closest`, `_hip.DeviceSurfaceND`) for 1 <= d <= 16: exact, the minimum
 over all fan triangles, lowest triangle on ties, bit for bit what a brute-force loop gives.
 """
+import contextlib
+
 import numpy as np
 
 from . import _hip
+from ._meshargs import checked_faces
 
 MAX_DIM = 16
 
 
 def _surface_arrays(coords, faces):
     x = np.ascontiguousarray(coords, dtype=np.float64)
-    f = np.asarray(faces)
     if x.ndim != 2 or x.shape[0] == 0 or not 1 <= x.shape[1] <= MAX_DIM:
         raise ValueError("coords must be a non-empty (n, d) array with 1 <= d <= %d" % MAX_DIM)
-    if f.ndim != 2 or f.shape[0] == 0 or f.shape[1] < 3:
-        raise ValueError("faces must be a non-empty (F, verts_per_face >= 3) array")
+    f = checked_faces(faces, noun="faces")
     if not np.issubdtype(f.dtype, np.integer) or f.min() < 0 or f.max() >= x.shape[0]:
         raise ValueError("faces must hold vertex ids in 0 .. %d" % (x.shape[0] - 1))
     return x, np.ascontiguousarray(f, dtype=np.int32)
@@ -40,19 +41,16 @@ def closest_points_on_embedded_surface(queries, coords, faces, ctx=None, surface
     q = np.ascontiguousarray(queries, dtype=np.float64)
     if q.ndim != 2 or q.shape[0] == 0:
         raise ValueError("queries must be a non-empty (q, d) array")
-    built = None
+    own = contextlib.nullcontext()
     if surface is None:
         x, f = _surface_arrays(coords, faces)
         if q.shape[1] != x.shape[1]:
             raise ValueError("queries have %d coordinates, the surface %d" % (q.shape[1], x.shape[1]))
-        surface = built = _hip.DeviceSurfaceND(x, f, ctx=ctx)
+        surface = own = _hip.DeviceSurfaceND(x, f, ctx=ctx)
     elif q.shape[1] != surface.d:
         raise ValueError("queries have %d coordinates, the surface %d" % (q.shape[1], surface.d))
-    try:
+    with own:
         face, vertices, bary, d2 = surface.closest(q, exhaustive=exhaustive)
-    finally:
-        if built is not None:
-            built.close()
     return {"face": face, "vertices": vertices, "bary": bary, "d2": d2}
 
 

@@ -64,8 +64,7 @@ class _ExpectationMaximisation(object):
     def register(self, callback=lambda **kwargs: None):
         """EM loop.  The posterior sums P1 / Pt1 / PX and the moving set TY stay on the device: per iteration
         only the M-step's small moment sums come back and the new transform parameters go in."""
-        dev = _hip.DeviceCpd(self.X, self.Y, ctx=self._ctx)
-        try:
+        with _hip.DeviceCpd(self.X, self.Y, ctx=self._ctx) as dev:
             self._on_device(dev)
             self._apply(dev)
             while self.iteration < self.max_iterations and self.diff > self.tolerance:
@@ -79,8 +78,6 @@ class _ExpectationMaximisation(object):
             self.TY, P1, Pt1, PX = dev.download()
             self.P1, self.Pt1, self.PX = P1.copy(), Pt1.copy(), PX.copy()
             self._finish()
-        finally:
-            dev.close()
         return self.TY, self.get_registration_parameters()
 
     def _on_device(self, dev):

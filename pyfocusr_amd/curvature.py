@@ -25,48 +25,14 @@ are a capability of their own: `Graph(..., list_features_to_calc=["curvature"])`
 import numpy as np
 
 from . import _hip
-from . import vtk_functions
+from ._meshargs import AttrDict, checked_mesh
 from .spectral_descriptors import signature_on_mesh
 
 _METHODS = {"defect": ("k_min", "k_max"), "tensor": ("tensor_k_min", "tensor_k_max")}
 
 
-class Curvatures(dict):
+class Curvatures(AttrDict):
     """The result of `discrete_curvatures`: a dict whose keys are also attributes."""
-
-    def __getattr__(self, name):
-        try:
-            return self[name]
-        except KeyError:
-            raise AttributeError(name)
-
-
-def _triangle_mesh(mesh_or_points, faces):
-    """(points (n, 3) f64, faces (m, 3) i32), checked: ValueError before anything loads the library."""
-    if faces is None:
-        if isinstance(mesh_or_points, (tuple, list)) and len(mesh_or_points) == 2:
-            pts, faces = mesh_or_points
-        else:
-            pts, faces = vtk_functions.mesh_arrays(mesh_or_points)
-    else:
-        pts = mesh_or_points
-    pts = np.ascontiguousarray(pts, dtype=np.float64)
-    faces = np.asarray(faces)
-    if pts.ndim != 2 or pts.shape[1] != 3 or pts.shape[0] == 0:
-        raise ValueError("mesh points must be a non-empty (n, 3) array")
-    if faces.ndim != 2 or faces.shape[0] == 0:
-        raise ValueError("mesh faces must be a non-empty (m, 3) array")
-    if faces.shape[1] != 3:
-        raise ValueError("curvatures need triangles: faces are (m, %d), triangulate them first" % faces.shape[1])
-    if not np.issubdtype(faces.dtype, np.integer):
-        raise ValueError("face indices must be integers")
-    if 3 * faces.shape[0] >= 2**31 or pts.shape[0] >= 2**31:
-        raise ValueError("the mesh is too large: 3 x faces and points must stay below 2^31")
-    if not np.isfinite(pts).all():
-        raise ValueError("mesh points must be finite")
-    if faces.min() < 0 or faces.max() >= pts.shape[0]:
-        raise ValueError("face index out of range 0 .. %d" % (pts.shape[0] - 1))
-    return pts, np.ascontiguousarray(faces, dtype=np.int32)
 
 
 def discrete_curvatures(mesh_or_points, faces=None, ctx=None):
@@ -75,7 +41,7 @@ def discrete_curvatures(mesh_or_points, faces=None, ctx=None):
     (n, 3), normals (n, 3), boundary (n,) bool, topology (5,) int64, device_ms (the module's docstring has the
     definitions).  Values at boundary vertices are not meaningful curvatures: mask them with `boundary`.  The sign of
     `mean` and the normals assume outward faces: `topology.orient_faces` makes them so."""
-    pts, f = _triangle_mesh(mesh_or_points, faces)
+    pts, f = checked_mesh(mesh_or_points, faces, triangles="curvatures need", indices=True, finite=True)
     ctx = ctx or _hip.default_context()
     raw = ctx.curvatures(pts, f)
     k, dirs = raw.pop("k"), raw.pop("dirs")

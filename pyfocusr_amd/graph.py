@@ -28,6 +28,7 @@ An extra the reference does not have: `Graph(..., laplacian="cotangent")` replac
 random-walk Laplacian by the cotangent Laplace-Beltrami operator M^-1 (D - W) with lumped barycentric mass
 (`pf_graph_build_cotan`; see `laplace_beltrami.py`).  The default, `"inverse_length"`, is the reference's operator.
 """
+import contextlib
 import os
 
 import numpy as np
@@ -731,11 +732,8 @@ def recursive_eig(matrix, k, n_k_needed, k_buffer=1, sigma=1e-10, which="LM"):
         owned = True
     elif getattr(dev, "cotangent", False):
         solver_kw = _cotan_solver_kw(dev, n_k_needed)
-    try:
+    with dev if owned else contextlib.nullcontext():
         vals, vecs, _ = _device_eigs(dev, k, n_k_needed, k_buffer, minmax=False, verbose=True, **solver_kw)
         if getattr(dev, "cotangent", False):  # the device graph of M^-1 (D - W) iterates its symmetric twin
             vecs = _cotan_vectors(dev.mass, vecs, unit=True)
-    finally:
-        if owned:
-            dev.close()
     return vals, vecs

@@ -105,8 +105,7 @@ def icp_transform(target_points, target_faces, source_points, numberOfIterations
     if len(sp) == 0 or len(tp) == 0:
         raise ValueError("Can't execute with NULL or empty input")  # VTK's error text
     f32 = (lambda x: x.astype(np.float32).astype(np.float64)) if float_landmarks else (lambda x: x)
-    surface = _hip.DeviceSurface(tp, target_faces, ctx=ctx)
-    try:
+    with _hip.DeviceSurface(tp, target_faces, ctx=ctx) as surface:
         n = len(sp)
         step = n // number_landmarks if n > number_landmarks else 1
         nb = n // step
@@ -125,6 +124,4 @@ def icp_transform(target_points, target_faces, source_points, numberOfIterations
             if it >= numberOfIterations:
                 break
             a = f32(a @ m[:3, :3].T + m[:3, 3])
-    finally:
-        surface.close()
     return IcpTransform(acc, it, float(np.mean(np.sqrt(d2))), nb, transform_mode)

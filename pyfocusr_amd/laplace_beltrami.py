@@ -34,12 +34,9 @@ def _device(mesh, ctx):
 def cotangent_laplacian(mesh, ctx=None):
     """(L_c, mass): L_c = D - W as a scipy CSR matrix (symmetric, rows summing to 0, off-diagonals -w_ij - positive at
     obtuse angles) and the lumped barycentric vertex areas m; the generalised problem is L_c phi = lambda diag(m) phi."""
-    dev = _device(mesh, ctx)
-    try:
+    with _device(mesh, ctx) as dev:
         h, c = dev.download(), dev.cotan_download()
         n = dev.n
-    finally:
-        dev.close()
     W = sparse.csr_matrix((c["w"], h["colidx"], h["rowptr"]), shape=(n, n))
     L = sparse.csr_matrix(sparse.diags(c["diag"]) - W)
     L.sort_indices()
@@ -53,15 +50,12 @@ def laplace_beltrami_spectrum(mesh, k, ctx=None):
     back only when the mesh has fewer non-null pairs."""
     from .graph import _cotan_solver_kw, _cotan_vectors, _device_eigs
 
-    dev = _device(mesh, ctx)
-    try:
+    with _device(mesh, ctx) as dev:
         k = int(k)
         n_null = dev.n_components + dev.n_isolated
         vals, vecs, _ = _device_eigs(dev, k=k + n_null, n_k_needed=k, k_buffer=1, minmax=False, verbose=False,
                                      **_cotan_solver_kw(dev, k))
         vecs = _cotan_vectors(dev.mass, vecs, unit=False)
-    finally:
-        dev.close()
     return vals[:k], np.ascontiguousarray(vecs[:, :k])
 
 
@@ -69,12 +63,9 @@ def mean_curvature_normals(mesh, ctx=None):
     """(n, 3): M^-1 (D - W) applied to the vertex positions (`pf_cotan_apply`) - the discrete mean-curvature normal
     of length 2 H; with this sign (D - W, positive semi-definite) it points outward where the surface is convex; 0 on
     unreferenced vertices."""
-    dev = _device(mesh, ctx)
-    try:
+    with _device(mesh, ctx) as dev:
         points, _ = mesh_arrays(mesh)
         return dev.cotan_apply(np.asarray(points, dtype=np.float64))
-    finally:
-        dev.close()
 
 
 def mean_curvature(mesh, ctx=None):

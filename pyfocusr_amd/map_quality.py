@@ -27,14 +27,14 @@ import numpy as np
 
 from . import _hip
 from . import vtk_functions
-from .curvature import Curvatures, _triangle_mesh
+from ._meshargs import AttrDict, checked_mesh
 from .spectral_descriptors import signature_on_mesh
 
 VALID, COLLAPSED, FLIPPED, UNMAPPED = 1, 2, 4, 8
 _VERTEX_FIELDS = ("sigma_max", "sigma_min", "area", "flipped", "collapsed", "conformal", "isometric")
 
 
-class MapDistortion(Curvatures):
+class MapDistortion(AttrDict):
     """The result of `map_distortion`: a dict whose keys are also attributes."""
 
 
@@ -103,7 +103,7 @@ def map_distortion(source, target, vertex_map=None, surface_map=None, orientatio
     faces the target's `vertex_normals` decide which faces are flipped (a vertex without a normal votes with a zero
     vector); otherwise `flipped` is all False and the report's flipped counts are -1.  The module's docstring lists the
     keys."""
-    pts, faces = _triangle_mesh(source, None)
+    pts, faces = checked_mesh(source, triangles="curvatures need", indices=True, finite=True)
     tgt, tgt_faces = _target(target)
     vertices, weights = _map_arrays(vertex_map, surface_map, pts.shape[0], tgt.shape[0])
     mapped_targets = vertices[vertices[:, 0] != -1].ravel()

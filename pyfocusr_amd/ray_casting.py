@@ -15,17 +15,15 @@ import numpy as np
 
 from . import _hip
 from . import vtk_functions
-from .surface_distance import _mesh_arrays
+from ._meshargs import checked_mesh
 
 _FACING = {"any": 0, "front": 1, "back": -1}
 _DIRECTIONS = {"outward": 1.0, "inward": -1.0}
 
 
 def _rays(origins, directions):
-    o = np.ascontiguousarray(origins, dtype=np.float64)
+    o = _hip._queries(origins, "ray origins")
     d = np.ascontiguousarray(directions, dtype=np.float64)
-    if o.ndim != 2 or o.shape[1] != 3 or o.shape[0] == 0:
-        raise ValueError("ray origins must be a non-empty (n, 3) array")
     if d.shape != o.shape:
         raise ValueError("ray directions must have the shape of the origins, %r, not %r" % (o.shape, d.shape))
     return o, d
@@ -49,7 +47,7 @@ class _Surface(object):
 
     def __init__(self, mesh, ctx):
         self.given = mesh if hasattr(mesh, "raycast") else None
-        self.arrays = None if self.given is not None else _mesh_arrays(mesh)  # checked before any device call
+        self.arrays = None if self.given is not None else checked_mesh(mesh)  # checked before any device call
         self.ctx = ctx
 
     def __enter__(self):
@@ -122,7 +120,7 @@ def thickness_along_normals(mesh, other=None, direction="outward", t_max=np.inf,
     if direction not in _DIRECTIONS:
         raise ValueError("direction must be one of %r, not %r" % (tuple(_DIRECTIONS), direction))
     facing = _facing(facing)
-    pts, _ = _mesh_arrays(mesh)
+    pts, _ = checked_mesh(mesh)
     t_min = 0.0
     if other is None:
         t_min = 1e-9 * float(np.linalg.norm(pts.max(axis=0) - pts.min(axis=0)))

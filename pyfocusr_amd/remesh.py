@@ -20,7 +20,7 @@ connectivity, a density adapted to curvature beyond what a caller's own `mass` g
 import numpy as np
 
 from . import _hip
-from .topology import _triangle_mesh
+from ._meshargs import checked_mesh
 from .vtk_functions import PolyMesh
 
 __all__ = ["resample_mesh", "restrict_to_clusters", "prolong_from_clusters", "lift_point_map"]
@@ -80,9 +80,7 @@ def lift_point_map(T_coarse, labels_source, rep_target):
 
 def _checked(mesh, n_vertices, n_iter, placement, mass, seeds, point_data):
     """Everything that can be refused without the library."""
-    pts, faces = _triangle_mesh(mesh)
-    if not np.isfinite(pts).all():
-        raise ValueError("mesh points must be finite")
+    pts, faces = checked_mesh(mesh, triangles="topology needs", indices=True, finite=True)
     n, m = len(pts), int(n_vertices)
     if m != n_vertices or not 1 <= m <= n:
         raise ValueError("n_vertices must be an integer in 1 .. %d, the number of vertices" % n)
@@ -153,11 +151,8 @@ def resample_mesh(mesh, n_vertices, n_iter=20, placement="surface", mass=None, s
     elif placement == "vertex":
         new_pts = np.where((rep >= 0)[:, None], pts[np.maximum(rep, 0)], centroids)
     else:
-        surface = _hip.DeviceSurface(pts, faces, ctx=ctx)
-        try:
+        with _hip.DeviceSurface(pts, faces, ctx=ctx) as surface:
             new_pts = surface.closest(centroids)[0] if len(centroids) else centroids.copy()
-        finally:
-            surface.close()
     data = []
     if point_data == "average":
         for name, values in getattr(mesh, "point_data", []):

@@ -17,33 +17,17 @@ of all triangles seen from the point, over 4 pi.  1 inside and 0 outside a close
 holes, no normals or manifoldness needed: `winding_numbers`, `points_inside`, and the signs of `sign="winding"` for
 meshes that are open or non-manifold, where the pseudonormal sign flips near every boundary loop.
 """
+import contextlib
+
 import numpy as np
 
 from . import _hip
 from . import vtk_functions
-
-
-def _mesh_arrays(mesh):
-    """(points (n,3) f64, faces (F,v) i32) of a `PolyMesh`, a vtkPolyData or a `(points, faces)` pair, checked before
-    anything touches the device."""
-    if isinstance(mesh, (tuple, list)) and len(mesh) == 2:
-        pts, faces = mesh
-    else:
-        pts, faces = vtk_functions.mesh_arrays(mesh)
-    pts = np.ascontiguousarray(pts, dtype=np.float64)
-    faces = np.asarray(faces)
-    if pts.ndim != 2 or pts.shape[1] != 3 or pts.shape[0] == 0:
-        raise ValueError("mesh points must be a non-empty (n, 3) array")
-    if faces.ndim != 2 or faces.shape[0] == 0 or faces.shape[1] < 3:
-        raise ValueError("mesh faces must be a non-empty (F, verts_per_face >= 3) array")
-    return pts, np.ascontiguousarray(faces, dtype=np.int32)
+from ._meshargs import checked_mesh
 
 
 def _query_array(points):
-    q = np.ascontiguousarray(points, dtype=np.float64)
-    if q.ndim != 2 or q.shape[1] != 3 or q.shape[0] == 0:
-        raise ValueError("query points must be a non-empty (n, 3) array")
-    return q
+    return _hip._queries(points, "query points")
 
 
 def point_to_surface_distances(points, mesh, ctx=None):
@@ -54,12 +38,9 @@ def point_to_surface_distances(points, mesh, ctx=None):
     if hasattr(mesh, "distance"):  # a DeviceSurface
         d2, face, _ = mesh.distance(q)
         return np.sqrt(d2), face
-    pts, faces = _mesh_arrays(mesh)
-    surface = _hip.DeviceSurface(pts, faces, ctx=ctx)
-    try:
+    pts, faces = checked_mesh(mesh)
+    with _hip.DeviceSurface(pts, faces, ctx=ctx) as surface:
         d2, face, _ = surface.distance(q)
-    finally:
-        surface.close()
     return np.sqrt(d2), face
 
 
@@ -121,12 +102,9 @@ def winding_numbers(points, mesh, ctx=None, beta=0.0):
         raise ValueError("beta must be <= 0 (exact) or a finite value > 1, not %r" % beta)
     if hasattr(mesh, "winding_number"):  # a DeviceSurface
         return mesh.winding_number(q, beta=beta)[0]
-    pts, faces = _mesh_arrays(mesh)
-    surface = _hip.DeviceSurface(pts, faces, ctx=ctx)
-    try:
+    pts, faces = checked_mesh(mesh)
+    with _hip.DeviceSurface(pts, faces, ctx=ctx) as surface:
         return surface.winding_number(q, beta=beta)[0]
-    finally:
-        surface.close()
 
 
 def points_inside(points, mesh, ctx=None, threshold=0.5):
@@ -167,13 +145,13 @@ def signed_point_to_surface_distances(points, mesh, ctx=None, check_orientation=
     inconsistent edges raise (a reversed face subtracts its solid angle instead of adding it)."""
     q = _query_array(points)
     _check_sign(sign)
-    built = None
+    own = contextlib.nullcontext()
     if hasattr(mesh, "signed_distance"):  # a DeviceSurface
         surface = mesh
     else:
-        pts, faces = _mesh_arrays(mesh)
-        surface = built = _hip.DeviceSurface(pts, faces, ctx=ctx)
-    try:
+        pts, faces = checked_mesh(mesh)
+        surface = own = _hip.DeviceSurface(pts, faces, ctx=ctx)
+    with own:
         if check_orientation:
             t = surface.topology()
             if sign == "winding":
@@ -185,9 +163,6 @@ def signed_point_to_surface_distances(points, mesh, ctx=None, check_orientation=
                                  "non-manifold edges (check_orientation=False to compute them anyway)"
                                  % (t["n_inconsistent_edges"], t["n_nonmanifold_edges"]))
         sd, face = _signed_on_surface(surface, q, sign)
-    finally:
-        if built is not None:
-            built.close()
     return sd, face
 
 
@@ -217,7 +192,7 @@ def signed_distances_on_mesh(mesh, other, name="signed_distance", ctx=None, sign
     """Signed distances of `mesh`'s vertices to the surface of `other` (`signed_point_to_surface_distances`, orientation
     checked, `sign` as there), stored on `mesh` as the point-data array `name` (`set_mesh_scalars`; written by
     `write_vtk_mesh` with 17 digits, so they read back exactly).  Returns the distances."""
-    pts, _ = _mesh_arrays(mesh)
+    pts, _ = checked_mesh(mesh)
     _check_sign(sign)
     sd, _ = signed_point_to_surface_distances(pts, other, ctx=ctx, sign=sign)
     vtk_functions.set_mesh_scalars(mesh, sd, name=name)
@@ -239,15 +214,13 @@ def surface_distance_metrics(mesh_a, mesh_b, symmetric=True, ctx=None, surface_a
     not checked here; `topology()` of a surface tells whether its signs mean anything.  `sign="winding"` takes the
     signs from the generalized winding number instead (`signed_point_to_surface_distances`): the choice for open or
     non-manifold meshes; the unsigned entries are the same either way."""
-    pts_a, faces_a = _mesh_arrays(mesh_a)
-    pts_b, faces_b = _mesh_arrays(mesh_b)
+    pts_a, faces_a = checked_mesh(mesh_a)
+    pts_b, faces_b = checked_mesh(mesh_b)
     _check_sign(sign)
-    built = []
     sd_ab = sd_ba = None
-    try:
+    with contextlib.ExitStack() as built:
         if surface_b is None:
-            surface_b = _hip.DeviceSurface(pts_b, faces_b, ctx=ctx)
-            built.append(surface_b)
+            surface_b = built.enter_context(_hip.DeviceSurface(pts_b, faces_b, ctx=ctx))
         if signed:  # |sd| is the unsigned distance bit for bit: one search per direction
             sd_ab = _signed_on_surface(surface_b, pts_a, sign)[0]
             d_ab = np.abs(sd_ab)
@@ -256,16 +229,12 @@ def surface_distance_metrics(mesh_a, mesh_b, symmetric=True, ctx=None, surface_a
         d_ba = None
         if symmetric:
             if surface_a is None:
-                surface_a = _hip.DeviceSurface(pts_a, faces_a, ctx=ctx)
-                built.append(surface_a)
+                surface_a = built.enter_context(_hip.DeviceSurface(pts_a, faces_a, ctx=ctx))
             if signed:
                 sd_ba = _signed_on_surface(surface_a, pts_b, sign)[0]
                 d_ba = np.abs(sd_ba)
             else:
                 d_ba = np.sqrt(surface_a.distance(pts_b)[0])
-    finally:
-        for s in built:
-            s.close()
     out = summarize_distances(d_ab, d_ba)
     for tag, sd in (("a_to_b", sd_ab), ("b_to_a", sd_ba)):
         if sd is not None:

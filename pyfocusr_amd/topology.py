@@ -27,42 +27,16 @@ of a patch with such a vertex is not that of a surface.  The exact definitions a
 import numpy as np
 
 from . import _hip
-from . import vtk_functions
+from ._meshargs import AttrDict, checked_mesh
 from .vtk_functions import PolyMesh
 
 
-class MeshTopology(dict):
+class MeshTopology(AttrDict):
     """The result of `mesh_topology`: a dict whose keys are also attributes."""
 
-    def __getattr__(self, name):
-        try:
-            return self[name]
-        except KeyError:
-            raise AttributeError(name)
 
-
-def _triangle_mesh(mesh):
-    """(points (n, 3) f64, faces (m, 3) i32), checked: ValueError before anything loads the library."""
-    if isinstance(mesh, (tuple, list)) and len(mesh) == 2:
-        pts, faces = mesh
-    else:
-        pts, faces = getattr(mesh, "points", None), getattr(mesh, "faces", None)
-        if pts is None or faces is None:
-            pts, faces = vtk_functions.mesh_arrays(mesh)
-    pts, faces = np.asarray(pts), np.asarray(faces)
-    if pts.ndim != 2 or pts.shape[1] != 3 or pts.shape[0] == 0:
-        raise ValueError("mesh points must be a non-empty (n, 3) array")
-    if faces.ndim != 2 or faces.shape[0] == 0:
-        raise ValueError("mesh faces must be a non-empty (m, 3) array")
-    if faces.shape[1] != 3:
-        raise ValueError("topology needs triangles: faces are (m, %d), triangulate them first" % faces.shape[1])
-    if not np.issubdtype(faces.dtype, np.integer):
-        raise ValueError("face indices must be integers")
-    if 3 * faces.shape[0] >= 2**31 or pts.shape[0] >= 2**31:
-        raise ValueError("the mesh is too large: 3 x faces and points must stay below 2^31")
-    if faces.min() < 0 or faces.max() >= pts.shape[0]:
-        raise ValueError("face index out of range 0 .. %d: %d points do not cover the faces" % (pts.shape[0] - 1, pts.shape[0]))
-    return np.ascontiguousarray(pts, dtype=np.float64), np.ascontiguousarray(faces, dtype=np.int32)
+def _triangles(mesh):
+    return checked_mesh(mesh, triangles="topology needs", indices=True)
 
 
 def _patch_table(n_points, faces, raw):
@@ -120,14 +94,14 @@ def _topology(pts, faces, outward, ctx):
 def mesh_topology(mesh, outward=True, ctx=None):
     """`MeshTopology` of a triangle mesh: a `PolyMesh`, a vtkPolyData or a `(points, faces)` pair (the module's docstring
     has the fields).  `outward=False` leaves the points out: `flip` then only makes the faces of a patch agree."""
-    pts, faces = _triangle_mesh(mesh)
+    pts, faces = _triangles(mesh)
     return _topology(pts, faces, outward, ctx)
 
 
 def orient_faces(mesh, outward=True, ctx=None):
     """(new_mesh, topology): a `PolyMesh` with the same points and point data whose faces `topology.flip` marks have
     their second and third vertex swapped; `mesh` is not modified.  `topology` describes `mesh`, not the new mesh."""
-    pts, faces = _triangle_mesh(mesh)
+    pts, faces = _triangles(mesh)
     topo = _topology(pts, faces, outward, ctx)
     new_faces = faces.copy()
     new_faces[topo["flip"]] = faces[topo["flip"]][:, [0, 2, 1]]
@@ -136,7 +110,7 @@ def orient_faces(mesh, outward=True, ctx=None):
 
 def is_consistently_oriented(mesh, ctx=None):
     """Whether no edge is traversed twice in the same direction and no patch is a one-sided surface."""
-    pts, faces = _triangle_mesh(mesh)
+    pts, faces = _triangles(mesh)
     topo = _topology(pts, faces, False, ctx)
     return topo["n_inconsistent_edges"] == 0 and bool(np.all(topo["patches"]["orientable"]))
 
@@ -145,7 +119,7 @@ def extract_patches(mesh, which="largest", ctx=None):
     """(sub_mesh, vertex_index): the faces of the chosen patches (as they are: nothing is reversed) over the vertices they
     reference, `sub_mesh.points == mesh.points[vertex_index]`, point data carried.  `which`: "largest" (the most faces;
     the lower patch id on a tie), a patch id, or a sequence of ids."""
-    pts, faces = _triangle_mesh(mesh)
+    pts, faces = _triangles(mesh)
     if isinstance(which, str) and which != "largest":
         raise ValueError('which must be "largest", a patch id or a sequence of ids, not %r' % (which,))
     topo = _topology(pts, faces, False, ctx)
