@@ -378,7 +378,7 @@ def pool_poison(on=True):
 
 
 def orth_one_launch(on=True):
-    """Process-wide switch of the one-launch local Gram-Schmidt step (csrc/pf_operator.hip: k_orth_local); off: dot
+    """Process-wide switch of the one-launch local Gram-Schmidt step (csrc/pf_orth.hip: k_orth_local); off: dot
     products and projection as two launches, like every other step.  Results are bit-identical either way."""
     _check(load_library().pf_orth_one_launch(int(bool(on))))
 

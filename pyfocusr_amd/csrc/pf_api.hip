@@ -379,9 +379,9 @@ void pf_destroy(pf_ctx* c) {
     if (c->stage_ring) hipHostFree(c->stage_ring);
     for (hipEvent_t ev : c->stage_ev)
         if (ev) hipEventDestroy(ev);
-    for (auto& pb : c->pinned_pool) hipHostFree(pb.second);
+    for (auto& pb : c->pools.pinned_pool) hipHostFree(pb.second);
     if (c->pinned_scratch) hipHostFree(c->pinned_scratch);
-    for (hipEvent_t ev : c->event_pool) hipEventDestroy(ev);
+    for (hipEvent_t ev : c->pools.event_pool) hipEventDestroy(ev);
     pf_persist_release(c);
     if (c->persist_abort) hipHostFree(c->persist_abort);
     hipEventDestroy(c->ev0);

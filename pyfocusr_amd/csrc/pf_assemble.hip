@@ -1131,9 +1131,8 @@ void pf_graph_free(pf_graph* g) {
         auto& dq = g->ctx->deferred;
         dq.erase(std::remove(dq.begin(), dq.end(), g), dq.end());
     }
-    if (g->final_stats) g->ctx->pinned_pool.emplace_back(g->final_stats_cap, reinterpret_cast<double*>(g->final_stats));
-    if (g->final_ready) g->ctx->event_pool.push_back(g->final_ready);
-    if (g->final_done) g->ctx->event_pool.push_back(g->final_done);
+    g->final_land.release(g->ctx->pools);
+    g->ctx->pools.give_event(&g->final_done);
     pf_free(st, g->persist_ring);
     pf_free(st, g->persist_ring2);
     pf_free(st, g->final_vecs);
@@ -1160,7 +1159,7 @@ void pf_graph_free(pf_graph* g) {
     pf_free(st, g->perm);
     pf_free(st, g->iperm);
     pf_free(st, g->smooth);
-    pf_free(st, g->stage);
+    g->stage.release(st);
     pf_free(st, g->slice_ptr);
     pf_free(st, g->scol);
     pf_free(st, g->sval_rw);
@@ -1173,12 +1172,9 @@ void pf_graph_free(pf_graph* g) {
     pf_free(st, g->coef);
     pf_free(st, g->orth_counter);
     if (g->orth_pending >= 0 || g->small_pending > 0 || g->px_state == -2) pfl::sync(st);  // a step or a result nobody collected still writes its pinned buffer
-    if (g->orth_host) g->ctx->pinned_pool.emplace_back(g->orth_host_cap, g->orth_host);
-    if (g->orth_ev) g->ctx->event_pool.push_back(g->orth_ev);
-    if (g->px_host) g->ctx->pinned_pool.emplace_back(g->px_host_cap, g->px_host);
-    if (g->px_ev) g->ctx->event_pool.push_back(g->px_ev);
-    if (g->small_host) g->ctx->pinned_pool.emplace_back(g->small_host_cap, g->small_host);
-    if (g->small_ev) g->ctx->event_pool.push_back(g->small_ev);
+    g->orth_land.release(g->ctx->pools);
+    g->px_land.release(g->ctx->pools);
+    g->small_land.release(g->ctx->pools);
     delete g;
 }
 

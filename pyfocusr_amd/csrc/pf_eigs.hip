@@ -103,7 +103,7 @@ void give_up(pf_graph* g) {
         (void)pf_orth_end(g, h.data(), &nrm);
     }
     if (g->small_pending > 0) {  // an extraction was cut short between its halves
-        (void)hipEventSynchronize(g->small_ev);
+        (void)hipEventSynchronize(g->small_land.ev);
         g->small_pending = 0;
     }
     (void)pf_download_cancel(g);

@@ -170,12 +170,9 @@ struct pf_ctx {
     };
     std::vector<TimedSpan> spans_pending;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> spans_free;
-    // pinned host buffers and events of freed graphs, handed to the next graph (hipHostMalloc / hipHostFree and event
-    // creation cost 0.1-0.2 ms each: more than a 250k-vertex assembly kernel)
-    std::vector<std::pair<int32_t, double*>> pinned_pool;  // (capacity in doubles - 1, buffer)
+    HostPools pools;  // pinned host blocks and events of freed graphs, handed to the next graph's landings (pf_scratch.h)
     void* pinned_scratch = nullptr;  // small read-backs land here (pinned: one DMA instead of a staged copy each)
     size_t pinned_scratch_bytes = 0;
-    std::vector<hipEvent_t> event_pool;                    // created with hipEventDisableTiming
     // allocator state (pf_malloc / pf_free)
     std::multimap<size_t, void*> free_blocks;   // size -> block
     std::unordered_map<void*, size_t> live_blocks;
@@ -229,8 +226,7 @@ struct pf_graph {
     int32_t* iperm = nullptr; // [n]     original vertex -> solver row
     unsigned long long* order_bbox = nullptr;  // (during a build) the bounding box of the points, encoded (pf_reorder.hip)
     double* smooth = nullptr; // [n_pad] solver order: low-order polynomial of the vertex position (Krylov start vector)
-    double* stage = nullptr;  // [stage_cap] staging for permuted uploads/downloads
-    int64_t stage_cap = 0;
+    DevBuf<double> stage;     // staging for permuted uploads/downloads
     // SELL-64 operator storage (off-diagonals) + dense diagonal
     int64_t n_slices = 0, sell_entries = 0;
     int64_t* slice_ptr = nullptr; // [n_slices+1]
@@ -247,9 +243,7 @@ struct pf_graph {
     int32_t win_rows = 1024;
     std::vector<int64_t> h_slice_ptr;  // host copy of slice_ptr (LDS sizing)
     int32_t px_state = -1;         // -1 not tried, -2 in flight (pf_window_slots_begin), 0 this graph is not covered, 1 ready
-    double* px_host = nullptr;     // pinned: the per-window counts + the builder's flag on their way to the host
-    int32_t px_host_cap = 0;
-    hipEvent_t px_ev = nullptr;
+    HostLanding px_land;           // the per-window counts + the builder's flag on their way to the host
     int32_t* px_slot = nullptr;    // [sell_entries] window-local slot of every SELL column: own row, or win_rows + index
                                    // into the window's sorted list of outside rows
     int32_t* px_gh_cnt = nullptr;  // [windows]
@@ -292,16 +286,13 @@ struct pf_graph {
     int32_t coef_cap = 0;
     int64_t n_chunks = 0;
     // split-phase orthogonalisation (pf_orth_begin / pf_orth_end): results land in pinned host memory
-    double* orth_host = nullptr; // [orth_host_cap + 2] pinned: h, |w'|^2, verdict
-    int32_t orth_host_cap = 0;
+    HostLanding orth_land;       // h, |w'|^2, then (the two spare doubles) verdict and ticket
     int32_t orth_pending = -1;   // count of the orth in flight, -1 if none
-    hipEvent_t orth_ev = nullptr;
     // pf_gram_begin / pf_resnorms_begin -> pf_small_end: a few doubles on their way to the host
-    double* small_host = nullptr;  // [small_host_cap + 2] pinned
-    int32_t small_host_cap = 0, small_pending = 0;
+    HostLanding small_land;
+    int32_t small_pending = 0;
     bool small_root = false;       // pf_small_end returns square roots (residual norms)
-    hipEvent_t small_ev = nullptr;
-    hipEvent_t orth_wait = nullptr;  // the event pf_orth_end waits on: orth_ev, or the partner graph's after pf_orth_begin2
+    hipEvent_t orth_wait = nullptr;  // the event pf_orth_end waits on: orth_land.ev, or the partner graph's after pf_orth_begin2
     int32_t orth_w = 0, orth_first = 0, orth_normalize = 0;  // arguments of the orth in flight (pf_orth_end's second pass)
     int32_t orth_redone = 0;     // the last pf_orth_end ran the second Gram-Schmidt pass itself
     double orth_serial = 0.0;    // tickets handed to the fused Gram-Schmidt kernels so far
@@ -321,9 +312,8 @@ struct pf_graph {
     // its download in flight (pf_finalize_vectors_begin / _end): copies on the ctx's copy stream between two events
     int32_t final_pending = 0;         // > 0: column count of the result whose download pf_finalize_vectors_end has to collect; < 0: a remapped image
     double* final_params = nullptr;    // device: per-column parameters + a private copy of the statistics
-    void* final_stats = nullptr;       // pinned: the statistics as they arrive
-    int32_t final_stats_cap = 0;
-    hipEvent_t final_ready = nullptr, final_done = nullptr;
+    HostLanding final_land;            // the statistics as they arrive; its event: the result is ready on the ctx stream
+    hipEvent_t final_done = nullptr;   // (pooled like a landing's) the copies on the copy stream have finished
     // the host image that is still owed: a download that has not been queued yet (released behind the next long kernel,
     // pf_downloads_release; or by whoever collects it first)
     const double* dl_src = nullptr;
@@ -430,8 +420,40 @@ inline void pf_sort_pairs(Scratch& sc, const unsigned long long* k_in, unsigned 
 int pf_exclusive_scan_i32(hipStream_t st, const int32_t* in, int32_t* out, int64_t n);
 int pf_exclusive_scan_i64(hipStream_t st, const int64_t* in, int64_t* out, int64_t n);
 
-// pf_operator.hip
-int pf_reduce_ensure(pf_graph* g, int32_t count);
+// pf_operator.hip: what the other units of the solve's vector code (pf_orth, pf_reduce, pf_finalize, pf_rows) share
+int pf_check_slots(pf_graph* g, int32_t first, int32_t count, const char* who);  // also makes the ctx's device current
+const double* pf_op_values(pf_graph* g, int32_t op);  // the SELL values of PF_OP_RW / PF_OP_SYM; NULL: not available
+int64_t pf_op_bytes(const pf_graph* g);               // bytes one application of the operator moves
+// out = alpha * (shift * x - A x) - beta * prev, one launch on the ctx stream (prev may be NULL)
+int pf_launch_op(pf_graph* g, const double* vals, const double* x, const double* prev, double* out, double alpha, double shift,
+                 double beta);
+// the timed span around `n` operator launches: started by the constructor (when the ctx times this application), closed
+// by finish, which never blocks - the span is resolved in pf_timing_get
+struct OpTimer {
+    pf_ctx* c;
+    int64_t launches;
+    double bytes;
+    bool on;
+    int64_t persist_steps = 0;
+    double lds_bytes = 0.0;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    OpTimer(pf_ctx* ctx, int64_t n, double b);
+    int finish();
+};
+
+// pf_reduce.hip
+constexpr size_t PF_PARTIAL_BYTES = 48;  // per (vector, chunk) of g->partials: a double, or the VecStats of pf_finalize.hip
+int pf_reduce_ensure(pf_graph* g, int32_t count);  // g->partials and g->coef hold `count` vectors' worth from here on
+// d_out[b] = <slot first + b, slot w>, b < count, and d_acc[b] (+)= d_out[b] when d_acc is given; queued (recorded while
+// the head of a pair's solve is: pf_launch.h)
+int pf_dots_device(pf_graph* g, int32_t w, int32_t first, int32_t count, double* d_out, double* d_acc, int accumulate);
+// only the chunks' partial sums of those products, into partial[b][chunk] (a place inside g->partials)
+int pf_dot_partials(pf_graph* g, int32_t w, int32_t first, int32_t count, double* partial);
+// x *= 1 / sqrt(*nrm2), the norm still on the device; queued, or recorded like pf_dots_device
+int pf_scale_rsqrt(pf_graph* g, double* x, const double* nrm2);
+
+// pf_orth.hip
+int pf_multi_axpy(pf_graph* g, int32_t w, int32_t first, int32_t count, const double* d_h);  // w -= sum_b d_h[b] V_b, queued
 
 // pf_reorder.hip
 // d_overflow (device int, nullable): the Morton order by counting (pf_reorder.hip); set to 1 when a cell holds too many
@@ -458,7 +480,7 @@ int pf_knn_extent(hipStream_t st, const double* pts, int64_t n, int32_t d, unsig
 constexpr int PF_KNN_TREE_MIN_D = 7;
 int pf_knn_tree_run(pf_ctx* c);
 
-// pf_operator.hip: the split-phase forms behind the C++ Krylov driver (pf_eigs.hip)
+// pf_reduce.hip: the split-phase forms behind the C++ Krylov driver (pf_eigs.hip)
 int pf_gram_begin(pf_graph* g, int32_t first_a, int32_t count_a, int32_t first_b, int32_t count_b, int32_t append);
 int pf_resnorms_begin(pf_graph* g, int32_t ax_first, int32_t x_first, const double* lam, int32_t count);
 int pf_small_end(pf_graph* g, double* out);

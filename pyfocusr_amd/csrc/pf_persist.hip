@@ -1502,7 +1502,7 @@ void pf_persist_release(pf_ctx* ctx) {
     }
 }
 
-// the abort word on the device and its pinned twin (also raised by the one-launch Gram-Schmidt step of pf_operator.hip,
+// the abort word on the device and its pinned twin (also raised by the one-launch Gram-Schmidt step of pf_orth.hip,
 // whose grid-wide wait is bounded like the resident kernels')
 int pf_persist_sync_ensure(pf_ctx* ctx) {
     if (!ctx->persist_sync) {

@@ -1,11 +1,14 @@
 // Device memory as the host code of the library holds it: the scratch of one call (Scratch) and a buffer that grows and
-// stays (DevBuf), both on top of the ctx's caching allocator (pf_api.hip); and the timer of a call's stream work
-// (StreamTimer).  Only the HIP C API is needed here, so the failure paths of all three run on the CPU over test doubles
-// of the allocator and of the event calls (tests/csrc/scratch_paths.cpp).
+// stays (DevBuf), both on top of the ctx's caching allocator (pf_api.hip); the timer of a call's stream work
+// (StreamTimer); and the pinned host block with its event that a few results land in (HostLanding, over the ctx's
+// HostPools).  Only the HIP C API is needed here, so the failure paths of all four run on the CPU over test doubles of
+// the allocator, of the pinned allocation and of the event calls (tests/csrc/scratch_paths.cpp).
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include <stddef.h>
 #include <stdint.h>
+#include <algorithm>
+#include <utility>
 #include <vector>
 
 // Caching device allocator, one cache per ctx (pf_api.hip).  Every use of a block is enqueued on
@@ -128,5 +131,77 @@ struct DevBuf {
         pf_free(st, p);
         p = nullptr;
         cap = 0;
+    }
+};
+
+// Pinned host blocks and events of freed graphs, handed to the next graph (hipHostMalloc / hipHostFree and event creation
+// cost 0.1-0.2 ms each: more than a 250k-vertex assembly kernel).  One per ctx; pf_destroy frees what is left.
+struct HostPools {
+    std::vector<std::pair<int32_t, double*>> pinned_pool;  // (capacity in doubles, block of capacity + 2)
+    std::vector<hipEvent_t> event_pool;                    // created with hipEventDisableTiming
+
+    hipError_t take_event(hipEvent_t* ev) {  // *ev stays as it is when it holds one; NULL after a failure
+        if (*ev) return hipSuccess;
+        if (!event_pool.empty()) {
+            *ev = event_pool.back();
+            event_pool.pop_back();
+            return hipSuccess;
+        }
+        const hipError_t e = hipEventCreateWithFlags(ev, hipEventDisableTiming);
+        if (e != hipSuccess) *ev = nullptr;
+        return e;
+    }
+    void give_event(hipEvent_t* ev) {
+        if (*ev) event_pool.push_back(*ev);
+        *ev = nullptr;
+    }
+};
+
+// Where a few doubles of a graph land on the host: a pinned block of cap + 2 doubles (the two spare ones are the caller's
+// to use: the verdict and the ticket of a Gram-Schmidt step) and the event recorded behind the copy.  Block and event come
+// from the ctx's pools and go back there; no destructor: the owner releases (pf_graph_free).  A landing holds both or
+// neither: after a failed ensure it is empty, and may be ensured or released again.
+struct HostLanding {
+    double* host = nullptr;
+    int32_t cap = 0;  // doubles
+    hipEvent_t ev = nullptr;
+
+    // A block with cap >= need, and an event.  The block held is kept when it is large enough (the common case: two
+    // compares).  Otherwise it goes back to the pool - after `drain` has run dry, when the caller names a stream whose
+    // work may still write to it - and the first pooled block of max(need, floor) doubles or more takes its place, or a new
+    // one of that size (of `fresh` doubles, if that is more).
+    hipError_t ensure(HostPools& pools, int32_t need, int32_t floor, hipStream_t drain, int32_t fresh = 0) {
+        if (host && need <= cap) return hipSuccess;
+        return replace(pools, std::max(need, floor), drain, fresh);
+    }
+    void release(HostPools& pools) {
+        if (host) pools.pinned_pool.emplace_back(cap, host);
+        host = nullptr;
+        cap = 0;
+        pools.give_event(&ev);
+    }
+
+   private:
+    hipError_t replace(HostPools& pools, int32_t least, hipStream_t drain, int32_t fresh) {
+        hipError_t e = host && drain ? hipStreamSynchronize(drain) : hipSuccess;
+        if (host) pools.pinned_pool.emplace_back(cap, host);
+        host = nullptr;
+        cap = 0;
+        for (size_t i = 0; e == hipSuccess && i < pools.pinned_pool.size(); ++i)
+            if (pools.pinned_pool[i].first >= least) {  // a block a freed graph left behind
+                cap = pools.pinned_pool[i].first;
+                host = pools.pinned_pool[i].second;
+                pools.pinned_pool.erase(pools.pinned_pool.begin() + (long)i);
+                break;
+            }
+        if (e == hipSuccess && !host) {
+            void* p = nullptr;
+            const int32_t size = std::max(least, fresh);
+            e = hipHostMalloc(&p, sizeof(double) * (size_t)(size + 2), hipHostMallocDefault);
+            if (e == hipSuccess) host = (double*)p, cap = size;
+        }
+        if (e == hipSuccess) e = pools.take_event(&ev);
+        if (e != hipSuccess) release(pools);
+        return e;
     }
 };

@@ -392,28 +392,9 @@ int pf_window_slots_begin(pf_graph* g) {
     const int64_t tail = (nw + 1) & ~(int64_t)1;  // (the builder's flag: 8-byte aligned behind the counts)
     const size_t bytes = sizeof(int32_t) * (size_t)(tail + 2);
     const int32_t need_doubles = (int32_t)((bytes + 7) / 8);
-    if (!g->px_host) {  // a pinned block: from the pool a freed graph left behind, or new
-        const int32_t cap = std::max(need_doubles, 64);
-        for (size_t i = 0; i < c->pinned_pool.size(); ++i)
-            if (c->pinned_pool[i].first >= cap) {
-                g->px_host_cap = c->pinned_pool[i].first;
-                g->px_host = c->pinned_pool[i].second;
-                c->pinned_pool.erase(c->pinned_pool.begin() + (long)i);
-                break;
-            }
-        if (!g->px_host) {
-            PF_HIP(hipHostMalloc((void**)&g->px_host, sizeof(double) * (size_t)(cap + 2), hipHostMallocDefault));
-            g->px_host_cap = cap;
-        }
-    }
-    if (!g->px_ev) {
-        if (!c->event_pool.empty()) {
-            g->px_ev = c->event_pool.back();
-            c->event_pool.pop_back();
-        } else {
-            PF_HIP(hipEventCreateWithFlags(&g->px_ev, hipEventDisableTiming));
-        }
-    }
+    // a pinned block and its event: from the pool a freed graph left behind, or new (only when the graph has none: the
+    // need is the graph's own and does not change)
+    if (!g->px_land.host) PF_HIP(g->px_land.ensure(c->pools, need_doubles, 64, nullptr));
     int32_t* flags = nullptr;
     uint32_t* adj = nullptr;
     hipError_t e = pf_malloc(st, (void**)&flags, sizeof(int32_t));
@@ -436,10 +417,10 @@ int pf_window_slots_begin(pf_graph* g) {
     if (e == hipSuccess) e = pfl::memcpy_async(st, g->px_gh_cnt + tail, flags, sizeof(int32_t), hipMemcpyDeviceToDevice);
     if (e == hipSuccess) {
         const int32_t* src = g->px_gh_cnt;
-        double* dst = g->px_host;
+        double* dst = g->px_land.host;
         pfl::call(st, [=](hipStream_t s) { (void)pf_copy_by_kernel(s, src, dst, bytes); });
     }
-    if (e == hipSuccess) e = pfl::event_record(st, g->px_ev);
+    if (e == hipSuccess) e = pfl::event_record(st, g->px_land.ev);
     pf_free(st, flags);
     pf_free(st, adj);
     if (e != hipSuccess) {
@@ -457,12 +438,12 @@ int pf_window_slots_prepare(pf_graph* g) {
     g->px_state = 0;
     const int64_t nw = g->n_pad / g->win_rows;
     const int64_t tail = (nw + 1) & ~(int64_t)1;
-    if (hipEventSynchronize(g->px_ev) != hipSuccess) {
+    if (hipEventSynchronize(g->px_land.ev) != hipSuccess) {
         (void)hipGetLastError();
         pf_window_slots_free(g);
         return PF_OK;
     }
-    const int32_t* pin = reinterpret_cast<const int32_t*>(g->px_host);
+    const int32_t* pin = reinterpret_cast<const int32_t*>(g->px_land.host);
     g->h_px_gh_cnt.assign(pin, pin + nw);
     if (pin[tail]) {  // the builder's flag: a window reads more outside rows than the structures hold
         pf_window_slots_free(g);

@@ -15,6 +15,13 @@
 // twice, used after it, or never destroyed - with the n-th hipEventCreate failing, wanted and not wanted, through start,
 // stop and read and through every early end of a call: each event created is destroyed exactly once, the failure is the
 // call's error, and a timer that is not wanted makes no event call at all.
+// HostLanding runs over stand-ins of hipHostMalloc / hipHostFree (heap blocks of exactly the size asked for) and of
+// hipEventCreateWithFlags, each failing on the n-th call, against a HostPools of its own: a pooled block of cap >= need
+// is taken and leaves the pool, a smaller one is skipped; a block that is large enough is kept without any call; a grow
+// returns the old block to the pool exactly once, and only after the drain where the caller named a stream; after a
+// failed ensure - no block, no event, a failed grow - the landing is empty and may be ensured or released again; release
+// twice is harmless; and after every step each live block and each live event is held exactly once, by a landing or by a
+// pool, until the teardown frees each of them once.
 // Built with -fsanitize=address,undefined (tests/test_scratch_paths.py): a block freed twice, used after its release or
 // overrun by a copy stops the program there.  Exit status 0 and "ok" on the last line: every check held.
 #include <stdio.h>
@@ -84,8 +91,10 @@ hipError_t hipMemsetAsync(void* dst, int value, size_t bytes, hipStream_t) {
     memset(dst, value, bytes);
     return hipSuccess;
 }
+void (*g_on_sync)() = nullptr;  // what a sequence wants looked at while the stream is being drained
 hipError_t hipStreamSynchronize(hipStream_t) {
     ++g_hip_calls;
+    if (g_on_sync) g_on_sync();
     return hipSuccess;
 }
 hipError_t hipGetLastError(void) { return hipSuccess; }
@@ -107,6 +116,7 @@ hipError_t hipEventCreate(hipEvent_t* e) {
     g_events[*e] = 0;
     return hipSuccess;
 }
+hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { return hipEventCreate(e); }
 hipError_t hipEventDestroy(hipEvent_t e) {
     ++g_event_calls;
     if (g_events.erase(e) != 1) {
@@ -133,6 +143,32 @@ hipError_t hipEventElapsedTime(float* ms, hipEvent_t a, hipEvent_t b) {
         return hipErrorInvalidResourceHandle;
     }
     *ms = 1.5f;
+    return hipSuccess;
+}
+}
+
+// ---- the pinned allocation of HostLanding: heap blocks of exactly the size asked for
+namespace {
+int g_host_fail_at = -1;  // the hipHostMalloc call (counted from 0) that fails; -1: none
+int g_host_calls = 0, g_host_bad = 0;  // bad: a hipHostFree of a block that is not live
+std::map<void*, size_t> g_pinned;
+const hipError_t HOST_ERROR = hipErrorOutOfMemory;
+}  // namespace
+
+extern "C" {
+hipError_t hipHostMalloc(void** p, size_t bytes, unsigned) {
+    *p = nullptr;
+    if (g_host_calls++ == g_host_fail_at) return HOST_ERROR;
+    *p = malloc(bytes);
+    g_pinned[*p] = bytes;
+    return hipSuccess;
+}
+hipError_t hipHostFree(void* p) {
+    if (g_pinned.erase(p) != 1) {
+        ++g_host_bad;
+        return hipErrorInvalidValue;
+    }
+    free(p);
     return hipSuccess;
 }
 }
@@ -283,6 +319,138 @@ void timed(bool wanted, int event_fail_at, int stop_early) {
     if (!wanted) CHECK(g_event_calls == 0);
 }
 
+// ---- HostLanding over a HostPools of the sequence's own
+// every live block and every live event is held exactly once: by one of the landings, or by a pool
+void held_once(const HostPools& pools, const HostLanding* const* ls, int n) {
+    std::map<const void*, int> blocks, events;
+    for (auto& pb : pools.pinned_pool) ++blocks[pb.second];
+    for (hipEvent_t e : pools.event_pool) ++events[e];
+    for (int i = 0; i < n; ++i) {
+        CHECK((ls[i]->host != nullptr) == (ls[i]->ev != nullptr));  // both or neither
+        CHECK((ls[i]->host != nullptr) == (ls[i]->cap != 0));
+        if (ls[i]->host) ++blocks[ls[i]->host];
+        if (ls[i]->ev) ++events[ls[i]->ev];
+    }
+    CHECK(blocks.size() == g_pinned.size() && events.size() == g_events.size());  // none leaked, none invented
+    for (auto& kv : blocks) CHECK(kv.second == 1 && g_pinned.count(const_cast<void*>(kv.first)) == 1);
+    for (auto& kv : events) CHECK(kv.second == 1 && g_events.count(const_cast<void*>(kv.first)) == 1);
+    for (auto& pb : pools.pinned_pool) CHECK(g_pinned[pb.second] == sizeof(double) * (size_t)(pb.first + 2));
+}
+
+int in_pool(const HostPools& pools, const double* p) {
+    int n = 0;
+    for (auto& pb : pools.pinned_pool) n += pb.second == p;
+    return n;
+}
+
+// pf_destroy in miniature: what the pools hold goes back to the runtime, each once
+void teardown(HostPools& pools) {
+    for (auto& pb : pools.pinned_pool) (void)hipHostFree(pb.second);
+    for (hipEvent_t e : pools.event_pool) (void)hipEventDestroy(e);
+    pools.pinned_pool.clear();
+    pools.event_pool.clear();
+    CHECK(g_pinned.empty() && g_events.empty() && g_host_bad == 0 && g_event_bad == 0);
+    for (auto& kv : g_pinned) free(kv.first);  // (a leak is this sequence's failed check, not the next one's too)
+    for (auto& kv : g_events) free(kv.first);
+    g_pinned.clear();
+    g_events.clear();
+}
+
+void landing_reset(int host_fail_at, int event_fail_at) {
+    g_host_fail_at = host_fail_at, g_event_fail_at = event_fail_at;
+    g_host_calls = g_host_bad = g_event_creates = g_event_calls = g_event_bad = g_hip_calls = 0;
+    g_on_sync = nullptr;
+}
+
+const HostPools* g_watch_pools = nullptr;  // while the stream is drained, this block is not in this pool yet
+const double* g_watch_block = nullptr;
+int g_early_returns = 0;
+
+void landings_take_grow_release() {
+    landing_reset(-1, -1);
+    HostPools pools;
+    HostLanding a, b, c, d, e;
+    const HostLanding* const all[5] = {&a, &b, &c, &d, &e};
+    // nothing held, nothing pooled: a new block of the floor, with its two spare doubles, and a new event; no drain
+    CHECK(a.ensure(pools, 10, 64, ST) == hipSuccess && a.host && a.cap == 64 && a.ev);
+    a.host[65] = 1.0;
+    CHECK(g_host_calls == 1 && g_event_creates == 1 && g_hip_calls == 0);
+    held_once(pools, all, 5);
+    // large enough: kept as it is, no call of any kind
+    const double* const first = a.host;
+    const hipEvent_t first_ev = a.ev;
+    CHECK(a.ensure(pools, 64, 64, ST) == hipSuccess && a.host == first && a.cap == 64 && a.ev == first_ev);
+    CHECK(g_host_calls == 1 && g_event_creates == 1 && g_hip_calls == 0);
+    // outgrown: back to the pool once, and only after the stream the caller named has been drained; the event stays
+    g_watch_pools = &pools, g_watch_block = first, g_early_returns = 0;
+    g_on_sync = [] { g_early_returns += in_pool(*g_watch_pools, g_watch_block); };
+    CHECK(a.ensure(pools, 65, 64, ST) == hipSuccess && a.host && a.host != first && a.cap == 65 && a.ev == first_ev);
+    g_on_sync = nullptr;
+    CHECK(g_hip_calls == 1 && g_early_returns == 0 && in_pool(pools, first) == 1 && g_host_calls == 2 && g_event_creates == 1);
+    a.host[66] = 1.0;
+    held_once(pools, all, 5);
+    // the pooled block of 64 is too small for 200 (and for a floor of 128): skipped, it stays in the pool
+    CHECK(b.ensure(pools, 200, 128, nullptr) == hipSuccess && b.cap == 200 && in_pool(pools, first) == 1 && g_host_calls == 3);
+    CHECK(c.ensure(pools, 10, 128, nullptr) == hipSuccess && c.cap == 128 && in_pool(pools, first) == 1 && g_host_calls == 4);
+    // cap >= need and no floor: taken, and it leaves the pool; `fresh` only sizes a new block
+    CHECK(d.ensure(pools, 10, 0, nullptr, 384) == hipSuccess && d.host == first && d.cap == 64 && pools.pinned_pool.empty());
+    CHECK(e.ensure(pools, 10, 0, nullptr, 384) == hipSuccess && e.cap == 384 && g_host_calls == 5);
+    e.host[385] = 1.0;
+    CHECK(g_hip_calls == 1);  // no drain where no stream was named, or nothing was held
+    held_once(pools, all, 5);
+    // a grow without a drain (the finaliser's): the old block is pooled all the same
+    const double* const d_old = d.host;
+    CHECK(d.ensure(pools, 100, 0, nullptr, 384) == hipSuccess && d.cap == 384 && in_pool(pools, d_old) == 1 && g_hip_calls == 1);
+    held_once(pools, all, 5);
+    // release gives both back; twice is harmless; the next landing is served from the pools without a call
+    const double* const a_old = a.host;
+    a.release(pools);
+    CHECK(!a.host && !a.ev && a.cap == 0 && in_pool(pools, a_old) == 1 && pools.event_pool.size() == 1);
+    a.release(pools);
+    CHECK(in_pool(pools, a_old) == 1 && pools.event_pool.size() == 1);
+    held_once(pools, all, 5);
+    const int host_calls = g_host_calls, creates = g_event_creates;
+    CHECK(a.ensure(pools, 65, 64, ST) == hipSuccess && a.host == a_old && a.ev == first_ev && pools.event_pool.empty());
+    CHECK(g_host_calls == host_calls && g_event_creates == creates && g_hip_calls == 1);
+    held_once(pools, all, 5);
+    for (HostLanding* l : {&a, &b, &c, &d, &e}) l->release(pools);
+    held_once(pools, all, 5);
+    CHECK(pools.pinned_pool.size() == g_pinned.size() && g_pinned.size() == 6 && pools.event_pool.size() == 5);
+    teardown(pools);
+}
+
+// which: 0 no pinned block to be had, 1 no event to be had, 2 a grow that finds no block
+void landing_fails(int which) {
+    landing_reset(-1, -1);
+    HostPools pools;
+    HostLanding a;
+    const HostLanding* const all[1] = {&a};
+    if (which == 2) {
+        CHECK(a.ensure(pools, 10, 64, ST) == hipSuccess);
+        g_host_fail_at = g_host_calls;
+    } else if (which == 0) {
+        g_host_fail_at = 0;
+    } else {
+        g_event_fail_at = 0;
+    }
+    const double* const old = a.host;
+    const hipError_t err = a.ensure(pools, 100, 64, ST);
+    CHECK(err == (which == 1 ? EVENT_ERROR : HOST_ERROR));
+    CHECK(!a.host && !a.ev && a.cap == 0);  // empty: no stale pointer to the block that went back
+    if (which == 2) CHECK(in_pool(pools, old) == 1 && pools.event_pool.size() == 1);  // ... once, and its event with it
+    if (which == 1) CHECK(pools.pinned_pool.size() == 1 && pools.pinned_pool[0].first == 100);  // the block that had no event
+    held_once(pools, all, 1);
+    a.release(pools);  // safe, also twice
+    a.release(pools);
+    held_once(pools, all, 1);
+    g_host_fail_at = g_event_fail_at = -1;
+    CHECK(a.ensure(pools, 100, 64, ST) == hipSuccess && a.host && a.cap >= 100 && a.ev);  // and it can be ensured again
+    a.host[a.cap + 1] = 1.0;
+    held_once(pools, all, 1);
+    a.release(pools);
+    teardown(pools);
+}
+
 }  // namespace
 
 int main() {
@@ -291,6 +459,8 @@ int main() {
     for (int wanted = 0; wanted < 2; ++wanted)
         for (int event_fail_at = -1; event_fail_at < 2; ++event_fail_at)
             for (int stop_early = 0; stop_early < 3; ++stop_early) timed(wanted != 0, event_fail_at, stop_early);
+    landings_take_grow_release();
+    for (int which = 0; which < 3; ++which) landing_fails(which);
     for (auto& kv : g_live) free(kv.first);
     printf("%d sequences, %d checks failed\n", N_ALLOC + 1, g_failures);
     if (g_failures) return 1;

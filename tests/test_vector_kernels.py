@@ -1,4 +1,4 @@
-"""The Krylov vector kernels of csrc/pf_operator.hip called one by one, each against an exact reference (tests/_exact.py).
+"""The Krylov vector kernels of csrc/pf_operator.hip, pf_orth.hip, pf_reduce.hip, pf_finalize.hip and pf_rows.hip called one by one, each against an exact reference (tests/_exact.py).
 
 Graphs come from random sparse matrices (`pf_graph_from_matrix`): any row count, empty rows, rows wider than one
 SELL-64 slice.  A matrix graph keeps the caller's row order up to a degree sort inside windows of at most 4096 aligned
@@ -184,7 +184,7 @@ ORTH_CASES = [(n, c) for n in (65, 4097, 12289) for c in (1, 2, 3, 4, 5, 7, 63, 
 def test_orth_exact(hip, graphs, n, count):
     """pf_orth_begin / pf_orth_end below 400k rows against two exact classical Gram-Schmidt passes: counts 1-4 (k_orth_local
     with orth_one_launch on, k_orth_dots<1> / k_orth_project<1> with it off), 5 (the first count past k_orth_local), counts
-    that are not a multiple of 4, 255 (the largest fused count) and 256 (PF_ORTH_MAX: dots_device + k_multi_axpy, two
+    that are not a multiple of 4, 255 (the largest fused count) and 256 (PF_ORTH_MAX: pf_dots_device + k_multi_axpy, two
     passes always); normalize on and off, the device's second pass (orth_device_passes), a split basis (orth_split: junk in
     the slots between the two ranges), a step that needs no second pass and one that does."""
     g = graphs(n)
@@ -485,7 +485,7 @@ def test_spmv_multi_exact(operators):
 
 
 def test_op_step_formula(operators):
-    """pf_op_step (k_sell_op, launch_op): out = alpha (shift x - A x) - beta prev, the formula of pyfocusr_hip.h, for
+    """pf_op_step (k_sell_op, pf_launch_op): out = alpha (shift x - A x) - beta prev, the formula of pyfocusr_hip.h, for
     every combination of alpha (1, -1, 0.37), shift (0, 1.3) and beta (0, 1, 0.6), with prev, without (prev = -1), and
     with out aliasing prev."""
     for label, g, op, A, extra in operators:
@@ -517,7 +517,7 @@ def test_op_step_formula(operators):
 def test_cheb_steps_split_and_one_step_path(hip, operators):
     """pf_cheb_steps: a degree-p recurrence split as (k_first = 1, n1) + (k_first = n1 + 1, p - n1) gives the bits of one
     call, for n1 = 0, 1, 3 and p - 1; and the bits of pf_cheb with one step per launch (persist off: ChebRun forms
-    every step with launch_op and the same alpha = 1/(e rho) or 2/(e rho), shift = c, beta = 0 or 1/rho^2, so the same
+    every step with pf_launch_op and the same alpha = 1/(e rho) or 2/(e rho), shift = c, beta = 0 or 1/rho^2, so the same
     bits are required, not a bound).  Both against the numpy recurrence (test_spmv_and_cheb's tolerance), rho = 1 and
     1.3, and the returned (prev, cur) slots: cur holds y_p, prev y_(p - 1)."""
     hip.persist_enable(False)
@@ -722,6 +722,67 @@ def test_finalize_and_resident_rows(graphs, n):
     g.finalize_wait()
     assert np.array_equal(nrm, got[:, cols] * signs)
     assert np.array_equal(g.final_rows(rows), got[rows])  # the resident block itself is unchanged
+
+
+def test_landings_grow_recycle_and_come_from_the_pool(hip):
+    """The pinned landings of a graph (HostLanding, pf_scratch.h) through their sizes, on a context of the test's own
+    and a 600-vertex mesh (n_pad 4096, the least there is): orth with counts 3, 63, 64, 70, 3 on one graph (64 is the first count to outgrow
+    the floor of 64 doubles: the stream is drained and the block recycled; 70 grows again; 3 keeps the large block),
+    gram 8 x 8 and 9 x 8, finalize with 2, 64, 65, 2 columns (65 outgrows the finaliser's floor of 384 doubles).  Then the
+    graph is freed and a second one on the same context takes its landings from the context's pools: counts 70 and 3
+    again.  Every result against the exact references and tolerances of test_orth_exact (one pass), test_gram_exact and
+    test_finalize_and_resident_rows."""
+    from pyfocusr_amd.meshgen import blob_mesh
+
+    n = 600
+    m = blob_mesh(n, seed=5)
+    rng = np.random.default_rng(n)
+    Q, ws = orth_inputs(rng, n, 70)
+    w = ws["mild"]
+    h1 = np.array([ex.exact_dot(Q[:, b], w) for b in range(70)])
+    depth = ex.reduction_depth(n)
+    own = hip.Context()
+
+    def graph():
+        g = hip.DeviceLaplacian(m.points, m.faces, ctx=own)
+        assert g.info.n_pad == 4096  # (one reduction chunk, mostly padding)
+        g.op = hip.PF_OP_RW  # (finalize_vectors: the slots as they are, no G^1/2)
+        g.ws_ensure(72)
+        upload_cols(g, 1, Q)
+        return g
+
+    def orth(g, count, label):
+        g.upload(0, w)
+        g.orth_begin(0, 1, count, True)
+        h, nrm = g.orth_end()
+        assert not g.orth_redone and not g.orth_twice, label
+        check_orth_result(g, 0, h, nrm, w, pair_reference(Q, w, h1, count), True, False, label)
+
+    try:
+        g = graph()
+        try:
+            for count in (3, 63, 64, 70, 3):
+                orth(g, count, "first graph, count %d" % count)
+            for (fa, ca, fb, cb) in ((1, 8, 9, 8), (1, 9, 10, 8)):
+                G = g.gram(fa, ca, fb, cb)
+                A, B = Q[:, fa - 1:fa - 1 + ca], Q[:, fb - 1:fb - 1 + cb]
+                bound = depth * ex.EPS * (np.abs(A).T @ np.abs(B)) * (1 + 1e-6)
+                want = np.stack([ex.exact_rowdots(A.T, B[:, j]) for j in range(cb)], axis=1)
+                assert np.all(np.abs(G - want) <= bound), (ca, cb, np.max(np.abs(G - want) - bound))
+            for k in (2, 64, 65, 2):
+                _, exp = orc.canonicalize(np.arange(float(k)), Q[:, :k] / np.linalg.norm(Q[:, :k], axis=0))
+                raw = g.finalize_vectors(1, k, minmax=False)
+                np.testing.assert_allclose(raw, exp, rtol=1e-13, atol=1e-16, err_msg="finalize, %d columns" % k)
+        finally:
+            g.close()
+        g = graph()
+        try:
+            for count in (70, 3):
+                orth(g, count, "second graph, count %d" % count)
+        finally:
+            g.close()
+    finally:
+        own.close()
 
 
 def test_point_rows(hip, ctx):
