@@ -21,10 +21,28 @@
 // query, (c) a triangle whose own box is farther than the query's best x slack.  A box contains its triangles, a
 // packet's box its queries, so in exact arithmetic each of these distances is a lower bound of the point-triangle
 // distance, and what is skipped is strictly farther than a triangle already found: it can neither win nor tie.  In
-// floating point a box distance (d subtractions, squares and additions) carries a relative error of about
-// (d + 2) eps <= 4e-15 at d = 16, and so does the exact test's d2; the slack of 1e-9 covers both a million times over,
-// and a triangle within the slack is tested, not skipped.  Bounds only shrink, so a test made against an older, larger
-// bound errs on the side of testing.  Lanes and waves of a query merge with the same (d2, index) rule.
+// floating point the argument is monotone rounding, not an error bound relative to d2 (d2 is computed from a ROUNDED
+// closest point c, whose absolute error is about eps |coordinate|: against d2 that is eps |coordinate| / distance, which
+// no fixed slack covers in a frame far from the origin).  Per coordinate k the box term e_k = max(lo_k - p_k,
+// p_k - hi_k, 0) and the exact test's p_k - c_k are each ONE rounded subtraction from the same p_k.  If lo_k <= c_k <=
+// hi_k then |p_k - c_k| >= e_k as real numbers, rounding keeps that order, and squaring and adding non-negative terms
+// left to right keep it too: the COMPUTED d2 of a triangle is never below the COMPUTED distance of a box that holds
+// its computed closest point, with no slack at all.  c is in every box of its triangle (a) when it is a corner: the
+// vertex regions return the stored coordinates; (b) on an edge, a + v ab with 0 <= v <= 1, and in the face,
+// (a + ab v) + ac w with v, w, v + w in [0, 1], whenever the differences ab, ac are exact: then every partial sum lies
+// between two stored corner coordinates as a real number and rounding cannot carry it past a representable bound.  ab
+// and ac ARE exact when a triangle's coordinates share a binade (Sterbenz), which is the case of every triangle in a
+// frame whose offset is large against the mesh - the far frame is the safe one.  Only where corners differ in sign or
+// by more than a factor 2 in some coordinate (meshes around the origin) can c_k leave [lo_k, hi_k], by at most about one
+// ulp u of the larger corner coordinate and only if the exact closest point is within u of that face of the box (v, or
+// v + w, within eps of 1); d2 then falls short of the box distance by at most 2 u x distance, relatively 2 u /
+// distance, and PF_BOX_SLACK = 1 + 1e-9 covers that for every query farther than 4.5e-7 of that coordinate from the
+// surface.  Nearer than that, and with the exact point within an ulp of a box face that the query lies beyond, this
+// argument does not decide; no such query is known (tests/test_surface_hostile.py and the sweeps
+// tests/fuzz_surfaces.py, tests/fuzz_surface_nd.py compare with brute force bit for bit in frames up to 1e6 extents
+// out, on needles, coincident sheets and queries from rounding distance outwards; profiles/surface_fuzz.md).  A
+// triangle within the slack is tested, not skipped.  Bounds only shrink, so a test made against an older, larger bound
+// errs on the side of testing.  Lanes and waves of a query merge with the same (d2, index) rule.
 //
 // Depth.  Every helper that loops over coordinates is templated on D: the depth it is compiled for (loops unrolled, d
 // ignored), or D = 0 for any d <= PF_ND_MAX, unrolled to 16 behind the uniform guard k < d so that no array is indexed at

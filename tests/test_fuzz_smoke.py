@@ -9,7 +9,8 @@ import pytest
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SWEEPS = [("tools/fuzz_spectrum.py", 101, 40), ("tools/fuzz_pipeline.py", 102, 16), ("tools/fuzz_solvers.py", 103, 16),
           ("tools/fuzz_recursive_eig.py", 104, 12), ("tests/fuzz_kernels.py", 105, 8), ("tests/fuzz_knn.py", 106, 30),
-          ("tests/fuzz_assembly_icp.py", 107, 12), ("tests/fuzz_tail.py", 108, 20)]
+          ("tests/fuzz_assembly_icp.py", 107, 12), ("tests/fuzz_tail.py", 108, 20), ("tests/fuzz_surfaces.py", 109, 32),
+          ("tests/fuzz_surface_nd.py", 110, 48)]
 
 
 @pytest.mark.gpu
