@@ -947,6 +947,57 @@ int pf_map_distortion(pf_ctx* ctx, const double* src_pts, int64_t n_src, const i
                       double* vertex_area, double* vertex_sigma, uint8_t* vertex_flags, int32_t* target_count,
                       double* target_premass, double* totals, int64_t* report, double* device_ms);
 
+/* ---- a population of shapes in correspondence: Procrustes alignment and principal modes (pf_shapes.hip; an extra) --------
+ * S shapes of n vertices each, vertex i of every shape the same anatomical point: X [S][n][3] f64, optional weights w [n]
+ * (vertex areas; NULL: every weight is 1.0) and a reference shape r [n][3] (zeros after create) stay on the device.  The
+ * device does elementwise work and sums of a fixed order; every small dense step (3 x 3 SVDs, the S x S eigenproblem) is
+ * the caller's.  f64 throughout, separate multiplies and adds; tests/_shape_model_ref.py states the definitions in numpy.
+ *   T(.)       the sum over the vertices i in ascending order along the fixed tree of pf_map_distortion's totals: 256
+ *              consecutive terms left to right from 0.0, 256 of those sums likewise, the rest in order
+ *   dot3(a, b) (a0 b0 + a1 b1) + a2 b2
+ *   sums over the shapes go left to right from shape 0
+ *   pf_shapes_create         shapes [S][n][3], weights [n] or NULL (host): one upload.  W = T(w_i) is computed once (n
+ *                            without weights).  pf_shapes_weight_sum returns W.
+ *   pf_shapes_center         c_s[a] = T(w_i x_sia) / W -> centroids_out [S][3] (may be NULL); then x_sia <- x_sia - c_s[a]
+ *   pf_shapes_mean           m_i = ((x_first,i + x_first+1,i) + ...) / count per coordinate over the shapes first ..
+ *                            first + count - 1 (the sum starts with its first term: count = 1 makes that shape the
+ *                            reference bit for bit); change = T(w_i dot3(m_i - r_i, m_i - r_i)) against the reference as
+ *                            it was; then m becomes the reference.  mean_out [n][3] and change_out may be NULL.
+ *   pf_shapes_align_sums     cross_out [S][9]: H_s[a][b] = T((w_i x_sia) r_ib); norm2_out [S]: q_s = T(w_i dot3(x_si, x_si));
+ *                            ref_norm2_out: rho2 = T(w_i dot3(r_i, r_i)).  One pass over the population for all 10 S + 1
+ *                            sums.  Each may be NULL.
+ *   pf_shapes_transform      R [S][9] (row-major 3 x 3), scale [S], t [S][3] or NULL:
+ *                            y_b = scale_s ((x0 R[0][b] + x1 R[1][b]) + x2 R[2][b]), + t_s[b] when t is given; in place
+ *   pf_shapes_gram           with d_si = x_si - r_i: gram_out [S][S], G[s][t] = T(w_i dot3(d_si, d_ti)) for s <= t, G[t][s]
+ *                            the same bits
+ *   pf_shapes_combine        coeff [K][S], 1 <= K <= S -> out [K][n][3], out_k,i,c = sum over s of coeff[k][s] d_si,c, left to
+ *                            right from 0.0
+ *   pf_shapes_scores         modes [K][n][3], 1 <= K <= 1024 -> scores_out [S][K], b[s][k] = T(w_i dot3(d_si, p_ki))
+ *   pf_shapes_set_reference  ref [n][3] becomes r
+ *   pf_shapes_download       shapes_out [S][n][3]: the population as it stands
+ *   pf_shapes_device_ms      *last_ms (may be NULL) = the device time of the last primitive that ran while the timing was
+ *                            on, between its uploads and its downloads (HIP events); then the timing is set to `enable`
+ * No floating-point atomics, no kernel waits for another block: two calls give the same bits.  The Gram and the scores run
+ * 16 x 16 pairs per block over LDS tiles; their partial sums are kept per 256 vertices while that stays below 1 GiB and per
+ * 65 536 vertices beyond (the same terms in the same order either way), so the scratch does not grow like n S^2.
+ * PF_E_ARG for S outside 1..1024, n outside 1..2^31-1, K outside 1..S (combine) or 1..1024 (scores), first < 0, count < 1
+ * or first + count > S, a coordinate, weight, rotation, scale, translation, coefficient or mode that is not finite, and a
+ * negative weight; PF_E_DEGENERATE when W is 0.  These checks run on the host before anything is launched. */
+typedef struct pf_shapes pf_shapes;
+int pf_shapes_create(pf_ctx* ctx, const double* shapes, int32_t S, int64_t n, const double* weights, pf_shapes** out);
+void pf_shapes_free(pf_shapes* h);
+int pf_shapes_weight_sum(pf_shapes* h, double* weight_sum);
+int pf_shapes_center(pf_shapes* h, double* centroids_out);
+int pf_shapes_mean(pf_shapes* h, int32_t first, int32_t count, double* mean_out, double* change_out);
+int pf_shapes_align_sums(pf_shapes* h, double* cross_out, double* norm2_out, double* ref_norm2_out);
+int pf_shapes_transform(pf_shapes* h, const double* R, const double* scale, const double* t);
+int pf_shapes_gram(pf_shapes* h, double* gram_out);
+int pf_shapes_combine(pf_shapes* h, const double* coeff, int32_t K, double* out);
+int pf_shapes_scores(pf_shapes* h, const double* modes, int32_t K, double* scores_out);
+int pf_shapes_set_reference(pf_shapes* h, const double* ref);
+int pf_shapes_download(pf_shapes* h, double* shapes_out);
+int pf_shapes_device_ms(pf_shapes* h, int32_t enable, double* last_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -230,6 +230,19 @@ SIGNATURES = {
     "pf_map_distortion": (C.c_int, [C.c_void_p, _f64p, C.c_int64, _i32p, C.c_int64, _f64p, C.c_int64, _f64p, _i32p, _f64p, C.c_int32,
                                     _f64p, _f64p, C.POINTER(C.c_uint8), _f64p, _f64p, C.POINTER(C.c_uint8), _i32p, _f64p, _f64p,
                                     _i64p, _f64p]),
+    "pf_shapes_create": (C.c_int, [C.c_void_p, _f64p, C.c_int32, C.c_int64, _f64p, C.POINTER(C.c_void_p)]),
+    "pf_shapes_free": (None, [C.c_void_p]),
+    "pf_shapes_weight_sum": (C.c_int, [C.c_void_p, _f64p]),
+    "pf_shapes_center": (C.c_int, [C.c_void_p, _f64p]),
+    "pf_shapes_mean": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _f64p, _f64p]),
+    "pf_shapes_align_sums": (C.c_int, [C.c_void_p, _f64p, _f64p, _f64p]),
+    "pf_shapes_transform": (C.c_int, [C.c_void_p, _f64p, _f64p, _f64p]),
+    "pf_shapes_gram": (C.c_int, [C.c_void_p, _f64p]),
+    "pf_shapes_combine": (C.c_int, [C.c_void_p, _f64p, C.c_int32, _f64p]),
+    "pf_shapes_scores": (C.c_int, [C.c_void_p, _f64p, C.c_int32, _f64p]),
+    "pf_shapes_set_reference": (C.c_int, [C.c_void_p, _f64p]),
+    "pf_shapes_download": (C.c_int, [C.c_void_p, _f64p]),
+    "pf_shapes_device_ms": (C.c_int, [C.c_void_p, C.c_int32, _f64p]),
 }
 
 _lib = None
@@ -1275,6 +1288,127 @@ class DeviceCpd(_Handle):
         """Q^T diag(P1) Q with the P1 of the last E-step."""
         _check(self._lib.pf_cpd_weighted_gram(self._h, _f64(self._H)))
         return self._H
+
+
+SHAPES_MAX_S = 1024  # the limits of pf_shapes_create and pf_shapes_scores
+SHAPES_MAX_K = 1024
+
+
+def check_population(shapes, weights=None):
+    """The argument checks of `DeviceShapes`, which need no library: ValueError / TypeError, or (shapes (S, n, 3) f64
+    C-contiguous, weights (n,) f64 or None).  A list of (n, 3) arrays is stacked; an array must already be float64."""
+    if isinstance(shapes, (list, tuple)):
+        parts = [np.asarray(p) for p in shapes]
+        if len(parts) == 0:
+            raise ValueError("a population needs at least one shape")
+        if any(p.ndim != 2 or p.shape[1] != 3 for p in parts):
+            raise ValueError("every shape must be an (n, 3) array")
+        if any(p.shape != parts[0].shape for p in parts):
+            raise ValueError("the shapes of a population must have the same number of points (they are in correspondence)")
+        shapes = np.stack(parts)
+    shapes = np.asarray(shapes)
+    if shapes.dtype != np.float64:
+        raise TypeError("shapes must be float64, not %s" % shapes.dtype)
+    if shapes.ndim != 3 or shapes.shape[2] != 3:
+        raise ValueError("shapes must be an (S, n, 3) array")
+    if not 1 <= shapes.shape[0] <= SHAPES_MAX_S:
+        raise ValueError("S = %d shapes out of range (1 .. %d)" % (shapes.shape[0], SHAPES_MAX_S))
+    if shapes.shape[1] == 0:
+        raise ValueError("the shapes have no points")
+    if not shapes.flags.c_contiguous:
+        raise ValueError("shapes must be C-contiguous, not a strided view")
+    if not np.isfinite(shapes).all():
+        raise ValueError("shape coordinates must be finite")
+    if weights is not None:
+        weights = np.asarray(weights)
+        if weights.dtype != np.float64:
+            raise TypeError("weights must be float64, not %s" % weights.dtype)
+        if weights.shape != (shapes.shape[1],):
+            raise ValueError("weights must have one entry per point")
+        if not np.isfinite(weights).all() or (weights < 0.0).any():
+            raise ValueError("weights must be finite and not negative")
+        weights = np.ascontiguousarray(weights)
+    return shapes, weights
+
+
+class DeviceShapes(_Handle):
+    """A population of S shapes in correspondence (S, n, 3), optional per-point weights and a reference shape in HBM for
+    Procrustes alignment and principal modes (`pf_shapes_*`; the definitions are in include/pyfocusr_hip.h)."""
+
+    _free = "pf_shapes_free"
+
+    def __init__(self, shapes, weights=None, ctx=None):
+        X, w = check_population(shapes, weights)
+        _Handle.__init__(self, ctx)
+        self.S, self.n = X.shape[0], X.shape[1]
+        self._create("pf_shapes_create", self.ctx._h, _f64(X), self.S, self.n, _f64(w))
+        W = np.empty(1)
+        _check(self._lib.pf_shapes_weight_sum(self._h, _f64(W)))
+        self.weight_sum = float(W[0])
+
+    def center(self):
+        """Centres every shape on its weighted centroid; returns the centroids (S, 3)."""
+        c = np.empty((self.S, 3))
+        _check(self._lib.pf_shapes_center(self._h, _f64(c)))
+        return c
+
+    def mean(self, first=0, count=None, return_mean=True):
+        """(mean (n, 3) or None, change): the mean of the shapes first .. first + count - 1 becomes the reference."""
+        count = self.S - int(first) if count is None else int(count)
+        m = np.empty((self.n, 3)) if return_mean else None
+        change = np.empty(1)
+        _check(self._lib.pf_shapes_mean(self._h, int(first), count, _f64(m), _f64(change)))
+        return m, float(change[0])
+
+    def align_sums(self):
+        """(H (S, 3, 3), q (S,), rho2) of `pf_shapes_align_sums`."""
+        H, q, rho2 = np.empty((self.S, 3, 3)), np.empty(self.S), np.empty(1)
+        _check(self._lib.pf_shapes_align_sums(self._h, _f64(H), _f64(q), _f64(rho2)))
+        return H, q, float(rho2[0])
+
+    def transform(self, R, scale=None, t=None):
+        R = _c_f64(R, (self.S, 3, 3))
+        scale = np.ones(self.S) if scale is None else _c_f64(scale, (self.S,))
+        t = None if t is None else _c_f64(t, (self.S, 3))
+        _check(self._lib.pf_shapes_transform(self._h, _f64(R), _f64(scale), _f64(t)))
+
+    def gram(self):
+        G = np.empty((self.S, self.S))
+        _check(self._lib.pf_shapes_gram(self._h, _f64(G)))
+        return G
+
+    def combine(self, coeff):
+        """(K, n, 3): row k is the sum over the shapes of coeff[k][s] (x_s - reference)."""
+        coeff = _c_f64(coeff)
+        if coeff.ndim != 2 or coeff.shape[1] != self.S or not 1 <= coeff.shape[0] <= self.S:
+            raise ValueError("coeff must be (K, S = %d) with 1 <= K <= S" % self.S)
+        out = np.empty((coeff.shape[0], self.n, 3))
+        _check(self._lib.pf_shapes_combine(self._h, _f64(coeff), coeff.shape[0], _f64(out)))
+        return out
+
+    def scores(self, modes):
+        """(S, K): the weighted inner products of every shape's offset from the reference with the modes (K, n, 3)."""
+        modes = _c_f64(modes)
+        if modes.ndim != 3 or modes.shape[1:] != (self.n, 3) or not 1 <= modes.shape[0] <= SHAPES_MAX_K:
+            raise ValueError("modes must be (K, %d, 3) with 1 <= K <= %d" % (self.n, SHAPES_MAX_K))
+        b = np.empty((self.S, modes.shape[0]))
+        _check(self._lib.pf_shapes_scores(self._h, _f64(modes), modes.shape[0], _f64(b)))
+        return b
+
+    def set_reference(self, ref):
+        ref = _c_f64(ref, (self.n, 3))
+        _check(self._lib.pf_shapes_set_reference(self._h, _f64(ref)))
+
+    def download(self):
+        X = np.empty((self.S, self.n, 3))
+        _check(self._lib.pf_shapes_download(self._h, _f64(X)))
+        return X
+
+    def device_ms(self, enable=True):
+        """The device time of the last timed primitive in ms; switches the timing on or off for the next ones."""
+        ms = np.zeros(1)
+        _check(self._lib.pf_shapes_device_ms(self._h, int(bool(enable)), _f64(ms)))
+        return float(ms[0])
 
 
 def gaussian_gram_product(A, B, beta, V, ctx=None):
