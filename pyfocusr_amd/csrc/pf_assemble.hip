@@ -17,6 +17,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <optional>
 #include <string>
 
 #include "pf_internal.h"
@@ -614,12 +615,6 @@ struct k_label_original {
 }
 };
 
-template <typename T>
-int dev_alloc(hipStream_t st, T** p, int64_t count) {
-    PF_HIP(pf_malloc(st, (void**)p, sizeof(T) * (size_t)std::max<int64_t>(count, 1)));
-    return PF_OK;
-}
-
 }  // namespace
 
 namespace {
@@ -724,13 +719,11 @@ struct FinishJob {
     void* pin = nullptr;
     size_t slice_bytes = 0;
     int round = 0;
-    std::vector<void*> tmp;
+    std::optional<Scratch> sc;  // the job's temporaries and what it allocates for the graph (begin_stats_and_labels on)
 
     void release() {
-        for (void* q : tmp) pf_free(st, q);
-        tmp.clear();
+        if (sc) sc->release_from(0);
     }
-    ~FinishJob() { release(); }
 
     int begin() {
         PF_TRY(begin_stats_and_labels());
@@ -739,17 +732,16 @@ struct FinishJob {
 
     int begin_stats_and_labels() {
         st = g->ctx->stream;
+        sc.emplace(st);
         const int64_t n = g->n;
         // the resident filter's hand-off ring depends on n_pad alone: filled here, beside the labelling rounds where the
         // build has forked, instead of in front of the solve's first filter application
         PF_TRY(pf_persist_ring_prefill(g, g->side_stream ? g->side_stream : st));
-        PF_TRY(dev_alloc(st, &flags, 8 + PF_CC_ROUNDS));  // the flags and the labelling rounds' flags: one block, one fill
-        tmp.push_back(flags);
+        flags = sc->get<int32_t>(8 + PF_CC_ROUNDS);  // the flags and the labelling rounds' flags: one block, one fill
+        width64 = sc->get<int64_t>(g->n_slices + 1);
+        d_roots = sc->get<int32_t>(PF_MAX_ROOTS);
+        PF_HIP(sc->err);
         round_flags = flags + 8;
-        PF_TRY(dev_alloc(st, &width64, g->n_slices + 1));
-        tmp.push_back(width64);
-        PF_TRY(dev_alloc(st, &d_roots, PF_MAX_ROOTS));
-        tmp.push_back(d_roots);
         PF_HIP(pfl::memset_words(st, flags, 0, sizeof(int32_t) * (8 + PF_CC_ROUNDS)));
         stats = flags + 2;  // [0] isolated, [1] max degree, [2] asym, [3] changed, [4] n_roots
         pfl::launch<k_row_stats>(dim3(pf_blocks(n)), dim3(PF_BLOCK), 0, st, g->rowptr, n, stats);
@@ -874,9 +866,10 @@ struct FinishJob {
             for (int32_t i = 0; i < n_roots; ++i) g->roots[(size_t)i] = h_roots[i];
         }
         std::sort(g->roots.begin(), g->roots.end());
-        PF_TRY(dev_alloc(st, &g->scol, g->sell_entries));
-        PF_TRY(dev_alloc(st, &g->sval_rw, g->sell_entries));
-        if (g->is_symmetric) PF_TRY(dev_alloc(st, &g->sval_sym, g->sell_entries));
+        g->scol = sc->keep<int32_t>(g->sell_entries);
+        g->sval_rw = sc->keep<double>(g->sell_entries);
+        if (g->is_symmetric) g->sval_sym = sc->keep<double>(g->sell_entries);
+        PF_HIP(sc->err);
         pfl::launch<k_fill_sell_entries>(dim3((unsigned)g->n_slices), dim3(PF_BLOCK), 0, st, g->rowptr, g->col, g->w, g->deg, g->g, g->sg, g->perm_m, g->iperm_m, n,
                                                                         g->slice_ptr, g->scol, g->sval_rw, g->sval_sym, g->diag);
         PF_HIP(hipGetLastError());
@@ -906,7 +899,7 @@ struct MeshBuild {
     pf_graph* g = nullptr;
     int pos = 0;  // 0: alone or the first mesh of a pair, 1: the second
     hipStream_t st = nullptr;
-    std::vector<void*> tmp;
+    std::optional<Scratch> sc;  // the build's temporaries and what it allocates for the graph, on the ctx stream (prepare on)
     bool ok = false;
     FinishJob fin;
     int32_t h_flags[8] = {0};
@@ -915,20 +908,12 @@ struct MeshBuild {
     int64_t n_edges = 0;
 
     void release() {  // the temporaries, under the stream that used them
-        for (void* p : tmp) pf_free(st, p);
-        tmp.clear();
+        if (sc) sc->release_from(0);
         fin.release();
     }
-    ~MeshBuild() {
+    ~MeshBuild() {  // until the build has succeeded, the graph itself is the build's to free - after the temporaries
         release();
         if (!ok && g) pf_graph_free(g);
-    }
-
-    template <typename T>
-    int scratch(T** p, int64_t count) {
-        int r = dev_alloc(st, p, count);
-        if (r == PF_OK) tmp.push_back((void*)*p);
-        return r;
     }
 
     // The first half in four phases (a pair's two builds are queued phase by phase from ONE thread, see
@@ -952,6 +937,7 @@ struct MeshBuild {
         pos = pair_pos;
         pf_ctx* ctx = mesh->ctx;
         st = ctx->stream;
+        sc.emplace(st);
         const int64_t n = mesh->n, n_faces = mesh->n_faces;
         const int32_t vpf = mesh->vpf;
         n_edges = n_faces * vpf;
@@ -977,28 +963,27 @@ struct MeshBuild {
         const bool face_bound = vpf == 3 && n_faces > 0;
         if (k == 0) {  // storage, the Morton order and the renumbered mesh, the edge list counted and scattered
             // (the counters that start from zero share one block, and so do deg / g / sg: two memsets instead of seven launches)
-            int32_t* zeroed = nullptr;
             const int64_t zstride = (n + 1 + 7) & ~(int64_t)7;
-            PF_TRY(scratch(&zeroed, 2 * zstride + 8));
+            int32_t* zeroed = sc->get<int32_t>(2 * zstride + 8);
+            b_rank = sc->get<int32_t>(n_edges);
+            b_start = sc->get<int32_t>(n + 1);
+            b_rcol = sc->get<int32_t>(n_edges);
+            b_rw = sc->get<double>(n_edges);
+            g->rowptr = sc->keep<int32_t>(n + 1);
+            g->deg = sc->keep<double>(3 * g->n_pad);  // deg, g, sg: one allocation (g->g and g->sg point into it)
+            g->diag = sc->keep<double>(g->n_pad);
+            g->label = sc->keep<int32_t>(g->n_pad);
+            g->perm = sc->keep<int32_t>(g->n_pad);
+            g->iperm = sc->keep<int32_t>(g->n_pad);
+            g->smooth = sc->keep<double>(g->n_pad);
+            g->slice_ptr = sc->keep<int64_t>(g->n_slices + 1);
+            g->perm_m = sc->keep<int32_t>(g->n_pad);
+            g->iperm_m = sc->keep<int32_t>(g->n_pad);
+            PF_HIP(sc->err);
             b_cnt = zeroed, b_ucnt = zeroed + zstride, b_flags = zeroed + 2 * zstride;
-            PF_TRY(scratch(&b_rank, n_edges));
-            PF_TRY(scratch(&b_start, n + 1));
-            PF_TRY(scratch(&b_rcol, n_edges));
-            PF_TRY(scratch(&b_rw, n_edges));
-            PF_TRY(dev_alloc(st, &g->rowptr, n + 1));
-            PF_TRY(dev_alloc(st, &g->deg, 3 * g->n_pad));  // deg, g, sg: one allocation (g->g and g->sg point into it)
             g->g = g->deg + g->n_pad;
             g->sg = g->deg + 2 * g->n_pad;
             g->deg_block = true;
-            PF_TRY(dev_alloc(st, &g->diag, g->n_pad));
-            PF_TRY(dev_alloc(st, &g->label, g->n_pad));
-            PF_TRY(dev_alloc(st, &g->perm, g->n_pad));
-            PF_TRY(dev_alloc(st, &g->iperm, g->n_pad));
-            PF_TRY(dev_alloc(st, &g->smooth, g->n_pad));
-            PF_TRY(dev_alloc(st, &g->slice_ptr, g->n_slices + 1));
-
-            PF_TRY(dev_alloc(st, &g->perm_m, g->n_pad));
-            PF_TRY(dev_alloc(st, &g->iperm_m, g->n_pad));
             PF_HIP(pfl::memset_words(st, zeroed, 0, sizeof(int32_t) * (size_t)(2 * zstride + 8)));
             PF_HIP(pfl::memset_words(st, g->deg, 0, sizeof(double) * 3 * g->n_pad));
             if (pos == 0) PF_HIP(pfl::event_record(st, ctx->ev0));
@@ -1008,8 +993,9 @@ struct MeshBuild {
             // the algorithmic bytes in counter traffic on the shuffled synthetic meshes).  b_flags[1]: the counting
             // sort's overflow flag (piled vertices), read back with everything else.
             PF_TRY(pf_morton_order(g, mesh->pts, robust ? nullptr : b_flags + 1));
-            PF_TRY(scratch(&pts_m, 3 * n));
-            PF_TRY(scratch(&faces_m, n_edges));
+            pts_m = sc->get<double>(3 * n);
+            faces_m = sc->get<int32_t>(n_edges);
+            PF_HIP(sc->err);
             d_pts = pts_m, d_faces = faces_m;
             if (n) {
                 pfl::launch<k_renumber_points>(dim3(pf_blocks(3 * n)), dim3(PF_BLOCK), 0, st, mesh->pts, g->morder, n, pts_m);
@@ -1020,7 +1006,8 @@ struct MeshBuild {
                 PF_HIP(hipGetLastError());
             }
 
-            if (face_bound) PF_TRY(scratch(&pmin, 1));
+            if (face_bound) pmin = sc->get<unsigned long long>(1);
+            PF_HIP(sc->err);
             if (n_edges) {
                 pfl::launch<k_count_edges>(dim3(pf_blocks(n_edges)), dim3(PF_BLOCK), 0, st, d_faces, n_edges, vpf, n, b_cnt, b_rank, b_flags, reinterpret_cast<double*>(pmin));
                 PF_HIP(hipGetLastError());
@@ -1039,8 +1026,9 @@ struct MeshBuild {
         if (k == 1) {  // CSR(W), degrees, the face bound
             // (col / w are sized by the upper bound: the sorted rows land in them at once, see k_sort_unique_rows;
             // b_flags[2]: a row lost a repeated entry - k_compact_rows has work, and the read-back tells the host)
-            PF_TRY(dev_alloc(st, &g->col, n_edges));
-            PF_TRY(dev_alloc(st, &g->w, n_edges));
+            g->col = sc->keep<int32_t>(n_edges);
+            g->w = sc->keep<double>(n_edges);
+            PF_HIP(sc->err);
             pfl::launch<k_sort_unique_rows>(dim3(pf_blocks(n)), dim3(PF_BLOCK), 0, st, b_start, n, b_rcol, b_rw, b_ucnt, g->morder, g->col, g->w, g->deg, g->g,
                                             g->sg, b_flags + 2);
             PF_HIP(hipGetLastError());
@@ -1095,7 +1083,8 @@ struct MeshBuild {
             const double b = (1.0 + (1.0 + sqrt(disc > 0.0 ? disc : 0.0)) / 2.0) * (1.0 + 1e-12);
             g->spectral_bound = b < 2.0 ? b : 2.0;
         }
-        PF_TRY(dev_alloc(st, &g->pts, 3 * n));  // kept for pf_point_rows (the mesh object may go away before the graph)
+        g->pts = sc->keep<double>(3 * n);  // kept for pf_point_rows (the mesh object may go away before the graph)
+        PF_HIP(sc->err);
         PF_HIP(pfl::memcpy_async(st, g->pts, mesh->pts, sizeof(double) * 3 * n, hipMemcpyDeviceToDevice));
         return PF_OK;
     }
@@ -1192,18 +1181,15 @@ int pf_mesh_upload(pf_ctx* ctx, const double* pts, int64_t n, const int32_t* fac
     m->n = n;
     m->n_faces = n_faces;
     m->vpf = vpf;
-    hipStream_t st = ctx->stream;
-    int r = dev_alloc(st, &m->pts, 3 * n);
-    if (r == PF_OK) r = dev_alloc(st, &m->faces, n_faces * vpf);
-    hipError_t e = hipSuccess;
-    if (r == PF_OK) e = pfl::memcpy_async(ctx->stream, m->pts, pts, sizeof(double) * 3 * n, hipMemcpyHostToDevice);
-    if (r == PF_OK && e == hipSuccess && n_faces)
-        e = pfl::memcpy_async(ctx->stream, m->faces, faces, sizeof(int32_t) * n_faces * vpf, hipMemcpyHostToDevice);
-    if (r == PF_OK && e == hipSuccess) e = pfl::sync(ctx->stream);
-    if (r != PF_OK || e != hipSuccess) {
-        if (e != hipSuccess) pf_set_error("pf_mesh_upload: %s", hipGetErrorString(e));
+    Scratch sc(ctx->stream);
+    m->pts = sc.keep<double>(3 * n);
+    m->faces = sc.keep<int32_t>(n_faces * vpf);
+    if (sc.ok()) sc.note(pfl::memcpy_async(sc.st, m->pts, pts, sizeof(double) * 3 * n, hipMemcpyHostToDevice));
+    if (sc.ok() && n_faces) sc.note(pfl::memcpy_async(sc.st, m->faces, faces, sizeof(int32_t) * n_faces * vpf, hipMemcpyHostToDevice));
+    if (sc.ok()) sc.note(pfl::sync(sc.st));
+    if (!sc.ok()) {
         pf_mesh_free(m);
-        return r != PF_OK ? r : PF_E_HIP;
+        return pf_hip_failed("pf_mesh_upload", sc.err);
     }
     *out = m;
     return PF_OK;
@@ -1368,37 +1354,30 @@ int pf_graph_from_matrix(pf_ctx* ctx, int64_t n, const int32_t* rowptr, const in
     g->win_rows = pf_window_rows(g->n_pad);
     g->n_slices = g->n_pad / PF_WAVE;
     g->n_chunks = (g->n_pad + PF_DOT_CHUNK - 1) / PF_DOT_CHUNK;
-    struct Guard {
+    struct MatrixBuild {  // until the build has succeeded, the graph itself is the build's to free
         pf_graph* g;
-        std::vector<void*> tmp;
         bool ok = false;
-        ~Guard() {
-            for (void* p : tmp) pf_free(g->ctx->stream, p);
+        ~MatrixBuild() {
             if (!ok) pf_graph_free(g);
         }
-    } guard{g};
-    int32_t *rp = nullptr, *ci = nullptr, *cnt = nullptr, *flags = nullptr;
-    double* va = nullptr;
-    auto scratch = [&](auto** p, int64_t count) -> int {
-        int r = dev_alloc(st, p, count);
-        if (r == PF_OK) guard.tmp.push_back((void*)*p);
-        return r;
-    };
-    PF_TRY(scratch(&rp, n + 1));
-    PF_TRY(scratch(&ci, nnz));
-    PF_TRY(scratch(&va, nnz));
-    PF_TRY(scratch(&cnt, n + 1));
-    PF_TRY(scratch(&flags, 8));
-    PF_TRY(dev_alloc(st, &g->rowptr, n + 1));
-    PF_TRY(dev_alloc(st, &g->deg, g->n_pad));
-    PF_TRY(dev_alloc(st, &g->g, g->n_pad));
-    PF_TRY(dev_alloc(st, &g->sg, g->n_pad));
-    PF_TRY(dev_alloc(st, &g->diag, g->n_pad));
-    PF_TRY(dev_alloc(st, &g->label, g->n_pad));
-    PF_TRY(dev_alloc(st, &g->perm, g->n_pad));
-    PF_TRY(dev_alloc(st, &g->iperm, g->n_pad));
-    PF_TRY(dev_alloc(st, &g->smooth, g->n_pad));
-    PF_TRY(dev_alloc(st, &g->slice_ptr, g->n_slices + 1));
+    } job{g};
+    Scratch sc(st);  // (declared after job: the temporaries go back before the graph of a failed build does)
+    int32_t* rp = sc.get<int32_t>(n + 1);
+    int32_t* ci = sc.get<int32_t>(nnz);
+    double* va = sc.get<double>(nnz);
+    int32_t* cnt = sc.get<int32_t>(n + 1);
+    int32_t* flags = sc.get<int32_t>(8);
+    g->rowptr = sc.keep<int32_t>(n + 1);
+    g->deg = sc.keep<double>(g->n_pad);
+    g->g = sc.keep<double>(g->n_pad);
+    g->sg = sc.keep<double>(g->n_pad);
+    g->diag = sc.keep<double>(g->n_pad);
+    g->label = sc.keep<int32_t>(g->n_pad);
+    g->perm = sc.keep<int32_t>(g->n_pad);
+    g->iperm = sc.keep<int32_t>(g->n_pad);
+    g->smooth = sc.keep<double>(g->n_pad);
+    g->slice_ptr = sc.keep<int64_t>(g->n_slices + 1);
+    PF_HIP(sc.err);
     PF_HIP(pfl::memcpy_async(st, rp, rowptr, sizeof(int32_t) * (n + 1), hipMemcpyHostToDevice));
     if (nnz) {
         PF_HIP(pfl::memcpy_async(st, ci, colidx, sizeof(int32_t) * nnz, hipMemcpyHostToDevice));
@@ -1419,12 +1398,13 @@ int pf_graph_from_matrix(pf_ctx* ctx, int64_t n, const int32_t* rowptr, const in
     PF_HIP(pfl::sync(st));
     PF_CHECK(!h_flag, PF_E_ARG, "pf_graph_from_matrix: column indices must be in range, sorted and unique within each row");
     g->nnz_w = nnz32;
-    PF_TRY(dev_alloc(st, &g->col, g->nnz_w));
-    PF_TRY(dev_alloc(st, &g->w, g->nnz_w));
+    g->col = sc.keep<int32_t>(g->nnz_w);
+    g->w = sc.keep<double>(g->nnz_w);
+    PF_HIP(sc.err);
     pfl::launch<k_csr_split>(dim3(pf_blocks(n)), dim3(PF_BLOCK), 0, st, rp, ci, va, g->rowptr, n, g->col, g->w, g->deg, g->g, g->sg);
     PF_HIP(hipGetLastError());
     PF_TRY(pf_graph_finish_general(g, nullptr));
-    guard.ok = true;
+    job.ok = true;
     *out = g;
     return PF_OK;
 }
@@ -1452,90 +1432,75 @@ int pf_graph_download(pf_graph* g, int32_t* rowptr, int32_t* colidx, double* w, 
                       double* l_diag, int32_t* component_label) {
     PF_CHECK(g, PF_E_ARG, "pf_graph_download: graph is NULL");
     PF_HIP(hipSetDevice(g->ctx->device));
-    hipStream_t st = g->ctx->stream;
+    Scratch sc(g->ctx->stream);
+    hipStream_t st = sc.st;
+    const int64_t n = g->n, nnz = g->nnz_w;
+    auto back = [&](void* dst, const void* src, size_t bytes) {  // dst == NULL: the caller did not ask for it
+        if (sc.ok() && dst && bytes) sc.note(pfl::memcpy_async(st, dst, src, bytes, hipMemcpyDeviceToHost));
+    };
     if (g->morder) {  // assembled in m-space: the caller's order is made here
-        const int64_t n = g->n, nnz = g->nnz_w;
-        int32_t *len = nullptr, *rp = nullptr, *co = nullptr, *lab = nullptr, *small = nullptr;
-        double *wo = nullptr, *lo = nullptr, *dg = nullptr, *ld = nullptr;
-        int rc = PF_OK;
-        auto bad = [&](hipError_t e) {
-            if (e != hipSuccess && rc == PF_OK) {
-                pf_set_error("pf_graph_download: %s", hipGetErrorString(e));
-                rc = PF_E_HIP;
-            }
-            return e != hipSuccess;
-        };
-        do {
-            if (bad(pf_malloc(st, (void**)&len, sizeof(int32_t) * (size_t)(n + 1))) || bad(pf_malloc(st, (void**)&rp, sizeof(int32_t) * (size_t)(n + 1)))) break;
+        int32_t* len = sc.get<int32_t>(n + 1);
+        int32_t* rp = sc.get<int32_t>(n + 1);
+        if (sc.ok()) {
             pfl::launch<k_len_original>(dim3(pf_blocks(n + 1)), dim3(PF_BLOCK), 0, st, g->rowptr, g->mrank, n, len);
-            if (bad(hipGetLastError())) break;
-            if (pf_exclusive_scan_i32(st, len, rp, n + 1) != PF_OK) {
-                rc = PF_E_HIP;
-                break;
-            }
-            const size_t ne = (size_t)std::max<int64_t>(nnz, 1);
-            if (colidx && bad(pf_malloc(st, (void**)&co, sizeof(int32_t) * ne))) break;
-            if (w && bad(pf_malloc(st, (void**)&wo, sizeof(double) * ne))) break;
-            if (l_offdiag && bad(pf_malloc(st, (void**)&lo, sizeof(double) * ne))) break;
-            if (deg && bad(pf_malloc(st, (void**)&dg, sizeof(double) * (size_t)n))) break;
-            if (l_diag && bad(pf_malloc(st, (void**)&ld, sizeof(double) * (size_t)n))) break;
+            sc.launched();
+        }
+        if (sc.ok() && pf_exclusive_scan_i32(st, len, rp, n + 1) != PF_OK) {  // (its message stands)
+            (void)pfl::sync(st);
+            return PF_E_HIP;
+        }
+        int32_t* co = colidx ? sc.get<int32_t>(nnz) : nullptr;
+        double* wo = w ? sc.get<double>(nnz) : nullptr;
+        double* lo = l_offdiag ? sc.get<double>(nnz) : nullptr;
+        double* dg = deg ? sc.get<double>(n) : nullptr;
+        double* ld = l_diag ? sc.get<double>(n) : nullptr;
+        if (sc.ok()) {
             pfl::launch<k_rows_original>(dim3(pf_blocks(n)), dim3(PF_BLOCK), 0, st, g->rowptr, g->col, g->w, g->g, g->deg, g->mrank, g->morder, rp, n, co, wo, lo, dg, ld);
-            if (bad(hipGetLastError())) break;
-            if (component_label) {
-                if (bad(pf_malloc(st, (void**)&lab, sizeof(int32_t) * (size_t)n)) || bad(pf_malloc(st, (void**)&small, sizeof(int32_t) * (size_t)n))) break;
-                if (bad(pfl::memset_words(st, small, 0x7f, sizeof(int32_t) * (size_t)n))) break;
+            sc.launched();
+        }
+        if (component_label) {
+            int32_t* lab = sc.get<int32_t>(n);
+            int32_t* small = sc.get<int32_t>(n);
+            if (sc.ok()) sc.note(pfl::memset_words(st, small, 0x7f, sizeof(int32_t) * (size_t)n));
+            if (sc.ok()) {
                 pfl::launch<k_label_min_original>(dim3(pf_blocks(n)), dim3(PF_BLOCK), 0, st, g->label, g->morder, n, small);
                 pfl::launch<k_label_original>(dim3(pf_blocks(n)), dim3(PF_BLOCK), 0, st, g->label, g->mrank, small, n, lab);
-                if (bad(hipGetLastError())) break;
-                if (bad(pfl::memcpy_async(st, component_label, lab, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost))) break;
+                sc.launched();
             }
-            if (rowptr && bad(pfl::memcpy_async(st, rowptr, rp, sizeof(int32_t) * (size_t)(n + 1), hipMemcpyDeviceToHost))) break;
-            if (colidx && nnz && bad(pfl::memcpy_async(st, colidx, co, sizeof(int32_t) * (size_t)nnz, hipMemcpyDeviceToHost))) break;
-            if (w && nnz && bad(pfl::memcpy_async(st, w, wo, sizeof(double) * (size_t)nnz, hipMemcpyDeviceToHost))) break;
-            if (l_offdiag && nnz && bad(pfl::memcpy_async(st, l_offdiag, lo, sizeof(double) * (size_t)nnz, hipMemcpyDeviceToHost))) break;
-            if (deg && bad(pfl::memcpy_async(st, deg, dg, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost))) break;
-            if (l_diag && bad(pfl::memcpy_async(st, l_diag, ld, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost))) break;
-        } while (0);
-        bad(pfl::sync(st));
-        for (void* q : {(void*)len, (void*)rp, (void*)co, (void*)lab, (void*)small, (void*)wo, (void*)lo, (void*)dg, (void*)ld}) pf_free(st, q);
-        return rc;
-    }
-    double* tmp = nullptr;
-    if (rowptr) PF_HIP(pfl::memcpy_async(st, rowptr, g->rowptr, sizeof(int32_t) * (g->n + 1), hipMemcpyDeviceToHost));
-    if (colidx && g->nnz_w) PF_HIP(pfl::memcpy_async(st, colidx, g->col, sizeof(int32_t) * g->nnz_w, hipMemcpyDeviceToHost));
-    if (w && g->nnz_w) PF_HIP(pfl::memcpy_async(st, w, g->w, sizeof(double) * g->nnz_w, hipMemcpyDeviceToHost));
-    if (deg) PF_HIP(pfl::memcpy_async(st, deg, g->deg, sizeof(double) * g->n, hipMemcpyDeviceToHost));
-    double* tmp_diag = nullptr;
-    if (l_diag) {  // g->diag is stored in solver order: rebuild g_i deg_i in mesh order
-        PF_HIP(pf_malloc(st, (void**)&tmp_diag, sizeof(double) * g->n));
-        pfl::launch<k_l_diag>(dim3(pf_blocks(g->n)), dim3(PF_BLOCK), 0, st, g->deg, g->g, g->n, tmp_diag);
-        hipError_t ed = hipGetLastError();
-        if (ed == hipSuccess) ed = pfl::memcpy_async(st, l_diag, tmp_diag, sizeof(double) * g->n, hipMemcpyDeviceToHost);
-        if (ed != hipSuccess) {
-            pfl::sync(st);
-            pf_free(st, tmp_diag);
-            pf_set_error("pf_graph_download: %s", hipGetErrorString(ed));
-            return PF_E_HIP;
+            back(component_label, lab, sizeof(int32_t) * (size_t)n);
+        }
+        back(rowptr, rp, sizeof(int32_t) * (size_t)(n + 1));
+        back(colidx, co, sizeof(int32_t) * (size_t)nnz);
+        back(w, wo, sizeof(double) * (size_t)nnz);
+        back(l_offdiag, lo, sizeof(double) * (size_t)nnz);
+        back(deg, dg, sizeof(double) * (size_t)n);
+        back(l_diag, ld, sizeof(double) * (size_t)n);
+    } else {
+        back(rowptr, g->rowptr, sizeof(int32_t) * (size_t)(n + 1));
+        back(colidx, g->col, sizeof(int32_t) * (size_t)nnz);
+        back(w, g->w, sizeof(double) * (size_t)nnz);
+        back(deg, g->deg, sizeof(double) * (size_t)n);
+        if (l_diag) {  // g->diag is stored in solver order: rebuild g_i deg_i in mesh order
+            double* tmp_diag = sc.get<double>(n);
+            if (sc.ok()) {
+                pfl::launch<k_l_diag>(dim3(pf_blocks(n)), dim3(PF_BLOCK), 0, st, g->deg, g->g, n, tmp_diag);
+                sc.launched();
+            }
+            back(l_diag, tmp_diag, sizeof(double) * (size_t)n);
+        }
+        back(component_label, g->label, sizeof(int32_t) * (size_t)n);
+        if (l_offdiag && nnz) {
+            double* tmp = sc.get<double>(nnz);
+            if (sc.ok()) {
+                pfl::launch<k_l_offdiag>(dim3(pf_blocks(n)), dim3(PF_BLOCK), 0, st, g->rowptr, g->w, g->g, n, tmp);
+                sc.launched();
+            }
+            back(l_offdiag, tmp, sizeof(double) * (size_t)nnz);
         }
     }
-    if (component_label) PF_HIP(pfl::memcpy_async(st, component_label, g->label, sizeof(int32_t) * g->n, hipMemcpyDeviceToHost));
-    if (l_offdiag && g->nnz_w) {
-        PF_HIP(pf_malloc(st, (void**)&tmp, sizeof(double) * g->nnz_w));
-        pfl::launch<k_l_offdiag>(dim3(pf_blocks(g->n)), dim3(PF_BLOCK), 0, st, g->rowptr, g->w, g->g, g->n, tmp);
-        hipError_t e = hipGetLastError();
-        if (e == hipSuccess) e = pfl::memcpy_async(st, l_offdiag, tmp, sizeof(double) * g->nnz_w, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) {
-            pfl::sync(st);
-            pf_free(st, tmp);
-            pf_set_error("pf_graph_download: %s", hipGetErrorString(e));
-            return PF_E_HIP;
-        }
-    }
-    hipError_t e = pfl::sync(st);
-    pf_free(st, tmp);
-    pf_free(st, tmp_diag);
-    PF_HIP(e);
-    return PF_OK;
+    sc.note(pfl::sync(st));  // (also after a failure: the copies queued so far write the caller's arrays)
+    return sc.ok() ? PF_OK : pf_hip_failed("pf_graph_download", sc.err);
 }
 
 }  // extern "C"
+

@@ -405,8 +405,8 @@ static inline double* pf_tmp(pf_graph* g, int which) { return g->ws + (int64_t)(
 int pf_graph_finish_general(pf_graph* g, const double* d_pts);
 
 // pf_sort.hip: the stable radix sort of n < 2^31 (key, 32-bit value) pairs on key bits [0, end_bit), queued on sc's stream;
-// its temporary is scratch of sc, and it does nothing once sc has failed.  Sorts the Morton orders of the surfaces and of
-// the k-NN box hierarchy, the cells of the k-NN grid's large point sets, and the half-edges, patches, loop ends, cells,
+// its temporary is scratch of sc, and it does nothing once sc has failed.  Sorts the Morton orders of the graphs
+// (pf_reorder.hip), of the surfaces and of the k-NN box hierarchy, the cells of the k-NN grid's large point sets, and the half-edges, patches, loop ends, cells,
 // labels and dual faces of the mesh units.  Values are only moved, so unsigned ones go through the same instance.
 void pf_sort_pairs(Scratch& sc, const unsigned* k_in, unsigned* k_out, const int32_t* v_in, int32_t* v_out, int64_t n, int end_bit);
 void pf_sort_pairs(Scratch& sc, const unsigned long long* k_in, unsigned long long* k_out, const int32_t* v_in, int32_t* v_out,
@@ -464,7 +464,8 @@ int pf_compute_order(pf_graph* g, const double* d_pts, int32_t* d_overflow = nul
 int pf_morton_order(pf_graph* g, const double* d_pts, int32_t* d_overflow);
 
 // Rows per window of the resident Chebyshev kernel: one window per block, at most 256 blocks.
-static inline int32_t pf_window_rows(int64_t n_pad) { return n_pad <= 262144 ? 1024 : (n_pad <= 524288 ? 2048 : 4096); }
+constexpr int32_t pf_window_rows(int64_t n_pad) { return n_pad <= 262144 ? 1024 : (n_pad <= 524288 ? 2048 : 4096); }
+static_assert(pf_window_rows(INT64_MAX) <= 4096, "k_sort_windows (pf_reorder.hip) covers every window size pf_window_rows returns");
 
 // pf_knn.hip: pf_knn1_blocks with every column and scale 1 whose result stays on the device (ctx->knn_idx, ctx->knn_d2)
 int pf_knn1_device(pf_ctx* c, const double* ref_block, int64_t n_ref, int32_t ref_stride, const double* qry_block, int64_t n_qry,

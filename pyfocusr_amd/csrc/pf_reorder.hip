@@ -14,9 +14,7 @@
 //      windows - are its FIRST rows, so that the resident Chebyshev kernel (pf_persist.hip), whose
 //      blocks own one window each, can compute and publish exactly those rows first and do the
 //      interior rows while the published values travel.
-// perm[new] = old (-1 on padding rows), iperm[old] = new.  The radix sorts are hipCUB's.
-#include <hipcub/hipcub.hpp>
-
+// perm[new] = old (-1 on padding rows), iperm[old] = new.  The radix sort is the library's (pf_sort_pairs).
 #include "pf_internal.h"
 #include "pf_launch.h"
 #include "pf_wave.h"
@@ -259,7 +257,7 @@ struct k_smooth_start {
 
 
 // ---- Morton order without a general sort (round 3) ------------------------------------------------------------------
-// hipCUB hands arrays below 1M items to rocPRIM's merge sort: 16 launches, ~100 us for a 250k-vertex mesh.  The keys here
+// The library's radix sort hands arrays below 1M items to rocPRIM's merge sort: 16 launches, ~100 us for a 250k-vertex mesh.  The keys here
 // are cell codes of points spread over a bounding box, so a counting sort by the key's leading bits leaves buckets of a few
 // dozen vertices at most, and a vertex finds its final place by counting the bucket mates that precede it in (key,
 // index) order - the order a stable sort of the keys gives, whatever order the atomics filled the bucket in.  Six
@@ -317,238 +315,147 @@ struct k_order_rank {
 }
 };
 
+// The order by counting of n >= 4096 keys k0: order[] takes the vertices in (key, index) order.  k1 / v0: the bucketed keys
+// and vertices (v0's identity is not needed any more: the index is the thread's own).  A HIP failure is sc's; the scan
+// reports its own (PF_E_HIP, its message stands).
+int order_by_counting(Scratch& sc, const unsigned* k0, unsigned* k1, int32_t* v0, int64_t n, int32_t* order, int32_t* d_overflow) {
+    int bits = 12;
+    while (bits < 22 && ((int64_t)1 << bits) < 2 * n) ++bits;  // ~2 buckets per vertex, 4 M at most
+    const int shift = 30 - bits;
+    const int64_t nb = (int64_t)1 << bits;
+    int32_t* hist = sc.get<int32_t>(2 * nb + 2);  // [nb + 1] counts, then [nb] cursors: one block, one fill
+    int32_t* bstart = sc.get<int32_t>(nb + 1);
+    if (sc.ok()) sc.note(pfl::memset_words(sc.st, hist, 0, sizeof(int32_t) * (size_t)(2 * nb + 2)));
+    if (sc.ok()) {
+        pfl::launch<k_order_hist>(dim3(pf_blocks(n)), dim3(PF_BLOCK), 0, sc.st, k0, n, shift, hist);
+        sc.launched();
+    }
+    if (sc.ok() && pf_exclusive_scan_i32(sc.st, hist, bstart, nb + 1) != PF_OK) return PF_E_HIP;
+    if (sc.ok()) {
+        pfl::launch<k_order_scatter>(dim3(pf_blocks(n)), dim3(PF_BLOCK), 0, sc.st, k0, n, shift, bstart, hist + nb + 1, k1, v0);
+        pfl::launch<k_order_rank>(dim3(pf_blocks(n)), dim3(PF_BLOCK), 0, sc.st, k1, v0, n, shift, bstart, order, d_overflow);
+        sc.launched();
+    }
+    return PF_OK;
+}
+
+// The sort inside windows (k_sort_windows) on stream ls: out[r] = vals[..] of the rows of r's window in key order, the
+// rows' own positions with vals == NULL.  Every window size there is fits its LDS (pf_window_rows, pf_internal.h).
+void sort_in_windows(Scratch& sc, hipStream_t ls, const unsigned* keys, const int32_t* vals, int64_t n, int32_t win_rows, int32_t* out) {
+    if (!sc.ok()) return;
+    int32_t n_pow2 = 2;
+    while (n_pow2 < win_rows) n_pow2 <<= 1;
+    pfl::launch<k_sort_windows>(dim3((unsigned)((n + win_rows - 1) / win_rows)), dim3(1024), sizeof(unsigned long long) * (size_t)n_pow2, ls, keys, vals, n, win_rows, n_pow2, out);
+    sc.launched();
+}
+
 }  // namespace
 
 // The Morton order of a mesh's points, computed BEFORE the mesh is assembled (round 4): g->morder[m] = original vertex,
 // g->mrank[original] = m, g->order_bbox.  The assembler renumbers points and faces with it and builds everything in that
 // space; pf_compute_order then only refines the order inside windows.
 int pf_morton_order(pf_graph* g, const double* d_pts, int32_t* d_overflow) {
-    hipStream_t st = g->ctx->stream;
+    Scratch sc(g->ctx->stream);
+    hipStream_t st = sc.st;
     const int64_t n = g->n;
-    const int in = (int)n;
-    unsigned *k0 = nullptr, *k1 = nullptr;
-    int32_t* v0 = nullptr;
-    void* tmp = nullptr;
-    int32_t *hist = nullptr, *bstart = nullptr;
-    int rc = PF_OK;
-    auto fail = [&](hipError_t e) {
-        if (e != hipSuccess && rc == PF_OK) {
-            pf_set_error("pf_morton_order: %s", hipGetErrorString(e));
-            rc = PF_E_HIP;
-        }
-        return e != hipSuccess;
-    };
-    do {
-        if (fail(pf_malloc(st, (void**)&g->order_bbox, 6 * sizeof(unsigned long long)))) break;
-        if (fail(pf_malloc(st, (void**)&g->morder, sizeof(int32_t) * std::max<int64_t>(n, 1)))) break;
-        if (fail(pf_malloc(st, (void**)&g->mrank, sizeof(int32_t) * std::max<int64_t>(n, 1)))) break;
-        if (fail(pf_malloc(st, (void**)&k0, sizeof(unsigned) * std::max<int64_t>(n, 1))) ||
-            fail(pf_malloc(st, (void**)&k1, sizeof(unsigned) * std::max<int64_t>(n, 1))) ||
-            fail(pf_malloc(st, (void**)&v0, sizeof(int32_t) * std::max<int64_t>(n, 1))))
-            break;
-        if (fail(pfl::memset_words(st, g->order_bbox, 0, 6 * sizeof(unsigned long long)))) break;
-        if (n == 0) break;
+    g->order_bbox = sc.keep<unsigned long long>(6);
+    g->morder = sc.keep<int32_t>(n);
+    g->mrank = sc.keep<int32_t>(n);
+    unsigned* k0 = sc.get<unsigned>(n);
+    unsigned* k1 = sc.get<unsigned>(n);
+    int32_t* v0 = sc.get<int32_t>(n);
+    if (sc.ok()) sc.note(pfl::memset_words(st, g->order_bbox, 0, 6 * sizeof(unsigned long long)));
+    if (sc.ok() && n) {
         pfl::launch<k_bbox>(dim3(256), dim3(PF_BLOCK), 0, st, d_pts, n, g->order_bbox);
         pfl::launch<k_morton_keys>(dim3(pf_blocks(n)), dim3(PF_BLOCK), 0, st, d_pts, n, g->order_bbox, k0, v0);
-        if (fail(hipGetLastError())) break;
-        const bool counting = d_overflow != nullptr && n >= 4096;  // (else: the general sort)
-        if (counting) {
-            int bits = 12;
-            while (bits < 22 && ((int64_t)1 << bits) < 2 * n) ++bits;  // ~2 buckets per vertex, 4 M at most
-            const int shift = 30 - bits;
-            const int64_t nb = (int64_t)1 << bits;
-            if (fail(pf_malloc(st, (void**)&hist, sizeof(int32_t) * (size_t)(2 * nb + 2)))) break;  // [nb + 1] counts, then [nb] cursors
-            if (fail(pf_malloc(st, (void**)&bstart, sizeof(int32_t) * (size_t)(nb + 1)))) break;
-            if (fail(pfl::memset_words(st, hist, 0, sizeof(int32_t) * (size_t)(2 * nb + 2)))) break;
-            pfl::launch<k_order_hist>(dim3(pf_blocks(n)), dim3(PF_BLOCK), 0, st, k0, n, shift, hist);
-            if (fail(hipGetLastError())) break;
-            if (pf_exclusive_scan_i32(st, hist, bstart, nb + 1) != PF_OK) {
-                rc = PF_E_HIP;
-                break;
-            }
-            // k1 / v0: the bucketed keys and vertices (v0's identity is not needed any more: the index is the thread's own)
-            pfl::launch<k_order_scatter>(dim3(pf_blocks(n)), dim3(PF_BLOCK), 0, st, k0, n, shift, bstart, hist + nb + 1, k1, v0);
-            pfl::launch<k_order_rank>(dim3(pf_blocks(n)), dim3(PF_BLOCK), 0, st, k1, v0, n, shift, bstart, g->morder, d_overflow);
-            if (fail(hipGetLastError())) break;
-        } else {
-            size_t need = 0;
+        sc.launched();
+        if (d_overflow != nullptr && n >= 4096) {
+            if (order_by_counting(sc, k0, k1, v0, n, g->morder, d_overflow) != PF_OK) return PF_E_HIP;
+        } else if (sc.ok()) {  // the general sort
             pfl::flush_self();  // (a library sort launches at once: whatever this thread has recorded goes first)
-            if (fail(hipcub::DeviceRadixSort::SortPairs(nullptr, need, k0, k1, v0, g->morder, in, 0, 30, st))) break;
-            if (fail(pf_malloc(st, &tmp, need))) break;
-            if (fail(hipcub::DeviceRadixSort::SortPairs(tmp, need, k0, k1, v0, g->morder, in, 0, 30, st))) break;
+            pf_sort_pairs(sc, k0, k1, v0, g->morder, n, 30);
         }
-        pfl::launch<k_scatter_pos>(dim3(pf_blocks(n)), dim3(PF_BLOCK), 0, st, g->morder, n, g->mrank);
-        if (fail(hipGetLastError())) break;
-    } while (0);
-    pf_free(st, k0);
-    pf_free(st, k1);
-    pf_free(st, v0);
-    pf_free(st, tmp);
-    pf_free(st, hist);
-    pf_free(st, bstart);
-    return rc;
+        if (sc.ok()) {
+            pfl::launch<k_scatter_pos>(dim3(pf_blocks(n)), dim3(PF_BLOCK), 0, st, g->morder, n, g->mrank);
+            sc.launched();
+        }
+    }
+    return sc.ok() ? PF_OK : pf_hip_failed("pf_morton_order", sc.err);
 }
 
 // The order inside windows for a graph whose rows stand in Morton order already (g->morder set: a mesh assembled in
 // m-space; d_pts: the points in that order): boundary rows first, then by degree; g->perm_m / g->iperm_m (solver <-> m),
 // their compositions with morder in g->perm / g->iperm (solver <-> original), g->smooth.
 static int order_in_windows(pf_graph* g, const double* d_pts) {
-    hipStream_t st = g->ctx->stream;                        // blocks are taken and released on this one ...
-    hipStream_t ls = g->side_stream ? g->side_stream : st;  // ... the kernels may run on the build's side stream
+    Scratch sc(g->ctx->stream);                                // blocks are taken and released on this one ...
+    hipStream_t ls = g->side_stream ? g->side_stream : sc.st;  // ... the kernels may run on the build's side stream
     const int64_t n = g->n;
     const int32_t win_rows = g->win_rows;
-    unsigned *bflag = nullptr, *k0 = nullptr, *k1 = nullptr;
-    int32_t* v1 = nullptr;
-    void* tmp = nullptr;
-    int rc = PF_OK;
-    auto fail = [&](hipError_t e) {
-        if (e != hipSuccess && rc == PF_OK) {
-            pf_set_error("pf_compute_order: %s", hipGetErrorString(e));
-            rc = PF_E_HIP;
-        }
-        return e != hipSuccess;
-    };
-    do {
-        if (fail(pf_malloc(st, (void**)&bflag, sizeof(unsigned) * std::max<int64_t>(n, 1)))) break;
-        if (fail(pf_malloc(st, (void**)&k0, sizeof(unsigned) * std::max<int64_t>(n, 1)))) break;
-        if (fail(pfl::memset_words(ls, bflag, 0, sizeof(unsigned) * std::max<int64_t>(n, 1)))) break;
+    unsigned* bflag = sc.get<unsigned>(n);
+    unsigned* k0 = sc.get<unsigned>(n);
+    if (sc.ok()) sc.note(pfl::memset_words(ls, bflag, 0, sizeof(unsigned) * std::max<int64_t>(n, 1)));
+    if (sc.ok()) {
         pfl::launch<k_boundary_flags>(dim3(pf_blocks(n)), dim3(PF_BLOCK), 0, ls, nullptr, g->rowptr, g->col, nullptr, n, win_rows, bflag);
         pfl::launch<k_second_ring_flags>(dim3(pf_blocks(n)), dim3(PF_BLOCK), 0, ls, nullptr, g->rowptr, g->col, nullptr, n, bflag);
         pfl::launch<k_degree_keys>(dim3(pf_blocks(n)), dim3(PF_BLOCK), 0, ls, nullptr, g->rowptr, bflag, n, win_rows, k0);
-        if (fail(hipGetLastError())) break;
-        if (win_rows <= 4096) {
-            int32_t n_pow2 = 2;
-            while (n_pow2 < win_rows) n_pow2 <<= 1;
-            pfl::launch<k_sort_windows>(dim3((unsigned)((n + win_rows - 1) / win_rows)), dim3(1024), sizeof(unsigned long long) * (size_t)n_pow2, ls, k0, nullptr, n, win_rows, n_pow2, g->perm_m);
-            if (fail(hipGetLastError())) break;
-        } else {
-            int bits2 = 12;
-            for (int64_t w = (n + win_rows - 1) / win_rows; w > 0; w >>= 1) ++bits2;
-            if (fail(pf_malloc(st, (void**)&k1, sizeof(unsigned) * n)) || fail(pf_malloc(st, (void**)&v1, sizeof(int32_t) * n))) break;
-            pfl::launch<k_iota>(dim3(pf_blocks(n)), dim3(PF_BLOCK), 0, ls, v1, n);
-            size_t need = 0;
-            pfl::flush_self();  // (a library sort launches at once: whatever this thread has recorded goes first)
-            if (fail(hipcub::DeviceRadixSort::SortPairs(nullptr, need, k0, k1, v1, g->perm_m, (int)n, 0, bits2, ls))) break;
-            if (fail(pf_malloc(st, &tmp, need))) break;
-            if (fail(hipcub::DeviceRadixSort::SortPairs(tmp, need, k0, k1, v1, g->perm_m, (int)n, 0, bits2, ls))) break;
-        }
+        sc.launched();
+    }
+    sort_in_windows(sc, ls, k0, nullptr, n, win_rows, g->perm_m);
+    if (sc.ok()) {
         pfl::launch<k_finish_perm>(dim3(pf_blocks(g->n_pad)), dim3(PF_BLOCK), 0, ls, g->perm_m, g->iperm_m, n, g->n_pad);
         pfl::launch<k_compose_perm>(dim3(pf_blocks(g->n_pad)), dim3(PF_BLOCK), 0, ls, g->perm_m, g->morder, g->n_pad, g->perm, g->iperm);
         pfl::launch<k_smooth_start>(dim3(pf_blocks(g->n_pad)), dim3(PF_BLOCK), 0, ls, d_pts, g->perm_m, g->order_bbox, g->n_pad, g->smooth);
-        if (fail(hipGetLastError())) break;
-    } while (0);
-    pf_free(st, bflag);
-    pf_free(st, k0);
-    pf_free(st, k1);
-    pf_free(st, v1);
-    pf_free(st, tmp);
-    return rc;
+        sc.launched();
+    }
+    return sc.ok() ? PF_OK : pf_hip_failed("pf_compute_order", sc.err);
 }
 
 // Fills g->perm [n_pad], g->iperm [n] and g->smooth [n_pad] (all already allocated) - and g->perm_m / g->iperm_m for a
 // mesh assembled in m-space.
 int pf_compute_order(pf_graph* g, const double* d_pts, int32_t* d_overflow) {
     if (g->morder) return order_in_windows(g, d_pts);
-    hipStream_t st = g->ctx->stream;
+    Scratch sc(g->ctx->stream);
+    hipStream_t st = sc.st;
     const int64_t n = g->n;
-    const int in = (int)n;
-    unsigned long long* bbox = nullptr;
-    unsigned *k0 = nullptr, *k1 = nullptr;
-    int32_t *v0 = nullptr, *v1 = nullptr;
-    void* tmp = nullptr;
-    size_t tmp_bytes = 0, need = 0;
-    int rc = PF_OK;
-    auto fail = [&](hipError_t e) {
-        if (e != hipSuccess && rc == PF_OK) {
-            pf_set_error("pf_compute_order: %s", hipGetErrorString(e));
-            rc = PF_E_HIP;
-        }
-        return e != hipSuccess;
-    };
-    do {
-        // the box (minima inverted, so that it starts as zeroes) and the boundary flags: one block, one fill
-        if (fail(pf_malloc(st, (void**)&bbox, 6 * sizeof(unsigned long long) + sizeof(unsigned) * (size_t)n))) break;
-        unsigned* bflag = reinterpret_cast<unsigned*>(bbox + 6);
-        if (fail(pf_malloc(st, (void**)&k0, sizeof(unsigned) * n)) || fail(pf_malloc(st, (void**)&k1, sizeof(unsigned) * n))) break;
-        if (fail(pf_malloc(st, (void**)&v0, sizeof(int32_t) * n)) || fail(pf_malloc(st, (void**)&v1, sizeof(int32_t) * n))) break;
-        if (fail(pfl::memset_words(st, bbox, 0, 6 * sizeof(unsigned long long) + sizeof(unsigned) * (size_t)n))) break;
-        if (d_pts) {
-            pfl::launch<k_bbox>(dim3(256), dim3(PF_BLOCK), 0, st, d_pts, n, bbox);
-            pfl::launch<k_morton_keys>(dim3(pf_blocks(n)), dim3(PF_BLOCK), 0, st, d_pts, n, bbox, k0, v0);
-        } else {  // no geometry (graph handed in as a matrix): keep the caller's order, only sort degrees in windows
-            if (fail(pfl::memset_words(st, k0, 0, sizeof(unsigned) * n))) break;
-            pfl::launch<k_iota>(dim3(pf_blocks(n)), dim3(PF_BLOCK), 0, st, v0, n);
-        }
-        if (fail(hipGetLastError())) break;
-        const bool counting = d_pts != nullptr && d_overflow != nullptr && n >= 4096;  // (else: the general sort)
+    const int32_t win_rows = g->win_rows;
+    // the box (minima inverted, so that it starts as zeroes) and the boundary flags: one block, one fill
+    const size_t zeroed = 6 * sizeof(unsigned long long) + sizeof(unsigned) * (size_t)n;
+    unsigned long long* bbox = reinterpret_cast<unsigned long long*>(sc.get<char>(zeroed));
+    unsigned* k0 = sc.get<unsigned>(n);
+    unsigned* k1 = sc.get<unsigned>(n);
+    int32_t* v0 = sc.get<int32_t>(n);
+    int32_t* v1 = sc.get<int32_t>(n);
+    if (!sc.ok()) return pf_hip_failed("pf_compute_order", sc.err);
+    unsigned* bflag = reinterpret_cast<unsigned*>(bbox + 6);
+    sc.note(pfl::memset_words(st, bbox, 0, zeroed));
+    if (sc.ok() && d_pts) {
+        pfl::launch<k_bbox>(dim3(256), dim3(PF_BLOCK), 0, st, d_pts, n, bbox);
+        pfl::launch<k_morton_keys>(dim3(pf_blocks(n)), dim3(PF_BLOCK), 0, st, d_pts, n, bbox, k0, v0);
+    } else if (sc.ok()) {  // no geometry (graph handed in as a matrix): keep the caller's order, only sort degrees in windows
+        sc.note(pfl::memset_words(st, k0, 0, sizeof(unsigned) * n));
+        if (sc.ok()) pfl::launch<k_iota>(dim3(pf_blocks(n)), dim3(PF_BLOCK), 0, st, v0, n);
+    }
+    sc.launched();
+    if (d_pts != nullptr && d_overflow != nullptr && n >= 4096) {  // v1 = Morton order
+        if (order_by_counting(sc, k0, k1, v0, n, v1, d_overflow) != PF_OK) return PF_E_HIP;
+    } else if (sc.ok()) {  // the general sort
         pfl::flush_self();  // (a library sort launches at once: whatever this thread has recorded goes first)
-        if (fail(hipcub::DeviceRadixSort::SortPairs(nullptr, need, k0, k1, v0, v1, in, 0, 30, st))) break;
-        tmp_bytes = need;
-        const int32_t win_rows = g->win_rows;
-        int bits2 = 12;
-        for (int64_t w = (n + win_rows - 1) / win_rows; w > 0; w >>= 1) ++bits2;
-        pfl::flush_self();  // (a library sort launches at once: whatever this thread has recorded goes first)
-        if (fail(hipcub::DeviceRadixSort::SortPairs(nullptr, need, k0, k1, v0, v1, in, 0, bits2, st))) break;
-        tmp_bytes = need > tmp_bytes ? need : tmp_bytes;
-        if (fail(pf_malloc(st, &tmp, tmp_bytes))) break;
-        need = tmp_bytes;
-        if (counting) {
-            int bits = 12;
-            while (bits < 22 && ((int64_t)1 << bits) < 2 * n) ++bits;  // ~2 buckets per vertex, 4 M at most
-            const int shift = 30 - bits;
-            const int64_t nb = (int64_t)1 << bits;
-            int32_t* hist = nullptr;  // [nb + 1] counts, then [nb] cursors: one block, one fill
-            int32_t* bstart = nullptr;
-            if (fail(pf_malloc(st, (void**)&hist, sizeof(int32_t) * (size_t)(2 * nb + 2)))) break;
-            if (fail(pf_malloc(st, (void**)&bstart, sizeof(int32_t) * (size_t)(nb + 1)))) {
-                pf_free(st, hist);
-                break;
-            }
-            bool bad = fail(pfl::memset_words(st, hist, 0, sizeof(int32_t) * (size_t)(2 * nb + 2)));
-            if (!bad) {
-                pfl::launch<k_order_hist>(dim3(pf_blocks(n)), dim3(PF_BLOCK), 0, st, k0, n, shift, hist);
-                bad = fail(hipGetLastError()) || pf_exclusive_scan_i32(st, hist, bstart, nb + 1) != PF_OK;
-            }
-            if (!bad) {
-                // k1 / v0: the bucketed keys and vertices (v0's identity is not needed any more: the index is the thread's own)
-                pfl::launch<k_order_scatter>(dim3(pf_blocks(n)), dim3(PF_BLOCK), 0, st, k0, n, shift, bstart, hist + nb + 1, k1, v0);
-                pfl::launch<k_order_rank>(dim3(pf_blocks(n)), dim3(PF_BLOCK), 0, st, k1, v0, n, shift, bstart, v1, d_overflow);
-                bad = fail(hipGetLastError());
-            }
-            pf_free(st, hist);
-            pf_free(st, bstart);
-            if (bad) {
-                if (rc == PF_OK) rc = PF_E_HIP;
-                break;
-            }
-        } else if (fail(hipcub::DeviceRadixSort::SortPairs(tmp, need, k0, k1, v0, v1, in, 0, 30, st))) {  // v1 = Morton order
-            break;
-        }
+        pf_sort_pairs(sc, k0, k1, v0, v1, n, 30);
+    }
+    if (sc.ok()) {
         // v0 <- Morton position of every vertex (scratch until the second sort); the boundary flags in their zeroed block
         pfl::launch<k_scatter_pos>(dim3(pf_blocks(n)), dim3(PF_BLOCK), 0, st, v1, n, v0);
         pfl::launch<k_boundary_flags>(dim3(pf_blocks(n)), dim3(PF_BLOCK), 0, st, v1, g->rowptr, g->col, v0, n, win_rows, bflag);
         pfl::launch<k_second_ring_flags>(dim3(pf_blocks(n)), dim3(PF_BLOCK), 0, st, v1, g->rowptr, g->col, v0, n, bflag);
         pfl::launch<k_degree_keys>(dim3(pf_blocks(n)), dim3(PF_BLOCK), 0, st, v1, g->rowptr, bflag, n, win_rows, k0);
-        if (fail(hipGetLastError())) break;
-        if (win_rows <= 4096) {
-            int32_t n_pow2 = 2;
-            while (n_pow2 < win_rows) n_pow2 <<= 1;
-            pfl::launch<k_sort_windows>(dim3((unsigned)((n + win_rows - 1) / win_rows)), dim3(1024), sizeof(unsigned long long) * (size_t)n_pow2, st, k0, v1, n, win_rows, n_pow2, g->perm);
-            if (fail(hipGetLastError())) break;
-        } else {
-            need = tmp_bytes;
-            if (fail(hipcub::DeviceRadixSort::SortPairs(tmp, need, k0, k1, v1, g->perm, in, 0, bits2, st))) break;
-        }
+        sc.launched();
+    }
+    sort_in_windows(sc, st, k0, v1, n, win_rows, g->perm);
+    if (sc.ok()) {
         pfl::launch<k_finish_perm>(dim3(pf_blocks(g->n_pad)), dim3(PF_BLOCK), 0, st, g->perm, g->iperm, n, g->n_pad);
         if (d_pts) pfl::launch<k_smooth_start>(dim3(pf_blocks(g->n_pad)), dim3(PF_BLOCK), 0, st, d_pts, g->perm, bbox, g->n_pad, g->smooth);
-        else if (fail(pfl::memset_words(st, g->smooth, 0, sizeof(double) * g->n_pad))) break;  // start vector = noise only
-        if (fail(hipGetLastError())) break;
-    } while (0);
-    pf_free(st, bbox);
-    pf_free(st, k0);
-    pf_free(st, k1);
-    pf_free(st, v0);
-    pf_free(st, v1);
-    pf_free(st, tmp);
-    return rc;
+        else sc.note(pfl::memset_words(st, g->smooth, 0, sizeof(double) * g->n_pad));  // start vector = noise only
+        sc.launched();
+    }
+    return sc.ok() ? PF_OK : pf_hip_failed("pf_compute_order", sc.err);
 }

@@ -1,5 +1,5 @@
-// The library's one entry to the device radix sort (pf_sort_pairs, declared in pf_internal.h): every unit but
-// pf_reorder.hip sorts through it, so hipCUB's sort kernels are instantiated here, once per key width.
+// The library's one entry to the device radix sort (pf_sort_pairs, declared in pf_internal.h): every unit
+// sorts through it, so hipCUB's sort kernels are instantiated here, once per key width.
 #include <hipcub/hipcub.hpp>
 
 #include "pf_internal.h"

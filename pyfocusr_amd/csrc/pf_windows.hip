@@ -25,8 +25,95 @@ namespace {
 constexpr int WB_CAP = 4096;  // outside-column candidates of a window before deduplication
 constexpr int WB_ADJ_WORDS = PF_WIN_MAX / 32;
 
-// pass 1: which windows read which (bit matrix), and the extent of each window's externally read rows.  A window's
-// outside entries hit a handful of neighbours: merged in LDS first (same-address atomics in memory serialise at ~10 ns)
+// ---- pieces the three passes share (every thread of the block calls them)
+
+// who reads whom, gathered per block in LDS first: a window's outside entries hit a handful of neighbours, and same-address
+// atomics in memory serialise at ~10 ns.  l_adj: row A of the bit matrix; l_need[B]: the extent of B's rows that A reads.
+__device__ __forceinline__ void readers_clear(uint32_t* l_adj, int32_t* l_need, int tid) {
+    for (int i = tid; i < WB_ADJ_WORDS; i += PF_WIN_THREADS) l_adj[i] = 0u;
+    for (int i = tid; i < PF_WIN_MAX; i += PF_WIN_THREADS) l_need[i] = 0;
+}
+__device__ __forceinline__ void readers_note(uint32_t* l_adj, int32_t* l_need, int32_t c, int32_t B, int32_t win_rows) {
+    atomicOr(&l_adj[B >> 5], 1u << (B & 31));
+    atomicMax(&l_need[B], c - B * win_rows + 1);
+}
+// (behind a barrier) row A of the matrix is this block's alone; row 0 of every window is always published (extra outside
+// rows point at it)
+__device__ __forceinline__ void readers_publish(const uint32_t* l_adj, const int32_t* l_need, int32_t A, int32_t n_windows,
+                                                uint32_t* __restrict__ adj, int32_t* __restrict__ need, int tid) {
+    for (int i = tid; i < WB_ADJ_WORDS; i += PF_WIN_THREADS)
+        if (l_adj[i]) adj[(int64_t)A * WB_ADJ_WORDS + i] = l_adj[i];
+    for (int32_t B = tid; B < n_windows; B += PF_WIN_THREADS)
+        if (l_need[B] > 0) atomicMax(&need[B], l_need[B]);
+    if (tid == 0) atomicMax(&need[A], 1);
+}
+
+// bitonic sort of cand[0, cap) ascending, cap = the power of two that holds the cnt candidates (INT_MAX padding sorts to
+// the end; a window has ~500 of them, not WB_CAP); cnt is block-uniform.  Returns cap.
+__device__ __forceinline__ int candidates_sort(int32_t* cand, int cnt, int tid) {
+    int cap = 64;
+    while (cap < cnt) cap <<= 1;
+    for (int k = 2; k <= cap; k <<= 1) {
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int i = tid; i < cap; i += PF_WIN_THREADS) {
+                const int ixj = i ^ j;
+                if (ixj > i) {
+                    const int32_t a = cand[i], b = cand[ixj];
+                    const bool up = (i & k) == 0;
+                    if ((a > b) == up) {
+                        cand[i] = b;
+                        cand[ixj] = a;
+                    }
+                }
+            }
+            __syncthreads();
+        }
+    }
+    return cap;
+}
+
+// unique: an entry of the sorted cand[0, cap) that differs from its predecessor starts a new outside row; positions by
+// ballot / popcount within a wave and a running total over the waves (a serial pass by one thread cost ~40 us of the
+// kernel's 95).  rows[] takes the first PF_WIN_GHOSTS of them; returns how many there are (behind a barrier).
+__device__ __forceinline__ int candidates_unique(const int32_t* cand, int cap, int32_t* rows, int tid, int lane) {
+    __shared__ int wave_tot[PF_WIN_THREADS / PF_WAVE];
+    __shared__ int running;
+    if (tid == 0) running = 0;
+    __syncthreads();
+    for (int base = 0; base < cap; base += PF_WIN_THREADS) {  // (block-uniform trip count, at least one)
+        const int i = base + tid;
+        const int32_t c = i < cap ? cand[i] : INT_MAX;
+        const bool fresh = c != INT_MAX && (i == 0 || cand[i - 1] != c);
+        const unsigned long long m = __ballot(fresh);
+        const int before = __popcll(m & ((1ull << lane) - 1ull));
+        if (lane == 0) wave_tot[tid / PF_WAVE] = __popcll(m);
+        __syncthreads();
+        int off = running;
+        for (int w = 0; w < tid / PF_WAVE; ++w) off += wave_tot[w];
+        if (fresh && off + before < PF_WIN_GHOSTS) rows[off + before] = c;
+        __syncthreads();
+        if (tid == 0) {
+            int t = running;
+            for (int w = 0; w < PF_WIN_THREADS / PF_WAVE; ++w) t += wave_tot[w];
+            running = t;
+        }
+        __syncthreads();
+    }
+    return running;
+}
+
+// lower bound: the first index of the sorted rows[0, count) whose entry is not below c
+__device__ __forceinline__ int rows_lower_bound(const int32_t* rows, int count, int32_t c) {
+    int lo = 0, hi = count;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (rows[mid] < c) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// pass 1: which windows read which (bit matrix), and the extent of each window's externally read rows
 struct k_win_scan {
     static constexpr int BOUNDS = PF_WIN_THREADS;
     static __device__ __forceinline__ void run(const int64_t* __restrict__ slice_ptr, const int32_t* __restrict__ scol,
@@ -38,8 +125,7 @@ struct k_win_scan {
     const int lane = tid & (PF_WAVE - 1);
     const int32_t A = (int32_t)blockIdx.x;
     const int64_t r0 = (int64_t)A * win_rows;
-    for (int i = tid; i < WB_ADJ_WORDS; i += PF_WIN_THREADS) l_adj[i] = 0u;
-    for (int i = tid; i < PF_WIN_MAX; i += PF_WIN_THREADS) l_need[i] = 0;
+    readers_clear(l_adj, l_need, tid);
     __syncthreads();
     for (int32_t lr = tid; lr < win_rows; lr += PF_WIN_THREADS) {
         const int64_t s = (r0 + lr) >> 6;
@@ -48,18 +134,11 @@ struct k_win_scan {
         for (int32_t j = 0; j < width; ++j) {
             const int32_t c = scol[pf_sell_index(base, width, j, lane)];
             const int32_t B = c / win_rows;
-            if (B != A) {
-                atomicOr(&l_adj[B >> 5], 1u << (B & 31));
-                atomicMax(&l_need[B], c - B * win_rows + 1);
-            }
+            if (B != A) readers_note(l_adj, l_need, c, B, win_rows);
         }
     }
     __syncthreads();
-    for (int i = tid; i < WB_ADJ_WORDS; i += PF_WIN_THREADS)
-        if (l_adj[i]) adj[(int64_t)A * WB_ADJ_WORDS + i] = l_adj[i];  // row A of the matrix is this block's alone
-    for (int32_t B = tid; B < n_windows; B += PF_WIN_THREADS)
-        if (l_need[B] > 0) atomicMax(&need[B], l_need[B]);
-    if (tid == 0) atomicMax(&need[A], 1);  // row 0 of every window is always published (extra outside rows point at it)
+    readers_publish(l_adj, l_need, A, n_windows, adj, need, tid);
 }
 };
 
@@ -73,12 +152,12 @@ struct k_win_build {
                                                               int32_t* __restrict__ gh_row, int32_t* __restrict__ flags) {
     __shared__ int32_t cand[WB_CAP];
     __shared__ int32_t ghost[PF_WIN_GHOSTS];
-    __shared__ int32_t cnt, hcount;
+    __shared__ int32_t cnt;
     const int tid = threadIdx.x;
     const int lane = tid & (PF_WAVE - 1);
     const int32_t A = (int32_t)blockIdx.x;
     const int64_t r0 = (int64_t)A * win_rows;
-    if (tid == 0) cnt = 0, hcount = 0;
+    if (tid == 0) cnt = 0;
     for (int k = tid; k < WB_CAP; k += PF_WIN_THREADS) cand[k] = INT_MAX;
     __syncthreads();
     for (int32_t lr = tid; lr < win_rows; lr += PF_WIN_THREADS) {
@@ -107,56 +186,8 @@ struct k_win_build {
         if (tid == 0) atomicOr(flags, 1);
         return;
     }
-    // bitonic sort of cand[0, cap) ascending, cap = the power of two that holds the candidates (INT_MAX padding sorts to
-    // the end; a window has ~500 of them, not WB_CAP)
-    int cap = 64;
-    while (cap < cnt) cap <<= 1;  // block-uniform
-    for (int k = 2; k <= cap; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int i = tid; i < cap; i += PF_WIN_THREADS) {
-                const int ixj = i ^ j;
-                if (ixj > i) {
-                    const int32_t a = cand[i], b = cand[ixj];
-                    const bool up = (i & k) == 0;
-                    if ((a > b) == up) {
-                        cand[i] = b;
-                        cand[ixj] = a;
-                    }
-                }
-            }
-            __syncthreads();
-        }
-    }
-    // unique: an entry that differs from its predecessor starts a new outside row; positions by ballot / popcount within a
-    // wave and a running total over the waves (a serial pass by one thread cost ~40 us of the kernel's 95)
-    {
-        __shared__ int wave_tot[PF_WIN_THREADS / PF_WAVE];
-        __shared__ int running;
-        if (tid == 0) running = 0;
-        __syncthreads();
-        for (int base = 0; base < cap; base += PF_WIN_THREADS) {  // (block-uniform trip count)
-            const int i = base + tid;
-            const int32_t c = i < cap ? cand[i] : INT_MAX;
-            const bool fresh = c != INT_MAX && (i == 0 || cand[i - 1] != c);
-            const unsigned long long m = __ballot(fresh);
-            const int before = __popcll(m & ((1ull << lane) - 1ull));
-            if (lane == 0) wave_tot[tid / PF_WAVE] = __popcll(m);
-            __syncthreads();
-            int off = running;
-            for (int w = 0; w < tid / PF_WAVE; ++w) off += wave_tot[w];
-            if (fresh && off + before < PF_WIN_GHOSTS) ghost[off + before] = c;
-            __syncthreads();
-            if (tid == 0) {
-                int t = running;
-                for (int w = 0; w < PF_WIN_THREADS / PF_WAVE; ++w) t += wave_tot[w];
-                running = t;
-            }
-            __syncthreads();
-        }
-        if (tid == 0) hcount = running;
-    }
-    __syncthreads();
-    const int h = hcount;
+    const int cap = candidates_sort(cand, cnt, tid);
+    const int h = candidates_unique(cand, cap, ghost, tid, lane);
     if (h > PF_WIN_GHOSTS) {
         if (tid == 0) atomicOr(flags, 1);
         return;
@@ -170,19 +201,8 @@ struct k_win_build {
         for (int32_t j = 0; j < width; ++j) {
             const int64_t idx = pf_sell_index(base, width, j, lane);
             const int32_t c = scol[idx];
-            int32_t slot;
-            if (c >= r0 && c < r0 + win_rows) {
-                slot = (int32_t)(c - r0);
-            } else {
-                int lo = 0, hi = h;  // lower bound in the sorted list (c is in it)
-                while (lo < hi) {
-                    const int mid = (lo + hi) >> 1;
-                    if (ghost[mid] < c) lo = mid + 1;
-                    else hi = mid;
-                }
-                slot = win_rows + lo;
-            }
-            slot_out[idx] = slot;
+            const bool own = c >= r0 && c < r0 + win_rows;
+            slot_out[idx] = own ? (int32_t)(c - r0) : win_rows + rows_lower_bound(ghost, h, c);  // (c is in the list)
         }
     }
 }
@@ -210,7 +230,7 @@ struct k_win_rings {
     __shared__ int32_t ring2[PF_WIN_GHOSTS];
     __shared__ uint32_t l_adj[WB_ADJ_WORDS];
     __shared__ int32_t l_need[PF_WIN_MAX];
-    __shared__ int32_t cnt, hcount, wmax, entries;
+    __shared__ int32_t cnt, wmax, entries;
     const int tid = threadIdx.x;
     const int lane = tid & (PF_WAVE - 1);
     const int32_t A = (int32_t)blockIdx.x;
@@ -220,22 +240,11 @@ struct k_win_rings {
         if (tid == 0) atomicOr(flags, 1);
         return;
     }
-    if (tid == 0) cnt = 0, hcount = 0, wmax = 0, entries = 0;
+    if (tid == 0) cnt = 0, wmax = 0, entries = 0;
     for (int i = tid; i < g1; i += PF_WIN_THREADS) ring1[i] = gh_row[(int64_t)A * PF_WIN_GHOSTS + i];
     for (int k = tid; k < WB_CAP; k += PF_WIN_THREADS) cand[k] = INT_MAX;
-    for (int i = tid; i < WB_ADJ_WORDS; i += PF_WIN_THREADS) l_adj[i] = 0u;
-    for (int i = tid; i < PF_WIN_MAX; i += PF_WIN_THREADS) l_need[i] = 0;
+    readers_clear(l_adj, l_need, tid);
     __syncthreads();
-    auto in_ring1 = [&](int32_t c, int* where) {
-        int lo = 0, hi = g1;
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (ring1[mid] < c) lo = mid + 1;
-            else hi = mid;
-        }
-        *where = lo;
-        return lo < g1 && ring1[lo] == c;
-    };
     for (int i = tid; i < g1; i += PF_WIN_THREADS) {
         const int32_t row = ring1[i];
         const int64_t s = row >> 6;
@@ -243,8 +252,9 @@ struct k_win_rings {
         const int32_t width = (int32_t)((slice_ptr[s + 1] - base) >> 6);
         for (int32_t j = 0; j < width; ++j) {
             const int32_t c = scol[pf_sell_index(base, width, j, row & (PF_WAVE - 1))];
-            int where;
-            if ((c < r0 || c >= r0 + win_rows) && !in_ring1(c, &where)) {
+            if (c >= r0 && c < r0 + win_rows) continue;
+            const int where = rows_lower_bound(ring1, g1, c);
+            if (where == g1 || ring1[where] != c) {
                 const int p = atomicAdd(&cnt, 1);
                 if (p < WB_CAP) cand[p] = c;
             }
@@ -257,52 +267,8 @@ struct k_win_rings {
         if (tid == 0) atomicOr(flags, 1);
         return;
     }
-    int cap = 64;
-    while (cap < cnt) cap <<= 1;
-    for (int k = 2; k <= cap; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int i = tid; i < cap; i += PF_WIN_THREADS) {
-                const int ixj = i ^ j;
-                if (ixj > i) {
-                    const int32_t a = cand[i], b = cand[ixj];
-                    const bool up = (i & k) == 0;
-                    if ((a > b) == up) {
-                        cand[i] = b;
-                        cand[ixj] = a;
-                    }
-                }
-            }
-            __syncthreads();
-        }
-    }
-    {
-        __shared__ int wave_tot[PF_WIN_THREADS / PF_WAVE];
-        __shared__ int running;
-        if (tid == 0) running = 0;
-        __syncthreads();
-        for (int base = 0; base < cap; base += PF_WIN_THREADS) {
-            const int i = base + tid;
-            const int32_t c = i < cap ? cand[i] : INT_MAX;
-            const bool fresh = c != INT_MAX && (i == 0 || cand[i - 1] != c);
-            const unsigned long long m = __ballot(fresh);
-            const int before = __popcll(m & ((1ull << lane) - 1ull));
-            if (lane == 0) wave_tot[tid / PF_WAVE] = __popcll(m);
-            __syncthreads();
-            int off = running;
-            for (int w = 0; w < tid / PF_WAVE; ++w) off += wave_tot[w];
-            if (fresh && off + before < PF_WIN_GHOSTS) ring2[off + before] = c;
-            __syncthreads();
-            if (tid == 0) {
-                int t = running;
-                for (int w = 0; w < PF_WIN_THREADS / PF_WAVE; ++w) t += wave_tot[w];
-                running = t;
-            }
-            __syncthreads();
-        }
-        if (tid == 0) hcount = running;
-    }
-    __syncthreads();
-    const int h = hcount;
+    const int cap = candidates_sort(cand, cnt, tid);
+    const int h = candidates_unique(cand, cap, ring2, tid, lane);
     if (g1 + h > PF_WIN_GHOSTS) {
         if (tid == 0) atomicOr(flags, 1);
         return;
@@ -324,19 +290,11 @@ struct k_win_rings {
             const int64_t idx = pf_sell_index(base, width, j, row & (PF_WAVE - 1));
             const int32_t c = scol[idx];
             int32_t slot;
-            int where;
             if (c >= r0 && c < r0 + win_rows) {
                 slot = (int32_t)(c - r0);
-            } else if (in_ring1(c, &where)) {
-                slot = win_rows + where;
             } else {
-                int lo = 0, hi = h;
-                while (lo < hi) {
-                    const int mid = (lo + hi) >> 1;
-                    if (ring2[mid] < c) lo = mid + 1;
-                    else hi = mid;
-                }
-                slot = win_rows + g1 + lo;
+                const int where = rows_lower_bound(ring1, g1, c);
+                slot = where < g1 && ring1[where] == c ? win_rows + where : win_rows + g1 + rows_lower_bound(ring2, h, c);
             }
             const int64_t o = ((int64_t)A * PF_WIN_GW + j) * PF_WIN_G1 + i;
             g1_pos[o] = (int32_t)idx;
@@ -345,16 +303,10 @@ struct k_win_rings {
     }
     for (int i = tid; i < g1 + h; i += PF_WIN_THREADS) {
         const int32_t c = i < g1 ? ring1[i] : ring2[i - g1];
-        const int32_t B = c / win_rows;
-        atomicOr(&l_adj[B >> 5], 1u << (B & 31));
-        atomicMax(&l_need[B], c - B * win_rows + 1);
+        readers_note(l_adj, l_need, c, c / win_rows, win_rows);
     }
     __syncthreads();
-    for (int i = tid; i < WB_ADJ_WORDS; i += PF_WIN_THREADS)
-        if (l_adj[i]) adj2[(int64_t)A * WB_ADJ_WORDS + i] = l_adj[i];
-    for (int32_t B = tid; B < n_windows; B += PF_WIN_THREADS)
-        if (l_need[B] > 0) atomicMax(&need2[B], l_need[B]);
-    if (tid == 0) atomicMax(&need2[A], 1);
+    readers_publish(l_adj, l_need, A, n_windows, adj2, need2, tid);
 }
 };
 
@@ -381,6 +333,7 @@ struct k_win_rings_check {
 // block of the graph's own, event behind it) - the assembler calls it behind its SELL fill, so that the first filter
 // application of a solve finds them ready instead of building them with two synchronisations at its head (round 3:
 // ~70 us per graph) - and _prepare collects.  px_state: -1 not tried, -2 in flight, 0 not covered, 1 ready.
+// Any failure on the way means "not covered": the sticky error cleared, the blocks given back, PF_OK.
 int pf_window_slots_begin(pf_graph* g) {
     if (g->px_state != -1) return PF_OK;
     g->px_state = 0;
@@ -395,35 +348,35 @@ int pf_window_slots_begin(pf_graph* g) {
     // a pinned block and its event: from the pool a freed graph left behind, or new (only when the graph has none: the
     // need is the graph's own and does not change)
     if (!g->px_land.host) PF_HIP(g->px_land.ensure(c->pools, need_doubles, 64, nullptr));
-    int32_t* flags = nullptr;
-    uint32_t* adj = nullptr;
-    hipError_t e = pf_malloc(st, (void**)&flags, sizeof(int32_t));
-    if (e == hipSuccess) e = pf_malloc(st, (void**)&adj, sizeof(uint32_t) * (size_t)nw * WB_ADJ_WORDS);
-    if (e == hipSuccess) e = pf_malloc(st, (void**)&g->px_slot, sizeof(int32_t) * (size_t)g->sell_entries);
-    if (e == hipSuccess) e = pf_malloc(st, (void**)&g->px_gh_cnt, sizeof(int32_t) * (size_t)(nw + 4));  // [nw] counts, then the builder's flag
-    if (e == hipSuccess) e = pf_malloc(st, (void**)&g->px_need, sizeof(int32_t) * nw);
-    if (e == hipSuccess) e = pf_malloc(st, (void**)&g->px_gh_row, sizeof(int32_t) * nw * PF_WIN_GHOSTS);
-    if (e == hipSuccess) e = pfl::memset_words(st, flags, 0, sizeof(int32_t));
-    if (e == hipSuccess) e = pfl::memset_words(st, adj, 0, sizeof(uint32_t) * (size_t)nw * WB_ADJ_WORDS);
-    if (e == hipSuccess) e = pfl::memset_words(st, g->px_gh_cnt, 0, sizeof(int32_t) * (size_t)(nw + 4));
-    if (e == hipSuccess) e = pfl::memset_words(st, g->px_need, 0, sizeof(int32_t) * nw);
-    if (e == hipSuccess) {
+    Scratch sc(st);
+    auto zero = [&](void* p, size_t n_bytes) {  // (recorded with the rest of a pair build: not Scratch::zero)
+        if (sc.ok()) sc.note(pfl::memset_words(st, p, 0, n_bytes));
+    };
+    int32_t* flags = sc.get<int32_t>(1);
+    uint32_t* adj = sc.get<uint32_t>((size_t)nw * WB_ADJ_WORDS);
+    g->px_slot = sc.keep<int32_t>((size_t)g->sell_entries);
+    g->px_gh_cnt = sc.keep<int32_t>((size_t)(nw + 4));  // [nw] counts, then the builder's flag
+    g->px_need = sc.keep<int32_t>((size_t)nw);
+    g->px_gh_row = sc.keep<int32_t>((size_t)nw * PF_WIN_GHOSTS);
+    zero(flags, sizeof(int32_t));
+    zero(adj, sizeof(uint32_t) * (size_t)nw * WB_ADJ_WORDS);
+    zero(g->px_gh_cnt, sizeof(int32_t) * (size_t)(nw + 4));
+    zero(g->px_need, sizeof(int32_t) * nw);
+    if (sc.ok()) {
         pfl::launch<k_win_scan>(dim3((unsigned)nw), dim3(PF_WIN_THREADS), 0, st, g->slice_ptr, g->scol, g->win_rows, (int32_t)nw, adj, g->px_need);
         pfl::launch<k_win_build>(dim3((unsigned)nw), dim3(PF_WIN_THREADS), 0, st, g->slice_ptr, g->scol, g->win_rows, (int32_t)nw, adj, g->px_slot,
                                                              g->px_gh_cnt, g->px_gh_row, flags);
-        e = hipGetLastError();
+        sc.launched();
     }
     // the counts and the flag in ONE read-back through pinned memory and a copy kernel
-    if (e == hipSuccess) e = pfl::memcpy_async(st, g->px_gh_cnt + tail, flags, sizeof(int32_t), hipMemcpyDeviceToDevice);
-    if (e == hipSuccess) {
+    if (sc.ok()) sc.note(pfl::memcpy_async(st, g->px_gh_cnt + tail, flags, sizeof(int32_t), hipMemcpyDeviceToDevice));
+    if (sc.ok()) {
         const int32_t* src = g->px_gh_cnt;
         double* dst = g->px_land.host;
         pfl::call(st, [=](hipStream_t s) { (void)pf_copy_by_kernel(s, src, dst, bytes); });
+        sc.note(pfl::event_record(st, g->px_land.ev));
     }
-    if (e == hipSuccess) e = pfl::event_record(st, g->px_land.ev);
-    pf_free(st, flags);
-    pf_free(st, adj);
-    if (e != hipSuccess) {
+    if (!sc.ok()) {
         (void)hipGetLastError();
         pf_window_slots_free(g);
         return PF_OK;
@@ -482,48 +435,49 @@ int pf_window_rings_prepare(pf_graph* g) {
     g->px2_state = 0;
     PF_TRY(pf_window_slots_prepare(g));
     if (g->px_state != 1 || g->win_rows != PF_WIN_THREADS) return PF_OK;
-    const int64_t nw = g->n_pad / g->win_rows;
+    const size_t nw = (size_t)(g->n_pad / g->win_rows);
     hipStream_t st = g->ctx->stream;
-    int32_t* flags = nullptr;
-    uint32_t* adj2 = nullptr;
-    unsigned long long* totals = nullptr;
-    hipError_t e = pf_malloc(st, (void**)&flags, sizeof(int32_t));
-    if (e == hipSuccess) e = pf_malloc(st, (void**)&totals, 2 * sizeof(unsigned long long));
-    if (e == hipSuccess) e = pf_malloc(st, (void**)&adj2, sizeof(uint32_t) * (size_t)nw * WB_ADJ_WORDS);
-    if (e == hipSuccess) e = pf_malloc(st, (void**)&g->px_gh_cnt2, sizeof(int32_t) * nw);
-    if (e == hipSuccess) e = pf_malloc(st, (void**)&g->px_need2, sizeof(int32_t) * nw);
-    if (e == hipSuccess) e = pf_malloc(st, (void**)&g->px_g1_gw, sizeof(int32_t) * nw);
-    if (e == hipSuccess) e = pf_malloc(st, (void**)&g->px_g1_w, (size_t)nw * PF_WIN_G1);
-    if (e == hipSuccess) e = pf_malloc(st, (void**)&g->px_g1_pos, sizeof(int32_t) * (size_t)nw * PF_WIN_GW * PF_WIN_G1);
-    if (e == hipSuccess) e = pf_malloc(st, (void**)&g->px_g1_slot, sizeof(uint16_t) * (size_t)nw * PF_WIN_GW * PF_WIN_G1);
-    if (e == hipSuccess) e = pfl::memset_words(st, flags, 0, sizeof(int32_t));
-    if (e == hipSuccess) e = pfl::memset_words(st, totals, 0, 2 * sizeof(unsigned long long));
-    if (e == hipSuccess) e = pfl::memset_words(st, adj2, 0, sizeof(uint32_t) * (size_t)nw * WB_ADJ_WORDS);
-    if (e == hipSuccess) e = pfl::memset_words(st, g->px_gh_cnt2, 0, sizeof(int32_t) * nw);
-    if (e == hipSuccess) e = pfl::memset_words(st, g->px_need2, 0, sizeof(int32_t) * nw);
-    if (e == hipSuccess) e = pfl::memset_words(st, g->px_g1_gw, 0, sizeof(int32_t) * nw);
+    Scratch sc(st);
+    auto zero = [&](void* p, size_t n_bytes) {
+        if (sc.ok()) sc.note(pfl::memset_words(st, p, 0, n_bytes));
+    };
+    auto back = [&](void* dst, const void* src, size_t n_bytes) {
+        if (sc.ok()) sc.note(pfl::memcpy_async(st, dst, src, n_bytes, hipMemcpyDeviceToHost));
+    };
+    int32_t* flags = sc.get<int32_t>(1);
+    unsigned long long* totals = sc.get<unsigned long long>(2);
+    uint32_t* adj2 = sc.get<uint32_t>(nw * WB_ADJ_WORDS);
+    g->px_gh_cnt2 = sc.keep<int32_t>(nw);
+    g->px_need2 = sc.keep<int32_t>(nw);
+    g->px_g1_gw = sc.keep<int32_t>(nw);
+    g->px_g1_w = sc.keep<uint8_t>(nw * PF_WIN_G1);
+    g->px_g1_pos = sc.keep<int32_t>(nw * PF_WIN_GW * PF_WIN_G1);
+    g->px_g1_slot = sc.keep<uint16_t>(nw * PF_WIN_GW * PF_WIN_G1);
+    zero(flags, sizeof(int32_t));
+    zero(totals, 2 * sizeof(unsigned long long));
+    zero(adj2, sizeof(uint32_t) * nw * WB_ADJ_WORDS);
+    zero(g->px_gh_cnt2, sizeof(int32_t) * nw);
+    zero(g->px_need2, sizeof(int32_t) * nw);
+    zero(g->px_g1_gw, sizeof(int32_t) * nw);
     // one pinned block for everything the host wants back: flag, totals, ring-2 counts, widest ring-1 rows
-    const size_t back = sizeof(int32_t) * (2 + 2 * (size_t)nw) + 2 * sizeof(unsigned long long);
+    const size_t n_back = sizeof(int32_t) * (2 + 2 * nw) + 2 * sizeof(unsigned long long);
     void* pin = nullptr;
-    if (e == hipSuccess && pf_pinned_scratch(g->ctx, back, &pin) != PF_OK) e = hipErrorOutOfMemory;
-    if (e == hipSuccess) {
+    if (sc.ok() && pf_pinned_scratch(g->ctx, n_back, &pin) != PF_OK) sc.note(hipErrorOutOfMemory);
+    if (sc.ok()) {
         pfl::launch<k_win_rings>(dim3((unsigned)nw), dim3(PF_WIN_THREADS), 0, st, g->slice_ptr, g->scol, g->win_rows, (int32_t)nw, g->px_gh_cnt, g->px_gh_row,
                                                              g->px_gh_cnt2, g->px_need2, adj2, g->px_g1_w, g->px_g1_pos, g->px_g1_slot,
                                                              g->px_g1_gw, totals, flags);
-        pfl::launch<k_win_rings_check>(dim3((unsigned)std::min<int64_t>((nw * nw + PF_WIN_THREADS - 1) / PF_WIN_THREADS, 64)), dim3(PF_WIN_THREADS), 0, st, adj2, (int32_t)nw, flags);
-        e = hipGetLastError();
+        pfl::launch<k_win_rings_check>(dim3((unsigned)std::min<size_t>((nw * nw + PF_WIN_THREADS - 1) / PF_WIN_THREADS, 64)), dim3(PF_WIN_THREADS), 0, st, adj2, (int32_t)nw, flags);
+        sc.launched();
     }
     unsigned long long* p_tot = reinterpret_cast<unsigned long long*>(pin);
     int32_t* p_i = reinterpret_cast<int32_t*>(p_tot + 2);
-    if (e == hipSuccess) e = pfl::memcpy_async(st, p_tot, totals, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = pfl::memcpy_async(st, p_i, flags, sizeof(int32_t), hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = pfl::memcpy_async(st, p_i + 2, g->px_gh_cnt2, sizeof(int32_t) * nw, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = pfl::memcpy_async(st, p_i + 2 + nw, g->px_g1_gw, sizeof(int32_t) * nw, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = pfl::sync(st);
-    pf_free(st, flags);
-    pf_free(st, adj2);
-    pf_free(st, totals);
-    if (e != hipSuccess || p_i[0] != 0) {
+    back(p_tot, totals, 2 * sizeof(unsigned long long));
+    back(p_i, flags, sizeof(int32_t));
+    back(p_i + 2, g->px_gh_cnt2, sizeof(int32_t) * nw);
+    back(p_i + 2 + nw, g->px_g1_gw, sizeof(int32_t) * nw);
+    if (sc.ok()) sc.note(pfl::sync(st));
+    if (!sc.ok() || p_i[0] != 0) {
         (void)hipGetLastError();
         window_rings_free(g);
         return PF_OK;
