@@ -4,6 +4,10 @@
 // k_orth_project, one graph or both graphs of a pair), the whole local step of Lanczos with partial
 // reorthogonalisation in one launch with a grid-wide wait (k_orth_local), and - bases of PF_ORTH_MAX vectors and more -
 // the plain dot products (pf_reduce.hip) and k_multi_axpy twice.
+// The shapes give the same bits because they call the same statements of each rule: the sums of pf_sums.h (chunk, block,
+// column; axpy_sub / axpy_rows in ascending order of b) and, here, orth_slot / orth_vec (where basis vector b lives),
+// orth_verdict (Pythagoras, the threshold, the second pass's verdict) and orth_report (block 0's report, the ticket
+// last).  On the host orth_fused queues the fused step for one graph or two and orth_coef names the regions of g->coef.
 #include <math.h>
 #include <stdlib.h>
 
@@ -13,6 +17,7 @@
 #include <mutex>
 
 #include "pf_internal.h"
+#include "pf_sums.h"
 
 namespace {
 
@@ -20,47 +25,24 @@ namespace {
 __global__ __launch_bounds__(PF_BLOCK) void k_multi_axpy(double* __restrict__ ws, int64_t n_pad, int32_t first,
                                                          int32_t count, int32_t wslot, const double* __restrict__ h) {
     const int64_t i = 2 * ((int64_t)blockIdx.x * PF_BLOCK + threadIdx.x);
-    if (i >= n_pad) return;
-    double2 acc = *reinterpret_cast<double2*>(ws + (int64_t)wslot * n_pad + i);
-    for (int b = 0; b < count; ++b) {
-        const double hb = h[b];
-        const double2 v = *reinterpret_cast<const double2*>(ws + (int64_t)(first + b) * n_pad + i);
-        acc.x -= hb * v.x;
-        acc.y -= hb * v.y;
-    }
-    *reinterpret_cast<double2*>(ws + (int64_t)wslot * n_pad + i) = acc;
+    if (i < n_pad) axpy_rows(ws, n_pad, first, count, wslot, h, i);
 }
 
 // Fused forms for pf_orth_begin (one Gram-Schmidt pass = k_dot_partial + one of these; no separate finish launch):
-// every block finishes the per-chunk partial sums itself - in k_dot_finish's order, so all blocks (and the host) see
-// the same bits - then subtracts.  Block 0 also publishes the coefficients.
+// every block finishes the per-chunk partial sums itself - column_sum, as k_dot_finish does, so all blocks (and the
+// host) see the same bits - then subtracts.  Block 0 also publishes the coefficients.
 constexpr int PF_ORTH_MAX = 256;
 // k_axpy_finishing: a plain pass, hsum[b] (+)= h[b] (the second pass of the rare case below).
 __global__ __launch_bounds__(PF_BLOCK) void k_axpy_finishing(double* __restrict__ ws, int64_t n_pad, int32_t first, int32_t count,
                                                              int32_t wslot, const double* __restrict__ partial, int64_t n_chunks,
                                                              double* __restrict__ hsum, int accumulate) {
     __shared__ double hs[PF_ORTH_MAX];
-    const int lane = threadIdx.x & (PF_WAVE - 1);
-    for (int b = threadIdx.x / PF_WAVE; b < count; b += PF_BLOCK / PF_WAVE) {
-        double s = 0.0;
-        for (int64_t k = lane; k < n_chunks; k += PF_WAVE) s += partial[(int64_t)b * n_chunks + k];
-#pragma unroll
-        for (int off = PF_WAVE / 2; off > 0; off >>= 1) s += __shfl_down(s, off, PF_WAVE);
-        if (lane == 0) hs[b] = s;
-    }
+    column_sums(partial, n_chunks, count, hs);
     __syncthreads();
     if (blockIdx.x == 0)
         for (int b = threadIdx.x; b < count; b += PF_BLOCK) hsum[b] = accumulate ? hsum[b] + hs[b] : hs[b];
     const int64_t i = 2 * ((int64_t)blockIdx.x * PF_BLOCK + threadIdx.x);
-    if (i >= n_pad) return;
-    double2 acc = *reinterpret_cast<double2*>(ws + (int64_t)wslot * n_pad + i);
-    for (int b = 0; b < count; ++b) {
-        const double hb = hs[b];
-        const double2 v = *reinterpret_cast<const double2*>(ws + (int64_t)(first + b) * n_pad + i);
-        acc.x -= hb * v.x;
-        acc.y -= hb * v.y;
-    }
-    *reinterpret_cast<double2*>(ws + (int64_t)wslot * n_pad + i) = acc;
+    if (i < n_pad) axpy_rows(ws, n_pad, first, count, wslot, hs, i);
 }
 // The orthogonalisation step of one graph - or of the two graphs of a pair in the same two launches (blockIdx.z) - is
 // k_orth_dots + k_orth_project:
@@ -105,9 +87,56 @@ struct OrthArgs2 {
     OrthArgs g[2];
 };
 __device__ __forceinline__ int32_t orth_slot(const OrthArgs& a, int b) { return b < a.split ? a.first + b : a.first2 + (b - a.split); }
+__device__ __forceinline__ const double* orth_vec(const OrthArgs& a, int b) { return a.ws + (int64_t)orth_slot(a, b) * a.n_pad; }
+
+// The verdict on a pass from hs = [h (count), |w|^2], by one thread (the same sequence in every block: the same bits):
+// sum = h_0^2 + h_1^2 + ... in ascending order, |w'|^2 = |w|^2 - sum (Pythagoras).  `pass` as in OrthArgs; a kernel that
+// only ever runs one pass hands in the constant 0.
+struct OrthVerdict {
+    double redo;   // 0: fine; 1: the second pass is due; 2: it was, and ran
+    double after;  // |w'|^2
+    double scale;  // what w' is multiplied by: 1 / |w'| if it is to be normalised and the pass was fine
+};
+__device__ __forceinline__ OrthVerdict orth_verdict(const double* hs, int32_t count, double thresh, int32_t normalize, int32_t pass) {
+    double sum = 0.0;
+    for (int b = 0; b < count; ++b) sum += hs[b] * hs[b];
+    const double before = hs[count], after = before - sum;
+    // (false for NaN and for a vanished vector: take the second pass.  The second pass itself is final - "twice is
+    // enough" - unless it produced no number at all: verdict 1 then hands the step to pf_orth_end's own passes.
+    // The flag goes through a vector register on purpose: this compiler turned `fine ? 0.0 : 1.0` into an s_cselect on
+    // SCC behind a v_cmp that sets VCC - the verdict then was whatever the last scalar compare had left)
+    int fine = (pass == 2 ? (after == after) : after >= thresh * before) ? 1 : 0;
+    asm volatile("" : "+v"(fine));
+    return {fine ? (pass == 2 ? 2.0 : 0.0) : 1.0, after, (fine && normalize && after > 1e-280) ? 1.0 / sqrt(after) : 1.0};
+}
+
+// Block 0's report of a pass, by the whole block: h into a.hsum (h1 + h2 after a second pass), |w'|^2 into a.nrm2, a first
+// pass's verdict into a.verdict, and - unless a first pass asks for the second and leaves the report to it - all of it
+// into the pinned a.host_out.  The ticket goes out behind everything else (system-scope fences + the block's barrier):
+// the host polls it instead of waiting for an event behind the kernel - the coefficients are known long before the
+// projection has finished, and an event record would cost ~5 us of device time per step.
+__device__ __forceinline__ void orth_report(const OrthArgs& a, const double* hs, const OrthVerdict& v, int32_t pass) {
+    const int32_t count = a.count;
+    const bool report = !(pass == 1 && v.redo != 0.0);
+    for (int b = threadIdx.x; b < count; b += PF_BLOCK) {
+        const double hb = pass == 2 ? a.hsum[b] + hs[b] : hs[b];
+        a.hsum[b] = hb;
+        if (report) a.host_out[b] = hb;
+    }
+    if (threadIdx.x == 0) {
+        if (pass == 1) *a.verdict = v.redo;
+        *a.nrm2 = v.after;
+        if (report) {
+            a.host_out[count] = v.after;
+            a.host_out[count + 1] = v.redo;
+        }
+    }
+    __threadfence_system();
+    __syncthreads();
+    if (threadIdx.x == 0 && report) __hip_atomic_store(a.host_out + count + 2, a.ticket, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
 
 // partial[b][chunk] = <slot first+b, slot wslot> over the chunk, b < count; partial[count][chunk] = |w|^2 over the chunk
-// (k_dot_partial's sums, in its order)
 // VB: basis vectors per block.  1: the shape tuned for bases that live in the Infinity Cache (250k pairs: 6 TB/s).  4 (bases
 // beyond it: 1M rows x 50 vectors = 400 MB): the chunk of w is loaded ONCE for four vectors - with one vector per block it
 // came back from HBM once per vector, half of the kernel's traffic - and four vectors' 32 KB pieces are in flight per block.
@@ -120,39 +149,24 @@ __global__ __launch_bounds__(PF_BLOCK) void k_orth_dots(OrthArgs2 a2) {
     const int64_t chunk = blockIdx.x;
     if (a.pass < 0 || b0 > a.count || chunk >= a.n_chunks) return;  // (block-uniform: the grid is sized for the larger graph of a pair)
     if (a.pass == 2 && *a.verdict == 0.0) return;                   // (the first pass was fine)
-    const double* w = a.ws + (int64_t)a.wslot * a.n_pad;
-    const int64_t lo = chunk * PF_DOT_CHUNK;
-    // n_pad is a multiple of the chunk: every chunk is whole, every thread has PF_DOT_CHUNK / (2 PF_BLOCK) = 8 pairs, all
-    // of whose loads are issued before the first product waits for one (the sums keep their order)
-    constexpr int PAIRS = PF_DOT_CHUNK / (2 * PF_BLOCK);
-    double2 cs[PAIRS], xs[VB][PAIRS];
-#pragma unroll
-    for (int it = 0; it < PAIRS; ++it) cs[it] = *reinterpret_cast<const double2*>(w + lo + 2 * threadIdx.x + (int64_t)it * (2 * PF_BLOCK));
+    // n_pad is a multiple of the chunk: every chunk is whole, every thread has 8 pairs, all of whose loads are issued
+    // before the first product waits for one (the sums keep their order)
+    double2 cs[PF_CHUNK_PAIRS], xs[VB][PF_CHUNK_PAIRS];
+    chunk_load(cs, a.ws + (int64_t)a.wslot * a.n_pad, chunk);
 #pragma unroll
     for (int u = 0; u < VB; ++u) {
         const int b = b0 + u;
         if (b > a.count) continue;
-        const double* v = a.ws + (int64_t)(b == a.count ? a.wslot : orth_slot(a, b)) * a.n_pad;
-#pragma unroll
-        for (int it = 0; it < PAIRS; ++it) xs[u][it] = *reinterpret_cast<const double2*>(v + lo + 2 * threadIdx.x + (int64_t)it * (2 * PF_BLOCK));
+        chunk_load(xs[u], a.ws + (int64_t)(b == a.count ? a.wslot : orth_slot(a, b)) * a.n_pad, chunk);
     }
 #pragma unroll
     for (int u = 0; u < VB; ++u) {
         if (b0 + u > a.count) continue;
-        double s = 0.0;
-#pragma unroll
-        for (int it = 0; it < PAIRS; ++it) {
-            s += xs[u][it].x * cs[it].x;
-            s += xs[u][it].y * cs[it].y;
-        }
-#pragma unroll
-        for (int off = PF_WAVE / 2; off > 0; off >>= 1) s += __shfl_down(s, off, PF_WAVE);
-        if ((threadIdx.x & (PF_WAVE - 1)) == 0) red[u][threadIdx.x / PF_WAVE] = s;
+        block_sum_put(chunk_dot_regs(xs[u], cs), red[u]);
     }
     __syncthreads();
     if (threadIdx.x < VB && b0 + (int)threadIdx.x <= a.count)
-        a.partial[(int64_t)(b0 + threadIdx.x) * a.n_chunks + chunk] =
-            (red[threadIdx.x][0] + red[threadIdx.x][1]) + (red[threadIdx.x][2] + red[threadIdx.x][3]);
+        a.partial[(int64_t)(b0 + threadIdx.x) * a.n_chunks + chunk] = block_sum_get(red[threadIdx.x]);
 }
 
 // P: pairs of rows per thread.  1: a block owns 512 rows (many blocks: what fills the chip at 250k rows).  8 (bases beyond the
@@ -162,57 +176,17 @@ __global__ __launch_bounds__(PF_BLOCK) void k_orth_dots(OrthArgs2 a2) {
 template <int P>
 __global__ __launch_bounds__(PF_BLOCK) void k_orth_project(OrthArgs2 a2) {
     __shared__ double hs[PF_ORTH_MAX + 1];
-    __shared__ double s_scale, s_after, s_redo;
+    __shared__ OrthVerdict s_v;
     const OrthArgs& a = a2.g[blockIdx.z];
     if (a.pass < 0 || 2 * (int64_t)blockIdx.x * PF_BLOCK * P >= a.n_pad) return;  // (block-uniform)
     if (a.pass == 2 && *a.verdict == 0.0) return;
-    const int lane = threadIdx.x & (PF_WAVE - 1);
     const int32_t count = a.count;
-    for (int b = threadIdx.x / PF_WAVE; b < count + 1; b += PF_BLOCK / PF_WAVE) {
-        double s = 0.0;
-        for (int64_t k = lane; k < a.n_chunks; k += PF_WAVE) s += a.partial[(int64_t)b * a.n_chunks + k];
-#pragma unroll
-        for (int off = PF_WAVE / 2; off > 0; off >>= 1) s += __shfl_down(s, off, PF_WAVE);
-        if (lane == 0) hs[b] = s;
-    }
+    column_sums(a.partial, a.n_chunks, count + 1, hs);
     __syncthreads();
-    if (threadIdx.x == 0) {  // the same sequence in every block: the same bits
-        double sum = 0.0;
-        for (int b = 0; b < count; ++b) sum += hs[b] * hs[b];
-        const double before = hs[count], after = before - sum;
-        // (false for NaN and for a vanished vector: take the second pass.  The second pass itself is final - "twice is
-        // enough" - unless it produced no number at all: verdict 1 then hands the step to pf_orth_end's own passes)
-        const bool fine = a.pass == 2 ? (after == after) : after >= a.thresh * before;
-        s_redo = fine ? (a.pass == 2 ? 2.0 : 0.0) : 1.0;
-        s_after = after;
-        s_scale = (fine && a.normalize && after > 1e-280) ? 1.0 / sqrt(after) : 1.0;
-    }
+    if (threadIdx.x == 0) s_v = orth_verdict(hs, count, a.thresh, a.normalize, a.pass);
     __syncthreads();
-    if (blockIdx.x == 0) {
-        const bool report = !(a.pass == 1 && s_redo != 0.0);  // (a first pass that asks for the second leaves the report to it)
-        for (int b = threadIdx.x; b < count; b += PF_BLOCK) {
-            const double hb = a.pass == 2 ? a.hsum[b] + hs[b] : hs[b];
-            a.hsum[b] = hb;
-            if (report) a.host_out[b] = hb;
-        }
-        if (threadIdx.x == 0) {
-            if (a.pass == 1) *a.verdict = s_redo;
-            *a.nrm2 = s_after;
-            if (report) {
-                a.host_out[count] = s_after;
-                a.host_out[count + 1] = s_redo;
-            }
-        }
-        // the ticket goes out behind everything else (system-scope fences + the block's barrier): the host polls it
-        // instead of waiting for an event behind the kernel - the coefficients are known long before the projection
-        // below has finished, and an event record would cost ~5 us of device time per step
-        __threadfence_system();
-        __syncthreads();
-        if (threadIdx.x == 0 && report) {
-            __hip_atomic_store(a.host_out + count + 2, a.ticket, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
-    }
-    const double sc = s_scale;
+    if (blockIdx.x == 0) orth_report(a, hs, s_v, a.pass);
+    const double sc = s_v.scale;
     if constexpr (P == 1) {
         const int64_t i = 2 * ((int64_t)blockIdx.x * PF_BLOCK + threadIdx.x);
         if (i >= a.n_pad) return;
@@ -222,13 +196,9 @@ __global__ __launch_bounds__(PF_BLOCK) void k_orth_project(OrthArgs2 a2) {
         for (; b + 8 <= count; b += 8) {
             double2 vv[8];
 #pragma unroll
-            for (int u = 0; u < 8; ++u) vv[u] = *reinterpret_cast<const double2*>(a.ws + (int64_t)orth_slot(a, b + u) * a.n_pad + i);
+            for (int u = 0; u < 8; ++u) vv[u] = *reinterpret_cast<const double2*>(orth_vec(a, b + u) + i);
 #pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const double hb = hs[b + u];
-                acc.x -= hb * vv[u].x;
-                acc.y -= hb * vv[u].y;
-            }
+            for (int u = 0; u < 8; ++u) axpy_sub(acc, hs[b + u], vv[u]);
         }
         if (b < count) {
             // the last 1-7 vectors (a local step of Lanczos with partial reorthogonalisation has 3-4 in all): their loads in
@@ -239,14 +209,11 @@ __global__ __launch_bounds__(PF_BLOCK) void k_orth_project(OrthArgs2 a2) {
 #pragma unroll
             for (int u = 0; u < 7; ++u) {
                 const int bu = b + u < count ? b + u : count - 1;
-                vv[u] = *reinterpret_cast<const double2*>(a.ws + (int64_t)orth_slot(a, bu) * a.n_pad + i);
+                vv[u] = *reinterpret_cast<const double2*>(orth_vec(a, bu) + i);
                 hh[u] = b + u < count ? hs[bu] : 0.0;
             }
 #pragma unroll
-            for (int u = 0; u < 7; ++u) {
-                acc.x -= hh[u] * vv[u].x;
-                acc.y -= hh[u] * vv[u].y;
-            }
+            for (int u = 0; u < 7; ++u) axpy_sub(acc, hh[u], vv[u]);
         }
         acc.x *= sc;
         acc.y *= sc;
@@ -261,8 +228,8 @@ __global__ __launch_bounds__(PF_BLOCK) void k_orth_project(OrthArgs2 a2) {
         int b = 0;
         for (; b + 2 <= count; b += 2) {
             const double h0 = hs[b], h1 = hs[b + 1];
-            const double* v0 = a.ws + (int64_t)orth_slot(a, b) * a.n_pad + i0;
-            const double* v1 = a.ws + (int64_t)orth_slot(a, b + 1) * a.n_pad + i0;
+            const double* v0 = orth_vec(a, b) + i0;
+            const double* v1 = orth_vec(a, b + 1) + i0;
             double2 x0[P], x1[P];
 #pragma unroll
             for (int it = 0; it < P; ++it) x0[it] = *reinterpret_cast<const double2*>(v0 + (int64_t)it * (2 * PF_BLOCK));
@@ -270,23 +237,18 @@ __global__ __launch_bounds__(PF_BLOCK) void k_orth_project(OrthArgs2 a2) {
             for (int it = 0; it < P; ++it) x1[it] = *reinterpret_cast<const double2*>(v1 + (int64_t)it * (2 * PF_BLOCK));
 #pragma unroll
             for (int it = 0; it < P; ++it) {
-                acc[it].x -= h0 * x0[it].x;
-                acc[it].y -= h0 * x0[it].y;
-                acc[it].x -= h1 * x1[it].x;
-                acc[it].y -= h1 * x1[it].y;
+                axpy_sub(acc[it], h0, x0[it]);
+                axpy_sub(acc[it], h1, x1[it]);
             }
         }
         for (; b < count; ++b) {
             const double hb = hs[b];
-            const double* vb = a.ws + (int64_t)orth_slot(a, b) * a.n_pad + i0;
+            const double* vb = orth_vec(a, b) + i0;
             double2 vv[P];
 #pragma unroll
             for (int it = 0; it < P; ++it) vv[it] = *reinterpret_cast<const double2*>(vb + (int64_t)it * (2 * PF_BLOCK));
 #pragma unroll
-            for (int it = 0; it < P; ++it) {
-                acc[it].x -= hb * vv[it].x;
-                acc[it].y -= hb * vv[it].y;
-            }
+            for (int it = 0; it < P; ++it) axpy_sub(acc[it], hb, vv[it]);
         }
 #pragma unroll
         for (int it = 0; it < P; ++it) {
@@ -318,15 +280,16 @@ __device__ __forceinline__ int orth_meet(const OrthArgs& a, unsigned long long w
 
 // A LOCAL Gram-Schmidt step (Lanczos with partial reorthogonalisation: the null vectors and the last two basis vectors, 4
 // at most) in ONE launch.  A block owns a 4096-row chunk: it loads w and the basis vectors' pieces once, forms the chunk's
-// partial sums exactly as k_orth_dots does, publishes them, waits until every chunk of the graph has (a counter, bounded),
-// sums the partials exactly as k_orth_project does and projects the rows it still holds in registers - the same
-// operations in the same order on every number: the same bits as the two launches, one kernel boundary less (~5 us of a
-// ~16 us step).  The grid is one block per chunk and graph (122 at 250k, 490 at 1M rows): all resident.
+// partial sums with k_orth_dots' calls, publishes them, waits until every chunk of the graph has (a counter, bounded),
+// sums the partials in column_sum's order, takes k_orth_project's verdict and report (as one pass: pass = 0, a constant
+// here) and projects the rows it still holds in registers - the same operations in the same order on every number: the
+// same bits as the two launches, one kernel boundary less (~5 us of a ~16 us step).  The grid is one block per chunk and
+// graph (122 at 250k, 490 at 1M rows): all resident.
 constexpr int PF_ORTH_LOCAL_MAX = 4;
 __global__ __launch_bounds__(PF_BLOCK) void k_orth_local(OrthArgs2 a2) {
     __shared__ double red[PF_ORTH_LOCAL_MAX + 1][PF_BLOCK / PF_WAVE];
     __shared__ double hs[PF_ORTH_LOCAL_MAX + 1];
-    __shared__ double s_scale, s_after, s_redo;
+    __shared__ OrthVerdict s_v;
     __shared__ int s_ok;
     const OrthArgs& a = a2.g[blockIdx.z];
     const int64_t chunk = blockIdx.x;
@@ -334,37 +297,23 @@ __global__ __launch_bounds__(PF_BLOCK) void k_orth_local(OrthArgs2 a2) {
     const int32_t count = a.count;
     const int lane = threadIdx.x & (PF_WAVE - 1);
     double* w = a.ws + (int64_t)a.wslot * a.n_pad;
-    const int64_t lo = chunk * PF_DOT_CHUNK;
-    constexpr int PAIRS = PF_DOT_CHUNK / (2 * PF_BLOCK);
-    double2 cs[PAIRS], xs[PF_ORTH_LOCAL_MAX][PAIRS];
+    double2 cs[PF_CHUNK_PAIRS], xs[PF_ORTH_LOCAL_MAX][PF_CHUNK_PAIRS];
+    chunk_load(cs, w, chunk);
 #pragma unroll
-    for (int it = 0; it < PAIRS; ++it) cs[it] = *reinterpret_cast<const double2*>(w + lo + 2 * threadIdx.x + (int64_t)it * (2 * PF_BLOCK));
-#pragma unroll
-    for (int u = 0; u < PF_ORTH_LOCAL_MAX; ++u) {
-        const double* v = a.ws + (int64_t)orth_slot(a, u < count ? u : count - 1) * a.n_pad;  // (past the end: the last one again, unused)
-#pragma unroll
-        for (int it = 0; it < PAIRS; ++it) xs[u][it] = *reinterpret_cast<const double2*>(v + lo + 2 * threadIdx.x + (int64_t)it * (2 * PF_BLOCK));
-    }
-    // ---- the chunk's partial sums: k_orth_dots' operations in its order (column `count`: |w|^2)
+    for (int u = 0; u < PF_ORTH_LOCAL_MAX; ++u) chunk_load(xs[u], orth_vec(a, u < count ? u : count - 1), chunk);  // (past the end: the last again)
+    // ---- the chunk's partial sums: k_orth_dots' calls (column `count`: |w|^2)
 #pragma unroll
     for (int u = 0; u <= PF_ORTH_LOCAL_MAX; ++u) {
         if (u > count) continue;
-        double s = 0.0;
+        double2 x[PF_CHUNK_PAIRS];
 #pragma unroll
-        for (int it = 0; it < PAIRS; ++it) {
-            const double2 x = u == count ? cs[it] : xs[u < PF_ORTH_LOCAL_MAX ? u : 0][it];
-            s += x.x * cs[it].x;
-            s += x.y * cs[it].y;
-        }
-#pragma unroll
-        for (int off = PF_WAVE / 2; off > 0; off >>= 1) s += __shfl_down(s, off, PF_WAVE);
-        if (lane == 0) red[u][threadIdx.x / PF_WAVE] = s;
+        for (int it = 0; it < PF_CHUNK_PAIRS; ++it) x[it] = u == count ? cs[it] : xs[u < PF_ORTH_LOCAL_MAX ? u : 0][it];
+        block_sum_put(chunk_dot_regs(x, cs), red[u]);
     }
     __syncthreads();
     if ((int)threadIdx.x <= count) {
-        const double p = (red[threadIdx.x][0] + red[threadIdx.x][1]) + (red[threadIdx.x][2] + red[threadIdx.x][3]);
         __hip_atomic_store(reinterpret_cast<unsigned long long*>(a.partial) + (int64_t)threadIdx.x * a.n_chunks + chunk,
-                           (unsigned long long)__double_as_longlong(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                           (unsigned long long)__double_as_longlong(block_sum_get(red[threadIdx.x])), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // in memory before the block says it has arrived
     }
     __syncthreads();
@@ -372,73 +321,40 @@ __global__ __launch_bounds__(PF_BLOCK) void k_orth_local(OrthArgs2 a2) {
     if (threadIdx.x == 0) s_ok = orth_meet(a, a.target);
     __syncthreads();
     if (!s_ok) return;
-    // ---- the sums of the partials: k_orth_project's operations in its order (read from where the other XCDs wrote them)
-    {  // (the two vectors of a wave - b and b + 4 - with their loads in flight together; per vector the order of the sum is kept)
+    // ---- the sums of the partials, read from where the other XCDs wrote them: column_sum's additions in its order, of the
+    // two columns of a wave - b and b + 4 - at once so that their loads are in flight together
+    {
         const int b0 = threadIdx.x / PF_WAVE, b1 = b0 + PF_BLOCK / PF_WAVE;
+        auto part = [&](int b, int64_t k) {
+            return b < count + 1 ? __longlong_as_double((long long)__hip_atomic_load(reinterpret_cast<unsigned long long*>(a.partial) + (int64_t)b * a.n_chunks + k,
+                                                                                     __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+                                 : 0.0;
+        };
         double s0 = 0.0, s1 = 0.0;
         for (int64_t k = lane; k < a.n_chunks; k += PF_WAVE) {
-            const double x0 = b0 < count + 1 ? __longlong_as_double((long long)__hip_atomic_load(
-                                                   reinterpret_cast<unsigned long long*>(a.partial) + (int64_t)b0 * a.n_chunks + k, __ATOMIC_RELAXED,
-                                                   __HIP_MEMORY_SCOPE_AGENT))
-                                             : 0.0;
-            const double x1 = b1 < count + 1 ? __longlong_as_double((long long)__hip_atomic_load(
-                                                   reinterpret_cast<unsigned long long*>(a.partial) + (int64_t)b1 * a.n_chunks + k, __ATOMIC_RELAXED,
-                                                   __HIP_MEMORY_SCOPE_AGENT))
-                                             : 0.0;
+            const double x0 = part(b0, k), x1 = part(b1, k);
             s0 += x0;
             s1 += x1;
         }
-#pragma unroll
-        for (int off = PF_WAVE / 2; off > 0; off >>= 1) {
-            s0 += __shfl_down(s0, off, PF_WAVE);
-            s1 += __shfl_down(s1, off, PF_WAVE);
-        }
+        s0 = wave_sum_down(s0);
+        s1 = wave_sum_down(s1);
         if (lane == 0 && b0 < count + 1) hs[b0] = s0;
         if (lane == 0 && b1 < count + 1) hs[b1] = s1;
     }
     __syncthreads();
-    if (threadIdx.x == 0) {
-        double sum = 0.0;
-        for (int b = 0; b < count; ++b) sum += hs[b] * hs[b];
-        const double before = hs[count], after = before - sum;
-        // (one pass: a raised verdict is pf_orth_end's business.  The flag goes through a vector register on purpose: this
-        // compiler turned `fine ? 0.0 : 1.0` into an s_cselect on SCC behind a v_cmp that sets VCC - the verdict then was
-        // whatever the last scalar compare had left)
-        int fine = after >= a.thresh * before ? 1 : 0;
-        asm volatile("" : "+v"(fine));
-        s_redo = fine ? 0.0 : 1.0;
-        s_after = after;
-        s_scale = (fine && a.normalize && after > 1e-280) ? 1.0 / sqrt(after) : 1.0;
-    }
+    if (threadIdx.x == 0) s_v = orth_verdict(hs, count, a.thresh, a.normalize, 0);  // (one pass: a raised verdict is pf_orth_end's business)
     __syncthreads();
-    if (chunk == 0) {
-        for (int b = threadIdx.x; b < count; b += PF_BLOCK) {
-            a.hsum[b] = hs[b];
-            a.host_out[b] = hs[b];
-        }
-        if (threadIdx.x == 0) {
-            *a.nrm2 = s_after;
-            a.host_out[count] = s_after;
-            a.host_out[count + 1] = s_redo;
-        }
-        __threadfence_system();
-        __syncthreads();
-        if (threadIdx.x == 0) __hip_atomic_store(a.host_out + count + 2, a.ticket, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-    const double sc = s_scale;
+    if (chunk == 0) orth_report(a, hs, s_v, 0);
+    const double sc = s_v.scale;
 #pragma unroll
-    for (int it = 0; it < PAIRS; ++it) {
+    for (int it = 0; it < PF_CHUNK_PAIRS; ++it) {
         double2 acc = cs[it];
 #pragma unroll
-        for (int u = 0; u < PF_ORTH_LOCAL_MAX; ++u) {
-            if (u >= count) continue;
-            const double hb = hs[u];
-            acc.x -= hb * xs[u][it].x;
-            acc.y -= hb * xs[u][it].y;
-        }
+        for (int u = 0; u < PF_ORTH_LOCAL_MAX; ++u)
+            if (u < count) axpy_sub(acc, hs[u], xs[u][it]);
         acc.x *= sc;
         acc.y *= sc;
-        *reinterpret_cast<double2*>(w + lo + 2 * threadIdx.x + (int64_t)it * (2 * PF_BLOCK)) = acc;
+        *reinterpret_cast<double2*>(w + chunk * PF_DOT_CHUNK + 2 * threadIdx.x + (int64_t)it * (2 * PF_BLOCK)) = acc;
     }
 }
 __global__ __launch_bounds__(PF_BLOCK) void k_scale_finishing(double* __restrict__ x, int64_t n_pad, const double* __restrict__ partial,
@@ -446,10 +362,7 @@ __global__ __launch_bounds__(PF_BLOCK) void k_scale_finishing(double* __restrict
                                                               int32_t count, double* __restrict__ nrm2, double* __restrict__ host_out) {
     __shared__ double s_v;
     if (threadIdx.x < PF_WAVE) {
-        double s = 0.0;
-        for (int64_t k = threadIdx.x; k < n_chunks; k += PF_WAVE) s += partial[k];
-#pragma unroll
-        for (int off = PF_WAVE / 2; off > 0; off >>= 1) s += __shfl_down(s, off, PF_WAVE);
+        const double s = column_sum(partial, 0, n_chunks, threadIdx.x);
         if (threadIdx.x == 0) s_v = s;
     }
     __syncthreads();
@@ -585,7 +498,17 @@ static int orth_prepare(pf_graph* g, int32_t w, int32_t first, int32_t count, in
     return PF_OK;
 }
 
+// g->coef (pf_reduce_ensure: 8 x coef_cap doubles) as the Gram-Schmidt step uses it
+struct OrthCoef {
+    double *hpass, *hsum, *nrm2, *verdict;  // coefficients of the current pass; h1 + h2; |w'|^2; a first device pass's verdict
+};
+static OrthCoef orth_coef(const pf_graph* g) {
+    const int32_t cap = g->coef_cap;
+    return {g->coef, g->coef + cap, g->coef + 2 * cap, g->coef + 3 * cap};
+}
+
 static OrthArgs orth_args(pf_graph* g, int32_t w, int32_t first, int32_t count, int32_t normalize) {
+    const OrthCoef c = orth_coef(g);
     OrthArgs a{};
     a.ws = g->ws;
     a.n_pad = g->n_pad;
@@ -594,52 +517,77 @@ static OrthArgs orth_args(pf_graph* g, int32_t w, int32_t first, int32_t count, 
     a.split = g->orth_split_now >= 0 ? g->orth_split_now : count;
     a.first2 = g->orth_first2_now;
     a.partial = g->partials;
-    a.hsum = g->coef + g->coef_cap;
-    a.nrm2 = g->coef + 2 * g->coef_cap;
+    a.hsum = c.hsum;
+    a.nrm2 = c.nrm2;
     a.host_out = g->orth_land.host;
     a.thresh = g->orth_thresh;
     g->orth_serial += 1.0;
     a.ticket = g->orth_serial;
     g->orth_ticket = a.ticket;  // pf_orth_end polls for it
     a.pass = g->orth_device_passes ? 1 : 0;
-    a.verdict = g->coef + 3 * g->coef_cap;
+    a.verdict = c.verdict;
     return a;
 }
 
+// The fused step of ng graphs of one ctx (one, or the two of a pair), each with 0 < count < PF_ORTH_MAX, behind the same
+// launches: 2 launches (or k_orth_local's one) and no copies - the projection, its norm (Pythagoras) and the normalisation
+// ride behind one batch of dot products; the second Gram-Schmidt pass is queued as well with pf_orth_device_passes, and is
+// pf_orth_end's business otherwise in the rare step that needs it.  No event: the results carry tickets, pf_orth_end
+// polls for them.
+struct OrthStep {
+    pf_graph* g;
+    int32_t w, first, count, normalize;
+};
+static int orth_fused(const OrthStep* s, int ng) {
+    for (int q = 0; q < ng; ++q) PF_TRY(orth_prepare(s[q].g, s[q].w, s[q].first, s[q].count, s[q].normalize));
+    hipStream_t st = s[0].g->ctx->stream;
+    OrthArgs2 a2{};
+    pf_graph* gs[2] = {};
+    int64_t chunks = 0, pad = 0;  // (the grids are sized for the larger graph)
+    int32_t count = 0;
+    bool second = false;
+    for (int q = 0; q < ng; ++q) {
+        gs[q] = s[q].g;
+        a2.g[q] = orth_args(s[q].g, s[q].w, s[q].first, s[q].count, s[q].normalize);
+        chunks = std::max(chunks, gs[q]->n_chunks), pad = std::max(pad, gs[q]->n_pad), count = std::max(count, s[q].count);
+        second = second || a2.g[q].pass == 1;
+    }
+    PF_TRY(orth_launch_pass(a2, ng, chunks, pad, count, st, gs));
+    if (second) {  // the second pass of the graph(s) that asked for it, on the device's own verdict
+        for (int q = 0; q < ng; ++q) a2.g[q].pass = a2.g[q].pass == 1 ? 2 : -1;
+        PF_TRY(orth_launch_pass(a2, ng, chunks, pad, count, st));
+    }
+    for (int q = 0; q < ng; ++q) {
+        gs[q]->orth_wait = gs[q]->orth_land.ev;
+        gs[q]->orth_pending = s[q].count;
+    }
+    return PF_OK;
+}
+
 int pf_orth_begin(pf_graph* g, int32_t w, int32_t first, int32_t count, int32_t normalize) {
+    if (count > 0 && count < PF_ORTH_MAX) {
+        const OrthStep one = {g, w, first, count, normalize};
+        return orth_fused(&one, 1);
+    }
     PF_TRY(orth_prepare(g, w, first, count, normalize));
     hipStream_t st = g->ctx->stream;
-    const int32_t cap = g->coef_cap;
-    double* hpass = g->coef;           // coefficients of the current pass
-    double* hsum = g->coef + cap;      // h1 + h2
-    double* nrm2 = g->coef + 2 * cap;  // ||w||^2
-    if (count > 0 && count < PF_ORTH_MAX) {
-        // 2 launches and no copies: the projection, its norm (Pythagoras) and the normalisation ride behind one batch of
-        // dot products; the second Gram-Schmidt pass is pf_orth_end's business in the rare step that needs it
-        OrthArgs2 a2{};
-        a2.g[0] = orth_args(g, w, first, count, normalize);
-        pf_graph* const one[1] = {g};
-        PF_TRY(orth_launch_pass(a2, 1, g->n_chunks, g->n_pad, count, st, one));
-        if (a2.g[0].pass == 1) {  // the second pass, on the device's own verdict
-            a2.g[0].pass = 2;
-            PF_TRY(orth_launch_pass(a2, 1, g->n_chunks, g->n_pad, count, st));
-        }
-    } else if (count == 0) {
+    const OrthCoef c = orth_coef(g);
+    if (count == 0) {
         PF_TRY(pf_dot_partials(g, w, w, 1, g->partials));
         k_scale_finishing<<<pf_blocks(g->n_pad), PF_BLOCK, 0, st>>>(pf_slot(g, w), g->n_pad, g->partials, g->n_chunks, normalize ? 1 : 0,
-                                                              hsum, count, nrm2, g->orth_land.host);
+                                                              c.hsum, count, c.nrm2, g->orth_land.host);
         PF_HIP(hipGetLastError());
     } else {
         for (int pass = 0; pass < 2; ++pass) {
-            PF_TRY(pf_dots_device(g, w, first, count, hpass, hsum, pass));
-            PF_TRY(pf_multi_axpy(g, w, first, count, hpass));
+            PF_TRY(pf_dots_device(g, w, first, count, c.hpass, c.hsum, pass));
+            PF_TRY(pf_multi_axpy(g, w, first, count, c.hpass));
         }
-        PF_TRY(pf_dots_device(g, w, w, 1, nrm2, nullptr, 0));
-        if (normalize) PF_TRY(pf_scale_rsqrt(g, pf_slot(g, w), nrm2));
-        PF_HIP(hipMemcpyAsync(g->orth_land.host, hsum, sizeof(double) * count, hipMemcpyDeviceToHost, st));
-        PF_HIP(hipMemcpyAsync(g->orth_land.host + count, nrm2, sizeof(double), hipMemcpyDeviceToHost, st));
+        PF_TRY(pf_dots_device(g, w, w, 1, c.nrm2, nullptr, 0));
+        if (normalize) PF_TRY(pf_scale_rsqrt(g, pf_slot(g, w), c.nrm2));
+        PF_HIP(hipMemcpyAsync(g->orth_land.host, c.hsum, sizeof(double) * count, hipMemcpyDeviceToHost, st));
+        PF_HIP(hipMemcpyAsync(g->orth_land.host + count, c.nrm2, sizeof(double), hipMemcpyDeviceToHost, st));
     }
-    if (g->orth_ticket == 0.0) PF_HIP(hipEventRecord(g->orth_land.ev, st));  // (a ticketed step is polled for, not waited on)
+    PF_HIP(hipEventRecord(g->orth_land.ev, st));  // (no ticket from these kernels: pf_orth_end waits for the event)
     g->orth_wait = g->orth_land.ev;
     g->orth_pending = count;
     return PF_OK;
@@ -654,26 +602,8 @@ int pf_orth_begin2(pf_graph* ga, int32_t w_a, int32_t first_a, int32_t count_a, 
         PF_TRY(pf_orth_begin(ga, w_a, first_a, count_a, normalize_a));
         return pf_orth_begin(gb, w_b, first_b, count_b, normalize_b);
     }
-    PF_TRY(orth_prepare(ga, w_a, first_a, count_a, normalize_a));
-    PF_TRY(orth_prepare(gb, w_b, first_b, count_b, normalize_b));
-    hipStream_t st = ga->ctx->stream;
-    OrthArgs2 a2{};
-    a2.g[0] = orth_args(ga, w_a, first_a, count_a, normalize_a);
-    a2.g[1] = orth_args(gb, w_b, first_b, count_b, normalize_b);
-    const int64_t chunks2 = std::max(ga->n_chunks, gb->n_chunks), pad2 = std::max(ga->n_pad, gb->n_pad);
-    const int32_t count2 = std::max(count_a, count_b);
-    pf_graph* const two[2] = {ga, gb};
-    PF_TRY(orth_launch_pass(a2, 2, chunks2, pad2, count2, st, two));
-    if (a2.g[0].pass == 1 || a2.g[1].pass == 1) {  // the second pass of the graph(s) that asked for it, on the device's own verdict
-        for (int q = 0; q < 2; ++q) a2.g[q].pass = a2.g[q].pass == 1 ? 2 : -1;
-        PF_TRY(orth_launch_pass(a2, 2, chunks2, pad2, count2, st));
-    }
-    // (no event: both results carry tickets, pf_orth_end polls for them)
-    ga->orth_wait = ga->orth_land.ev;
-    gb->orth_wait = gb->orth_land.ev;
-    ga->orth_pending = count_a;
-    gb->orth_pending = count_b;
-    return PF_OK;
+    const OrthStep two[2] = {{ga, w_a, first_a, count_a, normalize_a}, {gb, w_b, first_b, count_b, normalize_b}};
+    return orth_fused(two, 2);
 }
 
 int pf_orth_end(pf_graph* g, double* h, double* nrm) {
@@ -723,24 +653,22 @@ int pf_orth_end(pf_graph* g, double* h, double* nrm) {
         // the first pass cancelled digits (or w vanished): second pass, exact norm, normalisation - synchronously.
         // Whatever was queued behind pf_orth_begin read a w that is only now final: pf_orth_redone tells the caller.
         hipStream_t st = g->ctx->stream;
-        double* hsum = g->coef + g->coef_cap;
-        double* nrm2 = g->coef + 2 * g->coef_cap;
-        const int32_t w = g->orth_w, first = g->orth_first;
-        const int32_t split = g->orth_split_now >= 0 ? g->orth_split_now : count;  // (two ranges: all dot products first, as in one)
-        if (split > 0) PF_TRY(pf_dot_partials(g, w, first, split, g->partials));
-        if (count > split) PF_TRY(pf_dot_partials(g, w, g->orth_first2_now, count - split, g->partials + (size_t)split * g->n_chunks));
-        if (split > 0) {
-            k_axpy_finishing<<<pf_blocks(g->n_pad / 2), PF_BLOCK, 0, st>>>(g->ws, g->n_pad, first, split, w, g->partials, g->n_chunks, hsum, 1);
-            PF_HIP(hipGetLastError());
-        }
-        if (count > split) {
-            k_axpy_finishing<<<pf_blocks(g->n_pad / 2), PF_BLOCK, 0, st>>>(g->ws, g->n_pad, g->orth_first2_now, count - split, w,
-                                                                      g->partials + (size_t)split * g->n_chunks, g->n_chunks, hsum + split, 1);
+        const OrthCoef c = orth_coef(g);
+        const int32_t w = g->orth_w;
+        const int32_t split = g->orth_split_now >= 0 ? g->orth_split_now : count;
+        // one range of the basis, or two: columns [at[r], at[r + 1]) are slots from[r] .. (all dot products first, as in one)
+        const int32_t from[2] = {g->orth_first, g->orth_first2_now}, at[3] = {0, split, count};
+        for (int r = 0; r < 2; ++r)
+            if (at[r + 1] > at[r]) PF_TRY(pf_dot_partials(g, w, from[r], at[r + 1] - at[r], g->partials + (size_t)at[r] * g->n_chunks));
+        for (int r = 0; r < 2; ++r) {
+            if (at[r + 1] == at[r]) continue;
+            k_axpy_finishing<<<pf_blocks(g->n_pad / 2), PF_BLOCK, 0, st>>>(g->ws, g->n_pad, from[r], at[r + 1] - at[r], w,
+                                                                      g->partials + (size_t)at[r] * g->n_chunks, g->n_chunks, c.hsum + at[r], 1);
             PF_HIP(hipGetLastError());
         }
         PF_TRY(pf_dot_partials(g, w, w, 1, g->partials));
         k_scale_finishing<<<pf_blocks(g->n_pad), PF_BLOCK, 0, st>>>(pf_slot(g, w), g->n_pad, g->partials, g->n_chunks, g->orth_normalize,
-                                                              hsum, count, nrm2, g->orth_land.host);
+                                                              c.hsum, count, c.nrm2, g->orth_land.host);
         PF_HIP(hipGetLastError());
         PF_HIP(hipStreamSynchronize(st));
         PF_TRY(pf_persist_check(g->ctx));

@@ -1,6 +1,8 @@
 // The small reductions of the solve over workspace slots, and their way to the host: dot products, Gram matrices and
 // residual norms (two-stage and atomic-free: per-chunk partial sums in g->partials, finished in a fixed order into
-// g->coef, so results are bitwise reproducible run to run), the basis rotation pf_combine and pf_scale.  The few
+// g->coef, so results are bitwise reproducible run to run), the basis rotation pf_combine and pf_scale.  The order of
+// every sum is pf_sums.h's: a first-stage kernel here is a chunk sum and the block sum, the one second stage (k_dot_finish,
+// finish_queue) is the column sum; pf_resnorm is pf_resnorms with a count of one.  The few
 // doubles of a result reach the host either at once (small_to_host: pinned scratch, a copy kernel, a wait) or in two
 // halves (small_begin / pf_small_end: the graph's own pinned landing and an event).
 #include <math.h>
@@ -10,12 +12,12 @@
 
 #include "pf_internal.h"
 #include "pf_launch.h"
+#include "pf_sums.h"
 
 namespace {
 
-// partial[b][chunk] = sum over the chunk's rows of V_b[i] * w[i]   (fixed order -> deterministic)
-// partial[b][chunk] = <slot first+b, slot wslot> over the chunk; with self_col >= 0 column b == self_col is w itself
-// (|w|^2 rides along)
+// partial[b][chunk] = <slot first+b, slot wslot> over the chunk (pf_sums.h: fixed order -> deterministic); with
+// self_col >= 0 column b == self_col is w itself (|w|^2 rides along)
 // (d_*: the body of k_* - the kernel itself, and the form pf_launch.h records when a pair's driver queues the heads of its
 // two solves in shared launches, f_*)
 __device__ __forceinline__ void d_dot_partial(const double* __restrict__ ws, int64_t n_pad, int32_t first,
@@ -26,20 +28,9 @@ __device__ __forceinline__ void d_dot_partial(const double* __restrict__ ws, int
     const int64_t chunk = blockIdx.x;
     const double* v = ws + (int64_t)(b == self_col ? wslot : first + b) * n_pad;
     const double* w = ws + (int64_t)wslot * n_pad;
-    const int64_t lo = chunk * PF_DOT_CHUNK;
-    const int64_t hi = lo + PF_DOT_CHUNK < n_pad ? lo + PF_DOT_CHUNK : n_pad;
-    double s = 0.0;
-    for (int64_t i = lo + 2 * threadIdx.x; i < hi; i += 2 * PF_BLOCK) {
-        const double2 a = *reinterpret_cast<const double2*>(v + i);
-        const double2 c = *reinterpret_cast<const double2*>(w + i);
-        s += a.x * c.x;
-        s += a.y * c.y;
-    }
-#pragma unroll
-    for (int off = PF_WAVE / 2; off > 0; off >>= 1) s += __shfl_down(s, off, PF_WAVE);
-    if ((threadIdx.x & (PF_WAVE - 1)) == 0) red[threadIdx.x / PF_WAVE] = s;
+    block_sum_put(chunk_dot(v, w, chunk, n_pad), red);
     __syncthreads();
-    if (threadIdx.x == 0) partial[(int64_t)b * n_chunks + chunk] = (red[0] + red[1]) + (red[2] + red[3]);
+    if (threadIdx.x == 0) partial[(int64_t)b * n_chunks + chunk] = block_sum_get(red);
 }
 __global__ __launch_bounds__(PF_BLOCK) void k_dot_partial(const double* __restrict__ ws, int64_t n_pad, int32_t first,
                                                           int32_t wslot, int64_t n_chunks, double* __restrict__ partial,
@@ -58,10 +49,7 @@ struct f_dot_partial {
 __device__ __forceinline__ void d_dot_finish(const double* __restrict__ partial, int64_t n_chunks,
                                              double* __restrict__ out, double* __restrict__ acc, int accumulate) {
     const int b = blockIdx.x;
-    double s = 0.0;
-    for (int64_t k = threadIdx.x; k < n_chunks; k += PF_WAVE) s += partial[(int64_t)b * n_chunks + k];
-#pragma unroll
-    for (int off = PF_WAVE / 2; off > 0; off >>= 1) s += __shfl_down(s, off, PF_WAVE);
+    const double s = column_sum(partial, b, n_chunks, threadIdx.x);
     if (threadIdx.x == 0) {
         out[b] = s;
         if (acc) acc[b] = accumulate ? acc[b] + s : s;
@@ -122,27 +110,7 @@ __global__ __launch_bounds__(PF_BLOCK) void k_combine(double* __restrict__ ws, i
         if (c < ncols) ws[(int64_t)(dst_first + c0 + c) * n_pad + i] = acc[c];
 }
 
-// partial sums of (ax - lam x)^2
-__global__ __launch_bounds__(PF_BLOCK) void k_resnorm_partial(const double* __restrict__ ax, const double* __restrict__ x,
-                                                              double lam, int64_t n_pad, int64_t n_chunks,
-                                                              double* __restrict__ partial) {
-    __shared__ double red[PF_BLOCK / PF_WAVE];
-    const int64_t lo = (int64_t)blockIdx.x * PF_DOT_CHUNK;
-    const int64_t hi = lo + PF_DOT_CHUNK < n_pad ? lo + PF_DOT_CHUNK : n_pad;
-    double s = 0.0;
-    for (int64_t i = lo + threadIdx.x; i < hi; i += PF_BLOCK) {
-        const double r = ax[i] - lam * x[i];
-        s += r * r;
-    }
-#pragma unroll
-    for (int off = PF_WAVE / 2; off > 0; off >>= 1) s += __shfl_down(s, off, PF_WAVE);
-    if ((threadIdx.x & (PF_WAVE - 1)) == 0) red[threadIdx.x / PF_WAVE] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
-}
-
-// the batched forms (pf_gram, pf_resnorms): one launch for all pairs / all vectors, k_dot_partial's and
-// k_resnorm_partial's sums in their order
+// the batched forms (pf_gram, pf_resnorms): one launch for all pairs / all vectors
 __global__ __launch_bounds__(PF_BLOCK) void k_gram_partial(const double* __restrict__ ws, int64_t n_pad, int32_t first_a, int32_t first_b,
                                                            int32_t count_b, int64_t n_chunks, double* __restrict__ partial) {
     __shared__ double red[PF_BLOCK / PF_WAVE];
@@ -150,22 +118,12 @@ __global__ __launch_bounds__(PF_BLOCK) void k_gram_partial(const double* __restr
     const int i = p / count_b, j = p - i * count_b;
     const double* v = ws + (int64_t)(first_b + j) * n_pad;
     const double* w = ws + (int64_t)(first_a + i) * n_pad;
-    const int64_t lo = (int64_t)blockIdx.x * PF_DOT_CHUNK;
-    const int64_t hi = lo + PF_DOT_CHUNK < n_pad ? lo + PF_DOT_CHUNK : n_pad;
-    double s = 0.0;
-    for (int64_t r = lo + 2 * threadIdx.x; r < hi; r += 2 * PF_BLOCK) {
-        const double2 a = *reinterpret_cast<const double2*>(v + r);
-        const double2 c = *reinterpret_cast<const double2*>(w + r);
-        s += a.x * c.x;
-        s += a.y * c.y;
-    }
-#pragma unroll
-    for (int off = PF_WAVE / 2; off > 0; off >>= 1) s += __shfl_down(s, off, PF_WAVE);
-    if ((threadIdx.x & (PF_WAVE - 1)) == 0) red[threadIdx.x / PF_WAVE] = s;
+    block_sum_put(chunk_dot(v, w, blockIdx.x, n_pad), red);
     __syncthreads();
-    if (threadIdx.x == 0) partial[(int64_t)p * n_chunks + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+    if (threadIdx.x == 0) partial[(int64_t)p * n_chunks + blockIdx.x] = block_sum_get(red);
 }
 
+// partial[b][chunk] = |slot ax_first+b - lam[b] slot x_first+b|^2 over the chunk
 constexpr int PF_RESNORMS_MAX = 64;
 struct LamArgs {
     double lam[PF_RESNORMS_MAX];
@@ -177,19 +135,9 @@ __global__ __launch_bounds__(PF_BLOCK) void k_resnorms_partial(const double* __r
     const int b = blockIdx.y;
     const double* ax = ws + (int64_t)(ax_first + b) * n_pad;
     const double* x = ws + (int64_t)(x_first + b) * n_pad;
-    const double lam = la.lam[b];
-    const int64_t lo = (int64_t)blockIdx.x * PF_DOT_CHUNK;
-    const int64_t hi = lo + PF_DOT_CHUNK < n_pad ? lo + PF_DOT_CHUNK : n_pad;
-    double s = 0.0;
-    for (int64_t i = lo + threadIdx.x; i < hi; i += PF_BLOCK) {
-        const double r = ax[i] - lam * x[i];
-        s += r * r;
-    }
-#pragma unroll
-    for (int off = PF_WAVE / 2; off > 0; off >>= 1) s += __shfl_down(s, off, PF_WAVE);
-    if ((threadIdx.x & (PF_WAVE - 1)) == 0) red[threadIdx.x / PF_WAVE] = s;
+    block_sum_put(chunk_resid2(ax, x, la.lam[b], blockIdx.x, n_pad), red);
     __syncthreads();
-    if (threadIdx.x == 0) partial[(int64_t)b * n_chunks + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+    if (threadIdx.x == 0) partial[(int64_t)b * n_chunks + blockIdx.x] = block_sum_get(red);
 }
 
 // `count` doubles of device memory to the host behind whatever is queued on the ctx stream, and wait for them: through
@@ -211,22 +159,26 @@ int small_to_host(pf_graph* g, const double* d_src, double* out, size_t count) {
     return PF_OK;
 }
 
+// the second stage of every reduction here: columns [0, count) of g->partials summed into out[0 .. count), acc[b] (+)= out[b]
+int finish_queue(pf_graph* g, int32_t count, double* out, double* acc = nullptr, int accumulate = 0) {
+    k_dot_finish<<<(unsigned)count, PF_WAVE, 0, g->ctx->stream>>>(g->partials, g->n_chunks, out, acc, accumulate);
+    PF_HIP(hipGetLastError());
+    return PF_OK;
+}
+
 }  // namespace
 
 int pf_dots_device(pf_graph* g, int32_t w, int32_t first, int32_t count, double* d_out, double* d_acc, int accumulate) {
     hipStream_t st = g->ctx->stream;
     PF_TRY(pf_reduce_ensure(g, count));
-    dim3 grid((unsigned)g->n_chunks, (unsigned)count);
     if (pfl::tl_rec) {  // the head of a pair's solve is being recorded: the partner's dot products share the launches
+        const dim3 grid((unsigned)g->n_chunks, (unsigned)count);
         pfl::launch<f_dot_partial>(grid, dim3(PF_BLOCK), 0, st, g->ws, g->n_pad, first, w, g->n_chunks, g->partials, -1);
         pfl::launch<f_dot_finish>(dim3((unsigned)count), dim3(PF_WAVE), 0, st, g->partials, g->n_chunks, d_out, d_acc, accumulate);
         return PF_OK;
     }
-    k_dot_partial<<<grid, PF_BLOCK, 0, st>>>(g->ws, g->n_pad, first, w, g->n_chunks, g->partials);
-    PF_HIP(hipGetLastError());
-    k_dot_finish<<<(unsigned)count, PF_WAVE, 0, st>>>(g->partials, g->n_chunks, d_out, d_acc, accumulate);
-    PF_HIP(hipGetLastError());
-    return PF_OK;
+    PF_TRY(pf_dot_partials(g, w, first, count, g->partials));
+    return finish_queue(g, count, d_out, d_acc, accumulate);
 }
 
 int pf_dot_partials(pf_graph* g, int32_t w, int32_t first, int32_t count, double* partial) {
@@ -354,27 +306,6 @@ int pf_combine2(pf_graph* g, int32_t src_first, int32_t m, const double* Y, int3
     return PF_OK;
 }
 
-extern "C" {
-
-int pf_resnorm(pf_graph* g, int32_t ax, int32_t x, double lam, double* out) {
-    PF_TRY(pf_check_slots(g, ax, 1, "pf_resnorm"));
-    PF_TRY(pf_check_slots(g, x, 1, "pf_resnorm"));
-    PF_CHECK(out != nullptr, PF_E_ARG, "pf_resnorm: out is NULL");
-    hipStream_t st = g->ctx->stream;
-    PF_TRY(pf_reduce_ensure(g, 1));
-    k_resnorm_partial<<<(unsigned)g->n_chunks, PF_BLOCK, 0, st>>>(pf_slot(g, ax), pf_slot(g, x), lam, g->n_pad, g->n_chunks, g->partials);
-    PF_HIP(hipGetLastError());
-    k_dot_finish<<<1, PF_WAVE, 0, st>>>(g->partials, g->n_chunks, g->coef, nullptr, 0);
-    PF_HIP(hipGetLastError());
-    double r2 = 0.0;
-    PF_HIP(hipMemcpyAsync(&r2, g->coef, sizeof(double), hipMemcpyDeviceToHost, st));
-    PF_HIP(hipStreamSynchronize(st));
-    *out = sqrt(r2 > 0.0 ? r2 : 0.0);
-    return PF_OK;
-}
-
-}  // extern "C"
-
 // The queueing half of pf_gram / pf_gram_begin and of pf_resnorms / pf_resnorms_begin: the checks (args_ok: what the caller
 // found of the arguments that are its own), the partial sums and their finish into g->coef.
 static int gram_queue(pf_graph* g, int32_t first_a, int32_t count_a, int32_t first_b, int32_t count_b, bool args_ok) {
@@ -382,13 +313,10 @@ static int gram_queue(pf_graph* g, int32_t first_a, int32_t count_a, int32_t fir
     PF_TRY(pf_check_slots(g, first_b, count_b, "pf_gram"));
     PF_CHECK(args_ok && count_a > 0 && count_b > 0, PF_E_ARG, "pf_gram: bad argument");
     PF_TRY(pf_reduce_ensure(g, count_a * count_b));  // partials: one column per pair
-    hipStream_t st = g->ctx->stream;
-    k_gram_partial<<<dim3((unsigned)g->n_chunks, (unsigned)(count_a * count_b)), PF_BLOCK, 0, st>>>(g->ws, g->n_pad, first_a, first_b, count_b,
-                                                                                                 g->n_chunks, g->partials);
+    k_gram_partial<<<dim3((unsigned)g->n_chunks, (unsigned)(count_a * count_b)), PF_BLOCK, 0, g->ctx->stream>>>(
+        g->ws, g->n_pad, first_a, first_b, count_b, g->n_chunks, g->partials);
     PF_HIP(hipGetLastError());
-    k_dot_finish<<<(unsigned)(count_a * count_b), PF_WAVE, 0, st>>>(g->partials, g->n_chunks, g->coef, nullptr, 0);
-    PF_HIP(hipGetLastError());
-    return PF_OK;
+    return finish_queue(g, count_a * count_b, g->coef);
 }
 
 static int resnorms_queue(pf_graph* g, int32_t ax_first, int32_t x_first, const double* lam, int32_t count, bool args_ok) {
@@ -404,8 +332,7 @@ static int resnorms_queue(pf_graph* g, int32_t ax_first, int32_t x_first, const 
         k_resnorms_partial<<<dim3((unsigned)g->n_chunks, (unsigned)nb), PF_BLOCK, 0, st>>>(g->ws, g->n_pad, ax_first + at, x_first + at, la,
                                                                                         g->n_chunks, g->partials);
         PF_HIP(hipGetLastError());
-        k_dot_finish<<<(unsigned)nb, PF_WAVE, 0, st>>>(g->partials, g->n_chunks, g->coef + at, nullptr, 0);
-        PF_HIP(hipGetLastError());
+        PF_TRY(finish_queue(g, nb, g->coef + at));
     }
     return PF_OK;
 }
@@ -415,6 +342,20 @@ extern "C" {
 int pf_gram(pf_graph* g, int32_t first_a, int32_t count_a, int32_t first_b, int32_t count_b, double* out) {
     PF_TRY(gram_queue(g, first_a, count_a, first_b, count_b, out != nullptr));
     return small_to_host(g, g->coef, out, (size_t)count_a * count_b);
+}
+
+// (one vector: the batched kernels with a count of one)
+int pf_resnorm(pf_graph* g, int32_t ax, int32_t x, double lam, double* out) {
+    PF_TRY(pf_check_slots(g, ax, 1, "pf_resnorm"));
+    PF_TRY(pf_check_slots(g, x, 1, "pf_resnorm"));
+    PF_CHECK(out != nullptr, PF_E_ARG, "pf_resnorm: out is NULL");
+    PF_TRY(resnorms_queue(g, ax, x, &lam, 1, true));
+    hipStream_t st = g->ctx->stream;
+    double r2 = 0.0;
+    PF_HIP(hipMemcpyAsync(&r2, g->coef, sizeof(double), hipMemcpyDeviceToHost, st));
+    PF_HIP(hipStreamSynchronize(st));
+    *out = sqrt(r2 > 0.0 ? r2 : 0.0);
+    return PF_OK;
 }
 
 int pf_resnorms(pf_graph* g, int32_t ax_first, int32_t x_first, const double* lam, int32_t count, double* out) {

@@ -1,6 +1,7 @@
 // Device helpers that belong to no one search: the order-preserving integer encoding of a double, the bit spread of the
 // 30-bit Morton keys, and the reductions across the 64 lanes of a wave.  Every one is a fixed butterfly: the same order of
-// operations on every run, the result in every lane.
+// operations on every run, the result in every lane - but for wave_sum_down, the sum of the solve's vector kernels
+// (pf_sums.h), whose result is lane 0's alone.
 #pragma once
 #include "pf_internal.h"
 
@@ -34,6 +35,14 @@ __device__ __forceinline__ double wave_max(double v) {
 
 __device__ __forceinline__ double wave_sum(double v) {
     for (int off = PF_WAVE / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, PF_WAVE);
+    return v;
+}
+
+// The other sum of a wave, and not interchangeable with wave_sum (other pairings: other bits): lane l adds lane l + off for
+// off = 32, 16, 8, 4, 2, 1.  The result is in lane 0 only.
+__device__ __forceinline__ double wave_sum_down(double v) {
+#pragma unroll
+    for (int off = PF_WAVE / 2; off > 0; off >>= 1) v += __shfl_down(v, off, PF_WAVE);
     return v;
 }
 

@@ -324,7 +324,7 @@ def test_gram_exact(graphs, n):
 @pytest.mark.parametrize("n", [65, 4097, 12289])
 def test_resnorms_exact(graphs, n):
     """pf_resnorms (k_resnorms_partial in batches of PF_RESNORMS_MAX = 64 vectors: counts 1, 63, 64, 65, 130 take one,
-    two and three batches) and pf_resnorm (k_resnorm_partial), a distinct lambda per vector so that a lambda taken from
+    two and three batches) and pf_resnorm (the same kernel, one vector), a distinct lambda per vector so that a lambda taken from
     the wrong batch or slot fails.  Bound on the squared norm: (depth + 5) 2^-53 sum (|ax| + |lam x|)^2 (each residual
     carries two roundings)."""
     g = graphs(n)
@@ -349,6 +349,56 @@ def test_resnorms_exact(graphs, n):
     for b in (0, 63, 64, 129):
         check(g.resnorm(b, 130 + b, lams[b]), b, (n, "single", b))
     assert_padding_zero(g, 0, 259)
+
+
+# -------------------------------------------------------------------------------- one statement of every sum
+@pytest.mark.parametrize("n", [65, 4097, 12289, N_BELOW, N_ABOVE])
+def test_kernels_that_share_a_sum_agree_bit_for_bit(request, hip, graphs, n):
+    """The kernels that form the same sum (csrc/pf_sums.h: chunk, block and column sum) return the same bits, not close
+    ones.  n = 65, 4097, 12289 (one chunk, two, four with one real row in the last), the mild vector of orth_inputs (planted
+    rows) against a basis of 5:  dots(w, first, 5) == the row of gram(w, first, 5) (k_dot_partial, k_gram_partial) == the h
+    of a one-pass Gram-Schmidt step of count 5 (k_orth_dots<1> + k_orth_project<1>);  at count 4 the h of the step in one
+    launch (k_orth_local) == the h of the two launches == dots;  resnorm == the matching entry of resnorms.  At 397312 and
+    397313 rows (big_pair: k_orth_dots<1> / k_orth_project<1> and k_orth_dots<4> / k_orth_project<8>): the h of a count-6
+    step == dots(w, 1, 6)."""
+    if n >= N_BELOW:
+        g, _, w, _ = request.getfixturevalue("big_pair")[n]
+        g.upload(0, w)
+        d = g.dots(0, 1, 6)
+        g.orth_begin(0, 1, 6, True)
+        h, _ = g.orth_end()
+        assert not g.orth_redone and not g.orth_twice
+        assert np.array_equal(h, d), (n, h - d)
+        return
+    g = graphs(n)
+    rng = np.random.default_rng(n + 9)
+    Q, ws = orth_inputs(rng, n, 5)
+    w = ws["mild"]
+    g.ws_ensure(12)
+    g.upload(0, w)
+    upload_cols(g, 1, Q)
+    d = g.dots(0, 1, 5)
+    G = g.gram(0, 1, 1, 5)
+    assert G.shape == (1, 5) and np.array_equal(G[0], d), (n, G[0] - d)
+    try:
+        g.orth_device_passes(False)
+        for count, modes in ((5, (True,)), (4, (True, False))):
+            for one_launch in modes:
+                hip.orth_one_launch(one_launch)
+                g.upload(0, w)
+                g.orth_begin(0, 1, count, False)
+                h, _ = g.orth_end()
+                assert not g.orth_redone and not g.orth_twice, (n, count, one_launch)  # (one pass: h is that pass's)
+                assert np.array_equal(h, d[:count]), (n, count, one_launch, h - d[:count])
+    finally:
+        hip.orth_one_launch(True)
+    AX, X = planted(rng, n, 3), planted(rng, n, 3)
+    upload_cols(g, 6, AX)
+    upload_cols(g, 9, X)
+    lams = np.array([0.25, -1.5, 3.0])
+    r = g.resnorms(6, 9, lams)
+    for b in range(3):
+        assert g.resnorm(6 + b, 9 + b, lams[b]) == r[b], (n, b)
 
 
 # ------------------------------------------------------------------------------------------------------- combine
