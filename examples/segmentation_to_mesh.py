@@ -1,0 +1,35 @@
+#!/usr/bin/env python3
+"""From a segmentation to a mesh the spectral pipeline can take: a synthetic label map -> `mask_to_mesh` -> `resample_mesh`
+-> the spectrum of its `Graph`.
+
+    python examples/segmentation_to_mesh.py [n_vertices]
+
+The mask is a bone-like solid (two ellipsoid heads on a shaft) with anisotropic voxels, as a scanner delivers them."""
+import os
+import sys
+
+import numpy as np
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+import pyfocusr_amd as pf  # noqa: E402
+
+n_vertices = int(sys.argv[1]) if len(sys.argv) > 1 else 2000
+spacing, origin = (0.6, 0.6, 1.2), (-20.0, -20.0, -45.0)
+shape = (68, 68, 76)
+x, y, z = np.meshgrid(*[origin[a] + spacing[a] * np.arange(shape[a]) for a in range(3)], indexing="ij")
+shaft = (x ** 2 + y ** 2 < 6.0 ** 2) & (np.abs(z) < 30.0)
+head = ((x / 14.0) ** 2 + (y / 11.0) ** 2 + ((z - 30.0) / 9.0) ** 2 < 1.0) | ((x / 11.0) ** 2 + (y / 13.0) ** 2 + ((z + 30.0) / 8.0) ** 2 < 1.0)
+mask = shaft | head
+
+mesh, info = pf.mask_to_mesh(mask, spacing, origin, return_info=True)
+topo = pf.mesh_topology(mesh)
+print("mask of %d voxels -> %d vertices, %d faces in %.2f ms on the device; closed %s, genus %d"
+      % (mask.sum(), len(mesh.points), len(mesh.faces), info.device_ms, bool(topo.patches["closed"][0]), topo.patches["genus"][0]))
+
+uniform = pf.resample_mesh(mesh, n_vertices)
+print("resampled to %d vertices, %d faces" % (len(uniform.points), len(uniform.faces)))
+
+graph = pf.Graph(uniform, n_spectral_features=5, verbose=False)
+graph.get_graph_spectrum()
+print("first eigenvalues of its graph Laplacian:", np.round(graph.eig_vals, 6))

@@ -998,6 +998,43 @@ int pf_shapes_set_reference(pf_shapes* h, const double* ref);
 int pf_shapes_download(pf_shapes* h, double* shapes_out);
 int pf_shapes_device_ms(pf_shapes* h, int32_t enable, double* last_ms);
 
+/* ---- the isosurface of a sampled scalar field: marching tetrahedra (pf_isosurface.hip; the reference has none: an extra) ----
+ * values [nx][ny][nz] f64, C-contiguous, host; every extent >= 2; nx ny nz < 2^31.  The sample (i, j, k) sits at
+ * origin + (i sx, j sy, k sz) with spacing = (sx, sy, sz).  A lattice point is inside when value < level: a value equal to
+ * the level is outside.  tests/_isosurface_ref.py states the definition in numpy and the device returns its bits.
+ *   cells      each of the (nx-1)(ny-1)(nz-1) cubes is cut into six tetrahedra, one per permutation (a, b, c) of the axes in
+ *              lexicographic order (012 021 102 120 201 210): v0 = p, v1 = v0 + e_a, v2 = v1 + e_b, v3 = p + (1,1,1).  The
+ *              cut is the same in every cube, so the face diagonals of neighbouring cubes agree.
+ *   vertices   one per lattice edge whose two ends differ in `inside`.  The edges that leave a lattice point p have the
+ *              kinds 0..6 = (1,0,0) (0,1,0) (0,0,1) (1,1,0) (1,0,1) (0,1,1) (1,1,1); edges that leave the volume do not
+ *              exist.  The key of an edge is 7 ((i ny + j) nz + k) + kind, taken at its lower end p; the vertices are
+ *              numbered in ascending key.  Position, always from the lower end p to the upper end q:
+ *              t = (level - v_p) / (v_q - v_p), then per coordinate P_c + t (Q_c - P_c) with P_c = origin_c + i_c s_c and
+ *              Q_c = origin_c + (i_c + d_c) s_c: separate multiplies and adds.
+ *   faces      a tetrahedron with one inside or one outside vertex l gives the triangle (l r0, l r1, l r2) over its other
+ *              vertices r0 < r1 < r2 in local order; one with two inside vertices a < b and outside vertices c < d the
+ *              quad (ac, ad, bd, bc), split into (ac, ad, bd) and (ac, bd, bc).  Orientation: the normal points from
+ *              inside to outside.  A triangle's last two vertices are swapped when, with its vertices at the edge
+ *              midpoints of the unit cube, normal . (centroid of the outside corners - centroid of the inside corners) < 0.
+ *              Order: ascending cell index (i (ny-1) + j)(nz-1) + k, then the tetrahedra in permutation order, then the
+ *              triangles as above.
+ *   zero area  triangles of zero area are kept.  They arise where a value equals the level: t is then 0 or 1 and the
+ *              vertices of different edges coincide in position.  The connectivity stays that of a manifold.
+ *   pf_isosurface_create  the surface stays on the device behind *handle.  report [8] (may be NULL): vertices | faces |
+ *              cells with a face | lattice points | cells | 0 | 0 | 0.  device_ms (may be NULL): between the upload and the
+ *              last kernel (HIP events); it contains the host's one read of the two totals that size the outputs.  A
+ *              surface without vertices is a success with zero counts.  flags must be 0.
+ *   pf_isosurface_fetch   pts [V][3] f64, faces [F][3] i32, vertex_key [V] i64 (the edge key of each vertex) or NULL,
+ *              face_cell [F] i32 (the cell index of each face) or NULL; pts / faces may be NULL when V / F is 0.
+ * Ordinary launches only, no kernel waits for another block; the only atomics are the integer totals: two calls give the
+ * same bits.  PF_E_ARG for an extent below 2, 2^31 or more samples, a value, level, spacing or origin that is not finite,
+ * flags other than 0, and for a surface of 2^31 or more vertices or with 3 faces >= 2^31 (the message names the count). */
+typedef struct pf_isosurface pf_isosurface;
+int pf_isosurface_create(pf_ctx* ctx, const double* values, int64_t nx, int64_t ny, int64_t nz, double level, const double* spacing,
+                         const double* origin, uint32_t flags, pf_isosurface** handle, int64_t* report, double* device_ms);
+int pf_isosurface_fetch(pf_isosurface* h, double* pts, int32_t* faces, int64_t* vertex_key, int32_t* face_cell);
+void pf_isosurface_free(pf_isosurface* h);
+
 #ifdef __cplusplus
 }
 #endif

@@ -243,6 +243,10 @@ SIGNATURES = {
     "pf_shapes_set_reference": (C.c_int, [C.c_void_p, _f64p]),
     "pf_shapes_download": (C.c_int, [C.c_void_p, _f64p]),
     "pf_shapes_device_ms": (C.c_int, [C.c_void_p, C.c_int32, _f64p]),
+    "pf_isosurface_create": (C.c_int, [C.c_void_p, _f64p, C.c_int64, C.c_int64, C.c_int64, C.c_double, _f64p, _f64p, C.c_uint32,
+                                       C.POINTER(C.c_void_p), _i64p, _f64p]),
+    "pf_isosurface_fetch": (C.c_int, [C.c_void_p, _f64p, _i32p, _i64p, _i32p]),
+    "pf_isosurface_free": (None, [C.c_void_p]),
 }
 
 _lib = None
@@ -727,6 +731,17 @@ class Context(object):
         return {"face_neighbours": nbr, "patch": patch, "flip": flip.astype(bool), "boundary_loop": loop,
                 "patch_orientable": orientable[:P].astype(bool), "patch_volume": volume[:P].copy(), "report": report,
                 "device_ms": ms.value}
+
+    # ---- isosurface extraction ---------------------------------------------------------
+    def isosurface(self, values, level=0.0, spacing=(1.0, 1.0, 1.0), origin=(0.0, 0.0, 0.0)):
+        """`pf_isosurface_create` / `_fetch` / `_free` of the volume (nx, ny, nz): a dict with `points` (V, 3) f64, `faces`
+        (F, 3) int32, `vertex_key` (V,) int64 = 7 * lattice index + edge kind, `face_cell` (F,) int32, `report` (8,) int64 =
+        vertices | faces | cells with a face | lattice points | cells | 0 | 0 | 0, and `device_ms`.  `value < level` is
+        inside and the normals point outside.  Shapes and finiteness are checked here (`check_volume`)."""
+        with DeviceIsosurface(values, level, spacing, origin, ctx=self) as iso:
+            pts, faces, key, cell = iso.fetch()
+            return {"points": pts, "faces": faces, "vertex_key": key, "face_cell": cell, "report": iso.report,
+                    "device_ms": iso.device_ms}
 
     # ---- mesh resampling ---------------------------------------------------------------
     def cluster_mesh(self, points, faces, mass, seeds=None, n_iter=20, centroids=None, labels=None, update_only=False):
@@ -1409,6 +1424,55 @@ class DeviceShapes(_Handle):
         ms = np.zeros(1)
         _check(self._lib.pf_shapes_device_ms(self._h, int(bool(enable)), _f64(ms)))
         return float(ms[0])
+
+
+def check_volume(values, level=0.0, spacing=(1.0, 1.0, 1.0), origin=(0.0, 0.0, 0.0)):
+    """The argument checks of `DeviceIsosurface`, which need no library: ValueError, or (values (nx, ny, nz) f64
+    C-contiguous, level, spacing (3,) f64, origin (3,) f64).  Any real dtype is cast to float64 here."""
+    values = np.asarray(values)
+    if values.ndim != 3:
+        raise ValueError("a volume must be an (nx, ny, nz) array, not one of %d dimensions" % values.ndim)
+    if min(values.shape) < 2:
+        raise ValueError("every extent of a volume must be at least 2, not %r" % (values.shape,))
+    if values.size >= 2 ** 31:
+        raise ValueError("a volume must have fewer than 2^31 samples, not %d" % values.size)
+    if values.dtype.kind not in "fiub":
+        raise TypeError("a volume must hold real numbers, not %s" % values.dtype)
+    values = np.ascontiguousarray(values, dtype=np.float64)
+    if not np.isfinite(values).all():
+        raise ValueError("the values of a volume must be finite")
+    level = float(level)
+    spacing, origin = _c_f64(spacing).reshape(-1), _c_f64(origin).reshape(-1)
+    if spacing.shape != (3,) or origin.shape != (3,):
+        raise ValueError("spacing and origin must have three entries each")
+    if not (np.isfinite(level) and np.isfinite(spacing).all() and np.isfinite(origin).all()):
+        raise ValueError("level, spacing and origin must be finite")
+    return values, level, spacing, origin
+
+
+class DeviceIsosurface(_Handle):
+    """The isosurface of a sampled scalar field, extracted on the device and held there until fetched
+    (`pf_isosurface_*`; the definition is in include/pyfocusr_hip.h).  `report` (8,) int64 = vertices | faces | cells with a
+    face | lattice points | cells | 0 | 0 | 0."""
+
+    _free = "pf_isosurface_free"
+
+    def __init__(self, values, level=0.0, spacing=(1.0, 1.0, 1.0), origin=(0.0, 0.0, 0.0), ctx=None):
+        v, level, spacing, origin = check_volume(values, level, spacing, origin)
+        _Handle.__init__(self, ctx)
+        self.report = np.zeros(8, dtype=np.int64)
+        h, ms = C.c_void_p(), C.c_double(0.0)
+        _check(self._lib.pf_isosurface_create(self.ctx._h, _f64(v), v.shape[0], v.shape[1], v.shape[2], level, _f64(spacing),
+                                              _f64(origin), 0, C.byref(h), _ptr(self.report), C.byref(ms)))
+        self._adopt(h)
+        self.n_vertices, self.n_faces, self.device_ms = int(self.report[0]), int(self.report[1]), ms.value
+
+    def fetch(self):
+        """(points (V, 3) f64, faces (F, 3) int32, vertex_key (V,) int64, face_cell (F,) int32)."""
+        pts, faces = np.empty((self.n_vertices, 3)), np.empty((self.n_faces, 3), dtype=np.int32)
+        key, cell = np.empty(self.n_vertices, dtype=np.int64), np.empty(self.n_faces, dtype=np.int32)
+        _check(self._lib.pf_isosurface_fetch(self._h, _f64(pts), _ptr(faces), _ptr(key), _ptr(cell)))
+        return pts, faces, key, cell
 
 
 def gaussian_gram_product(A, B, beta, V, ctx=None):
