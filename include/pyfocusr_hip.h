@@ -1035,6 +1035,57 @@ int pf_isosurface_create(pf_ctx* ctx, const double* values, int64_t nx, int64_t 
 int pf_isosurface_fetch(pf_isosurface* h, double* pts, int32_t* faces, int64_t* vertex_key, int32_t* face_cell);
 void pf_isosurface_free(pf_isosurface* h);
 
+/* ---- explicit smoothing of a triangle mesh: Laplacian and Taubin fairing (pf_smooth.hip; the reference has none: an extra) ----
+ * pts [n][3] f64, faces [n_faces][3] i32 (host; triangles only).  f64 throughout, separate multiplies and adds, sums left to
+ * right.  tests/_smoothing_ref.py states the definition in numpy and the device returns its bits.
+ *   neighbours N(v): the distinct vertices u != v that share an edge of some face with v, in ascending u.  A face that
+ *              repeats a vertex contributes its proper edges only; a half-edge from a vertex to itself is no edge.
+ *   kinds      kind [n] u8 = 1 (boundary: v is an end of an edge with exactly one half-edge, as in pf_curvatures) | 2 (pinned:
+ *              the caller's pinned[v] != 0) | 4 (movable, below).
+ *   weights    PF_SMOOTH_UNIFORM: w_vu = 1.  PF_SMOOTH_COTANGENT: w_vu = max(0, the sum, over the half-edges h = 3 t + j of
+ *              the edge {v, u} in ascending h, of the half cotangent at the opposite corner k = (j + 2) % 3 of t).  The half
+ *              cotangent at corner k is 0.5 ((a . b) / |a x b|) with a, b the edges that leave the corner for the next corner
+ *              and the one after; 0 at all three corners of a triangle where |a x b| is 0 or not finite at one of them.
+ *              Computed once from pts, never updated.
+ *   sweep      with factor f, every movable vertex: x'_v = x_v + f (s / W - x_v), s the running sum from 0.0 of w_vu x_u over
+ *              N(v) in ascending u and W that of the w_vu; with uniform weights s is the plain running sum of the x_u and W
+ *              the count as a double.  Every other vertex keeps its bits.  All reads come from the previous sweep (Jacobi).
+ *   boundary   PF_SMOOTH_FREE: boundary vertices move like all others.  PF_SMOOTH_FIXED: they do not move.
+ *              PF_SMOOTH_CURVE: a boundary vertex sums only the neighbours joined to it by a boundary edge, with weight 1
+ *              and W their count, whatever the weights.  A pinned vertex never moves.  movable: not pinned, not a boundary
+ *              vertex under PF_SMOOTH_FIXED, and W > 0.
+ *   clamp      with bounds c [ncols] >= 0, after every clamp_every-th sweep (the sweeps count from 1), per component of a
+ *              movable vertex: x < x0 - c ? x0 - c : x, then x > x0 + c ? x0 + c : x, with x0 the run's input.
+ *   stats [6]  (values == NULL only) signed volume of the input, of the result | vertex mean of the result [3] | largest
+ *              |x - x0| over all components.  Volume: the sum over the faces in ascending order of x0 . (x1 x x2), the cross
+ *              product component-wise, the dot product left to right, along the library's fixed tree (256 consecutive terms
+ *              left to right from 0.0, 256 of those sums likewise, the rest in order), divided by 6; the mean: each
+ *              coordinate's sum over the vertices along the same tree, divided by n.
+ *   pf_smoother_create     uploads once and builds the adjacency (CSR, int32): two stable radix sorts (half-edges by edge key,
+ *              directed entries by source vertex), one read-back (the edge count) and a second wait.  pinned [n] may be NULL.
+ *   pf_smoother_info       counts [6] = edges | boundary edges | non-manifold edges (three or more half-edges) | entries |
+ *              largest row | movable vertices.
+ *   pf_smoother_adjacency  rowptr [n + 1], col [entries], w [entries] (1.0 with uniform weights), kind [n]; each may be NULL.
+ *   pf_smoother_run        values [n][ncols] (host), or NULL: the mesh's own points (ncols = 3, no upload).  factors
+ *              [n_sweeps]: sweep s uses factors[s] (Laplacian: lambda, lambda, ...; Taubin: lambda, mu, lambda, mu, ...).
+ *              clamp (may be NULL) [ncols].  out [n][ncols].  One upload, n_sweeps launches that ping-pong two buffers, one
+ *              download, one wait; n_sweeps = 0 returns the input's bits.  stats and device_ms (the device time between the
+ *              upload and the download, HIP events) may be NULL.
+ * No floating-point atomics, no kernel waits for another block: two calls give the same bits.  PF_E_ARG for a vertex id
+ * outside 0..n-1, n outside 1..2^31-1, n_faces < 1, 3 n_faces >= 2^31 or 2^31 entries or more, an unknown weights or
+ * boundary_mode, ncols outside 1..32 (or not 3 with values == NULL), stats with values, a factor that is not finite, a
+ * negative or NaN bound, clamp_every < 1 with a clamp. */
+enum { PF_SMOOTH_UNIFORM = 0, PF_SMOOTH_COTANGENT = 1 };
+enum { PF_SMOOTH_FREE = 0, PF_SMOOTH_FIXED = 1, PF_SMOOTH_CURVE = 2 };
+typedef struct pf_smoother pf_smoother;
+int pf_smoother_create(pf_ctx* ctx, const double* pts, int64_t n, const int32_t* faces, int64_t n_faces, int32_t weights,
+                       int32_t boundary_mode, const uint8_t* pinned, pf_smoother** handle);
+int pf_smoother_info(const pf_smoother* h, int64_t* counts);
+int pf_smoother_adjacency(pf_smoother* h, int32_t* rowptr, int32_t* col, double* w, uint8_t* kind);
+int pf_smoother_run(pf_smoother* h, const double* values, int32_t ncols, const double* factors, int32_t n_sweeps, int32_t clamp_every,
+                    const double* clamp, double* out, double* stats, double* device_ms);
+void pf_smoother_free(pf_smoother* h);
+
 #ifdef __cplusplus
 }
 #endif

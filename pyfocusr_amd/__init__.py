@@ -25,6 +25,7 @@ from .ray_casting import (hit_points, ray_crossings, ray_mesh_intersections, thi
                           vertex_normals)
 from .remesh import lift_point_map, prolong_from_clusters, resample_mesh, restrict_to_clusters
 from .shape_model import ShapeModel, build_shape_model, generalized_procrustes, population_from_template
+from .smoothing import MeshSmoother, smooth_mask_mesh, smooth_mesh, smooth_point_data
 from .spectral_descriptors import (descriptor_coefficients, descriptor_correspondences, functional_map_from_descriptors,
                                    heat_kernel_signature, signature_on_mesh, spectral_descriptors, wave_kernel_signature)
 from .surface_distance import (point_to_surface_distances, points_inside, signed_distances_on_mesh,

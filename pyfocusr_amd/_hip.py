@@ -247,6 +247,12 @@ SIGNATURES = {
                                        C.POINTER(C.c_void_p), _i64p, _f64p]),
     "pf_isosurface_fetch": (C.c_int, [C.c_void_p, _f64p, _i32p, _i64p, _i32p]),
     "pf_isosurface_free": (None, [C.c_void_p]),
+    "pf_smoother_create": (C.c_int, [C.c_void_p, _f64p, C.c_int64, _i32p, C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_uint8),
+                                     C.POINTER(C.c_void_p)]),
+    "pf_smoother_info": (C.c_int, [C.c_void_p, _i64p]),
+    "pf_smoother_adjacency": (C.c_int, [C.c_void_p, _i32p, _i32p, _f64p, C.POINTER(C.c_uint8)]),
+    "pf_smoother_run": (C.c_int, [C.c_void_p, _f64p, C.c_int32, _f64p, C.c_int32, C.c_int32, _f64p, _f64p, _f64p, _f64p]),
+    "pf_smoother_free": (None, [C.c_void_p]),
 }
 
 _lib = None
@@ -1473,6 +1479,48 @@ class DeviceIsosurface(_Handle):
         key, cell = np.empty(self.n_vertices, dtype=np.int64), np.empty(self.n_faces, dtype=np.int32)
         _check(self._lib.pf_isosurface_fetch(self._h, _f64(pts), _ptr(faces), _ptr(key), _ptr(cell)))
         return pts, faces, key, cell
+
+
+SMOOTH_WEIGHTS = {"uniform": 0, "cotangent": 1}  # PF_SMOOTH_UNIFORM, PF_SMOOTH_COTANGENT
+SMOOTH_BOUNDARY = {"free": 0, "fixed": 1, "curve": 2}  # PF_SMOOTH_FREE, PF_SMOOTH_FIXED, PF_SMOOTH_CURVE
+SMOOTH_MAX_COLUMNS = 32  # the limit of pf_smoother_run
+SMOOTH_COUNTS = ("edges", "boundary_edges", "non_manifold_edges", "entries", "largest_row", "movable_vertices")
+
+
+class DeviceSmoother(_Handle):
+    """The adjacency of a triangle mesh in HBM (CSR, weights, vertex kinds) with its points, for explicit smoothing sweeps
+    (`pf_smoother_*`; the definitions are in include/pyfocusr_hip.h).  The arguments are the library's own: points (n, 3)
+    f64, faces (m, 3) i32, the codes of SMOOTH_WEIGHTS and SMOOTH_BOUNDARY, pinned (n,) uint8 or None
+    (`pyfocusr_amd.smoothing` checks and converts what a user passes)."""
+
+    _free = "pf_smoother_free"
+
+    def __init__(self, points, faces, weights=0, boundary=1, pinned=None, ctx=None):
+        _Handle.__init__(self, ctx)
+        self.n, self.n_faces = points.shape[0], faces.shape[0]
+        self._create("pf_smoother_create", self.ctx._h, _f64(points), self.n, _ptr(faces), self.n_faces, int(weights), int(boundary),
+                     _ptr(pinned))
+        self.counts = np.zeros(len(SMOOTH_COUNTS), dtype=np.int64)
+        _check(self._lib.pf_smoother_info(self._h, _ptr(self.counts)))
+
+    def adjacency(self):
+        """(rowptr (n + 1,) i32, col (entries,) i32, w (entries,) f64, kind (n,) u8: 1 boundary | 2 pinned | 4 movable)."""
+        nnz = int(self.counts[3])
+        rowptr, col = np.empty(self.n + 1, dtype=np.int32), np.empty(nnz, dtype=np.int32)
+        w, kind = np.empty(nnz), np.empty(self.n, dtype=np.uint8)
+        _check(self._lib.pf_smoother_adjacency(self._h, _ptr(rowptr), _ptr(col), _f64(w), _ptr(kind)))
+        return rowptr, col, w, kind
+
+    def run(self, values, factors, clamp_every=1, clamp=None, stats=False):
+        """(out, stats (6,) or None, device_ms) of `pf_smoother_run`: values (n, c) f64 or None (the mesh's own points),
+        factors (s,) f64, clamp (c,) f64 or None."""
+        ncols = 3 if values is None else values.shape[1]
+        out = np.empty((self.n, ncols))
+        st = np.zeros(6) if stats else None
+        ms = C.c_double(0.0)
+        _check(self._lib.pf_smoother_run(self._h, _f64(values), ncols, _f64(factors), len(factors), int(clamp_every), _f64(clamp),
+                                         _f64(out), _f64(st), C.byref(ms)))
+        return out, st, ms.value
 
 
 def gaussian_gram_product(A, B, beta, V, ctx=None):

@@ -12,7 +12,7 @@
 //                  vertex i to LDS, thread q then adds the 256 terms of quantity q left to right: level 1 of the tree
 //   k_sh_mean      one block per 256 vertices: thread i adds the shapes' coordinates left to right, divides, takes the
 //                  term of `change` against the old reference and overwrites the reference; thread 0 adds the terms
-//   k_sh_level     levels 2 and 3 of the tree for every quantity (partials are [node][quantity])
+//   k_tree_level   levels 2 and 3 of the tree for every quantity (pf_tree.h; partials are [node][quantity])
 //   k_sh_pairs     T(w . dot3(a_s, b_t)) for 16 x 16 pairs (s, t) per block, one pair per thread, the 2 x 16 shapes
 //                  staged through LDS 32 vertices at a time; the Gram (a = b = x - r, the tiles of the upper triangle) and
 //                  the scores (b = the modes, every tile)
@@ -35,6 +35,7 @@
 #include <cstdlib>
 
 #include "pf_internal.h"
+#include "pf_tree.h"
 
 struct pf_shapes {
     pf_ctx* ctx = nullptr;
@@ -58,6 +59,7 @@ constexpr int SH_ROW = 3 * SH_SUB + 1;     // a staged shape's row; odd, so that
 constexpr int SH_KT = 16;                  // outputs of pf_shapes_combine a thread keeps in registers per pass over the population
 constexpr int64_t SH_LEVEL1_MAX = (int64_t)1 << 27;  // doubles of level-1 partials k_sh_pairs may write (1 GiB)
 static_assert(SH_GROUP % SH_SUB == 0 && SH_TILE * SH_TILE == PF_BLOCK && SH_GROUP == PF_BLOCK, "k_sh_pairs' tiling");
+static_assert(SH_GROUP == PF_TREE_GROUP, "level 1 here, the levels above it in pf_tree.h");
 
 __device__ __forceinline__ double sh_dot3(const double* a, const double* b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
 
@@ -148,19 +150,6 @@ __global__ __launch_bounds__(PF_BLOCK) void k_sh_align_sums(const double* __rest
         for (int k = 0; k < cnt; ++k) sum += term[q][k];
         lev1[g * rows + (q < 10 ? s * 10 + q : (int64_t)S * 10)] = sum;
     }
-}
-
-// One level of the tree over `rows` quantities, partials as [node][quantity]: out[o][q] = in[group o .. group (o + 1))[q]
-// summed left to right from 0.0 as far as the nodes go; group == 0: every node (n_out == 1).
-__global__ __launch_bounds__(PF_BLOCK) void k_sh_level(const double* __restrict__ in, int64_t n_in, double* __restrict__ out, int64_t n_out,
-                                                       int64_t rows, int64_t group) {
-    const int64_t idx = (int64_t)blockIdx.x * PF_BLOCK + threadIdx.x;
-    if (idx >= rows * n_out) return;
-    const int64_t o = idx / rows, q = idx - o * rows;
-    const int64_t lo = group * o, hi = group ? min(lo + group, n_in) : n_in;
-    double sum = 0.0;
-    for (int64_t k = lo; k < hi; ++k) sum += in[k * rows + q];
-    out[o * rows + q] = sum;
 }
 
 // y_b = scale_s ((x0 R[0][b] + x1 R[1][b]) + x2 R[2][b]) (+ t_s[b]) in place.  P [S][13] = R [9] | scale | t [3].  Grid (blocks of n, S).
@@ -273,7 +262,7 @@ bool all_finite(const double* p, int64_t count) {
     return true;
 }
 
-// T(w_i) on the host, as k_sh_level adds it
+// T(w_i) on the host, as k_tree_level adds it
 double tree_sum_host(const double* w, int64_t n) {
     double total = 0.0, a2 = 0.0, a1 = 0.0;
     int c1 = 0, c2 = 0;
@@ -291,23 +280,6 @@ double tree_sum_host(const double* w, int64_t n) {
 
 int64_t runs_of(int64_t n) { return (n + SH_GROUP - 1) / SH_GROUP; }
 
-// levels 2 and 3 over lev1 [n1][rows] -> the device block of the `rows` sums (from level 2 on: lev [n_nodes][rows] at `level`)
-double* reduce_levels(Scratch& sc, double* lev, int64_t n_nodes, int64_t rows, int level) {
-    hipStream_t st = sc.st;
-    if (level == 1) {
-        const int64_t n2 = runs_of(n_nodes);
-        double* lev2 = sc.get<double>(n2 * rows);
-        if (sc.ok()) k_sh_level<<<pf_blocks(rows * n2), PF_BLOCK, 0, st>>>(lev, n_nodes, lev2, n2, rows, SH_GROUP);
-        lev = lev2, n_nodes = n2;
-    }
-    double* sums = sc.get<double>(rows);
-    if (sc.ok()) {
-        k_sh_level<<<pf_blocks(rows), PF_BLOCK, 0, st>>>(lev, n_nodes, sums, 1, rows, 0);
-        sc.launched();
-    }
-    return sums;
-}
-
 // the pair sums of k_sh_pairs on the device as out [SA][SB] (a Scratch block)
 double* pair_sums(Scratch& sc, const pf_shapes* h, const double* B, const double* rb, int32_t SB, int tri) {
     const int64_t n = h->n, n1 = runs_of(n), n2 = runs_of(n1);
@@ -322,7 +294,7 @@ double* pair_sums(Scratch& sc, const pf_shapes* h, const double* B, const double
     double* out = sc.get<double>((int64_t)h->S * SB);
     if (sc.ok())
         k_sh_pairs<<<dim3((unsigned)nodes, (unsigned)tiles), PF_BLOCK, 0, sc.st>>>(h->X, h->r, h->S, B, rb, SB, h->w, n, tri, tiles_b, carry, rows, part);
-    double* sums = reduce_levels(sc, part, nodes, rows, carry ? 2 : 1);
+    double* sums = pf_tree_reduce(sc, part, nodes, rows, carry ? 2 : 1);
     if (sc.ok()) {
         k_sh_pairs_finish<<<pf_blocks((int64_t)h->S * SB), PF_BLOCK, 0, sc.st>>>(sums, h->S, SB, tri, tiles_b, out);
         sc.launched();
@@ -396,7 +368,7 @@ int pf_shapes_center(pf_shapes* h, double* centroids_out) {
     double* lev1 = sc.get<double>(n1 * rows);
     timer.start(sc);
     if (sc.ok()) k_sh_center_sums<<<dim3((unsigned)n1, (unsigned)h->S), PF_BLOCK, 0, st>>>(h->X, h->w, n, rows, lev1);
-    double* c = reduce_levels(sc, lev1, n1, rows, 1);
+    double* c = pf_tree_reduce(sc, lev1, n1, rows, 1);
     if (sc.ok()) {
         k_sh_divide<<<pf_blocks(rows), PF_BLOCK, 0, st>>>(c, rows, h->W);
         k_sh_center_apply<<<dim3(pf_blocks(3 * n), (unsigned)h->S), PF_BLOCK, 0, st>>>(h->X, 3 * n, c);
@@ -419,7 +391,7 @@ int pf_shapes_mean(pf_shapes* h, int32_t first, int32_t count, double* mean_out,
     double* lev1 = sc.get<double>(n1);
     timer.start(sc);
     if (sc.ok()) k_sh_mean<<<(unsigned)n1, PF_BLOCK, 0, st>>>(h->X, h->w, h->r, n, first, count, lev1);
-    double* change = reduce_levels(sc, lev1, n1, 1, 1);
+    double* change = pf_tree_reduce(sc, lev1, n1, 1, 1);
     timer.stop(sc);
     sc.download(mean_out, h->r, 3 * n);
     sc.download(change_out, change, 1);
@@ -438,7 +410,7 @@ int pf_shapes_align_sums(pf_shapes* h, double* cross_out, double* norm2_out, dou
     double* lev1 = sc.get<double>(n1 * rows);
     timer.start(sc);
     if (sc.ok()) k_sh_align_sums<<<dim3((unsigned)n1, (unsigned)S), PF_BLOCK, 0, st>>>(h->X, h->w, h->r, n, S, rows, lev1);
-    double* d_sums = reduce_levels(sc, lev1, n1, rows, 1);
+    double* d_sums = pf_tree_reduce(sc, lev1, n1, rows, 1);
     timer.stop(sc);
     sc.download(sums.data(), d_sums, rows);
     PF_TRY(finish(h, sc, timer, "pf_shapes_align_sums"));
