@@ -1086,6 +1086,50 @@ int pf_smoother_run(pf_smoother* h, const double* values, int32_t ncols, const d
                     const double* clamp, double* out, double* stats, double* device_ms);
 void pf_smoother_free(pf_smoother* h);
 
+/* ---- the exact Euclidean distance transform of a binary volume, with its feature transform (pf_edt.hip; the reference has
+ * none: an extra) ----
+ * mask [nx][ny][nz] u8, C-contiguous (z fastest), host; every extent >= 1 (a 2-D image is (nx, ny, 1)); nx ny nz < 2^31.  A
+ * voxel with mask != 0 is a feature.  spacing = (sx, sy, sz), positive and finite.  tests/_edt_ref.py states the definition
+ * in numpy and the device returns its bits.  For a voxel p = (i, j, k) and a feature q = (i', j', k'), the integer
+ * differences d_a converted to double, separate multiplies and adds:
+ *     t_a(p, q) = (s_a d_a) (s_a d_a)    per axis a
+ *     c(p, q)   = (t_z + t_y) + t_x
+ *     dist2(p)  = min over all features q of c(p, q);   dist(p) = sqrt(dist2(p))  (the device's double square root)
+ *   nearest    is defined in stages, which is what a separable pass computes and keeps every tie decidable:
+ *              stage z  the feature k' of p's own z-line with the smallest t_z, the lower k' on a tie: g_z(i, j, k);
+ *              stage y  the j' that minimises fl(g_z(i, j', k) + t_y) over the y-line, the lower j' on a tie: g_zy(i, j, k);
+ *              stage x  the i' that minimises fl(g_zy(i', j, k) + t_x) over the x-line, the lower i' on a tie.
+ *              nearest(p) [N] i32 is the flat index (i' ny + j') nz + k' of the feature that survives.  Addition and
+ *              multiplication are monotone, so the staged value is dist2(p) bit for bit and c(p, nearest(p)) == dist2(p)
+ *              exactly; where every sum is exact (integer spacings) nearest(p) is the lowest flat index among the minimisers.
+ *              A line without a feature carries +inf and -1 through; a volume without one gives dist2 = dist = +inf and
+ *              nearest = -1.
+ *   signed     PF_EDT_SIGNED: dist(p) = dist_to_foreground(p) - dist_to_background(p), one of which is 0: negative inside
+ *              the mask, like pf_surface_signed_distance.  dist2 is the square of the magnitude (the other class's dist2) and nearest
+ *              the nearest voxel of the other class.  With an empty class the values are +inf (no foreground) or -inf (no
+ *              background) and nearest = -1.
+ *   pf_edt_create      one upload; per transform a bit-packing pass, stage z on the packed words (count-leading / -trailing
+ *              zeros) and the stages y and x as searches outward from p that stop at t(r) > best; signed mode transforms
+ *              the mask and its complement and combines them.  The results stay on the device behind *handle.  report [8]
+ *              (may be NULL): samples | foreground | background | 0 ...  device_ms (may be NULL): between the upload and the
+ *              last kernel (HIP events).  flags must be 0.
+ *   pf_edt_fetch       dist [N] f64, dist2 [N] f64, nearest [N] i32; each may be NULL.
+ *   pf_edt_isosurface  the isosurface of the resident dist (the signed field in signed mode) at `level` on the lattice of the
+ *              given origin and the handle's spacing: the body of pf_isosurface_create without the download and upload of the
+ *              field, with the same outputs and report; the result is a pf_isosurface like any other.
+ * Ordinary launches only, no kernel waits for another block, the only atomic is the integer foreground count: two calls
+ * give the same bits.  PF_E_ARG for an extent below 1, 2^31 or more samples, a spacing that is not positive and finite, one
+ * whose squared distances leave the normal doubles (s s subnormal, or the squared diagonal of the volume not finite: t_a would
+ * stop growing with |d_a|), an unknown mode, flags other than 0; pf_edt_isosurface: any extent below 2, a level or origin
+ * that is not finite, and a field that is not finite because a class is empty. */
+enum { PF_EDT_UNSIGNED = 0, PF_EDT_SIGNED = 1 };
+typedef struct pf_edt pf_edt;
+int pf_edt_create(pf_ctx* ctx, const uint8_t* mask, int64_t nx, int64_t ny, int64_t nz, const double* spacing, int32_t mode,
+                  uint32_t flags, pf_edt** handle, int64_t* report, double* device_ms);
+int pf_edt_fetch(pf_edt* h, double* dist, double* dist2, int32_t* nearest);
+int pf_edt_isosurface(pf_edt* h, double level, const double* origin, pf_isosurface** out, int64_t* report, double* device_ms);
+void pf_edt_free(pf_edt* h);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,6 +17,8 @@ from .functional_maps import (fast_zoomout_correspondences, functional_map_from_
                               soft_p2p_from_functional_map, zoomout_correspondences, zoomout_refine)
 from .map_quality import (conformal_distortion, distortion_on_mesh, isometric_distortion, map_distortion,
                           symmetric_dirichlet)
+from .distance_transform import (close_mask, dilate_mask, distance_transform, erode_mask, mask_offset_surface, nearest_feature,
+                                 open_mask, propagate_labels, signed_distance_of_mask)
 from .isosurface import isosurface, mask_to_mesh, offset_surface, signed_distance_volume, voxel_remesh
 from .neighbours import inverse_distance_average, k_nearest_neighbours
 from .laplace_beltrami import cotangent_laplacian, laplace_beltrami_spectrum, mean_curvature, mean_curvature_normals

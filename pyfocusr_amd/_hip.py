@@ -253,6 +253,11 @@ SIGNATURES = {
     "pf_smoother_adjacency": (C.c_int, [C.c_void_p, _i32p, _i32p, _f64p, C.POINTER(C.c_uint8)]),
     "pf_smoother_run": (C.c_int, [C.c_void_p, _f64p, C.c_int32, _f64p, C.c_int32, C.c_int32, _f64p, _f64p, _f64p, _f64p]),
     "pf_smoother_free": (None, [C.c_void_p]),
+    "pf_edt_create": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint8), C.c_int64, C.c_int64, C.c_int64, _f64p, C.c_int32, C.c_uint32,
+                                C.POINTER(C.c_void_p), _i64p, _f64p]),
+    "pf_edt_fetch": (C.c_int, [C.c_void_p, _f64p, _f64p, _i32p]),
+    "pf_edt_isosurface": (C.c_int, [C.c_void_p, C.c_double, _f64p, C.POINTER(C.c_void_p), _i64p, _f64p]),
+    "pf_edt_free": (None, [C.c_void_p]),
 }
 
 _lib = None
@@ -748,6 +753,18 @@ class Context(object):
             pts, faces, key, cell = iso.fetch()
             return {"points": pts, "faces": faces, "vertex_key": key, "face_cell": cell, "report": iso.report,
                     "device_ms": iso.device_ms}
+
+    # ---- distance transforms of masks ---------------------------------------------------
+    def distance_transform(self, mask, spacing=(1.0, 1.0, 1.0), signed=False, dist=True, dist2=True, nearest=True):
+        """`pf_edt_create` / `_fetch` / `_free` of the mask (nx, ny, nz): a dict with `dist` and `dist2` (nx, ny, nz) f64,
+        `nearest` (nx, ny, nz) int32 = the flat index of the nearest feature or -1 (each only if asked for), `report` (8,)
+        int64 = samples | foreground | background | 0 ... and `device_ms`.  Shapes and spacing are checked here
+        (`check_mask`)."""
+        with DeviceDistanceTransform(mask, spacing, signed, ctx=self) as edt:
+            out = dict(zip(("dist", "dist2", "nearest"), edt.fetch(dist, dist2, nearest)))
+            out = {k: v for k, v in out.items() if v is not None}
+            out.update(report=edt.report, device_ms=edt.device_ms)
+            return out
 
     # ---- mesh resampling ---------------------------------------------------------------
     def cluster_mesh(self, points, faces, mass, seeds=None, n_iter=20, centroids=None, labels=None, update_only=False):
@@ -1463,13 +1480,18 @@ class DeviceIsosurface(_Handle):
 
     _free = "pf_isosurface_free"
 
-    def __init__(self, values, level=0.0, spacing=(1.0, 1.0, 1.0), origin=(0.0, 0.0, 0.0), ctx=None):
-        v, level, spacing, origin = check_volume(values, level, spacing, origin)
-        _Handle.__init__(self, ctx)
+    def __init__(self, values, level=0.0, spacing=(1.0, 1.0, 1.0), origin=(0.0, 0.0, 0.0), ctx=None, _source=None):
         self.report = np.zeros(8, dtype=np.int64)
         h, ms = C.c_void_p(), C.c_double(0.0)
-        _check(self._lib.pf_isosurface_create(self.ctx._h, _f64(v), v.shape[0], v.shape[1], v.shape[2], level, _f64(spacing),
-                                              _f64(origin), 0, C.byref(h), _ptr(self.report), C.byref(ms)))
+        if _source is not None:  # (DeviceDistanceTransform, level, origin): the field that handle holds (pf_edt_isosurface)
+            edt, level, origin = _source
+            _Handle.__init__(self, edt.ctx)
+            _check(self._lib.pf_edt_isosurface(edt._h, level, _f64(origin), C.byref(h), _ptr(self.report), C.byref(ms)))
+        else:
+            v, level, spacing, origin = check_volume(values, level, spacing, origin)
+            _Handle.__init__(self, ctx)
+            _check(self._lib.pf_isosurface_create(self.ctx._h, _f64(v), v.shape[0], v.shape[1], v.shape[2], level, _f64(spacing),
+                                                  _f64(origin), 0, C.byref(h), _ptr(self.report), C.byref(ms)))
         self._adopt(h)
         self.n_vertices, self.n_faces, self.device_ms = int(self.report[0]), int(self.report[1]), ms.value
 
@@ -1479,6 +1501,71 @@ class DeviceIsosurface(_Handle):
         key, cell = np.empty(self.n_vertices, dtype=np.int64), np.empty(self.n_faces, dtype=np.int32)
         _check(self._lib.pf_isosurface_fetch(self._h, _f64(pts), _ptr(faces), _ptr(key), _ptr(cell)))
         return pts, faces, key, cell
+
+
+PF_EDT_UNSIGNED, PF_EDT_SIGNED = 0, 1
+_TINY = np.finfo(np.float64).tiny
+
+
+def check_mask(mask, spacing=(1.0, 1.0, 1.0)):
+    """The argument checks of `DeviceDistanceTransform`, which need no library: ValueError or TypeError, or (mask
+    (nx, ny, nz) bool C-contiguous, True where the argument is not 0, spacing (3,) f64; one number is all three).  A
+    contiguous boolean mask comes back as it is, so checking twice costs nothing."""
+    mask = np.asarray(mask)
+    if mask.ndim != 3:
+        raise ValueError("a mask must be an (nx, ny, nz) array, not one of %d dimensions" % mask.ndim)
+    if min(mask.shape) < 1:
+        raise ValueError("every extent of a mask must be at least 1, not %r" % (mask.shape,))
+    if mask.size >= 2 ** 31:
+        raise ValueError("a mask must have fewer than 2^31 samples, not %d" % mask.size)
+    if mask.dtype.kind not in "biu":
+        raise TypeError("a mask must be boolean or a label map of integers, not %s" % mask.dtype)
+    mask = np.ascontiguousarray(mask if mask.dtype == np.bool_ else mask != 0)
+    spacing = np.asarray(spacing, dtype=np.float64)
+    spacing = np.repeat(spacing, 3) if spacing.ndim == 0 else _c_f64(spacing).reshape(-1)
+    if spacing.shape != (3,):
+        raise ValueError("spacing must be one number or three")
+    if not (np.isfinite(spacing).all() and (spacing > 0.0).all()):
+        raise ValueError("spacing must be positive and finite")
+    with np.errstate(over="ignore", under="ignore"):
+        diagonal2 = float(np.sum((spacing * np.maximum(np.array(mask.shape) - 1, 1)) ** 2))
+        if (spacing * spacing < _TINY).any() or not np.isfinite(diagonal2):
+            raise ValueError("spacing %r: the squared distances leave the range of normal doubles" % (spacing.tolist(),))
+    return mask, spacing
+
+
+class DeviceDistanceTransform(_Handle):
+    """The exact Euclidean distance transform of a mask and its feature transform, computed on the device and held there
+    until fetched (`pf_edt_*`; the definition is in include/pyfocusr_hip.h).  `report` (8,) int64 = samples | foreground |
+    background | 0 ..."""
+
+    _free = "pf_edt_free"
+
+    def __init__(self, mask, spacing=(1.0, 1.0, 1.0), signed=False, ctx=None):
+        m, spacing = check_mask(mask, spacing)
+        _Handle.__init__(self, ctx)
+        self.shape, self.spacing, self.signed = m.shape, spacing, bool(signed)
+        self.report = np.zeros(8, dtype=np.int64)
+        h, ms = C.c_void_p(), C.c_double(0.0)
+        _check(self._lib.pf_edt_create(self.ctx._h, _ptr(m.view(np.uint8)), m.shape[0], m.shape[1], m.shape[2], _f64(spacing),
+                                       PF_EDT_SIGNED if signed else PF_EDT_UNSIGNED, 0, C.byref(h), _ptr(self.report), C.byref(ms)))
+        self._adopt(h)
+        self.n_foreground, self.n_background, self.device_ms = int(self.report[1]), int(self.report[2]), ms.value
+
+    def fetch(self, dist=True, dist2=True, nearest=True):
+        """(dist (nx, ny, nz) f64, dist2 (nx, ny, nz) f64, nearest (nx, ny, nz) int32), None for what was not asked for."""
+        d = np.empty(self.shape) if dist else None
+        d2 = np.empty(self.shape) if dist2 else None
+        near = np.empty(self.shape, dtype=np.int32) if nearest else None
+        _check(self._lib.pf_edt_fetch(self._h, _f64(d), _f64(d2), _ptr(near)))
+        return d, d2, near
+
+    def isosurface(self, level=0.0, origin=(0.0, 0.0, 0.0)):
+        """The `DeviceIsosurface` of the resident field at `level` (`pf_edt_isosurface`: no download, no upload)."""
+        origin = _c_f64(origin).reshape(-1)
+        if origin.shape != (3,) or not (np.isfinite(origin).all() and np.isfinite(float(level))):
+            raise ValueError("level and origin (three entries) must be finite")
+        return DeviceIsosurface(None, _source=(self, float(level), origin))
 
 
 SMOOTH_WEIGHTS = {"uniform": 0, "cotangent": 1}  # PF_SMOOTH_UNIFORM, PF_SMOOTH_COTANGENT

@@ -420,6 +420,13 @@ inline void pf_sort_pairs(Scratch& sc, const unsigned long long* k_in, unsigned 
 int pf_exclusive_scan_i32(hipStream_t st, const int32_t* in, int32_t* out, int64_t n);
 int pf_exclusive_scan_i64(hipStream_t st, const int64_t* in, int64_t* out, int64_t n);
 
+// pf_isosurface.hip: the body of pf_isosurface_create over values that are on the device already (d_values [nx][ny][nz],
+// finite; the extents, level, spacing and origin checked by the caller, who names itself in `fn`).  `sc` is the caller's
+// scratch: whatever it queued before (the upload of pf_isosurface_create) stays outside device_ms.  Used by pf_edt_isosurface.
+int pf_isosurface_extract(pf_ctx* ctx, const char* fn, Scratch& sc, const double* d_values, int64_t nx, int64_t ny, int64_t nz,
+                          double level, const double* spacing, const double* origin, pf_isosurface** out, int64_t* report,
+                          double* device_ms);
+
 // pf_operator.hip: what the other units of the solve's vector code (pf_orth, pf_reduce, pf_finalize, pf_rows) share
 int pf_check_slots(pf_graph* g, int32_t first, int32_t count, const char* who);  // also makes the ctx's device current
 const double* pf_op_values(pf_graph* g, int32_t op);  // the SELL values of PF_OP_RW / PF_OP_SYM; NULL: not available

@@ -16,6 +16,8 @@
 // The tables (ISO) are derived at compile time from the orientation rule; nothing is typed in.  Ordinary launches only: no
 // block waits for another, the totals are integer atomics, there is no floating-point sum at all: two calls give the same
 // bits.  Arithmetic: separate multiplies and adds (-ffp-contract=off).
+// pf_isosurface_create checks and uploads; everything above is pf_isosurface_extract, over values that are on the device,
+// which pf_edt_isosurface (pf_edt.hip) calls on the distance field it holds.
 #include <cmath>
 
 #include "pf_internal.h"
@@ -276,6 +278,79 @@ __global__ __launch_bounds__(PF_BLOCK) void k_iso_faces(IsoGrid g, const uint8_t
 
 }  // namespace
 
+// The extraction itself, over values that are on the device already: pf_isosurface_create uploads and calls it,
+// pf_edt_isosurface (pf_edt.hip) hands it the distance field it holds.
+int pf_isosurface_extract(pf_ctx* ctx, const char* fn, Scratch& sc, const double* d_values, int64_t nx, int64_t ny, int64_t nz,
+                          double level, const double* spacing, const double* origin, pf_isosurface** out, int64_t* report,
+                          double* device_ms) {
+    const int64_t lim = (int64_t)1 << 31;
+    const int64_t N = nx * ny * nz, n_cells = (nx - 1) * (ny - 1) * (nz - 1);
+    IsoGrid g;
+    g.nx = nx, g.ny = ny, g.nz = nz, g.words = (nz + 63) / 64, g.level = level;
+    for (int a = 0; a < 3; ++a) g.spacing[a] = spacing[a], g.origin[a] = origin[a];
+    hipStream_t st = ctx->stream;
+    StreamTimer timer(device_ms != nullptr);
+    unsigned long long totals[3] = {0, 0, 0};
+    pf_isosurface* h = new pf_isosurface();
+    h->ctx = ctx;
+    int rc = PF_OK;
+    unsigned long long* bits = sc.get<unsigned long long>(nx * ny * g.words);
+    uint8_t* mask = sc.get<uint8_t>(N);
+    int32_t *cnt = sc.get<int32_t>(N), *first = sc.get<int32_t>(N);
+    uint8_t* corner = sc.get<uint8_t>(n_cells);
+    int32_t *tcnt = sc.get<int32_t>(n_cells), *tfirst = sc.get<int32_t>(n_cells);
+    unsigned long long* d_totals = sc.get<unsigned long long>(3);
+    sc.zero(d_totals, sizeof(unsigned long long) * 3);
+    timer.start(sc);
+    if (sc.ok()) {
+        k_iso_classify<<<(unsigned)((nx * ny * g.words + ISO_LINE - 1) / ISO_LINE), PF_BLOCK, 0, st>>>(d_values, g, bits);
+        k_iso_edges<<<pf_blocks(N), PF_BLOCK, 0, st>>>(bits, g, mask, cnt, d_totals);
+        k_iso_cells<<<pf_blocks(n_cells), PF_BLOCK, 0, st>>>(bits, g, corner, tcnt, d_totals);
+        sc.launched();
+    }
+    sc.download(totals, d_totals, 3);
+    // (the totals are the atomics' 64-bit sums: one of 2^31 or more wraps the 32-bit scans, whose output is then not used)
+    if (sc.ok() && pf_exclusive_scan_i32(st, cnt, first, N) != PF_OK) sc.note(hipErrorUnknown);
+    if (sc.ok() && pf_exclusive_scan_i32(st, tcnt, tfirst, n_cells) != PF_OK) sc.note(hipErrorUnknown);
+    sc.sync();  // the one wait before the outputs are sized
+    const int64_t V = (int64_t)totals[0], F = (int64_t)totals[1];
+    if (sc.ok() && V >= lim) {
+        pf_set_error("%s: %lld vertices out of range (< 2^31)", fn, (long long)V);
+        rc = PF_E_ARG;
+    } else if (sc.ok() && 3 * F >= lim) {
+        pf_set_error("%s: %lld faces out of range (3 faces < 2^31)", fn, (long long)F);
+        rc = PF_E_ARG;
+    }
+    if (rc == PF_OK) {
+        h->n_vertices = V, h->n_faces = F;
+        h->pts = sc.keep<double>(3 * V);
+        h->vkey = sc.keep<int64_t>(V);
+        h->faces = sc.keep<int32_t>(3 * F);
+        h->fcell = sc.keep<int32_t>(F);
+        if (sc.ok() && V > 0) {
+            k_iso_vertices<<<pf_blocks(N), PF_BLOCK, 0, st>>>(d_values, g, mask, first, h->pts, h->vkey);
+            sc.launched();
+        }
+        if (sc.ok() && F > 0) {
+            k_iso_faces<<<pf_blocks(n_cells), PF_BLOCK, 0, st>>>(g, corner, tfirst, mask, first, h->faces, h->fcell);
+            sc.launched();
+        }
+        timer.stop(sc);
+        sc.sync();
+        timer.read(sc, device_ms);
+    }
+    if (!sc.ok() || rc != PF_OK) {
+        pf_isosurface_free(h);
+        return !sc.ok() ? pf_hip_failed(fn, sc.err) : rc;
+    }
+    if (report) {
+        report[0] = h->n_vertices, report[1] = h->n_faces, report[2] = (int64_t)totals[2], report[3] = N, report[4] = n_cells;
+        report[5] = report[6] = report[7] = 0;
+    }
+    *out = h;
+    return PF_OK;
+}
+
 extern "C" {
 
 void pf_isosurface_free(pf_isosurface* h) {
@@ -302,80 +377,13 @@ int pf_isosurface_create(pf_ctx* ctx, const double* values, int64_t nx, int64_t 
     PF_CHECK(std::isfinite(level), PF_E_ARG, "pf_isosurface_create: the level is not finite");
     for (int a = 0; a < 3; ++a)
         PF_CHECK(std::isfinite(spacing[a]) && std::isfinite(origin[a]), PF_E_ARG, "pf_isosurface_create: spacing or origin is not finite");
-    const int64_t N = nx * ny * nz, n_cells = (nx - 1) * (ny - 1) * (nz - 1);
+    const int64_t N = nx * ny * nz;
     for (int64_t i = 0; i < N; ++i) PF_CHECK(std::isfinite(values[i]), PF_E_ARG, "pf_isosurface_create: value %lld is not finite", (long long)i);
-    IsoGrid g;
-    g.nx = nx, g.ny = ny, g.nz = nz, g.words = (nz + 63) / 64, g.level = level;
-    for (int a = 0; a < 3; ++a) g.spacing[a] = spacing[a], g.origin[a] = origin[a];
     PF_HIP(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    StreamTimer timer(device_ms != nullptr);
-    unsigned long long totals[3] = {0, 0, 0};
-    pf_isosurface* h = new pf_isosurface();
-    h->ctx = ctx;
-    int rc = PF_OK;
-    hipError_t err;
-    {
-        Scratch sc(st);
-        double* d_values = sc.get<double>(N);
-        unsigned long long* bits = sc.get<unsigned long long>(nx * ny * g.words);
-        uint8_t* mask = sc.get<uint8_t>(N);
-        int32_t *cnt = sc.get<int32_t>(N), *first = sc.get<int32_t>(N);
-        uint8_t* corner = sc.get<uint8_t>(n_cells);
-        int32_t *tcnt = sc.get<int32_t>(n_cells), *tfirst = sc.get<int32_t>(n_cells);
-        unsigned long long* d_totals = sc.get<unsigned long long>(3);
-        sc.upload(d_values, values, N);
-        sc.zero(d_totals, sizeof(unsigned long long) * 3);
-        timer.start(sc);
-        if (sc.ok()) {
-            k_iso_classify<<<(unsigned)((nx * ny * g.words + ISO_LINE - 1) / ISO_LINE), PF_BLOCK, 0, st>>>(d_values, g, bits);
-            k_iso_edges<<<pf_blocks(N), PF_BLOCK, 0, st>>>(bits, g, mask, cnt, d_totals);
-            k_iso_cells<<<pf_blocks(n_cells), PF_BLOCK, 0, st>>>(bits, g, corner, tcnt, d_totals);
-            sc.launched();
-        }
-        sc.download(totals, d_totals, 3);
-        // (the totals are the atomics' 64-bit sums: one of 2^31 or more wraps the 32-bit scans, whose output is then not used)
-        if (sc.ok() && pf_exclusive_scan_i32(st, cnt, first, N) != PF_OK) sc.note(hipErrorUnknown);
-        if (sc.ok() && pf_exclusive_scan_i32(st, tcnt, tfirst, n_cells) != PF_OK) sc.note(hipErrorUnknown);
-        sc.sync();  // the one wait before the outputs are sized
-        const int64_t V = (int64_t)totals[0], F = (int64_t)totals[1];
-        if (sc.ok() && V >= lim) {
-            pf_set_error("pf_isosurface_create: %lld vertices out of range (< 2^31)", (long long)V);
-            rc = PF_E_ARG;
-        } else if (sc.ok() && 3 * F >= lim) {
-            pf_set_error("pf_isosurface_create: %lld faces out of range (3 faces < 2^31)", (long long)F);
-            rc = PF_E_ARG;
-        }
-        if (rc == PF_OK) {
-            h->n_vertices = V, h->n_faces = F;
-            h->pts = sc.keep<double>(3 * V);
-            h->vkey = sc.keep<int64_t>(V);
-            h->faces = sc.keep<int32_t>(3 * F);
-            h->fcell = sc.keep<int32_t>(F);
-            if (sc.ok() && V > 0) {
-                k_iso_vertices<<<pf_blocks(N), PF_BLOCK, 0, st>>>(d_values, g, mask, first, h->pts, h->vkey);
-                sc.launched();
-            }
-            if (sc.ok() && F > 0) {
-                k_iso_faces<<<pf_blocks(n_cells), PF_BLOCK, 0, st>>>(g, corner, tfirst, mask, first, h->faces, h->fcell);
-                sc.launched();
-            }
-            timer.stop(sc);
-            sc.sync();
-            timer.read(sc, device_ms);
-        }
-        err = sc.err;
-    }
-    if (err != hipSuccess || rc != PF_OK) {
-        pf_isosurface_free(h);
-        return err != hipSuccess ? pf_hip_failed("pf_isosurface_create", err) : rc;
-    }
-    if (report) {
-        report[0] = h->n_vertices, report[1] = h->n_faces, report[2] = (int64_t)totals[2], report[3] = N, report[4] = n_cells;
-        report[5] = report[6] = report[7] = 0;
-    }
-    *out = h;
-    return PF_OK;
+    Scratch sc(ctx->stream);
+    double* d_values = sc.get<double>(N);
+    sc.upload(d_values, values, N);
+    return pf_isosurface_extract(ctx, "pf_isosurface_create", sc, d_values, nx, ny, nz, level, spacing, origin, out, report, device_ms);
 }
 
 int pf_isosurface_fetch(pf_isosurface* h, double* pts, int32_t* faces, int64_t* vertex_key, int32_t* face_cell) {

@@ -5,7 +5,7 @@ the exact signed distances of `surface_distance`.
   `PolyMesh` (marching tetrahedra on the Kuhn decomposition of every cube: `pf_isosurface_create`, the exact definition is
   in include/pyfocusr_hip.h).  Vertices are welded, the faces are consistently oriented with their normals pointing from
   inside to outside, and two calls give the same bits.
-* `mask_to_mesh(mask)`: the boundary of a segmentation.
+* `mask_to_mesh(mask)`: the boundary of a segmentation; `method="distance"` places it by the mask's own distance field.
 * `signed_distance_volume(mesh)`: the signed distance of a mesh sampled on a lattice around it.
 * `voxel_remesh(mesh, spacing)`: a broken surface (holes, self-intersections, non-manifold patches) re-meshed through its
   distance field; `offset_surface(mesh, distance, spacing)`: the same at another level (shells, margins).
@@ -19,11 +19,13 @@ import numpy as np
 
 from . import _hip
 from ._meshargs import AttrDict, checked_mesh
+from .distance_transform import signed_field_surface
 from .remesh import resample_mesh
 from .surface_distance import signed_point_to_surface_distances
 from .vtk_functions import PolyMesh
 
 _INSIDE = ("below", "above")
+_METHODS = ("staircase", "distance")
 
 
 def _three(value, name):
@@ -78,11 +80,29 @@ def isosurface(volume, level=0.0, spacing=(1.0, 1.0, 1.0), origin=(0.0, 0.0, 0.0
                           n_crossing_cells=int(raw["report"][2]), report=raw["report"], device_ms=raw["device_ms"])
 
 
-def mask_to_mesh(mask, spacing=(1.0, 1.0, 1.0), origin=(0.0, 0.0, 0.0), closed=True, return_info=False, ctx=None):
-    """The boundary of a segmentation: `isosurface(mask.astype(float), 0.5, inside="above")`.  `mask` is boolean or a
-    0 / 1 label map; the surface runs half a step outside the voxel centres."""
-    return isosurface(np.asarray(mask).astype(np.float64), 0.5, spacing, origin, inside="above", closed=closed,
-                      return_info=return_info, ctx=ctx)
+def mask_to_mesh(mask, spacing=(1.0, 1.0, 1.0), origin=(0.0, 0.0, 0.0), closed=True, return_info=False, ctx=None,
+                 method="staircase"):
+    """The boundary of a segmentation.  `mask` is boolean or a 0 / 1 label map.
+
+    method   "staircase": `isosurface(mask.astype(float), 0.5, inside="above")`; the surface runs half a step outside the
+             voxel centres.  "distance": level 0 of the mask's signed Euclidean distance field (`distance_transform`),
+             computed and meshed on the device without a round trip.  The inside set is the same, so are the faces and
+             the vertex keys; the vertices sit where the distances to the two classes balance along each lattice edge.
+             `closed` then pads the mask with one layer of background instead of padding a float volume."""
+    if method not in _METHODS:
+        raise ValueError("method must be one of %r, not %r" % (_METHODS, method))
+    if method == "staircase":
+        return isosurface(np.asarray(mask).astype(np.float64), 0.5, spacing, origin, inside="above", closed=closed,
+                          return_info=return_info, ctx=ctx)
+    raw, shape, origin = signed_field_surface(mask, 0.0, _three(spacing, "spacing"), origin, 1 if closed else 0, ctx=ctx)
+    if raw is None:  # a class is empty: no crossing
+        raw = {"points": np.zeros((0, 3)), "faces": np.zeros((0, 3), dtype=np.int32), "vertex_key": np.zeros(0, dtype=np.int64),
+               "face_cell": np.zeros(0, dtype=np.int32), "report": np.zeros(8, dtype=np.int64), "device_ms": 0.0}
+    mesh = PolyMesh(raw["points"], raw["faces"])
+    if not return_info:
+        return mesh
+    return mesh, AttrDict(vertex_key=raw["vertex_key"], face_cell=raw["face_cell"], shape=shape, origin=origin,
+                          n_crossing_cells=int(raw["report"][2]), report=raw["report"], device_ms=raw["device_ms"])
 
 
 def signed_distance_volume(mesh, spacing=None, shape=None, padding=2, sign="pseudonormal", check_orientation=True, ctx=None):
