@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""From a segmentation to a mesh the spectral pipeline can take: a synthetic label map -> `close_mask` -> `mask_to_mesh`
+"""From a segmentation to a mesh the spectral pipeline can take: a synthetic label map -> `keep_largest_components` ->
+`fill_holes` -> `mask_to_mesh`
 -> `smooth_mask_mesh` -> `resample_mesh` -> the spectrum of its `Graph`; and a 3 mm margin around it (`mask_offset_surface`).
 
     python examples/segmentation_to_mesh.py [n_vertices]
@@ -23,13 +24,22 @@ head = ((x / 14.0) ** 2 + (y / 11.0) ** 2 + ((z - 30.0) / 9.0) ** 2 < 1.0) | ((x
 mask = shaft | head
 # what a segmentation brings along: pinholes inside and a speck outside.  Each would be a patch of its own in the surface
 rng = np.random.default_rng(0)
-holes = np.argwhere(mask)[rng.choice(int(mask.sum()), size=5, replace=False)]
-mask[tuple(holes.T)] = False
-mask[3, 3, 3] = True
+# pinholes are drawn where all 26 neighbours are solid, so each is a closed cavity (one on the surface would be a dent,
+# which is no hole and which `fill_holes` rightly leaves open)
+inner = np.pad(mask, 1)
+inner = np.logical_and.reduce([inner[1 + a:1 + a + shape[0], 1 + b:1 + b + shape[1], 1 + c:1 + c + shape[2]]
+                               for a in (-1, 0, 1) for b in (-1, 0, 1) for c in (-1, 0, 1)])
+holes = np.argwhere(inner)[rng.choice(int(inner.sum()), size=5, replace=False)]
+placed = np.zeros(shape, dtype=bool)
+placed[tuple(holes.T)] = True
+placed[3, 3, 3] = True  # the speck
+mask = mask ^ placed
 patches = pf.mesh_topology(pf.mask_to_mesh(mask, spacing, origin)).n_patches
-mask = pf.open_mask(pf.close_mask(mask, 1.3, spacing), 1.3, spacing)  # balls of 1.3 mm on the anisotropic voxels
-print("closing and opening with a ball of 1.3 mm: %d surface patches -> %d"
-      % (patches, pf.mesh_topology(pf.mask_to_mesh(mask, spacing, origin)).n_patches))
+raw, mask = mask, pf.fill_holes(pf.keep_largest_components(mask))  # the largest component, its cavities filled: no surface moves
+# mask = pf.open_mask(pf.close_mask(mask, 1.3, spacing), 1.3, spacing)  # balls of 1.3 mm instead: moves the whole surface
+print("largest component with its holes filled: %d surface patches -> %d; %d voxels changed, %d of them other than the speck "
+      "and the pinholes" % (patches, pf.mesh_topology(pf.mask_to_mesh(mask, spacing, origin)).n_patches,
+                            int((mask != raw).sum()), int(((mask != raw) & ~placed).sum())))
 
 mesh, info = pf.mask_to_mesh(mask, spacing, origin, return_info=True)
 topo = pf.mesh_topology(mesh)

@@ -1130,6 +1130,53 @@ int pf_edt_fetch(pf_edt* h, double* dist, double* dist2, int32_t* nearest);
 int pf_edt_isosurface(pf_edt* h, double level, const double* origin, pf_isosurface** out, int64_t* report, double* device_ms);
 void pf_edt_free(pf_edt* h);
 
+/* ---- connected components of a mask or a label map, with exact integer statistics (pf_ccl.hip; the reference has none: an
+ * extra) ----
+ * vol [nx][ny][nz] i32, C-contiguous (z fastest), host; every extent >= 1; N = nx ny nz < 2^31.  tests/_ccl_ref.py states the
+ * definition in numpy and the device returns its bytes.
+ *   background    a voxel with vol == 0.  connectivity is 6, 18 or 26: neighbours differ by at most 1 on every axis, in at
+ *                 most 1, 2 or 3 axes.
+ *   modes         PF_CCL_BINARY: two neighbouring voxels are joined if both are non-zero.  PF_CCL_BY_VALUE: if both are
+ *                 non-zero and equal.  PF_CCL_BACKGROUND: PF_CCL_BINARY on the complement: the zero voxels are labelled and
+ *                 the non-zero ones are the background (what hole filling needs).
+ *   components    a component is a class of the transitive closure.  Its root is its lowest flat index (i ny + j) nz + k.
+ *                 Components are numbered 1..C by ascending root.  component [N] i32: 0 on the background, otherwise the
+ *                 component's number.  In binary mode this is scipy.ndimage.label with generate_binary_structure(3, 1 | 2 | 3),
+ *                 numbering included.  Without a labelled voxel C = 0, every label is 0 and the tables are empty.
+ *   statistics    per component, exact integers: count i64; value i32, the input at the root (0 in background mode); root i32;
+ *                 lo [3], hi [3] i32, the inclusive bounding box in index space; border u8, 1 if a voxel of the component has
+ *                 an index of 0 or extent - 1 on any axis; sum [3] i64, the sums of i, j and k.  Centroids in millimetres
+ *                 and volumes are host arithmetic on these.
+ *   pf_ccl_create one upload; the labelling and the tables stay on the device behind *handle.  Runs along z come from
+ *                 bit-packed lines without a union; run starts are joined across the backward half of the neighbouring
+ *                 lines by lock-free unions (atomicMin, the larger root under the smaller; a retry means another thread got
+ *                 there first and strictly lowers the index retried with, so every launch ends on any input); roots are
+ *                 flagged, scanned and numbered; the tables are filled with integer atomics, one per field and wave where a
+ *                 wave's voxels share their component.  report [8] (may be NULL): samples | labelled voxels | components |
+ *                 retries of the unions | largest count | 0 ...  The retries depend on scheduling: they are the one number
+ *                 of a call that two calls need not share.  device_ms (may be NULL): between the upload and the last kernel
+ *                 (HIP events; the read-back of C that sizes the tables lies inside).  flags must be 0.
+ *   pf_ccl_fetch  component [N] i32, count [C] i64, value [C] i32, root [C] i32, lo [C][3] i32, hi [C][3] i32, border [C] u8,
+ *                 sum [C][3] i64; each may be NULL.
+ *   pf_ccl_select out [N] u8 = component > 0 && keep[component - 1] (keep [C] u8; may be NULL when C = 0): one gather launch
+ *                 and one download.  The host chooses components from the tables, the device applies the choice.
+ *   pf_ccl_info   C.
+ *   pf_ccl_combine_stats  for measurements: 0 sends every voxel's statistics with atomics of its own (the tables are the
+ *                 same bytes either way); 1, the default, combines within a wave.  Process-wide.
+ * Ordinary launches only, no kernel waits for another block, no floating point: two calls give the same bytes.  PF_E_ARG for
+ * NULL arguments, an extent below 1, 2^31 or more samples, a connectivity other than 6, 18 or 26, an unknown mode, flags
+ * other than 0. */
+enum { PF_CCL_BINARY = 0, PF_CCL_BY_VALUE = 1, PF_CCL_BACKGROUND = 2 };
+typedef struct pf_ccl pf_ccl;
+int pf_ccl_create(pf_ctx* ctx, const int32_t* vol, int64_t nx, int64_t ny, int64_t nz, int32_t connectivity, int32_t mode,
+                  uint32_t flags, pf_ccl** handle, int64_t* report, double* device_ms);
+int pf_ccl_fetch(pf_ccl* h, int32_t* component, int64_t* count, int32_t* value, int32_t* root, int32_t* lo, int32_t* hi,
+                 uint8_t* border, int64_t* sum);
+int pf_ccl_select(pf_ccl* h, const uint8_t* keep, uint8_t* out);
+int pf_ccl_info(const pf_ccl* h, int64_t* n_components);
+int pf_ccl_combine_stats(int on);
+void pf_ccl_free(pf_ccl* h);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,6 +9,8 @@ missing — there is no CPU fallback.
 from . import vtk_functions
 from .assignment import euclidean_assignment
 from .correspondence import closest_points_on_embedded_surface, interpolate_on_surface, transfer_point_data
+from .components import (ComponentStats, component_boxes, connected_components, fill_holes, keep_largest_components,
+                         largest_component_per_label, remove_small_components)
 from .curvature import (curvature_on_mesh, curvedness, discrete_curvatures, principal_curvatures, shape_index)
 from .eigsort import eigsort
 from .focusr import *  # noqa: F401,F403

@@ -258,6 +258,13 @@ SIGNATURES = {
     "pf_edt_fetch": (C.c_int, [C.c_void_p, _f64p, _f64p, _i32p]),
     "pf_edt_isosurface": (C.c_int, [C.c_void_p, C.c_double, _f64p, C.POINTER(C.c_void_p), _i64p, _f64p]),
     "pf_edt_free": (None, [C.c_void_p]),
+    "pf_ccl_create": (C.c_int, [C.c_void_p, _i32p, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_uint32,
+                                C.POINTER(C.c_void_p), _i64p, _f64p]),
+    "pf_ccl_fetch": (C.c_int, [C.c_void_p, _i32p, _i64p, _i32p, _i32p, _i32p, _i32p, C.POINTER(C.c_uint8), _i64p]),
+    "pf_ccl_select": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)]),
+    "pf_ccl_info": (C.c_int, [C.c_void_p, _i64p]),
+    "pf_ccl_combine_stats": (C.c_int, [C.c_int]),
+    "pf_ccl_free": (None, [C.c_void_p]),
 }
 
 _lib = None
@@ -764,6 +771,24 @@ class Context(object):
             out = dict(zip(("dist", "dist2", "nearest"), edt.fetch(dist, dist2, nearest)))
             out = {k: v for k, v in out.items() if v is not None}
             out.update(report=edt.report, device_ms=edt.device_ms)
+            return out
+
+    # ---- connected components of masks and label maps ----------------------------------
+    def connected_components(self, vol, connectivity=6, mode=0, component=True, stats=True, keep=None):
+        """`pf_ccl_create` / `_fetch` / `_free` of the volume (nx, ny, nz): a dict with `n`, `component` (nx, ny, nz) int32,
+        the tables `count`, `value`, `root`, `lo`, `hi`, `border`, `sum` (each group only if asked for), `selected`
+        (nx, ny, nz) bool = `pf_ccl_select` of `keep` (a function of the tables dict, or an array; only if given), `report`
+        (8,) int64 = samples | labelled voxels | components | union retries | largest count | 0 ... and `device_ms`.
+        Shape, dtype and connectivity are checked here (`check_label_volume`)."""
+        with DeviceComponents(vol, connectivity, mode, ctx=self) as ccl:
+            comp, tables = ccl.fetch(component, stats or callable(keep))
+            out = {"n": ccl.n, "report": ccl.report, "device_ms": ccl.device_ms}
+            if comp is not None:
+                out["component"] = comp
+            if stats:
+                out.update(tables)
+            if keep is not None:
+                out["selected"] = ccl.select(keep(tables) if callable(keep) else keep)
             return out
 
     # ---- mesh resampling ---------------------------------------------------------------
@@ -1566,6 +1591,78 @@ class DeviceDistanceTransform(_Handle):
         if origin.shape != (3,) or not (np.isfinite(origin).all() and np.isfinite(float(level))):
             raise ValueError("level and origin (three entries) must be finite")
         return DeviceIsosurface(None, _source=(self, float(level), origin))
+
+
+PF_CCL_BINARY, PF_CCL_BY_VALUE, PF_CCL_BACKGROUND = 0, 1, 2
+CCL_TABLES = ("count", "value", "root", "lo", "hi", "border", "sum")  # the statistics of pf_ccl_fetch, in its order
+
+
+def check_label_volume(vol, connectivity=6):
+    """The argument checks of `DeviceComponents`, which need no library: ValueError or TypeError, or (vol (nx, ny, nz)
+    int32 C-contiguous, connectivity).  The rules of shape, size and dtype are `check_mask`'s (`check_volume` is the
+    isosurface's check of a float field): bool and integers are taken, floats refused.  Integers wider than 32 bits keep
+    which voxels are 0 and which are equal only if they fit int32, which is checked."""
+    vol = np.asarray(vol)
+    if vol.ndim != 3:
+        raise ValueError("a volume must be an (nx, ny, nz) array, not one of %d dimensions" % vol.ndim)
+    if min(vol.shape) < 1:
+        raise ValueError("every extent of a volume must be at least 1, not %r" % (vol.shape,))
+    if vol.size >= 2 ** 31:
+        raise ValueError("a volume must have fewer than 2^31 samples, not %d" % vol.size)
+    if vol.dtype.kind not in "biu":
+        raise TypeError("a volume must be boolean or a label map of integers, not %s" % vol.dtype)
+    if connectivity not in (6, 18, 26):
+        raise ValueError("connectivity must be 6, 18 or 26, not %r" % (connectivity,))
+    if vol.dtype != np.int32:
+        if vol.dtype.itemsize >= 4 and vol.dtype.kind in "iu" and (vol.max() > 2 ** 31 - 1 or vol.min() < -2 ** 31):
+            raise ValueError("the values of a label map must fit int32")
+        vol = vol.astype(np.int32)
+    return np.ascontiguousarray(vol), int(connectivity)
+
+
+class DeviceComponents(_Handle):
+    """The connected components of a mask or label map, labelled on the device and held there with their statistics until
+    fetched (`pf_ccl_*`; the definition is in include/pyfocusr_hip.h).  `n` components; `report` (8,) int64 = samples |
+    labelled voxels | components | retries of the unions | largest count | 0 ..."""
+
+    _free = "pf_ccl_free"
+
+    def __init__(self, vol, connectivity=6, mode=PF_CCL_BINARY, ctx=None):
+        v, connectivity = check_label_volume(vol, connectivity)
+        if mode not in (PF_CCL_BINARY, PF_CCL_BY_VALUE, PF_CCL_BACKGROUND):
+            raise ValueError("mode must be PF_CCL_BINARY, PF_CCL_BY_VALUE or PF_CCL_BACKGROUND, not %r" % (mode,))
+        _Handle.__init__(self, ctx)
+        self.shape, self.connectivity, self.mode = v.shape, connectivity, int(mode)
+        self.report = np.zeros(8, dtype=np.int64)
+        h, ms = C.c_void_p(), C.c_double(0.0)
+        _check(self._lib.pf_ccl_create(self.ctx._h, _ptr(v), v.shape[0], v.shape[1], v.shape[2], connectivity, int(mode), 0,
+                                       C.byref(h), _ptr(self.report), C.byref(ms)))
+        self._adopt(h)
+        n = C.c_int64(0)
+        _check(self._lib.pf_ccl_info(self._h, C.byref(n)))
+        self.n, self.device_ms = int(n.value), ms.value
+
+    def fetch(self, component=True, stats=True):
+        """(component (nx, ny, nz) int32 or None, a dict of the tables `CCL_TABLES` or None): count (C,) int64, value and
+        root (C,) int32, lo and hi (C, 3) int32, border (C,) uint8, sum (C, 3) int64."""
+        n = self.n
+        comp = np.empty(self.shape, dtype=np.int32) if component else None
+        t = None
+        if stats:
+            t = {"count": np.empty(n, dtype=np.int64), "value": np.empty(n, dtype=np.int32), "root": np.empty(n, dtype=np.int32),
+                 "lo": np.empty((n, 3), dtype=np.int32), "hi": np.empty((n, 3), dtype=np.int32),
+                 "border": np.empty(n, dtype=np.uint8), "sum": np.empty((n, 3), dtype=np.int64)}
+        _check(self._lib.pf_ccl_fetch(self._h, _ptr(comp), *[_ptr(t[k]) if t else None for k in CCL_TABLES]))
+        return comp, t
+
+    def select(self, keep):
+        """(nx, ny, nz) bool: the voxels of the components c (0-based) with keep[c] (`pf_ccl_select`)."""
+        keep = np.ascontiguousarray(np.asarray(keep) != 0).reshape(-1)
+        if keep.shape != (self.n,):
+            raise ValueError("keep must have one entry per component (%d), not %r" % (self.n, keep.shape))
+        out = np.empty(self.shape, dtype=np.uint8)
+        _check(self._lib.pf_ccl_select(self._h, _ptr(keep.view(np.uint8)) if self.n else None, _ptr(out)))
+        return out.view(np.bool_)
 
 
 SMOOTH_WEIGHTS = {"uniform": 0, "cotangent": 1}  # PF_SMOOTH_UNIFORM, PF_SMOOTH_COTANGENT
